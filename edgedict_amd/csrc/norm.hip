@@ -32,7 +32,12 @@ __device__ __forceinline__ float row_sum(const T* x, const T* r, int D, int vec_
             for (int i = 0; i < VEC; ++i) s += a[i];
         }
     } else {
-        for (int c = lane; c < D; c += 64) s += ElemIO<T>::load(x + c) + (r ? ElemIO<T>::load(r + c) : 0.f);
+        // the vector path's lane -> element map and summation order, element by element, and the same explicit
+        // fmaf (left to itself the compiler contracts one path and packs the other into separate multiplies and
+        // adds): a row gives the same statistics and outputs, bit for bit, whichever path its alignment selects
+        for (int c0 = lane * VEC; c0 < D; c0 += 64 * VEC)
+            for (int c = c0; c < c0 + VEC && c < D; ++c)
+                s += ElemIO<T>::load(x + c) + (r ? ElemIO<T>::load(r + c) : 0.f);
     }
     return wave_sum(s);
 }
@@ -55,14 +60,15 @@ __device__ __forceinline__ float row_sqdev(const T* x, const T* r, float mean, i
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
                 const float d = a[i] - mean;
-                s += d * d;
+                s = fmaf(d, d, s);
             }
         }
     } else {
-        for (int c = lane; c < D; c += 64) {
-            const float d = ElemIO<T>::load(x + c) + (r ? ElemIO<T>::load(r + c) : 0.f) - mean;
-            s += d * d;
-        }
+        for (int c0 = lane * VEC; c0 < D; c0 += 64 * VEC)
+            for (int c = c0; c < c0 + VEC && c < D; ++c) {
+                const float d = ElemIO<T>::load(x + c) + (r ? ElemIO<T>::load(r + c) : 0.f) - mean;
+                s = fmaf(d, d, s);
+            }
     }
     return wave_sum(s);
 }
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd(
                         for (int i = 0; i < VEC; ++i) a[i] += r2[i];
                     }
 #pragma unroll
-                    for (int i = 0; i < VEC; ++i) o[i] += (a[i] - mean[k]) * rstd[k] * gm[i] + bt[i];
+                    for (int i = 0; i < VEC; ++i) o[i] += fmaf((a[i] - mean[k]) * rstd[k], gm[i], bt[i]);
                 }
                 if (reduce > 1) {
 #pragma unroll
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd(
                     if (!have[k]) break;
                     float a = ElemIO<T>::load(x + (irow0 + k) * D + c);
                     if (res) a += ElemIO<T>::load(res + (irow0 + k) * D + c);
-                    o += (a - mean[k]) * rstd[k] * gamma[c] + beta[c];
+                    o += fmaf((a - mean[k]) * rstd[k], gamma[c], beta[c]);
                 }
                 ElemIO<T>::store(yr + c, o * inv_red);
             }

@@ -281,10 +281,11 @@ class _Plan:
         cN = torch.stack([b["Cx"][-1] for b in self.layer_bufs], 0).clone()
         return hN, cN
 
-    def backward(self, dout, params, in_norm):
+    def backward(self, dout, params, in_norm, all_trainable=True):
         """Returns (dig, dib, per-layer grads) or None when every gradient was accumulated straight
         into the parameters' existing fp32 .grad buffers (flat-buffer training: no AccumulateGrad
-        adds, no temporaries)."""
+        adds, no temporaries).  ``all_trainable`` False (a parameter is frozen): the gradients come
+        out together, so they are all returned, and autograd drops the frozen ones."""
         dev = dout.device
         B, H = self.B, self.H
         grads = []
@@ -295,7 +296,7 @@ class _Plan:
         for pk, w_ih, w_hh in self.packs:      # ... or not at all yet (no prepack: first step, plain autograd use)
             fill_backward_images(pk, w_ih, w_hh)
         everyone = list(params) + list(in_norm)
-        direct = config.DEFER_WEIGHT_GRADS and all(
+        direct = all_trainable and config.DEFER_WEIGHT_GRADS and all(
             p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous() for p in everyone)
         zeros = None if direct else torch.zeros(2 * H * self.L + 2 * self.I0, dtype=F32, device=dev)
         for l in range(self.L):
@@ -390,7 +391,9 @@ class EncoderStackFn(torch.autograd.Function):
         if dout.dtype != BF16:
             dout = dout.to(BF16)
         with ops.timed("enc_stack_bwd_T%d_L%d" % (plan.T0, plan.L)):
-            res = plan.backward(dout, ctx.params, ctx.in_norm)
+            # inputs 1, 2: the input norm's gamma / beta; 8...: six tensors per layer
+            trainable = all(ctx.needs_input_grad[1:3]) and all(ctx.needs_input_grad[8:])
+            res = plan.backward(dout, ctx.params, ctx.in_norm, trainable)
         if res is None:        # accumulated in place
             return (None,) * (8 + len(ctx.params))
         dig, dib, grads = res

@@ -110,6 +110,11 @@ def _state(t):
     return t.contiguous()
 
 
+def _accumulates_in_place(p):
+    """May the weight gradient of ``p`` be added straight into its existing .grad (flat-buffer training)?"""
+    return p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()
+
+
 def _grads_ready(params, device):
     """Tell the data-parallel gradient exchange (dp.BucketedAllReduce.ready) that ``params`` were
     accumulated in place by work enqueued on the auxiliary stream up to now."""
@@ -209,24 +214,36 @@ class _LSTMBlockFn(torch.autograd.Function):
             else:
                 dx = ops.gemm(dG, wih.t()).view(B, T, I)
         b_ih, b_hh = ctx.biases
-        if config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
-                p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()
-                for p in (w_ih, w_hh, b_ih, b_hh)):
+        # a parameter frozen after its .grad buffer exists (FlatParams) gets nothing, as plain autograd would do
+        need = ctx.needs_input_grad[1:5]
+        live = tuple(p for p, n in zip((w_ih, w_hh, b_ih, b_hh), need) if n)
+        if live and config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
+                _accumulates_in_place(p) for p in live):
             # ... so they accumulate straight into the .grad buffers on the auxiliary stream, under the next
             # layer's BPTT (as the joint's dW2 does, side.py)
             with side.deferred(dG.device, G, x, Hprev):
-                ops.gemm(dG.t(), x2.t(), out=w_ih.grad, accumulate=True, split_k=ops.pick_split_k(4 * H, I, M))
-                ops.gemm(dG.t(), Hprev.view(M, H).t(), out=w_hh.grad, accumulate=True,
-                         split_k=ops.pick_split_k(4 * H, H, M))
-                ops.colsum(dG, out=b_ih.grad)
-                ops.colsum(dG, out=b_hh.grad)
-            _grads_ready((w_ih, w_hh, b_ih, b_hh), dG.device)      # no autograd hook fires for them (dp.py)
+                if need[0]:
+                    ops.gemm(dG.t(), x2.t(), out=w_ih.grad, accumulate=True, split_k=ops.pick_split_k(4 * H, I, M))
+                if need[1]:
+                    ops.gemm(dG.t(), Hprev.view(M, H).t(), out=w_hh.grad, accumulate=True,
+                             split_k=ops.pick_split_k(4 * H, H, M))
+                if need[2]:
+                    ops.colsum(dG, out=b_ih.grad)
+                if need[3]:
+                    ops.colsum(dG, out=b_hh.grad)
+            _grads_ready(live, dG.device)      # no autograd hook fires for them (dp.py)
             return (dx, None, None, None, None, dgamma, dbeta, None, None, None, None, None)
-        dw_ih = ops.gemm(dG.t(), x2.t(), out_dtype=F32, split_k=ops.pick_split_k(4 * H, I, M))
-        dw_hh = ops.gemm(dG.t(), Hprev.view(M, H).t(), out_dtype=F32,
-                         split_k=ops.pick_split_k(4 * H, H, M))
-        db = ops.colsum(dG)
-        return (dx, dw_ih, dw_hh, db, db.clone(), dgamma, dbeta, None, None, None, None, None)
+        dw_ih = dw_hh = db_ih = db_hh = None
+        if need[0]:
+            dw_ih = ops.gemm(dG.t(), x2.t(), out_dtype=F32, split_k=ops.pick_split_k(4 * H, I, M))
+        if need[1]:
+            dw_hh = ops.gemm(dG.t(), Hprev.view(M, H).t(), out_dtype=F32,
+                             split_k=ops.pick_split_k(4 * H, H, M))
+        if need[2] or need[3]:
+            db = ops.colsum(dG)
+            db_ih = db if need[2] else None
+            db_hh = (db.clone() if need[2] else db) if need[3] else None
+        return (dx, dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta, None, None, None, None, None)
 
 
 class _GRUBlockFn(torch.autograd.Function):
@@ -348,18 +365,22 @@ class _LinearFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dy2, WEIGHTS.get(w, cd).t()).view(*shp)
-        if config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
-                p is None or (p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()) for p in (w, b)):
+        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
+        need_w, need_b = ctx.needs_input_grad[1], has_b and ctx.needs_input_grad[2]
+        live = tuple(p for p, n in ((w, need_w), (b, need_b)) if n)
+        if live and config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
+                _accumulates_in_place(p) for p in live):
             with side.deferred(dy2.device, dy2, x2):
-                ops.gemm(dy2.t(), x2.t(), out=w.grad, accumulate=True,
-                         split_k=ops.pick_split_k(w.shape[0], w.shape[1], M))
-                if has_b:
+                if need_w:
+                    ops.gemm(dy2.t(), x2.t(), out=w.grad, accumulate=True,
+                             split_k=ops.pick_split_k(w.shape[0], w.shape[1], M))
+                if need_b:
                     ops.colsum(dy2, out=b.grad)
-            _grads_ready((w, b) if has_b else (w,), dy2.device)     # no autograd hook fires for them (dp.py)
+            _grads_ready(live, dy2.device)     # no autograd hook fires for them (dp.py)
             return dx, None, None, None
         dw = ops.gemm(dy2.t(), x2.t(), out_dtype=F32,
-                      split_k=ops.pick_split_k(w.shape[0], w.shape[1], M))
-        db = ops.colsum(dy2) if has_b else None
+                      split_k=ops.pick_split_k(w.shape[0], w.shape[1], M)) if need_w else None
+        db = ops.colsum(dy2) if need_b else None
         return dx, dw, db, None
 
 
@@ -421,18 +442,21 @@ class _JointFn(torch.autograd.Function):
         # weight gradients feed nothing downstream: when the parameters already own fp32 .grad
         # buffers they are accumulated in place on the auxiliary stream, under the encoder's
         # backward pass (side.py); otherwise they are returned to autograd as usual
-        defer = config.DEFER_WEIGHT_GRADS and all(
-            p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()
-            for p in (w1, ctx.b1, w2, ctx.b2))
+        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
+        need = ctx.needs_input_grad[2:6]
+        live = tuple(p for p, n in zip((w1, ctx.b1, w2, ctx.b2), need) if n)
+        defer = bool(live) and config.DEFER_WEIGHT_GRADS and all(_accumulates_in_place(p) for p in live)
         dw1 = db1 = dw2 = db2 = None
         with ops.timed("joint_dhid_gemm"):
             # dl x W2 with W2^T materialised once per optimiser step (1.3 M elements): both
             # operands K-contiguous -> the direct-to-LDS kernel (gemm_nt.hip)
             dhid = ops.gemm(dl, WEIGHTS.get(w2, cd, transposed=True))
         if not defer:
-            with ops.timed("joint_dw2_gemm"):
-                dw2 = ops.gemm(dl.t(), hid2.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
-            db2 = ops.colsum(dl)
+            if need[2]:
+                with ops.timed("joint_dw2_gemm"):
+                    dw2 = ops.gemm(dl.t(), hid2.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
+            if need[3]:
+                db2 = ops.colsum(dl)
         dE1, dD1 = ops.joint_hidden_bwd(dhid.view(B, T, U1, J), hid)
         del dhid
         dE1c = ops.cast(dE1, cd).view(B * T, J)
@@ -443,21 +467,27 @@ class _JointFn(torch.autograd.Function):
             # enqueued AFTER the critical-path products above: the auxiliary stream starts when
             # they are done and its MFMA work runs under the latency-bound recurrences that follow
             with side.deferred(dl.device, dl, hid, dE1c, dD1c, dD1, enc2, dec2):
-                ops.gemm(dl.t(), hid2.t(), out=w2.grad, accumulate=True, split_k=8,
-                         max_wg_per_cu=2)
-                ops.colsum(dl, out=ctx.b2.grad)
-                g1 = w1.grad
-                ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
-                         split_k=ops.pick_split_k(J, P, B * T))
-                ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
-                         split_k=ops.pick_split_k(J, P2, B * U1))
-                ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
-            _grads_ready((w1, ctx.b1, w2, ctx.b2), dl.device)
+                if need[2]:
+                    ops.gemm(dl.t(), hid2.t(), out=w2.grad, accumulate=True, split_k=8,
+                             max_wg_per_cu=2)
+                if need[3]:
+                    ops.colsum(dl, out=ctx.b2.grad)
+                if need[0]:
+                    g1 = w1.grad
+                    ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
+                             split_k=ops.pick_split_k(J, P, B * T))
+                    ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
+                             split_k=ops.pick_split_k(J, P2, B * U1))
+                if need[1]:
+                    ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
+            _grads_ready(live, dl.device)
         if not defer:
-            dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
-            ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
-            ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
-            db1 = ops.colsum(dD1.view(B * U1, J))
+            if need[0]:
+                dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
+                ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
+                ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
+            if need[1]:
+                db1 = ops.colsum(dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
         return denc, ddec, dw1, db1, dw2, db2, None
 
@@ -540,9 +570,10 @@ class _JointLossFn(torch.autograd.Function):
         gscale = gout.contiguous().float()
         w1c = WEIGHTS.get(w1, cd)
         w2t = WEIGHTS.get(w2, cd, transposed=True)
-        defer = config.DEFER_WEIGHT_GRADS and all(
-            p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()
-            for p in (w1, ctx.b1, w2, ctx.b2))
+        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
+        need = ctx.needs_input_grad[2:6]
+        live = tuple(p for p, n in zip((w1, ctx.b1, w2, ctx.b2), need) if n)
+        defer = bool(live) and config.DEFER_WEIGHT_GRADS and all(_accumulates_in_place(p) for p in live)
         dw1 = db1 = dw2 = db2 = None
         dE1 = torch.empty(B, T, J, dtype=F32, device=dl.device)
         dD1 = torch.empty(B, U1, J, dtype=F32, device=dl.device)
@@ -566,8 +597,10 @@ class _JointLossFn(torch.autograd.Function):
             _lib.call("joint_hidden_bwd_packed", _lib.dtype_code(cd), dhid, hid, dE1, dD1, al_d, ll_d,
                       off_d, B, T, U1, J)
         if not defer:
-            dw2 = ops.gemm(dl.t(), hid.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
-            db2 = ops.colsum(dl if db2_parts is None else db2_parts)
+            if need[2]:
+                dw2 = ops.gemm(dl.t(), hid.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
+            if need[3]:
+                db2 = ops.colsum(dl if db2_parts is None else db2_parts)
         del dhid
         dE1c = ops.cast(dE1, cd).view(B * T, J)
         dD1c = ops.cast(dD1, cd).view(B * U1, J)
@@ -575,20 +608,26 @@ class _JointLossFn(torch.autograd.Function):
         ddec = ops.gemm(dD1c, w1c[:, P:].t()).view(B, U1, P2)
         if defer:
             with side.deferred(dl.device, dl, hid, dE1c, dD1c, dD1, enc2, dec2, db2_parts):
-                ops.gemm(dl.t(), hid.t(), out=w2.grad, accumulate=True, split_k=8, max_wg_per_cu=2)
-                ops.colsum(dl if db2_parts is None else db2_parts, out=ctx.b2.grad)
-                g1 = w1.grad
-                ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
-                         split_k=ops.pick_split_k(J, P, B * T))
-                ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
-                         split_k=ops.pick_split_k(J, P2, B * U1))
-                ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
-            _grads_ready((w1, ctx.b1, w2, ctx.b2), dl.device)
+                if need[2]:
+                    ops.gemm(dl.t(), hid.t(), out=w2.grad, accumulate=True, split_k=8, max_wg_per_cu=2)
+                if need[3]:
+                    ops.colsum(dl if db2_parts is None else db2_parts, out=ctx.b2.grad)
+                if need[0]:
+                    g1 = w1.grad
+                    ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
+                             split_k=ops.pick_split_k(J, P, B * T))
+                    ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
+                             split_k=ops.pick_split_k(J, P2, B * U1))
+                if need[1]:
+                    ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
+            _grads_ready(live, dl.device)
         else:
-            dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
-            ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
-            ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
-            db1 = ops.colsum(dD1.view(B * U1, J))
+            if need[0]:
+                dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
+                ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
+                ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
+            if need[1]:
+                db1 = ops.colsum(dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
         return denc, ddec, dw1, db1, dw2, db2, None, None, None, None, None
 

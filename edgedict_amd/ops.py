@@ -353,9 +353,17 @@ def gru_backward(G, dY, Hprev, HN, WhhT):
     return DH
 
 
+def _check_tokens(tokens):
+    # the kernels read token (b, u) at tokens[b * tok_stride + u]: int32 with unit column stride
+    if tokens.shape[1] > 0 and (tokens.dtype != torch.int32 or tokens.stride(1) != 1):
+        raise ValueError("embedding: tokens must be int32 [B,U] with unit column stride (got %s, strides %s)"
+                         % (tokens.dtype, tuple(tokens.stride())))
+
+
 def embedding_fwd(tokens, weight, out_dtype, prepend_bos, bos):
     """tokens int32 [B,U] -> [B, U(+1), E] in out_dtype; weight may be the fp32 master."""
     require_cuda(weight)
+    _check_tokens(tokens)
     B, U = tokens.shape
     V, E = weight.shape
     Uout = U + (1 if prepend_bos else 0)
@@ -368,6 +376,7 @@ def embedding_fwd(tokens, weight, out_dtype, prepend_bos, bos):
 
 
 def embedding_bwd(tokens, dout, V, prepend_bos, bos, pad):
+    _check_tokens(tokens)
     B, Uout, E = dout.shape
     U = tokens.shape[1]
     demb = torch.zeros(V, E, dtype=torch.float32, device=dout.device)
