@@ -41,10 +41,6 @@ DEFER_WEIGHT_GRADS = os.environ.get("EDGEDICT_DEFER_DW", "1") != "0"
 # instead of a pass over the gradient matrix on the auxiliary stream
 FUSED_DB2 = os.environ.get("EDGEDICT_FUSED_DB2", "1") != "0"
 
-# the same for the per-layer LSTM blocks (fp32 mode, prediction network, small encoders): dW_ih / dW_hh / db of a layer
-# run on the auxiliary stream under the BPTT of the layer below
-DEFER_LSTM_WEIGHT_GRADS = os.environ.get("EDGEDICT_DEFER_LSTM_DW", "1") != "0"
-
 # Transducer.forward runs the prediction network on the auxiliary stream, concurrently with the
 # encoder (and, through autograd's stream replay, its backward concurrently with the encoder's)
 DECODER_ON_AUX_STREAM = os.environ.get("EDGEDICT_DECODER_AUX", "1") != "0"

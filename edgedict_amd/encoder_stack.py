@@ -13,7 +13,7 @@ import weakref
 
 import torch
 
-from . import _lib, config, ops
+from . import _lib, config, ops, side
 from ._lib import check, dtype_code, ptr, stream_ptr
 
 F32 = torch.float32
@@ -66,11 +66,6 @@ BWD_SK = os.environ.get("EDGEDICT_STACK_BWD_SK_PACK", "1") != "0"
 
 def _p(t):
     return None if t is None else t.data_ptr()
-
-
-def side_stream(device):
-    from . import side
-    return side.stream(device)
 
 
 def supported(cd, H, I0, L, reductions):
@@ -296,8 +291,7 @@ class _Plan:
         for pk, w_ih, w_hh in self.packs:      # ... or not at all yet (no prepack: first step, plain autograd use)
             fill_backward_images(pk, w_ih, w_hh)
         everyone = list(params) + list(in_norm)
-        direct = all_trainable and config.DEFER_WEIGHT_GRADS and all(
-            p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous() for p in everyone)
+        direct = all_trainable and config.DEFER_WEIGHT_GRADS and all(side.accumulates_in_place(p) for p in everyone)
         zeros = None if direct else torch.zeros(2 * H * self.L + 2 * self.I0, dtype=F32, device=dev)
         for l in range(self.L):
             y = self.larr[l]
@@ -332,7 +326,7 @@ class _Plan:
         from . import dp
         cb = None
         if direct and dp.READY_HOOK is not None:
-            hook, aux = dp.READY_HOOK, side_stream(dev)
+            hook, aux = dp.READY_HOOK, side.stream(dev)
 
             errors = []
 

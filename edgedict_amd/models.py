@@ -110,19 +110,6 @@ def _state(t):
     return t.contiguous()
 
 
-def _accumulates_in_place(p):
-    """May the weight gradient of ``p`` be added straight into its existing .grad (flat-buffer training)?"""
-    return p.grad is not None and p.grad.dtype == F32 and p.grad.is_contiguous()
-
-
-def _grads_ready(params, device):
-    """Tell the data-parallel gradient exchange (dp.BucketedAllReduce.ready) that ``params`` were
-    accumulated in place by work enqueued on the auxiliary stream up to now."""
-    from . import dp
-    if dp.READY_HOOK is not None:
-        dp.READY_HOOK(params, side.stream(device))
-
-
 # ----------------------------------------------------------------------------------------
 # autograd plumbing around the kernels
 class _InputNormFn(torch.autograd.Function):
@@ -213,37 +200,13 @@ class _LSTMBlockFn(torch.autograd.Function):
                 ops.gemm(dG, wih.t(), out=ds.view(M, I), accumulate=True)
             else:
                 dx = ops.gemm(dG, wih.t()).view(B, T, I)
-        b_ih, b_hh = ctx.biases
-        # a parameter frozen after its .grad buffer exists (FlatParams) gets nothing, as plain autograd would do
-        need = ctx.needs_input_grad[1:5]
-        live = tuple(p for p, n in zip((w_ih, w_hh, b_ih, b_hh), need) if n)
-        if live and config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
-                _accumulates_in_place(p) for p in live):
-            # ... so they accumulate straight into the .grad buffers on the auxiliary stream, under the next
-            # layer's BPTT (as the joint's dW2 does, side.py)
-            with side.deferred(dG.device, G, x, Hprev):
-                if need[0]:
-                    ops.gemm(dG.t(), x2.t(), out=w_ih.grad, accumulate=True, split_k=ops.pick_split_k(4 * H, I, M))
-                if need[1]:
-                    ops.gemm(dG.t(), Hprev.view(M, H).t(), out=w_hh.grad, accumulate=True,
-                             split_k=ops.pick_split_k(4 * H, H, M))
-                if need[2]:
-                    ops.colsum(dG, out=b_ih.grad)
-                if need[3]:
-                    ops.colsum(dG, out=b_hh.grad)
-            _grads_ready(live, dG.device)      # no autograd hook fires for them (dp.py)
-            return (dx, None, None, None, None, dgamma, dbeta, None, None, None, None, None)
-        dw_ih = dw_hh = db_ih = db_hh = None
-        if need[0]:
-            dw_ih = ops.gemm(dG.t(), x2.t(), out_dtype=F32, split_k=ops.pick_split_k(4 * H, I, M))
-        if need[1]:
-            dw_hh = ops.gemm(dG.t(), Hprev.view(M, H).t(), out_dtype=F32,
-                             split_k=ops.pick_split_k(4 * H, H, M))
-        if need[2] or need[3]:
-            db = ops.colsum(dG)
-            db_ih = db if need[2] else None
-            db_hh = (db.clone() if need[2] else db) if need[3] else None
-        return (dx, dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta, None, None, None, None, None)
+        # ... so they may accumulate into the .grad buffers on the auxiliary stream, under the next layer's BPTT (side.py)
+        with side.WeightGrads(ctx, 1, (w_ih, w_hh) + ctx.biases, G, x, Hprev) as wg:
+            wg.gemm(0, dG.t(), x2.t(), split_k=ops.pick_split_k(4 * H, I, M))
+            wg.gemm(1, dG.t(), Hprev.view(M, H).t(), split_k=ops.pick_split_k(4 * H, H, M))
+            wg.colsum(2, dG)
+            wg.colsum(3, dG)
+        return (dx, *wg.grads, dgamma, dbeta, None, None, None, None, None)
 
 
 class _GRUBlockFn(torch.autograd.Function):
@@ -348,14 +311,13 @@ class _LinearFn(torch.autograd.Function):
         y = ops.gemm(x2, wc, bias=b.detach() if b is not None else None)
         ctx.save_for_backward(x2, w)
         ctx.bias = b
-        ctx.cfg = (cd, shp, b is not None)
+        ctx.cfg = (cd, shp)
         return y.view(*shp[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
-        cd, shp, has_b = ctx.cfg
-        b = ctx.bias
+        cd, shp = ctx.cfg
         dy2 = dy.reshape(-1, w.shape[0])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
@@ -365,23 +327,10 @@ class _LinearFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dy2, WEIGHTS.get(w, cd).t()).view(*shp)
-        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
-        need_w, need_b = ctx.needs_input_grad[1], has_b and ctx.needs_input_grad[2]
-        live = tuple(p for p, n in ((w, need_w), (b, need_b)) if n)
-        if live and config.DEFER_WEIGHT_GRADS and config.DEFER_LSTM_WEIGHT_GRADS and all(
-                _accumulates_in_place(p) for p in live):
-            with side.deferred(dy2.device, dy2, x2):
-                if need_w:
-                    ops.gemm(dy2.t(), x2.t(), out=w.grad, accumulate=True,
-                             split_k=ops.pick_split_k(w.shape[0], w.shape[1], M))
-                if need_b:
-                    ops.colsum(dy2, out=b.grad)
-            _grads_ready(live, dy2.device)     # no autograd hook fires for them (dp.py)
-            return dx, None, None, None
-        dw = ops.gemm(dy2.t(), x2.t(), out_dtype=F32,
-                      split_k=ops.pick_split_k(w.shape[0], w.shape[1], M)) if need_w else None
-        db = ops.colsum(dy2) if need_b else None
-        return dx, dw, db, None
+        with side.WeightGrads(ctx, 1, (w, ctx.bias), dy2, x2) as wg:
+            wg.gemm(0, dy2.t(), x2.t(), split_k=ops.pick_split_k(w.shape[0], w.shape[1], M))
+            wg.colsum(1, dy2)
+        return (dx, *wg.grads, None)
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -439,57 +388,27 @@ class _JointFn(torch.autograd.Function):
         hid2 = hid.view(M, J)
         w1c = WEIGHTS.get(w1, cd)
         w2c = WEIGHTS.get(w2, cd)
-        # weight gradients feed nothing downstream: when the parameters already own fp32 .grad
-        # buffers they are accumulated in place on the auxiliary stream, under the encoder's
-        # backward pass (side.py); otherwise they are returned to autograd as usual
-        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
-        need = ctx.needs_input_grad[2:6]
-        live = tuple(p for p, n in zip((w1, ctx.b1, w2, ctx.b2), need) if n)
-        defer = bool(live) and config.DEFER_WEIGHT_GRADS and all(_accumulates_in_place(p) for p in live)
-        dw1 = db1 = dw2 = db2 = None
         with ops.timed("joint_dhid_gemm"):
             # dl x W2 with W2^T materialised once per optimiser step (1.3 M elements): both
             # operands K-contiguous -> the direct-to-LDS kernel (gemm_nt.hip)
             dhid = ops.gemm(dl, WEIGHTS.get(w2, cd, transposed=True))
-        if not defer:
-            if need[2]:
-                with ops.timed("joint_dw2_gemm"):
-                    dw2 = ops.gemm(dl.t(), hid2.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
-            if need[3]:
-                db2 = ops.colsum(dl)
         dE1, dD1 = ops.joint_hidden_bwd(dhid.view(B, T, U1, J), hid)
         del dhid
         dE1c = ops.cast(dE1, cd).view(B * T, J)
         dD1c = ops.cast(dD1, cd).view(B * U1, J)
         denc = ops.gemm(dE1c, w1c[:, :P].t()).view(B, T, P)
         ddec = ops.gemm(dD1c, w1c[:, P:].t()).view(B, U1, P2)
-        if defer:
-            # enqueued AFTER the critical-path products above: the auxiliary stream starts when
-            # they are done and its MFMA work runs under the latency-bound recurrences that follow
-            with side.deferred(dl.device, dl, hid, dE1c, dD1c, dD1, enc2, dec2):
-                if need[2]:
-                    ops.gemm(dl.t(), hid2.t(), out=w2.grad, accumulate=True, split_k=8,
-                             max_wg_per_cu=2)
-                if need[3]:
-                    ops.colsum(dl, out=ctx.b2.grad)
-                if need[0]:
-                    g1 = w1.grad
-                    ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
-                             split_k=ops.pick_split_k(J, P, B * T))
-                    ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
-                             split_k=ops.pick_split_k(J, P2, B * U1))
-                if need[1]:
-                    ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
-            _grads_ready(live, dl.device)
-        if not defer:
-            if need[0]:
-                dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
-                ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
-                ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
-            if need[1]:
-                db1 = ops.colsum(dD1.view(B * U1, J))
+        # the weight gradients feed nothing downstream: enqueued AFTER the critical-path products above, so that on the
+        # auxiliary stream (side.py) they start when those are done and their MFMA work runs under the latency-bound
+        # recurrences that follow
+        with side.WeightGrads(ctx, 2, (w1, ctx.b1, w2, ctx.b2), dl, hid, dE1c, dD1c, dD1, enc2, dec2) as wg:
+            wg.gemm(2, dl.t(), hid2.t(), split_k=ops.pick_split_k(V, J, M), aux=dict(split_k=8, max_wg_per_cu=2))
+            wg.colsum(3, dl)
+            wg.gemm(0, dE1c.t(), enc2.t(), cols=slice(None, P), split_k=ops.pick_split_k(J, P, B * T))
+            wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
+            wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return denc, ddec, dw1, db1, dw2, db2, None
+        return (denc, ddec, *wg.grads, None)
 
 
 class _JointLossFn(torch.autograd.Function):
@@ -570,11 +489,6 @@ class _JointLossFn(torch.autograd.Function):
         gscale = gout.contiguous().float()
         w1c = WEIGHTS.get(w1, cd)
         w2t = WEIGHTS.get(w2, cd, transposed=True)
-        # frozen parameters (requires_grad off, .grad kept by FlatParams) get nothing, as plain autograd would do
-        need = ctx.needs_input_grad[2:6]
-        live = tuple(p for p, n in zip((w1, ctx.b1, w2, ctx.b2), need) if n)
-        defer = bool(live) and config.DEFER_WEIGHT_GRADS and all(_accumulates_in_place(p) for p in live)
-        dw1 = db1 = dw2 = db2 = None
         dE1 = torch.empty(B, T, J, dtype=F32, device=dl.device)
         dD1 = torch.empty(B, U1, J, dtype=F32, device=dl.device)
         # (pipelining the loss gradient against the dhid product by utterance groups on two streams was measured:
@@ -596,40 +510,19 @@ class _JointLossFn(torch.autograd.Function):
         with ops.timed("joint_hidden_bwd"):
             _lib.call("joint_hidden_bwd_packed", _lib.dtype_code(cd), dhid, hid, dE1, dD1, al_d, ll_d,
                       off_d, B, T, U1, J)
-        if not defer:
-            if need[2]:
-                dw2 = ops.gemm(dl.t(), hid.t(), out_dtype=F32, split_k=ops.pick_split_k(V, J, M))
-            if need[3]:
-                db2 = ops.colsum(dl if db2_parts is None else db2_parts)
         del dhid
         dE1c = ops.cast(dE1, cd).view(B * T, J)
         dD1c = ops.cast(dD1, cd).view(B * U1, J)
         denc = ops.gemm(dE1c, w1c[:, :P].t()).view(B, T, P)
         ddec = ops.gemm(dD1c, w1c[:, P:].t()).view(B, U1, P2)
-        if defer:
-            with side.deferred(dl.device, dl, hid, dE1c, dD1c, dD1, enc2, dec2, db2_parts):
-                if need[2]:
-                    ops.gemm(dl.t(), hid.t(), out=w2.grad, accumulate=True, split_k=8, max_wg_per_cu=2)
-                if need[3]:
-                    ops.colsum(dl if db2_parts is None else db2_parts, out=ctx.b2.grad)
-                if need[0]:
-                    g1 = w1.grad
-                    ops.gemm(dE1c.t(), enc2.t(), out=g1[:, :P], accumulate=True,
-                             split_k=ops.pick_split_k(J, P, B * T))
-                    ops.gemm(dD1c.t(), dec2.t(), out=g1[:, P:], accumulate=True,
-                             split_k=ops.pick_split_k(J, P2, B * U1))
-                if need[1]:
-                    ops.colsum(dD1.view(B * U1, J), out=ctx.b1.grad)
-            _grads_ready(live, dl.device)
-        else:
-            if need[0]:
-                dw1 = torch.empty(J, P + P2, dtype=F32, device=dl.device)
-                ops.gemm(dE1c.t(), enc2.t(), out=dw1[:, :P], split_k=ops.pick_split_k(J, P, B * T))
-                ops.gemm(dD1c.t(), dec2.t(), out=dw1[:, P:], split_k=ops.pick_split_k(J, P2, B * U1))
-            if need[1]:
-                db1 = ops.colsum(dD1.view(B * U1, J))
+        with side.WeightGrads(ctx, 2, (w1, ctx.b1, w2, ctx.b2), dl, hid, dE1c, dD1c, dD1, enc2, dec2, db2_parts) as wg:
+            wg.gemm(2, dl.t(), hid.t(), split_k=ops.pick_split_k(V, J, M), aux=dict(split_k=8, max_wg_per_cu=2))
+            wg.colsum(3, dl if db2_parts is None else db2_parts)
+            wg.gemm(0, dE1c.t(), enc2.t(), cols=slice(None, P), split_k=ops.pick_split_k(J, P, B * T))
+            wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
+            wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return denc, ddec, dw1, db1, dw2, db2, None, None, None, None, None
+        return (denc, ddec, *wg.grads, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------
