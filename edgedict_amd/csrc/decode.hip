@@ -13,6 +13,8 @@
 // host between frames; token ids and scores stay on the device until the caller reads them.
 #include "common.hpp"
 
+#include <algorithm>
+#include <functional>
 #include <vector>
 
 // decode_fused.hip: a frame as five fused launches (bf16 and fp32)
@@ -307,6 +309,8 @@ struct BeamPtrs {
     int32_t* lens;       // [B]
     int32_t* flags;      // [0] expansion cap hit, [1] node cap hit
     long long* total_exp;// [1]
+    int32_t* root_tok;   // [B] last token of the tree root (node -1); null: BOS (the offline search)
+    long long* stream_exp;// [B] expansions per utterance, or null
 };
 
 // (max, first position) of a workgroup's per-thread candidates: butterfly inside a wave, the four waves through LDS.
@@ -433,7 +437,7 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
             node = nn;
             ref = W + ep;
         }
-        tok = node < 0 ? bos : p.nodes[(size_t)b * NODES + node].y;
+        tok = node < 0 ? (p.root_tok ? p.root_tok[b] : bos) : p.nodes[(size_t)b * NODES + node].y;
         pool[idx] = -INFINITY;
         p.exp_node[b * EM + e] = node;
         p.exp_ref[b * EM + e] = ref;
@@ -516,6 +520,7 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
         p.max_b[b] = mb;
         p.e_count[b] = e + 1;
         atomicAdd((unsigned long long*)p.total_exp, 1ull);
+        if (p.stream_exp) p.stream_exp[b] += 1;
         if (j + 1 >= W && mb >= amax) {
             p.open[b] = 0;
         } else if (e + 1 >= EM) {
@@ -672,6 +677,155 @@ inline BeamWs beam_layout(int esz, int B, int T, int J, int V, int E, int L, int
     return w;
 }
 
+
+// The arguments of one search call: weights and shapes as edgedict_beam_search takes them ...
+struct BeamNet {
+    int dtype, esz;
+    const void* E1;
+    long long e_row_stride, e_frame_stride;
+    int B, J;
+    const void* W1d;
+    long long ldw1;
+    const float* b1;
+    int P2;
+    const void* W2;
+    const float* b2;
+    int V;
+    const void* emb;
+    int emb_dtype, E, L;
+    const void* const* w_ih;
+    const void* const* w_hh;
+    const float* const* b_ih;
+    const float* const* b_hh;
+    int H;
+    const void* Wp;
+    const float* bp;
+    int blank, bos, W, EM, NODES;
+};
+// ... and the per-iteration buffers of the prediction-network step and the joint
+struct BeamBufs {
+    void *D1, *hid;
+    float* logits;
+    int32_t* pred;
+    void *x, *G, *Hprev, *Y[2];
+    float *Cst, *h_new, *c_new;
+    void* dec_new;
+    float *h_state, *c_state;
+    void* node_pred;
+};
+
+// The frame loop shared by the offline search and the streaming one: frames [0, maxlen), utterance b taking part in
+// frames t < lens[b]; per frame: frame begin -> lockstep pop / step / expand iterations -> frame end.  The survivors'
+// states alternate between bp_h/bp_c[0] and [1], starting in [0]: after the loop utterance b's are in [lens[b] & 1].
+// prefix = 1: `prefix_merge(t, E1 of frame t)` runs the host list logic before every frame after the first.
+int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, int maxlen, int prefix,
+                    const std::function<int(int, const char*)>& prefix_merge, hipStream_t s) {
+    const int dtype = net.dtype, esz = net.esz, B = net.B, J = net.J, P2 = net.P2, V = net.V, emb_dtype = net.emb_dtype,
+              E = net.E, L = net.L, H = net.H, blank = net.blank, bos = net.bos, W = net.W, EM = net.EM,
+              NODES = net.NODES;
+    const void* E1 = net.E1;
+    const long long e_row_stride = net.e_row_stride, e_frame_stride = net.e_frame_stride, ldw1 = net.ldw1;
+    const void *W1d = net.W1d, *W2 = net.W2, *emb = net.emb, *Wp = net.Wp;
+    const float *b1 = net.b1, *b2 = net.b2, *bp = net.bp;
+    const void* const* w_ih = net.w_ih;
+    const void* const* w_hh = net.w_hh;
+    const float* const* b_ih = net.b_ih;
+    const float* const* b_hh = net.b_hh;
+    void *D1 = u.D1, *hid = u.hid, *x = u.x, *G = u.G, *Hprev = u.Hprev, *dec_new = u.dec_new, *node_pred = u.node_pred;
+    void* const* Y = u.Y;
+    float *logits = u.logits, *Cst = u.Cst, *h_new = u.h_new, *c_new = u.c_new, *h_state = u.h_state,
+          *c_state = u.c_state;
+    int32_t* pred = u.pred;
+    std::vector<int32_t> open_h(B);
+    const bool fused_step = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    int cur = 0;
+    for (int t = 0; t < maxlen; ++t) {
+        const char* e1t = (const char*)E1 + (size_t)t * e_frame_stride * esz;
+        if (prefix && t > 0) {
+            const int rc = prefix_merge(t, e1t);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, EM, V);
+        for (int it = 0;; ++it) {
+            int rc;
+            hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, V, EM, L, H, B, NODES,
+                               bos, pred, h_state, c_state);
+            if (fused_step) {
+                // prediction-network step + projection + joint hidden + logits as 3 + L fused launches (decode_fused.hip)
+                if ((rc = ed_decode_fused_beam_step(dtype, e1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
+                                                    emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, h_state, c_state,
+                                                    pred, dec_new, hid, logits, h_new, c_new, Y[0], Y[1], s)))
+                    return rc;
+                if (prefix) {
+                    if (dtype == ED_F32)
+                        hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
+                                           (float*)node_pred, EM, NODES, P2);
+                    else
+                        hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
+                                           (bf16_t*)node_pred, EM, NODES, P2);
+                }
+                hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V, EM, L, H, B,
+                                   blank);
+            } else {
+            // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132)
+            if ((rc = edgedict_embedding_fwd(dtype, emb_dtype, pred, 1, emb, x, B, 1, E, V, 0, 0, s)))
+                return rc;
+            const void* xin = x;
+            int xin_dim = E;
+            for (int k = 0; k < L; ++k) {
+                if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, w_ih[k], xin_dim, 1, G, 4 * H,
+                                        B, 4 * H, xin_dim, b_ih[k], b_hh[k], 0, 1, s)))
+                    return rc;
+                if ((rc = edgedict_lstm_forward(dtype, G, Hprev, Y[k & 1], Cst, w_hh[k], nullptr,
+                                                h_state + (size_t)k * B * H, c_state + (size_t)k * B * H,
+                                                h_new + (size_t)k * B * H, c_new + (size_t)k * B * H,
+                                                B, 1, H, nullptr, s)))
+                    return rc;
+                xin = Y[k & 1];
+                xin_dim = H;
+            }
+            if ((rc = edgedict_gemm(dtype, dtype, xin, H, 1, Wp, H, 1, dec_new, P2, B, P2, H, bp,
+                                    nullptr, 0, 1, s)))
+                return rc;
+            if (prefix) {        // Sequence.g of the children (models.py:183): this expansion's prediction, kept per node
+                if (dtype == ED_F32)
+                    hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
+                                       (float*)node_pred, EM, NODES, P2);
+                else
+                    hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
+                                       (bf16_t*)node_pred, EM, NODES, P2);
+            }
+            // joint(x_t, pred) (models.py:165): D1 = pred W1d^T + b1; hid = tanh(E1[:,t] + D1); logits
+            if ((rc = edgedict_gemm(dtype, dtype, dec_new, P2, 1, W1d, ldw1, 1, D1, J, B, J, P2, b1,
+                                    nullptr, 0, 1, s)))
+                return rc;
+            if (dtype == ED_F32)
+                hipLaunchKernelGGL(add_tanh_rows<float>, dim3(ed_grid_for((long long)B * J, 256)),
+                                   dim3(256), 0, s, (const float*)e1t, e_row_stride,
+                                   (const float*)D1, (float*)hid, B, J);
+            else
+                hipLaunchKernelGGL(add_tanh_rows<bf16_t>, dim3(ed_grid_for((long long)B * J, 256)),
+                                   dim3(256), 0, s, (const bf16_t*)e1t, e_row_stride,
+                                   (const bf16_t*)D1, (bf16_t*)hid, B, J);
+            if ((rc = edgedict_gemm(dtype, ED_F32, hid, J, 1, W2, J, 1, logits, V, B, V, J, b2,
+                                    nullptr, 0, 1, s)))
+                return rc;
+            hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V,
+                               EM, L, H, B, blank);
+            }
+            if (it + 1 >= W) {   // B cannot hold W hypotheses before W expansions
+                ED_CHECK_HIP(hipMemcpyAsync(open_h.data(), q.open, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+                ED_CHECK_HIP(hipStreamSynchronize(s));
+                int any = 0;
+                for (int b = 0; b < B; ++b) any |= open_h[b];
+                if (!any) break;
+            }
+        }
+        hipLaunchKernelGGL(beam_frame_end, dim3(B), dim3(256), 0, s, q, t, cur, W, EM, L, H);
+        cur ^= 1;
+    }
+    return ED_OK;
+}
 }  // namespace
 
 extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
@@ -743,6 +897,8 @@ extern "C" int edgedict_beam_search(
     q.lens = (int32_t*)(p + w.lens);
     q.flags = (int32_t*)(p + w.flags);
     q.total_exp = (long long*)(p + w.total_exp);
+    q.root_tok = nullptr;
+    q.stream_exp = nullptr;
 
     const size_t LH = (size_t)L * H;
     ED_CHECK_HIP(hipMemcpyAsync(q.lens, lens_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
@@ -754,7 +910,6 @@ extern "C" int edgedict_beam_search(
     ED_CHECK_HIP(hipMemsetAsync(c_state, 0, (size_t)B * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(pred, 0, (size_t)B * 4, s));
     hipLaunchKernelGGL(beam_init, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W);
-    std::vector<int32_t> open_h(B);
     int maxlen = 0;
     for (int b = 0; b < B; ++b) maxlen = lens_host[b] > maxlen ? lens_host[b] : maxlen;
 
@@ -879,92 +1034,13 @@ extern "C" int edgedict_beam_search(
         return ED_OK;
     };
 
-    const bool fused_step = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
-    int cur = 0;
-    for (int t = 0; t < maxlen; ++t) {
-        const char* e1t = (const char*)E1 + (size_t)t * e_frame_stride * esz;
-        if (prefix && t > 0) {
-            const int rc = prefix_merge(t, e1t);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, EM, V);
-        for (int it = 0;; ++it) {
-            int rc;
-            hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, V, EM, L, H, B, NODES,
-                               bos, pred, h_state, c_state);
-            if (fused_step) {
-                // prediction-network step + projection + joint hidden + logits as 3 + L fused launches (decode_fused.hip)
-                if ((rc = ed_decode_fused_beam_step(dtype, e1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
-                                                    emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, h_state, c_state,
-                                                    pred, dec_new, hid, logits, h_new, c_new, Y[0], Y[1], s)))
-                    return rc;
-                if (prefix) {
-                    if (dtype == ED_F32)
-                        hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
-                                           (float*)node_pred, EM, NODES, P2);
-                    else
-                        hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
-                                           (bf16_t*)node_pred, EM, NODES, P2);
-                }
-                hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V, EM, L, H, B,
-                                   blank);
-            } else {
-            // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132)
-            if ((rc = edgedict_embedding_fwd(dtype, emb_dtype, pred, 1, emb, x, B, 1, E, V, 0, 0, s)))
-                return rc;
-            const void* xin = x;
-            int xin_dim = E;
-            for (int k = 0; k < L; ++k) {
-                if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, w_ih[k], xin_dim, 1, G, 4 * H,
-                                        B, 4 * H, xin_dim, b_ih[k], b_hh[k], 0, 1, s)))
-                    return rc;
-                if ((rc = edgedict_lstm_forward(dtype, G, Hprev, Y[k & 1], Cst, w_hh[k], nullptr,
-                                                h_state + (size_t)k * B * H, c_state + (size_t)k * B * H,
-                                                h_new + (size_t)k * B * H, c_new + (size_t)k * B * H,
-                                                B, 1, H, nullptr, s)))
-                    return rc;
-                xin = Y[k & 1];
-                xin_dim = H;
-            }
-            if ((rc = edgedict_gemm(dtype, dtype, xin, H, 1, Wp, H, 1, dec_new, P2, B, P2, H, bp,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            if (prefix) {        // Sequence.g of the children (models.py:183): this expansion's prediction, kept per node
-                if (dtype == ED_F32)
-                    hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
-                                       (float*)node_pred, EM, NODES, P2);
-                else
-                    hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
-                                       (bf16_t*)node_pred, EM, NODES, P2);
-            }
-            // joint(x_t, pred) (models.py:165): D1 = pred W1d^T + b1; hid = tanh(E1[:,t] + D1); logits
-            if ((rc = edgedict_gemm(dtype, dtype, dec_new, P2, 1, W1d, ldw1, 1, D1, J, B, J, P2, b1,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            if (dtype == ED_F32)
-                hipLaunchKernelGGL(add_tanh_rows<float>, dim3(ed_grid_for((long long)B * J, 256)),
-                                   dim3(256), 0, s, (const float*)e1t, e_row_stride,
-                                   (const float*)D1, (float*)hid, B, J);
-            else
-                hipLaunchKernelGGL(add_tanh_rows<bf16_t>, dim3(ed_grid_for((long long)B * J, 256)),
-                                   dim3(256), 0, s, (const bf16_t*)e1t, e_row_stride,
-                                   (const bf16_t*)D1, (bf16_t*)hid, B, J);
-            if ((rc = edgedict_gemm(dtype, ED_F32, hid, J, 1, W2, J, 1, logits, V, B, V, J, b2,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V,
-                               EM, L, H, B, blank);
-            }
-            if (it + 1 >= W) {   // B cannot hold W hypotheses before W expansions
-                ED_CHECK_HIP(hipMemcpyAsync(open_h.data(), q.open, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-                ED_CHECK_HIP(hipStreamSynchronize(s));
-                int any = 0;
-                for (int b = 0; b < B; ++b) any |= open_h[b];
-                if (!any) break;
-            }
-        }
-        hipLaunchKernelGGL(beam_frame_end, dim3(B), dim3(256), 0, s, q, t, cur, W, EM, L, H);
-        cur ^= 1;
+    const BeamNet net{dtype, esz, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype,
+                      E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, EM, NODES};
+    const BeamBufs bufs{D1, hid, logits, pred, x, G, Hprev, {Y[0], Y[1]}, Cst, h_new, c_new, dec_new, h_state, c_state,
+                        node_pred};
+    {
+        const int rc = beam_frame_loop(net, bufs, q, maxlen, prefix, prefix_merge, s);
+        if (rc) return rc;
     }
     ED_CHECK_LAUNCH("beam_search");
     // results: B[0] of the last frame (models.py:201-202), token tree walked on the host
@@ -993,6 +1069,420 @@ extern "C" int edgedict_beam_search(
         ED_CHECK_ARG(len <= max_tokens, "beam_search: hypothesis of %d tokens exceeds max_tokens = %d", len, max_tokens);
         for (int i = 0; i < len; ++i) tokens_host[(size_t)b * max_tokens + i] = rev[len - 1 - i];
         score_host[b] = -logp[(size_t)b * W];
+    }
+    return ED_OK;
+}
+
+
+// =====================================================================================
+// Streaming beam search: the frame loop above over a persistent per-stream state, so that frames [0, t1) and then
+// [t1, t2) give exactly what one offline call over [0, t2) gives (the reference's search is frame-synchronous and
+// carries nothing from frame to frame but its list B).  After every advance each stream's token tree is compacted
+// (beam_compact): nodes that are no ancestor of a survivor are dropped, the path from the root to the survivors' lowest
+// common ancestor moves to the caller's committed log, and that ancestor becomes the new root (node -1, its token kept
+// in root_tok).  The tree then holds only the part where the survivors still differ.
+// =====================================================================================
+namespace {
+
+// persistent state, per stream
+struct BeamStreamState {
+    size_t bp_logp, bp_node, n_bp, bp_h, bp_c, nodes, n_nodes, root_tok, n_committed, n_exp, total;
+};
+inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int NC) {
+    BeamStreamState w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    const size_t LH = (size_t)L * H;
+    w.bp_logp = take((size_t)S * W * 8);
+    w.bp_node = take((size_t)S * W * 4);
+    w.n_bp = take((size_t)S * 4);
+    w.bp_h = take((size_t)S * W * LH * 4);
+    w.bp_c = take((size_t)S * W * LH * 4);
+    w.nodes = take((size_t)S * NC * 8);
+    w.n_nodes = take((size_t)S * 4);
+    w.root_tok = take((size_t)S * 4);
+    w.n_committed = take((size_t)S * 8);
+    w.n_exp = take((size_t)S * 8);
+    w.total = o;
+    return w;
+}
+
+// per-call workspace: the frame loop's buffers (BeamWs without the state) and the compaction's scratch
+struct BeamStreamWs {
+    Ws step;
+    size_t h_state, c_state;
+    size_t pool, bp_h1, bp_c1, bn_logp, bn_node, bn_ref, n_b, max_b, blk_max, blk_arg, exp_node, exp_ref, exp_logp,
+        e_count, f_h, f_c, open, lens, flags, total_exp, c_old, c_mark, commit, n_commit, total;
+};
+inline BeamStreamWs beam_stream_ws_layout(int esz, int S, int J, int V, int E, int L, int H, int P2, int W, int EM,
+                                          int NC) {
+    BeamStreamWs w;
+    w.step = ws_layout(esz, S, J, V, E, L, H, P2);
+    size_t o = w.step.total;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    const size_t LH = (size_t)L * H;
+    w.h_state = take((size_t)S * LH * 4);
+    w.c_state = take((size_t)S * LH * 4);
+    w.pool = take((size_t)S * (W + (size_t)EM * V) * 8);
+    w.bp_h1 = take((size_t)S * W * LH * 4);
+    w.bp_c1 = take((size_t)S * W * LH * 4);
+    w.bn_logp = take((size_t)S * W * 8);
+    w.bn_node = take((size_t)S * W * 4);
+    w.bn_ref = take((size_t)S * W * 4);
+    w.n_b = take((size_t)S * 4);
+    w.max_b = take((size_t)S * 8);
+    w.blk_max = take((size_t)S * (EM + 1) * 8);
+    w.blk_arg = take((size_t)S * (EM + 1) * 4);
+    w.exp_node = take((size_t)S * EM * 4);
+    w.exp_ref = take((size_t)S * EM * 4);
+    w.exp_logp = take((size_t)S * EM * 8);
+    w.e_count = take((size_t)S * 4);
+    w.f_h = take((size_t)S * EM * LH * 4);
+    w.f_c = take((size_t)S * EM * LH * 4);
+    w.open = take((size_t)S * 4);
+    w.lens = take((size_t)S * 4);
+    w.flags = take(8);
+    w.total_exp = take(8);
+    w.c_old = take((size_t)S * NC * 8);
+    w.c_mark = take((size_t)S * NC * 4);
+    w.commit = take((size_t)S * NC * 4);
+    w.n_commit = take((size_t)S * 4);
+    w.total = o;
+    return w;
+}
+
+BeamPtrs beam_stream_ptrs(char* st, const BeamStreamState& a, char* ws, const BeamStreamWs& w) {
+    BeamPtrs q;
+    q.pool = (double*)(ws + w.pool);
+    q.bp_logp = (double*)(st + a.bp_logp);
+    q.bp_node = (int32_t*)(st + a.bp_node);
+    q.n_bp = (int32_t*)(st + a.n_bp);
+    q.bp_h[0] = (float*)(st + a.bp_h); q.bp_h[1] = (float*)(ws + w.bp_h1);
+    q.bp_c[0] = (float*)(st + a.bp_c); q.bp_c[1] = (float*)(ws + w.bp_c1);
+    q.bn_logp = (double*)(ws + w.bn_logp);
+    q.bn_node = (int32_t*)(ws + w.bn_node);
+    q.bn_ref = (int32_t*)(ws + w.bn_ref);
+    q.n_b = (int32_t*)(ws + w.n_b);
+    q.max_b = (double*)(ws + w.max_b);
+    q.blk_max = (double*)(ws + w.blk_max);
+    q.blk_arg = (int32_t*)(ws + w.blk_arg);
+    q.exp_node = (int32_t*)(ws + w.exp_node);
+    q.exp_ref = (int32_t*)(ws + w.exp_ref);
+    q.exp_logp = (double*)(ws + w.exp_logp);
+    q.e_count = (int32_t*)(ws + w.e_count);
+    q.f_h = (float*)(ws + w.f_h);
+    q.f_c = (float*)(ws + w.f_c);
+    q.nodes = (int2*)(st + a.nodes);
+    q.n_nodes = (int32_t*)(st + a.n_nodes);
+    q.open = (int32_t*)(ws + w.open);
+    q.lens = (int32_t*)(ws + w.lens);
+    q.flags = (int32_t*)(ws + w.flags);
+    q.total_exp = (long long*)(ws + w.total_exp);
+    q.root_tok = (int32_t*)(st + a.root_tok);
+    q.stream_exp = (long long*)(st + a.n_exp);
+    return q;
+}
+
+// streams [b0, b0 + n) with mask[b] != 0 (mask null: all) -> B = [empty hypothesis]: one survivor, logp 0, node -1
+// with BOS as its last token, zero prediction-network state; empty tree and committed log
+__global__ __launch_bounds__(256) void beam_stream_reset_kernel(BeamPtrs p, long long* n_committed,
+                                                                const int32_t* __restrict__ mask, int b0, int W, int L,
+                                                                int H, int bos) {
+    const int b = b0 + blockIdx.x, tid = threadIdx.x;
+    if (mask && !mask[b]) return;
+    const size_t n = (size_t)W * L * H;
+    float* h = p.bp_h[0] + (size_t)b * n;
+    float* c = p.bp_c[0] + (size_t)b * n;
+    for (size_t i = tid; i < n; i += 256) { h[i] = 0.f; c[i] = 0.f; }
+    if (tid == 0) {
+        p.n_bp[b] = 1;
+        p.bp_logp[(size_t)b * W] = 0.0;
+        p.bp_node[(size_t)b * W] = -1;
+        p.n_nodes[b] = 0;
+        p.root_tok[b] = bos;
+        n_committed[b] = 0;
+        p.stream_exp[b] = 0;
+    }
+}
+
+// the frame loop leaves the survivors' states of a stream that ran an odd number of frames in bp_h/bp_c[1] (workspace):
+// move them home
+__global__ __launch_bounds__(256) void beam_stream_settle(BeamPtrs p, int W, int L, int H) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (!(p.lens[b] & 1)) return;
+    const size_t LH = (size_t)L * H, n = (size_t)p.n_bp[b] * LH, o = (size_t)b * W * LH;
+    for (size_t i = tid; i < n; i += 256) {
+        p.bp_h[0][o + i] = p.bp_h[1][o + i];
+        p.bp_c[0][o + i] = p.bp_c[1][o + i];
+    }
+}
+
+constexpr int BEAM_COMPACT_LDS_NODES = 4096;    // trees up to this capacity walk their parent links in LDS (32 KiB)
+
+// One workgroup per stream that ran frames in this advance.
+//  1. the old tree is copied aside (c_old) and the parent links staged in LDS when they fit;
+//  2. one thread marks the ancestors of the survivors, survivor by survivor; a walk stops at the first node already
+//     marked (or the root), so the whole pass touches every live node once.  Node ids grow from parent to child, and
+//     the union of the walks so far is the chain root .. LCA plus branches below the LCA (ids > LCA), so a walk that
+//     stops at a node with id <= the current LCA stopped ON the chain, at the new LCA: LCA = min(node of survivor 0,
+//     stop node of every later walk), by node identity;
+//  3. the path root .. LCA is appended to the committed log (commit[b][0, n_commit[b])) and the LCA becomes the root;
+//  4. the nodes below the LCA that are marked are renumbered by an exclusive scan (order kept, so parents still precede
+//     their children), written back with rewritten parent links, and the survivors' node ids remapped.
+__global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, int use_lds, int2* __restrict__ c_old,
+                                                    int32_t* __restrict__ c_mark, int32_t* __restrict__ commit,
+                                                    int32_t* __restrict__ n_commit, long long* __restrict__ n_committed) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    extern __shared__ int s_dyn[];
+    __shared__ int s_scan[256];
+    __shared__ int s_lca;
+    if (p.lens[b] <= 0) {
+        if (tid == 0) n_commit[b] = 0;
+        return;
+    }
+    const int nn = p.n_nodes[b];
+    int2* old = c_old + (size_t)b * NC;
+    int2* tree = p.nodes + (size_t)b * NC;
+    int* mark = use_lds ? s_dyn : c_mark + (size_t)b * NC;
+    int* spar = use_lds ? s_dyn + NC : nullptr;
+    for (int i = tid; i < nn; i += 256) {
+        const int2 v = tree[i];
+        old[i] = v;
+        mark[i] = 0;
+        if (use_lds) spar[i] = v.x;
+    }
+    __syncthreads();
+    const int nb = p.n_bp[b];
+    if (tid == 0) {
+        int lca = p.bp_node[(size_t)b * W];
+        for (int j = 0; j < nb; ++j) {
+            int x = p.bp_node[(size_t)b * W + j];
+            while (x >= 0 && !mark[x]) {
+                mark[x] = 1;
+                x = use_lds ? spar[x] : old[x].x;
+            }
+            if (j > 0) lca = min(lca, x);
+        }
+        // the committed tokens: root .. LCA, written last to first
+        int d = 0;
+        for (int x = lca; x >= 0; x = use_lds ? spar[x] : old[x].x) ++d;
+        int k = d;
+        for (int x = lca; x >= 0; x = use_lds ? spar[x] : old[x].x) commit[(size_t)b * NC + --k] = old[x].y;
+        n_commit[b] = d;
+        n_committed[b] += d;
+        if (lca >= 0) p.root_tok[b] = old[lca].y;
+        s_lca = lca;
+    }
+    __syncthreads();
+    const int lca = s_lca;
+    // exclusive scan of keep[i] = mark[i] && i > lca over contiguous per-thread ranges
+    const int per = (nn + 255) / 256, lo = min(nn, tid * per), hi = min(nn, lo + per);
+    int cnt = 0;
+    for (int i = lo; i < hi; ++i) cnt += (mark[i] && i > lca) ? 1 : 0;
+    s_scan[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = tid >= off ? s_scan[tid - off] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    int k = s_scan[tid] - cnt;
+    const int kept = s_scan[255];
+    for (int i = lo; i < hi; ++i) mark[i] = (mark[i] && i > lca) ? k++ : -1;     // mark -> new id (-1: dropped)
+    __syncthreads();
+    for (int i = tid; i < nn; i += 256) {
+        const int ni = mark[i];
+        if (ni < 0) continue;
+        const int2 v = old[i];
+        tree[ni] = make_int2(v.x == lca ? -1 : mark[v.x], v.y);
+    }
+    if (tid < nb) {
+        const int x = p.bp_node[(size_t)b * W + tid];
+        p.bp_node[(size_t)b * W + tid] = x == lca ? -1 : mark[x];
+    }
+    if (tid == 0) p.n_nodes[b] = kept;
+}
+
+}  // namespace
+
+extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
+                                                   int max_expansions, int node_capacity) {
+    (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
+    if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
+    return beam_stream_state_layout(S, L, H, W, node_capacity).total;
+}
+
+extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                       int W, int max_expansions, int node_capacity) {
+    if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
+    return beam_stream_ws_layout(dtype == ED_F32 ? 4 : 2, S, J, V, E, L, H, P2, W, max_expansions, node_capacity).total;
+}
+
+extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                          int mask_on_host, void* state, void* stream_) {
+    ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0, "beam_stream_reset: bad shape");
+    ED_CHECK_ARG(state, "beam_stream_reset: null state");
+    hipStream_t s = (hipStream_t)stream_;
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity);
+    char* st = (char*)state;
+    BeamPtrs q{};
+    q.bp_logp = (double*)(st + a.bp_logp);
+    q.bp_node = (int32_t*)(st + a.bp_node);
+    q.n_bp = (int32_t*)(st + a.n_bp);
+    q.bp_h[0] = (float*)(st + a.bp_h);
+    q.bp_c[0] = (float*)(st + a.bp_c);
+    q.n_nodes = (int32_t*)(st + a.n_nodes);
+    q.root_tok = (int32_t*)(st + a.root_tok);
+    q.stream_exp = (long long*)(st + a.n_exp);
+    long long* n_committed = (long long*)(st + a.n_committed);
+    if (!mask || !mask_on_host) {
+        hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, n_committed, mask, 0, W, L, H, bos);
+    } else {            // host mask: one launch per run of selected streams
+        for (int b = 0; b < S;) {
+            if (!mask[b]) { ++b; continue; }
+            int e = b;
+            while (e < S && mask[e]) ++e;
+            hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(e - b), dim3(256), 0, s, q, n_committed,
+                               (const int32_t*)nullptr, b, W, L, H, bos);
+            b = e;
+        }
+    }
+    ED_CHECK_LAUNCH("beam_stream_reset");
+    return ED_OK;
+}
+
+extern "C" int edgedict_beam_stream_advance(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+    long long* expansions_host, void* state, void* workspace, void* stream_) {
+    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "beam_stream_advance: bad dtype");
+    ED_CHECK_ARG(S > 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0 && W > 0 && max_expansions >= W &&
+                     node_capacity > 0,
+                 "beam_stream_advance: bad shape (max_expansions must be >= W)");
+    ED_CHECK_ARG(W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp && bp && n_frames_host &&
+                     commit_host && ncommit_host && state && workspace,
+                 "beam_stream_advance: null pointer");
+    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "beam_stream_advance: blank/bos outside the vocabulary");
+    int maxlen = 0;
+    for (int b = 0; b < S; ++b) {
+        ED_CHECK_ARG(n_frames_host[b] >= 0, "beam_stream_advance: n_frames[%d] = %d < 0", b, n_frames_host[b]);
+        maxlen = std::max(maxlen, n_frames_host[b]);
+    }
+    ED_CHECK_ARG(maxlen == 0 || E1, "beam_stream_advance: null E1");
+    hipStream_t s = (hipStream_t)stream_;
+    const int esz = dtype == ED_F32 ? 4 : 2, EM = max_expansions, NC = node_capacity;
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC);
+    const BeamStreamWs w = beam_stream_ws_layout(esz, S, J, V, E, L, H, P2, W, EM, NC);
+    char* st = (char*)state;
+    char* p = (char*)workspace;
+    BeamPtrs q = beam_stream_ptrs(st, a, p, w);
+    for (int b = 0; b < S; ++b) ncommit_host[b] = 0;
+    if (expansions_host) *expansions_host = 0;
+    if (maxlen == 0) return ED_OK;
+
+    // every node a pop can create must fit: checked before anything runs, so an error leaves the state as it was
+    std::vector<int32_t> nn(S);
+    ED_CHECK_HIP(hipMemcpyAsync(nn.data(), q.n_nodes, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < S; ++b) {
+        const long long need = (long long)nn[b] + (long long)n_frames_host[b] * EM;
+        ED_CHECK_ARG(n_frames_host[b] == 0 || need <= NC,
+                     "beam_stream_advance: stream %d may need %lld token-tree nodes (%d live + %d frames x "
+                     "max_expansions %d) but node_capacity = %d",
+                     b, need, nn[b], n_frames_host[b], EM, NC);
+    }
+
+    const BeamBufs bufs{p + w.step.D1, p + w.step.hid, (float*)(p + w.step.logits), (int32_t*)(p + w.step.pred),
+                        p + w.step.x, p + w.step.G, p + w.step.Hprev, {p + w.step.Y0, p + w.step.Y1},
+                        (float*)(p + w.step.Cst), (float*)(p + w.step.h_new), (float*)(p + w.step.c_new),
+                        p + w.step.dec_new, (float*)(p + w.h_state), (float*)(p + w.c_state), nullptr};
+    const size_t LH = (size_t)L * H;
+    ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
+    // rows of finished / not yet popped streams flow through the step kernels: keep them finite
+    ED_CHECK_HIP(hipMemsetAsync(bufs.h_state, 0, (size_t)S * LH * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(bufs.c_state, 0, (size_t)S * LH * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(bufs.pred, 0, (size_t)S * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(q.flags, 0, 8, s));
+    ED_CHECK_HIP(hipMemsetAsync(q.total_exp, 0, 8, s));
+    const BeamNet net{dtype, esz, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype,
+                      E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, EM, NC};
+    {
+        const int rc = beam_frame_loop(net, bufs, q, maxlen, 0, [](int, const char*) { return (int)ED_OK; }, s);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(beam_stream_settle, dim3(S), dim3(256), 0, s, q, W, L, H);
+    const int use_lds = NC <= BEAM_COMPACT_LDS_NODES;
+    int32_t* commit = (int32_t*)(p + w.commit);
+    int32_t* n_commit = (int32_t*)(p + w.n_commit);
+    hipLaunchKernelGGL(beam_compact, dim3(S), dim3(256), use_lds ? (size_t)NC * 8 : 0, s, q, W, NC, use_lds,
+                       (int2*)(p + w.c_old), (int32_t*)(p + w.c_mark), commit, n_commit,
+                       (long long*)(st + a.n_committed));
+    ED_CHECK_LAUNCH("beam_stream_advance");
+    int32_t flags[2];
+    long long total = 0;
+    ED_CHECK_HIP(hipMemcpyAsync(flags, q.flags, 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(&total, q.total_exp, 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(ncommit_host, n_commit, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    ED_CHECK_ARG(!flags[0], "beam_stream_advance: a stream needed more than max_expansions = %d expansions in one frame",
+                 EM);
+    ED_CHECK_ARG(!flags[1], "beam_stream_advance: token tree overflow (node_capacity = %d)", NC);
+    if (expansions_host) *expansions_host = total;
+    int maxc = 0;
+    for (int b = 0; b < S; ++b) maxc = std::max(maxc, ncommit_host[b]);
+    if (maxc > 0) {
+        ED_CHECK_HIP(hipMemcpy2DAsync(commit_host, (size_t)NC * 4, commit, (size_t)NC * 4, (size_t)maxc * 4, (size_t)S,
+                                      hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    return ED_OK;
+}
+
+extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, const void* state,
+                                         int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+                                         double* score_host, long long* ncommitted_host, long long* expansions_host,
+                                         void* stream_) {
+    ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0 && max_tokens >= 0,
+                 "beam_stream_read: bad shape");
+    ED_CHECK_ARG(state && tokens_host && ntokens_host && score_host, "beam_stream_read: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    const int NC = node_capacity;
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC);
+    const char* st = (const char*)state;
+    std::vector<double> logp((size_t)S * W);
+    std::vector<int32_t> node((size_t)S * W), nn(S);
+    std::vector<long long> ncom(S), nexp(S);
+    ED_CHECK_HIP(hipMemcpyAsync(logp.data(), st + a.bp_logp, logp.size() * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(node.data(), st + a.bp_node, node.size() * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(nn.data(), st + a.n_nodes, nn.size() * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(ncom.data(), st + a.n_committed, ncom.size() * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(nexp.data(), st + a.n_exp, nexp.size() * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    int maxnn = 0;
+    for (int b = 0; b < S; ++b) maxnn = std::max(maxnn, nn[b]);
+    std::vector<int2> nodes((size_t)S * std::max(maxnn, 1));
+    if (maxnn > 0) {
+        ED_CHECK_HIP(hipMemcpy2DAsync(nodes.data(), (size_t)maxnn * 8, st + a.nodes, (size_t)NC * 8, (size_t)maxnn * 8,
+                                      (size_t)S, hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    std::vector<int32_t> rev;
+    for (int b = 0; b < S; ++b) {
+        rev.clear();
+        for (int n = node[(size_t)b * W]; n >= 0; n = nodes[(size_t)b * maxnn + n].x)
+            rev.push_back(nodes[(size_t)b * maxnn + n].y);
+        const int len = (int)rev.size();
+        ntokens_host[b] = len;
+        ED_CHECK_ARG(len <= max_tokens, "beam_stream_read: hypothesis tail of %d tokens exceeds max_tokens = %d", len,
+                     max_tokens);
+        for (int i = 0; i < len; ++i) tokens_host[(size_t)b * max_tokens + i] = rev[len - 1 - i];
+        score_host[b] = -logp[(size_t)b * W];
+        if (ncommitted_host) ncommitted_host[b] = ncom[b];
+        if (expansions_host) expansions_host[b] = nexp[b];
     }
     return ED_OK;
 }

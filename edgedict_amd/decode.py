@@ -7,7 +7,9 @@ symbol is not blank; blanks stay in the returned sequences, which are truncated 
 (un-scaled) ``xlen``; the score is ``-sum_t max log p``.
 
 ``beam_search_batch`` is the reference's legacy ``Transducer.beam_search`` (models.py:121-202,
-``prefix=False``) for a batch of utterances in lockstep (csrc/decode.hip, second half).
+``prefix=False``) for a batch of utterances in lockstep (csrc/decode.hip, second half);
+``beam_search_enc`` is the same search over a given encoder output, and ``StreamingBeamSearch`` runs it over
+encoder output that arrives chunk by chunk, carrying the beams from chunk to chunk.
 """
 import ctypes
 
@@ -106,54 +108,257 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     utterance the FIRST hypothesis of the last frame's B list, which is what the reference returns
     (its ``sorted`` calls are no-ops).  ``max_expansions`` bounds the pops per utterance and frame
     (default 8 W, at least 16); hitting it raises instead of truncating the search."""
-    from .models import WEIGHTS
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
     enc_out, _ = model.encoder(xs)
     enc_out = enc_out.contiguous()
-    cd = enc_out.dtype
     B, T, P = enc_out.shape
     if xlen is None:
-        lens = np.full(B, T, dtype=np.int32)
+        lens = None
     else:
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
+    return beam_search_enc(model, enc_out, lens, W, max_expansions, prefix)
+
+
+class _BeamNet:
+    """The prediction network's and the joint's weights in the compute dtype ``cd`` (converted once through
+    ``WEIGHTS``) with the shapes and ctypes arguments the native beam searches take."""
+
+    def __init__(self, model, cd):
+        from .models import WEIGHTS
+        dec = model.decoder
+        l1, l2 = model.joint.joint[0], model.joint.joint[2]
+        self.J, self.V = l1.weight.shape[0], l2.weight.shape[0]
+        self.P2 = dec.proj.weight.shape[0]
+        self.L, self.H = dec.lstm.num_layers, dec.lstm.hidden_size
+        self.E = dec.embed.weight.shape[1]
+        self.w1c = WEIGHTS.get(l1.weight, cd)
+        self.w2c = WEIGHTS.get(l2.weight, cd)
+        self.wpc = WEIGHTS.get(dec.proj.weight, cd)
+        self.w_ih = [WEIGHTS.get(dec.lstm.layer(k)[0], cd) for k in range(self.L)]
+        self.w_hh = [WEIGHTS.get(dec.lstm.layer(k)[1], cd) for k in range(self.L)]
+        self.b_ih = [dec.lstm.layer(k)[2].detach() for k in range(self.L)]
+        self.b_hh = [dec.lstm.layer(k)[3].detach() for k in range(self.L)]
+        self.b1, self.b2 = l1.bias.detach(), l2.bias.detach()
+        self.emb, self.bp = dec.embed.weight.detach(), dec.proj.bias.detach()
+        self.cd = cd
+
+    def e1(self, enc_out):
+        """The encoder half of the joint's first Linear for all frames of ``enc_out`` [B, T, P] at once: [B * T, J]."""
+        B, T, P = enc_out.shape
+        return ops.gemm(enc_out.reshape(B * T, P), self.w1c[:, :P]) if T > 0 else enc_out.new_empty(0, self.J)
+
+    def args(self, P):
+        """(W1d ... bp) of the native calls, for an encoder output of width P."""
+        w1d = self.w1c[:, P:]
+        return (self.J, _lib.ptr(w1d), ctypes.c_longlong(self.w1c.stride(0)), _lib.ptr(self.b1), self.P2,
+                _lib.ptr(self.w2c), _lib.ptr(self.b2), self.V, _lib.ptr(self.emb), dtype_code(self.emb.dtype),
+                self.E, self.L, _ptr_array(self.w_ih), _ptr_array(self.w_hh), _ptr_array(self.b_ih),
+                _ptr_array(self.b_hh), self.H, _lib.ptr(self.wpc), _lib.ptr(self.bp))
+
+
+def joint_rows(model, enc_out):
+    """E1 = enc_out [B, T, P] times the encoder half of the joint's first Linear, [B * T, J] in the compute dtype: the
+    rows both beam searches read (``beam_search_rows``, ``StreamingBeamSearch.advance``)."""
+    return _BeamNet(model, enc_out.dtype).e1(enc_out.contiguous())
+
+
+def beam_search_enc(model, enc_out, lens=None, W=10, max_expansions=None, prefix=False):
+    """``beam_search_batch`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
+    encoder frames per utterance; None: all T)."""
+    enc_out = enc_out.contiguous()
+    B, T, P = enc_out.shape
+    return beam_search_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, prefix)
+
+
+def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, prefix=False):
+    """``beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
+    width P."""
+    if W < 1:
+        raise ValueError("beam width must be >= 1")
+    cd = E1.dtype
+    lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
     EM = int(max_expansions) if max_expansions else max(16, 8 * W)
-    dec = model.decoder
-    l1, l2 = model.joint.joint[0], model.joint.joint[2]
-    J, V = l1.weight.shape[0], l2.weight.shape[0]
-    P2 = dec.proj.weight.shape[0]
-    L, H = dec.lstm.num_layers, dec.lstm.hidden_size
-    E = dec.embed.weight.shape[1]
-    w1c = WEIGHTS.get(l1.weight, cd)
-    w2c = WEIGHTS.get(l2.weight, cd)
-    wpc = WEIGHTS.get(dec.proj.weight, cd)
-    E1 = ops.gemm(enc_out.reshape(B * T, P), w1c[:, :P]) if T > 0 else enc_out.new_empty(0, J)
-    w_ih = [WEIGHTS.get(dec.lstm.layer(k)[0], cd) for k in range(L)]
-    w_hh = [WEIGHTS.get(dec.lstm.layer(k)[1], cd) for k in range(L)]
-    b_ih = [dec.lstm.layer(k)[2].detach() for k in range(L)]
-    b_hh = [dec.lstm.layer(k)[3].detach() for k in range(L)]
+    net = _BeamNet(model, cd)
     lib = _lib.load()
-    nbytes = lib.edgedict_beam_workspace_bytes(dtype_code(cd), B, T, J, V, E, L, H, P2, W, EM, int(bool(prefix)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=enc_out.device)
+    nbytes = lib.edgedict_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
+                                               int(bool(prefix)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=E1.device)
     max_tokens = T * EM + 1
     tokens = np.zeros((B, max_tokens), dtype=np.int32)
     ntok = np.zeros(B, dtype=np.int32)
     score = np.zeros(B, dtype=np.float64)
     nexp = ctypes.c_longlong(0)
-    w1d = w1c[:, P:]
     from .tokenizer import BOS
     rc = lib.edgedict_beam_search(
-        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * J), ctypes.c_longlong(J), B, T,
-        lens.ctypes.data_as(ctypes.c_void_p), J, _lib.ptr(w1d), ctypes.c_longlong(w1c.stride(0)),
-        _lib.ptr(l1.bias.detach()), P2, _lib.ptr(w2c), _lib.ptr(l2.bias.detach()), V,
-        _lib.ptr(dec.embed.weight.detach()), dtype_code(dec.embed.weight.dtype), E, L,
-        _ptr_array(w_ih), _ptr_array(w_hh), _ptr_array(b_ih), _ptr_array(b_hh), H, _lib.ptr(wpc),
-        _lib.ptr(dec.proj.bias.detach()), int(model.blank), int(BOS), int(W), EM, int(bool(prefix)),
+        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T,
+        lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM, int(bool(prefix)),
         tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
         score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp), _lib.ptr(ws), _lib.stream_ptr())
     _lib.check(rc, "beam_search")
     beam_search_batch.last_expansions = int(nexp.value)
     seqs = [tokens[b, :ntok[b]].astype(np.int64) for b in range(B)]
     return seqs, torch.from_numpy(score)
+
+
+class StreamingBeamSearch:
+    """The beam search of ``beam_search_batch`` for S streams whose encoder output arrives chunk by chunk.
+
+    The reference's search is frame-synchronous: all it carries from frame to frame is the list B (at most W
+    hypotheses with their log-probability, last token, prediction-network state and token sequence).  That list lives in
+    a persistent device state (csrc/decode.hip, ``edgedict_beam_stream_*``), so ``advance`` over frames [0, t1) and
+    then [t1, t2) gives exactly what ``beam_search_enc`` over [0, t2) gives, and ``best()`` after any chunk is what the
+    offline search would return if the audio ended there.  After every advance each stream's token tree is compacted:
+    the tokens down to the survivors' lowest common ancestor are committed (they can no longer change) and move to a
+    host-side log, so the device tree stays bounded by ``node_capacity`` however long a stream runs.
+
+    ``prefix=True`` (the reference's prefix-sum merge, models.py:145-161) is not supported: it would need the
+    prediction stored per token-tree node to survive compaction; asking for it raises ``ValueError``.
+
+    ``node_capacity`` bounds the token tree per stream: an advance whose streams could need more (live nodes +
+    frames x max_expansions) raises ``RuntimeError`` before it runs; it never truncates.  The default leaves room for
+    chunks of 32 frames on top of the live tree.
+    """
+
+    def __init__(self, model, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False):
+        if prefix:
+            raise ValueError("StreamingBeamSearch: prefix=True (the prefix-sum merge) is not supported when streaming")
+        if W < 1:
+            raise ValueError("beam width must be >= 1")
+        if n_streams < 1:
+            raise ValueError("n_streams must be >= 1")
+        self.model = model
+        self.S = int(n_streams)
+        self.W = int(W)
+        self.EM = int(max_expansions) if max_expansions else max(16, 8 * self.W)
+        self.NC = int(node_capacity) if node_capacity else 32 * self.EM + 1024
+        from .stream import _compute_dtype
+        self.cd = _compute_dtype(model)
+        self.device = model.decoder.embed.weight.device
+        net = self._weights()
+        lib = _lib.load()
+        sbytes = lib.edgedict_beam_stream_state_bytes(dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H,
+                                                      net.P2, self.W, self.EM, self.NC)
+        wbytes = lib.edgedict_beam_stream_workspace_bytes(dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L,
+                                                          net.H, net.P2, self.W, self.EM, self.NC)
+        self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+        self._commit_buf = np.zeros((self.S, self.NC), dtype=np.int32)
+        self._ncommit = np.zeros(self.S, dtype=np.int32)
+        self.last_expansions = 0
+        self.reset()
+
+    def _weights(self):
+        # converted once per parameter version by WEIGHTS (as run_search does); only the pointer bundle is rebuilt
+        return _BeamNet(self.model, self.cd)
+
+    def reset(self, mask=None):
+        """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log."""
+        from .tokenizer import BOS
+        net = self._weights()
+        lib = _lib.load()
+        if mask is None:
+            sel = np.ones(self.S, dtype=bool)
+            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), None, 0,
+                                                _lib.ptr(self._state), _lib.stream_ptr())
+        else:
+            m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+            sel = m.astype(bool).reshape(self.S)
+            mh = np.ascontiguousarray(sel, dtype=np.int32)
+            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS),
+                                                mh.ctypes.data_as(ctypes.c_void_p), 1, _lib.ptr(self._state),
+                                                _lib.stream_ptr())
+        _lib.check(rc, "beam_stream_reset")
+        if not hasattr(self, "_committed"):
+            self._committed = [[] for _ in range(self.S)]
+        for s in np.nonzero(sel)[0]:
+            self._committed[s] = []
+
+    def joint_rows(self, enc_out):
+        """The rows ``advance`` reads for ``enc_out`` [S, T, P]: see ``joint_rows``."""
+        return self._weights().e1(enc_out)
+
+    def advance(self, enc_out, n_frames=None):
+        """Advance every stream over the first ``n_frames[s]`` frames (host ints, default all T; 0: the stream sits
+        this chunk out) of ``enc_out`` [S, T, P] (compute dtype, on the device)."""
+        _lib.require_cuda(enc_out)
+        if enc_out.dim() != 3 or enc_out.shape[0] != self.S:
+            raise ValueError("advance: enc_out must be [S=%d, T, P]" % self.S)
+        if enc_out.dtype != self.cd:
+            raise TypeError("advance: enc_out is %s, the model computes in %s" % (enc_out.dtype, self.cd))
+        enc_out = enc_out.contiguous()
+        S, T, P = enc_out.shape
+        if n_frames is None:
+            nf = np.full(S, T, dtype=np.int32)
+        else:
+            nf = np.ascontiguousarray(n_frames.cpu().numpy() if torch.is_tensor(n_frames) else n_frames, dtype=np.int32)
+            if nf.shape != (S,) or (nf < 0).any() or (nf > T).any():
+                raise ValueError("advance: n_frames must be [S] ints in [0, %d]" % T)
+        net = self._weights()
+        self._advance(net, net.e1(enc_out), T, P, nf)
+
+    def advance_rows(self, E1, P, n_frames=None):
+        """``advance`` from the joint's encoder rows ``E1`` [S * T, J] (``joint_rows``) of an encoder output of width
+        P: what ``advance`` runs after its first product."""
+        _lib.require_cuda(E1)
+        net = self._weights()
+        if E1.dim() != 2 or E1.shape[1] != net.J or E1.shape[0] % self.S or not E1.is_contiguous():
+            raise ValueError("advance_rows: E1 must be contiguous [S * T, J=%d]" % net.J)
+        if E1.dtype != self.cd:
+            raise TypeError("advance_rows: E1 is %s, the model computes in %s" % (E1.dtype, self.cd))
+        T = E1.shape[0] // self.S
+        nf = np.full(self.S, T, dtype=np.int32) if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf.shape != (self.S,) or (nf < 0).any() or (nf > T).any():
+            raise ValueError("advance_rows: n_frames must be [S] ints in [0, %d]" % T)
+        self._advance(net, E1, T, P, nf)
+
+    def _advance(self, net, E1, T, P, nf):
+        from .tokenizer import BOS
+        lib = _lib.load()
+        nexp = ctypes.c_longlong(0)
+        rc = lib.edgedict_beam_stream_advance(
+            dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S,
+            nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
+            self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p), self._ncommit.ctypes.data_as(ctypes.c_void_p),
+            ctypes.byref(nexp), _lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
+        _lib.check(rc, "beam_stream_advance")
+        self.last_expansions = int(nexp.value)
+        for s in np.nonzero(self._ncommit)[0]:
+            self._committed[s].extend(self._commit_buf[s, :self._ncommit[s]].tolist())
+
+    def _read(self):
+        net = self._weights()
+        lib = _lib.load()
+        max_tokens = self.NC
+        tokens = np.zeros((self.S, max_tokens), dtype=np.int32)
+        ntok = np.zeros(self.S, dtype=np.int32)
+        score = np.zeros(self.S, dtype=np.float64)
+        ncom = np.zeros(self.S, dtype=np.int64)
+        nexp = np.zeros(self.S, dtype=np.int64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = lib.edgedict_beam_stream_read(self.S, net.L, net.H, self.W, self.NC, _lib.ptr(self._state), vp(tokens),
+                                           max_tokens, vp(ntok), vp(score), vp(ncom), vp(nexp), _lib.stream_ptr())
+        _lib.check(rc, "beam_stream_read")
+        for s in range(self.S):
+            if ncom[s] != len(self._committed[s]):
+                raise RuntimeError("beam_stream_read: stream %d has %d committed tokens on the device, %d in the log"
+                                   % (s, ncom[s], len(self._committed[s])))
+        return tokens, ntok, score, nexp
+
+    def best(self):
+        """Per stream the first hypothesis of the current list B, as ``beam_search_batch`` returns it:
+        ``(list of int64 arrays (tokens, no blanks), fp64 tensor [S] = -log p)``."""
+        tokens, ntok, score, _ = self._read()
+        seqs = [np.concatenate([np.asarray(self._committed[s], dtype=np.int64),
+                                tokens[s, :ntok[s]].astype(np.int64)]) for s in range(self.S)]
+        return seqs, torch.from_numpy(score)
+
+    def committed(self):
+        """Per stream the committed tokens (int64 arrays): a prefix of ``best()`` that no later frame can change."""
+        return [np.asarray(c, dtype=np.int64) for c in self._committed]
+
+    def expansions(self):
+        """int64 [S]: prediction-network steps (pops) of every stream since its reset."""
+        return self._read()[3]

@@ -7,6 +7,8 @@ does not have: S concurrent streams advance in lock-step on one GPU, state tenso
 ``[L, S, H]`` and ``reset`` takes a per-stream mask.  Both drive the same kernels: fused
 log-mel on the chunk, stateful encoder, then the on-device search loop of csrc/decode.hip in
 stream mode (raw-logit arg-max, the ``<unk>`` rule, prediction net advanced on non-blank).
+``BatchedStreamBeamDecoder`` runs the beam search instead, its beams carried from chunk to chunk
+(``decode.StreamingBeamSearch``).
 """
 import os
 import time
@@ -294,6 +296,69 @@ class BatchedStreamDecoder(StreamTransducerDecoder):
                                want_score=False)
         self.joint_elapsed.append(time.time() - t0)
         return tokens
+
+
+class BatchedStreamBeamDecoder(StreamTransducerDecoder):
+    """S streams decoded concurrently with the beam search of ``Transducer.beam_search`` instead of the greedy rule.
+
+    Same chunk geometry (``chunk_geometry``), feature transform and carried encoder (h, c) as
+    ``BatchedStreamDecoder``; the search is ``decode.StreamingBeamSearch``, which keeps every stream's beams from chunk
+    to chunk, so after any chunk a stream's ``best()`` is what the offline beam search over its audio so far returns.
+    There is no ``<unk>`` rule: the offline beam search has none.  ``prefix=True`` is not supported when streaming
+    (``ValueError``)."""
+
+    def __init__(self, transducer, flags, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False,
+                 dither=None):
+        from .decode import StreamingBeamSearch
+        self.model = transducer.eval()
+        self.flags = flags
+        self.S = n_streams
+        dev = transducer.decoder.embed.weight.device
+        self.device = dev
+        self.search = StreamingBeamSearch(transducer, n_streams, W=W, max_expansions=max_expansions,
+                                          node_capacity=node_capacity, prefix=prefix)
+        self.transform = StackedLogFbank(
+            n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
+            hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,
+            dither=1e-5 if dither is None else dither).to(dev)
+        self.reset_profile()
+        self.reset()
+
+    @torch.no_grad()
+    def reset(self, mask=None):
+        """Reset every stream, or only those where ``mask[s]`` is true."""
+        enc = self.model.encoder.lstm
+        L, H = len(enc.lstms), enc.hidden_size
+        if mask is None or not hasattr(self, "enc_h"):
+            self.enc_h = torch.zeros(L, self.S, H, device=self.device)
+            self.enc_c = torch.zeros(L, self.S, H, device=self.device)
+            self.search.reset()
+            return
+        m = torch.as_tensor(mask).to(self.device).bool()
+        self.enc_h[:, m] = 0
+        self.enc_c[:, m] = 0
+        self.search.reset(m)
+
+    @torch.no_grad()
+    def decode(self, frames):
+        """frames: float32 [S, win_size] on the device -> ``(list of int64 arrays, fp64 tensor [S])``: every stream's
+        best hypothesis over its audio so far (tokens without blanks, -log p), as ``best()`` returns it."""
+        t0 = time.time()
+        encoder_stack.check_wsr_error()
+        xs, _ = self.transform(frames)
+        enc_out, (self.enc_h, self.enc_c) = self.model.encoder(xs, (self.enc_h, self.enc_c))
+        self.encoder_elapsed.append(time.time() - t0)
+        t0 = time.time()
+        self.search.advance(enc_out.contiguous())
+        out = self.search.best()
+        self.joint_elapsed.append(time.time() - t0)
+        return out
+
+    def best(self):
+        return self.search.best()
+
+    def committed(self):
+        return self.search.committed()
 
 
 class PytorchStreamDecoder(StreamTransducerDecoder):

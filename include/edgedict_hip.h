@@ -642,6 +642,58 @@ int edgedict_beam_search(int dtype, const void* E1, long long e_row_stride,
                          int32_t* ntokens_host, double* score_host, long long* expansions_host,
                          void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Streaming beam search: edgedict_beam_search (prefix = 0) with its frame-to-frame list B kept in a
+ * persistent STATE for S streams, so that advancing over frames [0, t1) and then [t1, t2) gives
+ * exactly what one offline call over [0, t2) gives.  Per stream the state holds the survivors (fp64
+ * logp, token-tree node, prediction-network (h, c) [W][L][H], their count), the token tree
+ * (parent, token) with its node count and the last token of its root, and the count of committed
+ * tokens.  After every advance each stream's tree is compacted: nodes that are no ancestor of a
+ * survivor are dropped, the tokens from the root down to the survivors' lowest common ancestor are
+ * COMMITTED (they can no longer change) and returned to the caller, who keeps the log, and that
+ * ancestor becomes the new root.  The tree's size then does not depend on how long a stream has run.
+ *   node_capacity   token-tree nodes per stream; an advance whose streams may need more (live nodes +
+ *                   frames x max_expansions) fails before it runs, naming node_capacity
+ * beam_stream_state_bytes     device bytes of the state (contents undefined until a reset of all streams)
+ * beam_stream_workspace_bytes device bytes of the per-call workspace of beam_stream_advance
+ * beam_stream_reset           streams with mask[b] != 0 (mask null: all; mask_on_host: HOST int32 [S], else
+ *                             device) -> the empty hypothesis: one survivor, logp 0, `bos` fed first, zero
+ *                             state, empty tree and committed log
+ * beam_stream_advance         operands as edgedict_beam_search; E1 holds the encoder half of the joint's first
+ *                             Linear of this chunk's frames.  n_frames_host HOST int32 [S]: frames of each
+ *                             stream in this chunk (0: the stream sits the chunk out, its state unchanged).
+ *                             commit_host HOST int32 [S, node_capacity] / ncommit_host HOST int32 [S]: the
+ *                             tokens committed by this advance; expansions_host HOST, nullable: pops of
+ *                             this call.  Synchronises the stream.  After an error other than the capacity
+ *                             check the advanced streams' state is undefined (reset them).
+ * beam_stream_read            per stream: the uncommitted tail of B[0] (the tokens from the root to its node,
+ *                             no blanks, no BOS; the full hypothesis is the committed log followed by it),
+ *                             its score -logp (fp64), the number of committed tokens before the tail
+ *                             (ncommitted_host, nullable) and the expansions since the stream's reset
+ *                             (expansions_host, nullable).  Synchronises the stream.
+ */
+size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                        int W, int max_expansions, int node_capacity);
+size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H,
+                                            int P2, int W, int max_expansions, int node_capacity);
+int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos,
+                               const int32_t* mask, int mask_on_host, void* state, void* stream);
+int edgedict_beam_stream_advance(int dtype, const void* E1, long long e_row_stride,
+                                 long long e_frame_stride, int S, const int32_t* n_frames_host, int J,
+                                 const void* W1d, long long ldw1, const float* b1, int P2,
+                                 const void* W2, const float* b2, int V, const void* emb,
+                                 int emb_dtype, int E, int L, const void* const* w_ih,
+                                 const void* const* w_hh, const float* const* b_ih,
+                                 const float* const* b_hh, int H, const void* Wp, const float* bp,
+                                 int blank, int bos, int W, int max_expansions, int node_capacity,
+                                 int32_t* commit_host, int32_t* ncommit_host,
+                                 long long* expansions_host, void* state, void* workspace,
+                                 void* stream);
+int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, const void* state,
+                              int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+                              double* score_host, long long* ncommitted_host,
+                              long long* expansions_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
