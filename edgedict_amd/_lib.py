@@ -60,6 +60,10 @@ def load():
         lib.edgedict_beam_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_state_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_workspace_bytes.restype = ctypes.c_size_t
+        lib.edgedict_beam_lm_struct_bytes.restype = ctypes.c_size_t
+        lib.edgedict_beam_workspace_bytes_lm.restype = ctypes.c_size_t
+        lib.edgedict_beam_stream_state_bytes_lm.restype = ctypes.c_size_t
+        lib.edgedict_beam_stream_workspace_bytes_lm.restype = ctypes.c_size_t
         lib.edgedict_stream_encoder_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_blaslt_calls.restype = ctypes.c_longlong
         lib.edgedict_gelu_groupnorm_bwd_workspace_bytes.restype = ctypes.c_size_t

@@ -34,6 +34,12 @@ int ed_decode_fused_beam_step(int dtype, const void* E1t, long long e_row_stride
                               const void* Wp, const float* bp, const float* h_state, const float* c_state,
                               const int32_t* pred, void* dec_new, void* hid, float* logits, float* h_new, float* c_new,
                               void* Y0, void* Y1, hipStream_t s);
+bool ed_decode_fused_lm_ok(int dtype, int emb_dtype, int V, int E, int H);
+int ed_decode_fused_lm_step(int dtype, int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+                            const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
+                            const void* Wo, const float* bo, const float* h_state, const float* c_state,
+                            const int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, float* logits,
+                            hipStream_t s);
 
 namespace {
 
@@ -311,6 +317,17 @@ struct BeamPtrs {
     long long* total_exp;// [1]
     int32_t* root_tok;   // [B] last token of the tree root (node -1); null: BOS (the offline search)
     long long* stream_exp;// [B] expansions per utterance, or null
+    // LM shallow fusion (all null / 0 without an LM): the LM's (h, c) ride along with the prediction network's, under the
+    // same state references
+    float* lm_bp_h[2];   // [B][W][lm_L][lm_H] double-buffered per frame
+    float* lm_bp_c[2];
+    float* lm_f_h;       // [B][EM][lm_L][lm_H] states created in this frame
+    float* lm_f_c;
+    int32_t* lm_pred;    // [B] the token the LM consumes in this iteration
+    float* lm_h_state;   // [lm_L][B][lm_H] the popped hypothesis' LM state
+    float* lm_c_state;
+    const long long* n_committed;   // [B] committed tokens per stream, or null (offline: nothing committed)
+    int lm_L, lm_H, lm_bos;
 };
 
 // (max, first position) of a workgroup's per-thread candidates: butterfly inside a wave, the four waves through LDS.
@@ -443,6 +460,9 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
         p.exp_ref[b * EM + e] = ref;
         p.exp_logp[b * EM + e] = popped;
         pred[b] = tok;
+        // the LM's root token: lm_bos until the stream has committed a token, then the last committed one (root_tok)
+        if (p.lm_pred)
+            p.lm_pred[b] = node >= 0 ? tok : (p.n_committed && p.n_committed[b] > 0 ? p.root_tok[b] : p.lm_bos);
         s_ref = ref;
     }
     __syncthreads();
@@ -455,14 +475,31 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
         h_state[((size_t)l * B + b) * H + j] = sh[i];
         c_state[((size_t)l * B + b) * H + j] = sc[i];
     }
+    if (p.lm_pred) {
+        const int LL = p.lm_L, HL = p.lm_H;
+        const size_t LHl = (size_t)LL * HL;
+        const float* lh = ref < W ? p.lm_bp_h[cur] + ((size_t)b * W + ref) * LHl : p.lm_f_h + ((size_t)b * EM + (ref - W)) * LHl;
+        const float* lc = ref < W ? p.lm_bp_c[cur] + ((size_t)b * W + ref) * LHl : p.lm_f_c + ((size_t)b * EM + (ref - W)) * LHl;
+        for (int i = tid; i < (int)LHl; i += 256) {
+            const int l = i / HL, j = i % HL;
+            p.lm_h_state[((size_t)l * B + b) * HL + j] = lh[i];
+            p.lm_c_state[((size_t)l * B + b) * HL + j] = lc[i];
+        }
+    }
 }
 
 // log-softmax of the joint's logits; children into the pool, the blank child into B, the new
-// prediction-network state into the frame's state pool; then the reference's stop test
-__global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __restrict__ logits,
-                                                   const float* __restrict__ h_new,
-                                                   const float* __restrict__ c_new, int W, int V,
-                                                   int EM, int L, int H, int B, int blank) {
+// prediction-network state into the frame's state pool; then the reference's stop test.
+// LM: the LM's logits get the same log-softmax, and a non-blank child k scores
+//   base + (double)lp_rnnt[k] + (lm_w * (double)lp_lm[k] + lm_b)      (fp64, this order, no contraction)
+// the blank child keeps base + lp_rnnt[blank]; the LM's new state goes into its frame pool under the same slot.
+template <bool LM>
+__device__ __forceinline__ void beam_expand_body(BeamPtrs& p, const float* __restrict__ logits,
+                                                 const float* __restrict__ h_new, const float* __restrict__ c_new,
+                                                 const float* __restrict__ lm_logits,
+                                                 const float* __restrict__ lm_h_new,
+                                                 const float* __restrict__ lm_c_new, double lm_w, double lm_b,
+                                                 int W, int V, int EM, int L, int H, int B, int blank) {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (!p.open[b]) return;
     const float* z = logits + (size_t)b * V;
@@ -476,6 +513,17 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
     for (int v = tid; v < V; v += 256) s += expf(z[v] - m);
     s = block_sum_max(s, false, sf);
     const float logs = logf(s);
+    const float* zl = LM ? lm_logits + (size_t)b * V : nullptr;
+    float ml = 0.f, logsl = 0.f;
+    if constexpr (LM) {
+        ml = -INFINITY;
+        for (int v = tid; v < V; v += 256) ml = fmaxf(ml, zl[v]);
+        ml = block_sum_max(ml, true, sf);
+        float sl = 0.f;
+        for (int v = tid; v < V; v += 256) sl += expf(zl[v] - ml);
+        sl = block_sum_max(sl, false, sf);
+        logsl = logf(sl);
+    }
     const int e = p.e_count[b];
     const double base = p.exp_logp[b * EM + e];
     double* pool = p.pool + (size_t)b * (W + (size_t)EM * V);
@@ -484,7 +532,13 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
     double best = -INFINITY;
     int arg = 0x7fffffff;
     for (int v = tid; v < V; v += 256) {
-        const double c = v == blank ? -INFINITY : base + (double)((z[v] - m) - logs);
+        double c;
+        if constexpr (LM)
+            c = v == blank ? -INFINITY
+                           : base + (double)((z[v] - m) - logs) +
+                                 __dadd_rn(__dmul_rn(lm_w, (double)((zl[v] - ml) - logsl)), lm_b);
+        else
+            c = v == blank ? -INFINITY : base + (double)((z[v] - m) - logs);
         seg[v] = c;
         if (c > best) { best = c; arg = lo + v; }
     }
@@ -495,6 +549,17 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
         const int l = i / H, j = i % H;
         dh[i] = h_new[((size_t)l * B + b) * H + j];
         dc[i] = c_new[((size_t)l * B + b) * H + j];
+    }
+    if constexpr (LM) {
+        const int HL = p.lm_H;
+        const size_t LHl = (size_t)p.lm_L * HL;
+        float* lh = p.lm_f_h + ((size_t)b * EM + e) * LHl;
+        float* lc = p.lm_f_c + ((size_t)b * EM + e) * LHl;
+        for (int i = tid; i < (int)LHl; i += 256) {
+            const int l = i / HL, j = i % HL;
+            lh[i] = lm_h_new[((size_t)l * B + b) * HL + j];
+            lc[i] = lm_c_new[((size_t)l * B + b) * HL + j];
+        }
     }
     // the new segment's (max, first position), then max(A) = max over the segment maxima
     block_argmax(best, arg, sd, si);
@@ -530,6 +595,25 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
     }
 }
 
+__global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __restrict__ logits,
+                                                   const float* __restrict__ h_new,
+                                                   const float* __restrict__ c_new, int W, int V,
+                                                   int EM, int L, int H, int B, int blank) {
+    beam_expand_body<false>(p, logits, h_new, c_new, nullptr, nullptr, nullptr, 0.0, 0.0, W, V, EM, L, H, B, blank);
+}
+
+// beam_expand with LM shallow fusion (one workgroup per utterance; both rows are V <= a few thousand floats, so this is
+// latency-bound: the two log-softmaxes are four block reductions over L2-resident rows)
+__global__ __launch_bounds__(256) void beam_expand_lm(BeamPtrs p, const float* __restrict__ logits,
+                                                      const float* __restrict__ h_new, const float* __restrict__ c_new,
+                                                      const float* __restrict__ lm_logits,
+                                                      const float* __restrict__ lm_h_new,
+                                                      const float* __restrict__ lm_c_new, double lm_w, double lm_b,
+                                                      int W, int V, int EM, int L, int H, int B, int blank) {
+    beam_expand_body<true>(p, logits, h_new, c_new, lm_logits, lm_h_new, lm_c_new, lm_w, lm_b, W, V, EM, L, H, B,
+                           blank);
+}
+
 // B = B[:W] becomes the next frame's survivors (states gathered into the other buffer)
 __global__ __launch_bounds__(256) void beam_frame_end(BeamPtrs p, int t, int cur, int W, int EM,
                                                       int L, int H) {
@@ -544,6 +628,16 @@ __global__ __launch_bounds__(256) void beam_frame_end(BeamPtrs p, int t, int cur
         float* dh = p.bp_h[cur ^ 1] + ((size_t)b * W + j) * LH;
         float* dc = p.bp_c[cur ^ 1] + ((size_t)b * W + j) * LH;
         for (int i = tid; i < (int)LH; i += 256) { dh[i] = sh[i]; dc[i] = sc[i]; }
+        if (p.lm_pred) {
+            const size_t LHl = (size_t)p.lm_L * p.lm_H;
+            const float* lh = ref < W ? p.lm_bp_h[cur] + ((size_t)b * W + ref) * LHl
+                                      : p.lm_f_h + ((size_t)b * EM + (ref - W)) * LHl;
+            const float* lc = ref < W ? p.lm_bp_c[cur] + ((size_t)b * W + ref) * LHl
+                                      : p.lm_f_c + ((size_t)b * EM + (ref - W)) * LHl;
+            float* ldh = p.lm_bp_h[cur ^ 1] + ((size_t)b * W + j) * LHl;
+            float* ldc = p.lm_bp_c[cur ^ 1] + ((size_t)b * W + j) * LHl;
+            for (int i = tid; i < (int)LHl; i += 256) { ldh[i] = lh[i]; ldc[i] = lc[i]; }
+        }
     }
     if (tid < n) {
         p.bp_logp[b * W + tid] = p.bn_logp[b * W + tid];
@@ -677,6 +771,120 @@ inline BeamWs beam_layout(int esz, int B, int T, int J, int V, int E, int L, int
     return w;
 }
 
+// LM shallow fusion: the LM step's buffers and the LM state pools, appended behind a search's workspace (offsets from
+// `base`, a multiple of 256).  with_bp0: the survivors' buffer [0] lives here too (offline); the streaming search
+// keeps it in its persistent state (beam_stream_lm_state_layout).
+struct LmWs {
+    size_t pred, h_state, c_state, h_new, c_new, x, G, Hprev, Y0, Y1, Cst, logits, bp_h0, bp_c0, bp_h1, bp_c1, f_h, f_c,
+        total;
+};
+inline LmWs lm_ws_layout(size_t base, int esz, int B, int V, int L, int E, int H, int W, int EM, bool with_bp0) {
+    LmWs w;
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    const size_t LH = (size_t)L * H;
+    w.pred = take((size_t)B * 4);
+    w.h_state = take((size_t)B * LH * 4);
+    w.c_state = take((size_t)B * LH * 4);
+    w.h_new = take((size_t)B * LH * 4);
+    w.c_new = take((size_t)B * LH * 4);
+    w.x = take((size_t)B * E * esz);
+    w.G = take((size_t)B * 4 * H * esz);
+    w.Hprev = take((size_t)B * H * esz);
+    w.Y0 = take((size_t)B * H * esz);
+    w.Y1 = take((size_t)B * H * esz);
+    w.Cst = take((size_t)B * H * 4);
+    w.logits = take((size_t)B * V * 4);
+    w.bp_h0 = w.bp_c0 = 0;
+    if (with_bp0) {
+        w.bp_h0 = take((size_t)B * W * LH * 4);
+        w.bp_c0 = take((size_t)B * W * LH * 4);
+    }
+    w.bp_h1 = take((size_t)B * W * LH * 4);
+    w.bp_c1 = take((size_t)B * W * LH * 4);
+    w.f_h = take((size_t)B * EM * LH * 4);
+    w.f_c = take((size_t)B * EM * LH * 4);
+    w.total = o;
+    return w;
+}
+
+// the LM's buffers of one search call (null when there is no LM)
+struct LmBufs {
+    const edgedict_beam_lm_t* lm;
+    float *h_new, *c_new, *Cst, *logits;
+    void *x, *G, *Hprev, *Y[2];
+};
+inline LmBufs lm_bufs(const edgedict_beam_lm_t* lm, char* p, const LmWs& w) {
+    LmBufs u{};
+    u.lm = lm;
+    if (!lm) return u;
+    u.h_new = (float*)(p + w.h_new);
+    u.c_new = (float*)(p + w.c_new);
+    u.Cst = (float*)(p + w.Cst);
+    u.logits = (float*)(p + w.logits);
+    u.x = p + w.x;
+    u.G = p + w.G;
+    u.Hprev = p + w.Hprev;
+    u.Y[0] = p + w.Y0;
+    u.Y[1] = p + w.Y1;
+    return u;
+}
+// the LM fields of the pointer bundle that live in the workspace (the survivors' buffer [0] is set by the caller)
+inline void lm_ptrs(BeamPtrs& q, const edgedict_beam_lm_t* lm, char* p, const LmWs& w) {
+    if (!lm) return;
+    q.lm_bp_h[1] = (float*)(p + w.bp_h1);
+    q.lm_bp_c[1] = (float*)(p + w.bp_c1);
+    q.lm_f_h = (float*)(p + w.f_h);
+    q.lm_f_c = (float*)(p + w.f_c);
+    q.lm_pred = (int32_t*)(p + w.pred);
+    q.lm_h_state = (float*)(p + w.h_state);
+    q.lm_c_state = (float*)(p + w.c_state);
+    q.lm_L = lm->L;
+    q.lm_H = lm->H;
+    q.lm_bos = lm->bos;
+}
+// an LM that the search can use: status code and message, or ED_OK
+int lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what) {
+    if (!lm) return ED_OK;
+    ED_CHECK_ARG(!prefix, "%s: prefix = 1 with an LM is not supported (it would need LM log-probs per token-tree node)",
+                 what);
+    ED_CHECK_ARG(lm->V == V, "%s: the LM's ntoken = %d differs from the transducer's vocabulary V = %d", what, lm->V, V);
+    ED_CHECK_ARG(lm->L > 0 && lm->E > 0 && lm->H > 0, "%s: bad LM shape (L %d, E %d, H %d)", what, lm->L, lm->E, lm->H);
+    ED_CHECK_ARG(lm->emb && lm->w_ih && lm->w_hh && lm->b_ih && lm->b_hh && lm->Wo && lm->bo, "%s: null LM pointer",
+                 what);
+    for (int k = 0; k < lm->L; ++k)
+        ED_CHECK_ARG(lm->w_ih[k] && lm->w_hh[k] && lm->b_ih[k] && lm->b_hh[k], "%s: null LM layer %d pointer", what, k);
+    ED_CHECK_ARG(lm->bos >= 0 && lm->bos < V, "%s: LM bos = %d outside the vocabulary", what, lm->bos);
+    ED_CHECK_ARG(lm->emb_dtype == ED_F32 || lm->emb_dtype == ED_BF16, "%s: bad LM embedding dtype", what);
+    ED_CHECK_ARG(isfinite(lm->weight) && isfinite(lm->length_bonus), "%s: LM weight / length bonus not finite", what);
+    return ED_OK;
+}
+
+// one LM step for every row: token lm_pred[b] from (lm_h_state, lm_c_state) -> new state, fp32 logits [B, V]
+int lm_step(int dtype, int B, const edgedict_beam_lm_t& lm, const BeamPtrs& q, const LmBufs& u, hipStream_t s) {
+    const int L = lm.L, E = lm.E, H = lm.H, V = lm.V;
+    if (ed_decode_fused_lm_ok(dtype, lm.emb_dtype, V, E, H))
+        return ed_decode_fused_lm_step(dtype, B, V, lm.emb, lm.emb_dtype, E, L, lm.w_ih, lm.w_hh, lm.b_ih, lm.b_hh, H,
+                                       lm.Wo, lm.bo, q.lm_h_state, q.lm_c_state, q.lm_pred, u.h_new, u.c_new, u.Y[0],
+                                       u.Y[1], u.logits, s);
+    int rc;
+    if ((rc = edgedict_embedding_fwd(dtype, lm.emb_dtype, q.lm_pred, 1, lm.emb, u.x, B, 1, E, V, 0, 0, s))) return rc;
+    const void* xin = u.x;
+    int xin_dim = E;
+    for (int k = 0; k < L; ++k) {
+        if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, lm.w_ih[k], xin_dim, 1, u.G, 4 * H, B, 4 * H, xin_dim,
+                                lm.b_ih[k], lm.b_hh[k], 0, 1, s)))
+            return rc;
+        if ((rc = edgedict_lstm_forward(dtype, u.G, u.Hprev, u.Y[k & 1], u.Cst, lm.w_hh[k], nullptr,
+                                        q.lm_h_state + (size_t)k * B * H, q.lm_c_state + (size_t)k * B * H,
+                                        u.h_new + (size_t)k * B * H, u.c_new + (size_t)k * B * H, B, 1, H, nullptr, s)))
+            return rc;
+        xin = u.Y[k & 1];
+        xin_dim = H;
+    }
+    return edgedict_gemm(dtype, ED_F32, xin, H, 1, lm.Wo, H, 1, u.logits, V, B, V, H, lm.bo, nullptr, 0, 1, s);
+}
+
 
 // The arguments of one search call: weights and shapes as edgedict_beam_search takes them ...
 struct BeamNet {
@@ -718,7 +926,8 @@ struct BeamBufs {
 // frames t < lens[b]; per frame: frame begin -> lockstep pop / step / expand iterations -> frame end.  The survivors'
 // states alternate between bp_h/bp_c[0] and [1], starting in [0]: after the loop utterance b's are in [lens[b] & 1].
 // prefix = 1: `prefix_merge(t, E1 of frame t)` runs the host list logic before every frame after the first.
-int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, int maxlen, int prefix,
+// lmu.lm != null: every iteration also runs the LM step, and beam_expand_lm replaces beam_expand (prefix must be 0).
+int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, const LmBufs& lmu, int maxlen, int prefix,
                     const std::function<int(int, const char*)>& prefix_merge, hipStream_t s) {
     const int dtype = net.dtype, esz = net.esz, B = net.B, J = net.J, P2 = net.P2, V = net.V, emb_dtype = net.emb_dtype,
               E = net.E, L = net.L, H = net.H, blank = net.blank, bos = net.bos, W = net.W, EM = net.EM,
@@ -738,6 +947,14 @@ int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, in
     int32_t* pred = u.pred;
     std::vector<int32_t> open_h(B);
     const bool fused_step = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    auto expand = [&]() {
+        if (lmu.lm)
+            hipLaunchKernelGGL(beam_expand_lm, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, lmu.logits, lmu.h_new,
+                               lmu.c_new, lmu.lm->weight, lmu.lm->length_bonus, W, V, EM, L, H, B, blank);
+        else
+            hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V, EM, L, H, B,
+                               blank);
+    };
     int cur = 0;
     for (int t = 0; t < maxlen; ++t) {
         const char* e1t = (const char*)E1 + (size_t)t * e_frame_stride * esz;
@@ -750,6 +967,8 @@ int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, in
             int rc;
             hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, V, EM, L, H, B, NODES,
                                bos, pred, h_state, c_state);
+            // the LM's step on y*'s last token from y*'s LM state (its logits are only read by beam_expand_lm)
+            if (lmu.lm && (rc = lm_step(dtype, B, *lmu.lm, q, lmu, s))) return rc;
             if (fused_step) {
                 // prediction-network step + projection + joint hidden + logits as 3 + L fused launches (decode_fused.hip)
                 if ((rc = ed_decode_fused_beam_step(dtype, e1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
@@ -764,8 +983,7 @@ int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, in
                         hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
                                            (bf16_t*)node_pred, EM, NODES, P2);
                 }
-                hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V, EM, L, H, B,
-                                   blank);
+                expand();
             } else {
             // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132)
             if ((rc = edgedict_embedding_fwd(dtype, emb_dtype, pred, 1, emb, x, B, 1, E, V, 0, 0, s)))
@@ -810,8 +1028,7 @@ int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, in
             if ((rc = edgedict_gemm(dtype, ED_F32, hid, J, 1, W2, J, 1, logits, V, B, V, J, b2,
                                     nullptr, 0, 1, s)))
                 return rc;
-            hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V,
-                               EM, L, H, B, blank);
+            expand();
             }
             if (it + 1 >= W) {   // B cannot hold W hypotheses before W expansions
                 ED_CHECK_HIP(hipMemcpyAsync(open_h.data(), q.open, (size_t)B * 4, hipMemcpyDeviceToHost, s));
@@ -828,20 +1045,30 @@ int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, in
 }
 }  // namespace
 
-extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
-                                                int H, int P2, int W, int max_expansions, int prefix) {
+extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
+
+extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
+                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
     if (B <= 0 || W <= 0 || max_expansions <= 0) return 0;
-    return beam_layout(dtype == ED_F32 ? 4 : 2, B, T < 0 ? 0 : T, J, V, E, L, H, P2, W, max_expansions, prefix).total;
+    const int esz = dtype == ED_F32 ? 4 : 2;
+    const size_t base = beam_layout(esz, B, T < 0 ? 0 : T, J, V, E, L, H, P2, W, max_expansions, prefix).total;
+    if (!lm) return base;
+    return lm_ws_layout(base, esz, B, V, lm->L, lm->E, lm->H, W, max_expansions, true).total;
 }
 
-extern "C" int edgedict_beam_search(
+extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
+                                                int H, int P2, int W, int max_expansions, int prefix) {
+    return edgedict_beam_workspace_bytes_lm(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, nullptr);
+}
+
+extern "C" int edgedict_beam_search_lm(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
     const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
     const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
     const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
     const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
     int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, void* workspace, void* stream_) {
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "beam_search: bad dtype");
     ED_CHECK_ARG(B > 0 && T >= 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0 && W > 0 &&
                      max_expansions >= W && max_tokens >= 0,
@@ -852,6 +1079,10 @@ extern "C" int edgedict_beam_search(
     ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "beam_search: blank/bos outside the vocabulary");
     for (int b = 0; b < B; ++b)
         ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "beam_search: lens[%d] = %d outside [0, %d]", b, lens_host[b], T);
+    {
+        const int rc = lm_check(lm, V, prefix, "beam_search");
+        if (rc) return rc;
+    }
     hipStream_t s = (hipStream_t)stream_;
     const int esz = dtype == ED_F32 ? 4 : 2, EM = max_expansions;
     const int NODES = T * EM + 1;
@@ -871,7 +1102,7 @@ extern "C" int edgedict_beam_search(
     void* dec_new = p + w.step.dec_new;
     float* h_state = (float*)(p + w.h_state);
     float* c_state = (float*)(p + w.c_state);
-    BeamPtrs q;
+    BeamPtrs q{};
     q.pool = (double*)(p + w.pool);
     q.bp_logp = (double*)(p + w.bp_logp);
     q.bp_node = (int32_t*)(p + w.bp_node);
@@ -909,6 +1140,21 @@ extern "C" int edgedict_beam_search(
     ED_CHECK_HIP(hipMemsetAsync(h_state, 0, (size_t)B * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(c_state, 0, (size_t)B * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(pred, 0, (size_t)B * 4, s));
+    LmWs lw{};
+    if (lm) {
+        lw = lm_ws_layout(w.total, esz, B, V, lm->L, lm->E, lm->H, W, EM, true);
+        lm_ptrs(q, lm, p, lw);
+        q.lm_bp_h[0] = (float*)(p + lw.bp_h0);
+        q.lm_bp_c[0] = (float*)(p + lw.bp_c0);
+        const size_t LHl = (size_t)lm->L * lm->H;
+        // the LM's initial state is zero (LMModel.init_hidden, models.py:255-261); idle rows stay finite
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_h[0], 0, (size_t)B * W * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_c[0], 0, (size_t)B * W * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_h_state, 0, (size_t)B * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_c_state, 0, (size_t)B * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_pred, 0, (size_t)B * 4, s));
+    }
+    const LmBufs lmu = lm_bufs(lm, p, lw);
     hipLaunchKernelGGL(beam_init, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W);
     int maxlen = 0;
     for (int b = 0; b < B; ++b) maxlen = lens_host[b] > maxlen ? lens_host[b] : maxlen;
@@ -1039,7 +1285,7 @@ extern "C" int edgedict_beam_search(
     const BeamBufs bufs{D1, hid, logits, pred, x, G, Hprev, {Y[0], Y[1]}, Cst, h_new, c_new, dec_new, h_state, c_state,
                         node_pred};
     {
-        const int rc = beam_frame_loop(net, bufs, q, maxlen, prefix, prefix_merge, s);
+        const int rc = beam_frame_loop(net, bufs, q, lmu, maxlen, prefix, prefix_merge, s);
         if (rc) return rc;
     }
     ED_CHECK_LAUNCH("beam_search");
@@ -1071,6 +1317,20 @@ extern "C" int edgedict_beam_search(
         score_host[b] = -logp[(size_t)b * W];
     }
     return ED_OK;
+}
+
+extern "C" int edgedict_beam_search(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+    double* score_host, long long* expansions_host, void* workspace, void* stream_) {
+    return edgedict_beam_search_lm(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2,
+                                   b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
+                                   max_expansions, prefix, tokens_host, max_tokens, ntokens_host, score_host,
+                                   expansions_host, nullptr, workspace, stream_);
 }
 
 
@@ -1151,8 +1411,23 @@ inline BeamStreamWs beam_stream_ws_layout(int esz, int S, int J, int V, int E, i
     return w;
 }
 
+// LM shallow fusion: the survivors' LM (h, c) [S][W][lm_L][lm_H], appended behind the plain state (so that
+// edgedict_beam_stream_read serves both forms)
+struct BeamStreamLmState {
+    size_t bp_h, bp_c, total;
+};
+inline BeamStreamLmState beam_stream_lm_state_layout(size_t base, int S, int W, const edgedict_beam_lm_t& lm) {
+    BeamStreamLmState w;
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    w.bp_h = take((size_t)S * W * lm.L * lm.H * 4);
+    w.bp_c = take((size_t)S * W * lm.L * lm.H * 4);
+    w.total = o;
+    return w;
+}
+
 BeamPtrs beam_stream_ptrs(char* st, const BeamStreamState& a, char* ws, const BeamStreamWs& w) {
-    BeamPtrs q;
+    BeamPtrs q{};
     q.pool = (double*)(ws + w.pool);
     q.bp_logp = (double*)(st + a.bp_logp);
     q.bp_node = (int32_t*)(st + a.bp_node);
@@ -1180,6 +1455,7 @@ BeamPtrs beam_stream_ptrs(char* st, const BeamStreamState& a, char* ws, const Be
     q.total_exp = (long long*)(ws + w.total_exp);
     q.root_tok = (int32_t*)(st + a.root_tok);
     q.stream_exp = (long long*)(st + a.n_exp);
+    q.n_committed = (const long long*)(st + a.n_committed);
     return q;
 }
 
@@ -1194,6 +1470,12 @@ __global__ __launch_bounds__(256) void beam_stream_reset_kernel(BeamPtrs p, long
     float* h = p.bp_h[0] + (size_t)b * n;
     float* c = p.bp_c[0] + (size_t)b * n;
     for (size_t i = tid; i < n; i += 256) { h[i] = 0.f; c[i] = 0.f; }
+    if (p.lm_bp_h[0]) {           // the LM's initial state is zero too (LMModel.init_hidden)
+        const size_t nl = (size_t)W * p.lm_L * p.lm_H;
+        float* lh = p.lm_bp_h[0] + (size_t)b * nl;
+        float* lc = p.lm_bp_c[0] + (size_t)b * nl;
+        for (size_t i = tid; i < nl; i += 256) { lh[i] = 0.f; lc[i] = 0.f; }
+    }
     if (tid == 0) {
         p.n_bp[b] = 1;
         p.bp_logp[(size_t)b * W] = 0.0;
@@ -1214,6 +1496,13 @@ __global__ __launch_bounds__(256) void beam_stream_settle(BeamPtrs p, int W, int
     for (size_t i = tid; i < n; i += 256) {
         p.bp_h[0][o + i] = p.bp_h[1][o + i];
         p.bp_c[0][o + i] = p.bp_c[1][o + i];
+    }
+    if (p.lm_pred) {
+        const size_t LHl = (size_t)p.lm_L * p.lm_H, nl = (size_t)p.n_bp[b] * LHl, ol = (size_t)b * W * LHl;
+        for (size_t i = tid; i < nl; i += 256) {
+            p.lm_bp_h[0][ol + i] = p.lm_bp_h[1][ol + i];
+            p.lm_bp_c[0][ol + i] = p.lm_bp_c[1][ol + i];
+        }
     }
 }
 
@@ -1306,23 +1595,41 @@ __global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, i
 
 }  // namespace
 
-extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
-                                                   int max_expansions, int node_capacity) {
+extern "C" size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                      int W, int max_expansions, int node_capacity,
+                                                      const edgedict_beam_lm_t* lm) {
     (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
     if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
-    return beam_stream_state_layout(S, L, H, W, node_capacity).total;
+    const size_t base = beam_stream_state_layout(S, L, H, W, node_capacity).total;
+    return lm ? beam_stream_lm_state_layout(base, S, W, *lm).total : base;
+}
+
+extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
+                                                   int max_expansions, int node_capacity) {
+    return edgedict_beam_stream_state_bytes_lm(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, nullptr);
+}
+
+extern "C" size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                          int W, int max_expansions, int node_capacity,
+                                                          const edgedict_beam_lm_t* lm) {
+    if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
+    const int esz = dtype == ED_F32 ? 4 : 2;
+    const size_t base = beam_stream_ws_layout(esz, S, J, V, E, L, H, P2, W, max_expansions, node_capacity).total;
+    return lm ? lm_ws_layout(base, esz, S, V, lm->L, lm->E, lm->H, W, max_expansions, false).total : base;
 }
 
 extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
                                                        int W, int max_expansions, int node_capacity) {
-    if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
-    return beam_stream_ws_layout(dtype == ED_F32 ? 4 : 2, S, J, V, E, L, H, P2, W, max_expansions, node_capacity).total;
+    return edgedict_beam_stream_workspace_bytes_lm(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity,
+                                                   nullptr);
 }
 
-extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                          int mask_on_host, void* state, void* stream_) {
+extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                             int mask_on_host, const edgedict_beam_lm_t* lm, void* state,
+                                             void* stream_) {
     ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0, "beam_stream_reset: bad shape");
     ED_CHECK_ARG(state, "beam_stream_reset: null state");
+    ED_CHECK_ARG(!lm || (lm->L > 0 && lm->H > 0), "beam_stream_reset: bad LM shape");
     hipStream_t s = (hipStream_t)stream_;
     const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity);
     char* st = (char*)state;
@@ -1335,6 +1642,13 @@ extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_c
     q.n_nodes = (int32_t*)(st + a.n_nodes);
     q.root_tok = (int32_t*)(st + a.root_tok);
     q.stream_exp = (long long*)(st + a.n_exp);
+    if (lm) {
+        const BeamStreamLmState la = beam_stream_lm_state_layout(a.total, S, W, *lm);
+        q.lm_bp_h[0] = (float*)(st + la.bp_h);
+        q.lm_bp_c[0] = (float*)(st + la.bp_c);
+        q.lm_L = lm->L;
+        q.lm_H = lm->H;
+    }
     long long* n_committed = (long long*)(st + a.n_committed);
     if (!mask || !mask_on_host) {
         hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, n_committed, mask, 0, W, L, H, bos);
@@ -1352,13 +1666,18 @@ extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_c
     return ED_OK;
 }
 
-extern "C" int edgedict_beam_stream_advance(
+extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                          int mask_on_host, void* state, void* stream_) {
+    return edgedict_beam_stream_reset_lm(S, L, H, W, node_capacity, bos, mask, mask_on_host, nullptr, state, stream_);
+}
+
+extern "C" int edgedict_beam_stream_advance_lm(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
     int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
     const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
     int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, void* state, void* workspace, void* stream_) {
+    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "beam_stream_advance: bad dtype");
     ED_CHECK_ARG(S > 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0 && W > 0 && max_expansions >= W &&
                      node_capacity > 0,
@@ -1367,6 +1686,10 @@ extern "C" int edgedict_beam_stream_advance(
                      commit_host && ncommit_host && state && workspace,
                  "beam_stream_advance: null pointer");
     ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "beam_stream_advance: blank/bos outside the vocabulary");
+    {
+        const int rc = lm_check(lm, V, 0, "beam_stream_advance");
+        if (rc) return rc;
+    }
     int maxlen = 0;
     for (int b = 0; b < S; ++b) {
         ED_CHECK_ARG(n_frames_host[b] >= 0, "beam_stream_advance: n_frames[%d] = %d < 0", b, n_frames_host[b]);
@@ -1380,6 +1703,15 @@ extern "C" int edgedict_beam_stream_advance(
     char* st = (char*)state;
     char* p = (char*)workspace;
     BeamPtrs q = beam_stream_ptrs(st, a, p, w);
+    LmWs lw{};
+    if (lm) {
+        const BeamStreamLmState la = beam_stream_lm_state_layout(a.total, S, W, *lm);
+        lw = lm_ws_layout(w.total, esz, S, V, lm->L, lm->E, lm->H, W, EM, false);
+        lm_ptrs(q, lm, p, lw);
+        q.lm_bp_h[0] = (float*)(st + la.bp_h);
+        q.lm_bp_c[0] = (float*)(st + la.bp_c);
+    }
+    const LmBufs lmu = lm_bufs(lm, p, lw);
     for (int b = 0; b < S; ++b) ncommit_host[b] = 0;
     if (expansions_host) *expansions_host = 0;
     if (maxlen == 0) return ED_OK;
@@ -1406,12 +1738,18 @@ extern "C" int edgedict_beam_stream_advance(
     ED_CHECK_HIP(hipMemsetAsync(bufs.h_state, 0, (size_t)S * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(bufs.c_state, 0, (size_t)S * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(bufs.pred, 0, (size_t)S * 4, s));
+    if (lm) {
+        const size_t LHl = (size_t)lm->L * lm->H;
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_h_state, 0, (size_t)S * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_c_state, 0, (size_t)S * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_pred, 0, (size_t)S * 4, s));
+    }
     ED_CHECK_HIP(hipMemsetAsync(q.flags, 0, 8, s));
     ED_CHECK_HIP(hipMemsetAsync(q.total_exp, 0, 8, s));
     const BeamNet net{dtype, esz, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype,
                       E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, EM, NC};
     {
-        const int rc = beam_frame_loop(net, bufs, q, maxlen, 0, [](int, const char*) { return (int)ED_OK; }, s);
+        const int rc = beam_frame_loop(net, bufs, q, lmu, maxlen, 0, [](int, const char*) { return (int)ED_OK; }, s);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(beam_stream_settle, dim3(S), dim3(256), 0, s, q, W, L, H);
@@ -1440,6 +1778,19 @@ extern "C" int edgedict_beam_stream_advance(
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;
+}
+
+extern "C" int edgedict_beam_stream_advance(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+    long long* expansions_host, void* state, void* workspace, void* stream_) {
+    return edgedict_beam_stream_advance_lm(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1,
+                                           P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
+                                           blank, bos, W, max_expansions, node_capacity, commit_host, ncommit_host,
+                                           expansions_host, nullptr, state, workspace, stream_);
 }
 
 extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, const void* state,

@@ -809,3 +809,41 @@ int ed_decode_fused_frame(int dtype, const void* E1t, long long e_row_stride, in
     ED_CHECK_LAUNCH("decode_fused_frame");
     return ED_OK;
 }
+
+// LM shallow fusion of the beam search (decode.hip lm_step): the same rule as the search frame, for an LSTM LM with no
+// joint or projection (E, H multiples of 32, V % 4 == 0)
+bool ed_decode_fused_lm_ok(int dtype, int emb_dtype, int V, int E, int H) {
+    return ed_decode_fused_ok(dtype, emb_dtype, 32, V, E, H, 32);
+}
+
+namespace {
+template <typename ET>
+void lm_step_t(int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+               const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wo,
+               const float* bo, const float* h_state, const float* c_state, const int32_t* pred, float* h_new,
+               float* c_new, void* Y0, void* Y1, float* logits, hipStream_t s) {
+    const int RB = (B + 15) / 16;
+    void* Y[2] = {Y0, Y1};
+    launch_lstm_steps<ET>(2, nullptr, 0, -1, -1, const_cast<int32_t*>(pred), nullptr, 0, 0, nullptr, emb, emb_dtype, E, L,
+                          w_ih, w_hh, b_ih, b_hh, H, h_state, c_state, h_new, c_new, Y, B, V, s);
+    hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, (V + 63) / 64), dim3(256), 0, s, (const ET*)Y[(L - 1) & 1], H,
+                       (const ET*)Wo, bo, V, -1, 0, (PickPart*)nullptr, logits, B);
+}
+}  // namespace
+
+// one LM step for B rows: token pred[b] from (h_state, c_state) [L, B, H] fp32 -> h_new / c_new, logits fp32 [B, V]
+// = y_L Wo^T + bo; L + 1 launches (dec_lstm_step per layer, dec_logits_pick in its logits-out form)
+int ed_decode_fused_lm_step(int dtype, int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+                            const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
+                            const void* Wo, const float* bo, const float* h_state, const float* c_state,
+                            const int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, float* logits,
+                            hipStream_t s) {
+    if (dtype == ED_F32)
+        lm_step_t<float>(B, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wo, bo, h_state, c_state, pred, h_new,
+                         c_new, Y0, Y1, logits, s);
+    else
+        lm_step_t<bf16_t>(B, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wo, bo, h_state, c_state, pred, h_new,
+                          c_new, Y0, Y1, logits, s);
+    ED_CHECK_LAUNCH("decode_fused_lm_step");
+    return ED_OK;
+}

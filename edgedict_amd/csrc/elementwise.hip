@@ -382,7 +382,48 @@ __global__ void clip_coef_kernel(const float* sumsq, float max_norm, float pre_s
     *coef = fminf(1.f, max_norm / (nrm + 1e-6f));
 }
 
+// ---------------------------------------------------------------- row log-softmax
+// y[r, :] = (x[r, :] - max) - log(sum exp(x[r, :] - max)), fp32 arithmetic; one workgroup of 256 per row (the LM's
+// output rows are a few thousand wide: latency-bound, two block reductions through LDS)
+template <typename T>
+__global__ __launch_bounds__(256) void log_softmax_rows_kernel(const T* __restrict__ x, long long ldx,
+                                                               float* __restrict__ y, int N) {
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* xr = x + (long long)r * ldx;
+    __shared__ float part[4];
+    float m = -INFINITY;
+    for (int i = tid; i < N; i += 256) m = fmaxf(m, ElemIO<T>::load(xr + i));
+    m = wave_max(m);
+    if (lane == 0) part[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+    __syncthreads();
+    float se = 0.f;
+    for (int i = tid; i < N; i += 256) se += expf(ElemIO<T>::load(xr + i) - m);
+    se = wave_sum(se);
+    if (lane == 0) part[wave] = se;
+    __syncthreads();
+    const float logs = logf((part[0] + part[1]) + (part[2] + part[3]));
+    float* yr = y + (long long)r * N;
+    for (int i = tid; i < N; i += 256) yr[i] = (ElemIO<T>::load(xr + i) - m) - logs;
+}
+
 }  // namespace
+
+extern "C" int edgedict_log_softmax_rows(int x_dtype, const void* x, long long ldx, float* y, int M, int N,
+                                         void* stream_) {
+    ED_CHECK_ARG(x_dtype == ED_F32 || x_dtype == ED_BF16, "log_softmax_rows: bad dtype");
+    ED_CHECK_ARG(M >= 0 && N > 0 && ldx >= N, "log_softmax_rows: bad shape (M %d, N %d, ldx %lld)", M, N, ldx);
+    if (M == 0) return ED_OK;
+    ED_CHECK_ARG(x && y, "log_softmax_rows: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    if (x_dtype == ED_F32)
+        hipLaunchKernelGGL(log_softmax_rows_kernel<float>, dim3(M), dim3(256), 0, s, (const float*)x, ldx, y, N);
+    else
+        hipLaunchKernelGGL(log_softmax_rows_kernel<bf16_t>, dim3(M), dim3(256), 0, s, (const bf16_t*)x, ldx, y, N);
+    ED_CHECK_LAUNCH("log_softmax_rows");
+    return ED_OK;
+}
 
 extern "C" int edgedict_cast(int src_dtype, const void* src, int dst_dtype, void* dst,
                              long long n, void* stream_) {

@@ -10,6 +10,17 @@ symbol is not blank; blanks stay in the returned sequences, which are truncated 
 ``prefix=False``) for a batch of utterances in lockstep (csrc/decode.hip, second half);
 ``beam_search_enc`` is the same search over a given encoder output, and ``StreamingBeamSearch`` runs it over
 encoder output that arrives chunk by chunk, carrying the beams from chunk to chunk.
+
+Every beam search here takes an optional external language model for shallow fusion (``lm=``, an
+``edgedict_amd.lm.LMModel``: the reference's ``LMModel``, models.py:224-261).  A popped hypothesis y* with fp64 score
+``base`` feeds its last token to the LM from y*'s stored LM state; with ``lp_lm = log_softmax(LM logits)`` (fp32) a
+non-blank child k scores ``base + (double)lp_rnnt[k] + (lm_weight * (double)lp_lm[k] + length_bonus)`` (fp64, in this
+order), the blank child ``base + (double)lp_rnnt[blank]`` (the LM sees no blank).  There is no end-of-sentence term.
+The stop test and the B[:W] / B[0] rules are unchanged and apply to the fused scores; the returned score is -(fused
+log p).  The LM's root token is ``lm_bos`` (default 1, the start token ``cli/train_lm.py`` prepends) from a zero state,
+or, when streaming, the last committed token once a stream has committed one.  ``lm_weight = length_bonus = 0`` gives
+tokens, scores and expansion counts bit-equal to the search without an LM.  A positive ``length_bonus`` can raise the
+pops per frame; hitting ``max_expansions`` stays an error.
 """
 import ctypes
 
@@ -97,7 +108,12 @@ def greedy_decode_batch(model, xs, xlen):
     return [seq[:int(n)] for seq, n in zip(toks, lens)], score
 
 
-def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=False):
+def _vocab(model):
+    return model.joint.joint[2].weight.shape[0]
+
+
+def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
+                      length_bonus=0.0, lm_bos=1):
     """Graves (2012) beam search as the reference's legacy ``Transducer.beam_search`` runs it
     (models.py:121-202), batched: every utterance keeps its own A / B sets and all open utterances
     advance one expansion per lockstep iteration on the device.  ``prefix=True`` is the reference's
@@ -107,7 +123,12 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)``: per
     utterance the FIRST hypothesis of the last frame's B list, which is what the reference returns
     (its ``sorted`` calls are no-ops).  ``max_expansions`` bounds the pops per utterance and frame
-    (default 8 W, at least 16); hitting it raises instead of truncating the search."""
+    (default 8 W, at least 16); hitting it raises instead of truncating the search.
+
+    ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion, see the module docstring (``lm`` needs
+    ``lm_weight``; ``prefix=True`` with an LM and an LM of another vocabulary raise ``ValueError``)."""
+    from .lm import check_fusion_args
+    check_fusion_args(lm, lm_weight, _vocab(model), prefix)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -119,7 +140,8 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     else:
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
-    return beam_search_enc(model, enc_out, lens, W, max_expansions, prefix)
+    return beam_search_enc(model, enc_out, lens, W, max_expansions, prefix, lm=lm, lm_weight=lm_weight,
+                           length_bonus=length_bonus, lm_bos=lm_bos)
 
 
 class _BeamNet:
@@ -165,17 +187,24 @@ def joint_rows(model, enc_out):
     return _BeamNet(model, enc_out.dtype).e1(enc_out.contiguous())
 
 
-def beam_search_enc(model, enc_out, lens=None, W=10, max_expansions=None, prefix=False):
+def beam_search_enc(model, enc_out, lens=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
+                    length_bonus=0.0, lm_bos=1):
     """``beam_search_batch`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
     encoder frames per utterance; None: all T)."""
+    from .lm import check_fusion_args
+    check_fusion_args(lm, lm_weight, _vocab(model), prefix)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
-    return beam_search_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, prefix)
+    return beam_search_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, prefix, lm=lm,
+                            lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos)
 
 
-def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, prefix=False):
+def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, prefix=False, *, lm=None,
+                     lm_weight=None, length_bonus=0.0, lm_bos=1):
     """``beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
     width P."""
+    from .lm import FusionLM, check_fusion_args
+    check_fusion_args(lm, lm_weight, _vocab(model), prefix)
     if W < 1:
         raise ValueError("beam width must be >= 1")
     cd = E1.dtype
@@ -183,8 +212,13 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     EM = int(max_expansions) if max_expansions else max(16, 8 * W)
     net = _BeamNet(model, cd)
     lib = _lib.load()
-    nbytes = lib.edgedict_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
-                                               int(bool(prefix)))
+    flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
+    if flm is None:
+        nbytes = lib.edgedict_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W,
+                                                   EM, int(bool(prefix)))
+    else:
+        nbytes = lib.edgedict_beam_workspace_bytes_lm(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2,
+                                                      W, EM, int(bool(prefix)), flm.ref())
     ws = torch.empty(nbytes, dtype=torch.uint8, device=E1.device)
     max_tokens = T * EM + 1
     tokens = np.zeros((B, max_tokens), dtype=np.int32)
@@ -192,11 +226,14 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     score = np.zeros(B, dtype=np.float64)
     nexp = ctypes.c_longlong(0)
     from .tokenizer import BOS
-    rc = lib.edgedict_beam_search(
-        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T,
-        lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM, int(bool(prefix)),
-        tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
-        score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp), _lib.ptr(ws), _lib.stream_ptr())
+    args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T,
+            lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM,
+            int(bool(prefix)), tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
+            score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
+    if flm is None:
+        rc = lib.edgedict_beam_search(*args, _lib.ptr(ws), _lib.stream_ptr())
+    else:
+        rc = lib.edgedict_beam_search_lm(*args, flm.ref(), _lib.ptr(ws), _lib.stream_ptr())
     _lib.check(rc, "beam_search")
     beam_search_batch.last_expansions = int(nexp.value)
     seqs = [tokens[b, :ntok[b]].astype(np.int64) for b in range(B)]
@@ -220,9 +257,16 @@ class StreamingBeamSearch:
     ``node_capacity`` bounds the token tree per stream: an advance whose streams could need more (live nodes +
     frames x max_expansions) raises ``RuntimeError`` before it runs; it never truncates.  The default leaves room for
     chunks of 32 frames on top of the live tree.
+
+    ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion as in ``beam_search_batch`` (module
+    docstring).  The survivors' LM states are carried in the device state beside the prediction network's; the LM's
+    root token is ``lm_bos`` until a stream has committed a token, then its last committed token.
     """
 
-    def __init__(self, model, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False):
+    def __init__(self, model, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False, *, lm=None,
+                 lm_weight=None, length_bonus=0.0, lm_bos=1):
+        from .lm import check_fusion_args
+        check_fusion_args(lm, lm_weight, _vocab(model), prefix)
         if prefix:
             raise ValueError("StreamingBeamSearch: prefix=True (the prefix-sum merge) is not supported when streaming")
         if W < 1:
@@ -237,12 +281,18 @@ class StreamingBeamSearch:
         from .stream import _compute_dtype
         self.cd = _compute_dtype(model)
         self.device = model.decoder.embed.weight.device
+        self.lm = lm
+        self._lm_args = (lm_weight, length_bonus, lm_bos)
         net = self._weights()
+        flm = self._fusion()
         lib = _lib.load()
-        sbytes = lib.edgedict_beam_stream_state_bytes(dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H,
-                                                      net.P2, self.W, self.EM, self.NC)
-        wbytes = lib.edgedict_beam_stream_workspace_bytes(dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L,
-                                                          net.H, net.P2, self.W, self.EM, self.NC)
+        dims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.EM, self.NC)
+        if flm is None:
+            sbytes = lib.edgedict_beam_stream_state_bytes(*dims)
+            wbytes = lib.edgedict_beam_stream_workspace_bytes(*dims)
+        else:
+            sbytes = lib.edgedict_beam_stream_state_bytes_lm(*dims, flm.ref())
+            wbytes = lib.edgedict_beam_stream_workspace_bytes_lm(*dims, flm.ref())
         self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
         self._commit_buf = np.zeros((self.S, self.NC), dtype=np.int32)
@@ -254,22 +304,30 @@ class StreamingBeamSearch:
         # converted once per parameter version by WEIGHTS (as run_search does); only the pointer bundle is rebuilt
         return _BeamNet(self.model, self.cd)
 
+    def _fusion(self):
+        from .lm import FusionLM
+        return None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args)
+
     def reset(self, mask=None):
         """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log."""
         from .tokenizer import BOS
         net = self._weights()
+        flm = self._fusion()
         lib = _lib.load()
         if mask is None:
             sel = np.ones(self.S, dtype=bool)
-            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), None, 0,
-                                                _lib.ptr(self._state), _lib.stream_ptr())
+            mh, on_host = None, 0
         else:
             m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
             sel = m.astype(bool).reshape(self.S)
-            mh = np.ascontiguousarray(sel, dtype=np.int32)
-            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS),
-                                                mh.ctypes.data_as(ctypes.c_void_p), 1, _lib.ptr(self._state),
-                                                _lib.stream_ptr())
+            mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
+        mp = None if mh is None else mh.ctypes.data_as(ctypes.c_void_p)
+        if flm is None:
+            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
+                                                _lib.ptr(self._state), _lib.stream_ptr())
+        else:
+            rc = lib.edgedict_beam_stream_reset_lm(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
+                                                   flm.ref(), _lib.ptr(self._state), _lib.stream_ptr())
         _lib.check(rc, "beam_stream_reset")
         if not hasattr(self, "_committed"):
             self._committed = [[] for _ in range(self.S)]
@@ -318,11 +376,16 @@ class StreamingBeamSearch:
         from .tokenizer import BOS
         lib = _lib.load()
         nexp = ctypes.c_longlong(0)
-        rc = lib.edgedict_beam_stream_advance(
-            dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S,
-            nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
-            self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p), self._ncommit.ctypes.data_as(ctypes.c_void_p),
-            ctypes.byref(nexp), _lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
+        args = (dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S,
+                nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
+                self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p),
+                self._ncommit.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
+        flm = self._fusion()
+        if flm is None:
+            rc = lib.edgedict_beam_stream_advance(*args, _lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
+        else:
+            rc = lib.edgedict_beam_stream_advance_lm(*args, flm.ref(), _lib.ptr(self._state), _lib.ptr(self._ws),
+                                                     _lib.stream_ptr())
         _lib.check(rc, "beam_stream_advance")
         self.last_expansions = int(nexp.value)
         for s in np.nonzero(self._ncommit)[0]:

@@ -953,11 +953,14 @@ class Transducer(nn.Module):
         from .decode import greedy_decode_batch
         return greedy_decode_batch(self, xs, xlen)
 
-    def beam_search(self, xs, xlen=None, W=10, prefix=False, max_expansions=None):
+    def beam_search(self, xs, xlen=None, W=10, prefix=False, max_expansions=None, *, lm=None, lm_weight=None,
+                    length_bonus=0.0, lm_bos=1):
         """Beam search of the reference's legacy model (models.py:121-202), batched; see
-        ``decode.beam_search_batch``.  ``prefix=True`` is its prefix-sum variant (:145-161)."""
+        ``decode.beam_search_batch``.  ``prefix=True`` is its prefix-sum variant (:145-161).  ``lm`` (an
+        ``edgedict_amd.lm.LMModel``) with ``lm_weight`` adds LM shallow fusion (``decode`` module docstring)."""
         from .decode import beam_search_batch
-        return beam_search_batch(self, xs, xlen, W, max_expansions, prefix=prefix)
+        return beam_search_batch(self, xs, xlen, W, max_expansions, prefix=prefix, lm=lm, lm_weight=lm_weight,
+                                 length_bonus=length_bonus, lm_bos=lm_bos)
 
 
 class _CausalConvFn(torch.autograd.Function):

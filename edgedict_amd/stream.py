@@ -305,18 +305,22 @@ class BatchedStreamBeamDecoder(StreamTransducerDecoder):
     ``BatchedStreamDecoder``; the search is ``decode.StreamingBeamSearch``, which keeps every stream's beams from chunk
     to chunk, so after any chunk a stream's ``best()`` is what the offline beam search over its audio so far returns.
     There is no ``<unk>`` rule: the offline beam search has none.  ``prefix=True`` is not supported when streaming
-    (``ValueError``)."""
+    (``ValueError``).  ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion, as in
+    ``decode.StreamingBeamSearch``."""
 
     def __init__(self, transducer, flags, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False,
-                 dither=None):
-        from .decode import StreamingBeamSearch
+                 dither=None, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1):
+        from .decode import StreamingBeamSearch, _vocab
+        from .lm import check_fusion_args
+        check_fusion_args(lm, lm_weight, _vocab(transducer), prefix)
         self.model = transducer.eval()
         self.flags = flags
         self.S = n_streams
         dev = transducer.decoder.embed.weight.device
         self.device = dev
         self.search = StreamingBeamSearch(transducer, n_streams, W=W, max_expansions=max_expansions,
-                                          node_capacity=node_capacity, prefix=prefix)
+                                          node_capacity=node_capacity, prefix=prefix, lm=lm, lm_weight=lm_weight,
+                                          length_bonus=length_bonus, lm_bos=lm_bos)
         self.transform = StackedLogFbank(
             n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
             hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,

@@ -694,6 +694,88 @@ int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, con
                               double* score_host, long long* ncommitted_host,
                               long long* expansions_host, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * LM shallow fusion for both beam searches: an external LSTM language model (the reference's LMModel,
+ * models.py:224-261: Embedding -> nn.LSTM stack -> Linear -> log_softmax, trained by cli/train_lm.py on
+ * the transducer's vocabulary) runs one step per expansion beside the prediction network.  A popped
+ * hypothesis y* (fp64 score `base`) feeds its last token to the LM from y*'s stored LM state; with
+ * lp_lm = log_softmax(LM logits) (fp32, all ntoken entries) the children are scored, in fp64 and in
+ * exactly this order,
+ *   non-blank child k:  base + (double)lp_rnnt[k] + (weight * (double)lp_lm[k] + length_bonus)
+ *   blank child:        base + (double)lp_rnnt[blank]                       (the LM sees no blank)
+ * No end-of-sentence term (the LM has no EOS token).  The stop test, B[:W] and B[0] are the plain
+ * search's, applied to the fused scores; the returned score is -(fused logp).  The root of a tree the
+ * LM has never seen feeds `bos` (cli/train_lm.py:42 prepends 1) from a zero state (init_hidden); a
+ * stream that has committed tokens feeds its last committed token, as the prediction network does.
+ * weight = length_bonus = 0 gives tokens, scores and expansion counts bit-equal to the plain search.
+ * A positive length_bonus can raise the pops per frame: hitting max_expansions stays an error.
+ *   L, E, H, V   layers, embedding width, hidden width, ntoken (must equal the transducer's V)
+ *   emb          [V, E] in emb_dtype;  w_ih / w_hh / b_ih / b_hh: HOST arrays [L] of DEVICE pointers
+ *                ([4H, E or H], [4H, H] in the search's dtype; fp32 [4H]);  Wo [V, H] dtype, bo fp32 [V]
+ * The *_lm entry points take the plain ones' arguments plus `lm` (null: exactly the plain call).
+ * prefix = 1 with an LM is refused (it would need LM log-probs stored per token-tree node).  The
+ * streaming state of the _lm form appends the survivors' LM (h, c) behind the plain layout, so
+ * edgedict_beam_stream_read serves both; reset and advance of such a state must use the _lm forms.
+ * beam_lm_struct_bytes: sizeof(edgedict_beam_lm_t), for bindings that mirror it.
+ */
+typedef struct edgedict_beam_lm_t {
+    int L, E, H, V;
+    const void* emb;
+    int emb_dtype;
+    const void* const* w_ih;
+    const void* const* w_hh;
+    const float* const* b_ih;
+    const float* const* b_hh;
+    const void* Wo;
+    const float* bo;
+    int bos;
+    double weight;
+    double length_bonus;
+} edgedict_beam_lm_t;
+
+size_t edgedict_beam_lm_struct_bytes(void);
+size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H,
+                                        int P2, int W, int max_expansions, int prefix,
+                                        const edgedict_beam_lm_t* lm);
+int edgedict_beam_search_lm(int dtype, const void* E1, long long e_row_stride,
+                            long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
+                            const void* W1d, long long ldw1, const float* b1, int P2,
+                            const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
+                            int E, int L, const void* const* w_ih, const void* const* w_hh,
+                            const float* const* b_ih, const float* const* b_hh, int H,
+                            const void* Wp, const float* bp, int blank, int bos, int W,
+                            int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
+                            int32_t* ntokens_host, double* score_host, long long* expansions_host,
+                            const edgedict_beam_lm_t* lm, void* workspace, void* stream);
+size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H,
+                                           int P2, int W, int max_expansions, int node_capacity,
+                                           const edgedict_beam_lm_t* lm);
+size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H,
+                                               int P2, int W, int max_expansions,
+                                               int node_capacity, const edgedict_beam_lm_t* lm);
+int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos,
+                                  const int32_t* mask, int mask_on_host,
+                                  const edgedict_beam_lm_t* lm, void* state, void* stream);
+int edgedict_beam_stream_advance_lm(int dtype, const void* E1, long long e_row_stride,
+                                    long long e_frame_stride, int S, const int32_t* n_frames_host,
+                                    int J, const void* W1d, long long ldw1, const float* b1, int P2,
+                                    const void* W2, const float* b2, int V, const void* emb,
+                                    int emb_dtype, int E, int L, const void* const* w_ih,
+                                    const void* const* w_hh, const float* const* b_ih,
+                                    const float* const* b_hh, int H, const void* Wp,
+                                    const float* bp, int blank, int bos, int W, int max_expansions,
+                                    int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+                                    long long* expansions_host, const edgedict_beam_lm_t* lm,
+                                    void* state, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Row log-softmax (LMModel.forward's F.log_softmax(decoded, dim=-1), models.py:251):
+ *   x fp32 or bf16 (x_dtype) [M, N] rows of leading dimension ldx;  y fp32 [M, N] contiguous.
+ *   y = (x - max) - log(sum exp(x - max)) per row, fp32 arithmetic.
+ */
+int edgedict_log_softmax_rows(int x_dtype, const void* x, long long ldx, float* y, int M, int N,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
