@@ -11,35 +11,11 @@
 // the MFMA GEMM (gemm.hip), the LSTM cell (lstm.hip) and three tiny kernels from this file
 // (broadcast-add+tanh on one frame, row-wise pick, masked state commit).  Nothing returns to the
 // host between frames; token ids and scores stay on the device until the caller reads them.
-#include "common.hpp"
+#include "decode_net.hpp"
 
 #include <algorithm>
-#include <functional>
+#include <optional>
 #include <vector>
-
-// decode_fused.hip: a frame as five fused launches (bf16 and fp32)
-bool ed_decode_fused_ok(int dtype, int emb_dtype, int J, int V, int E, int H, int P2);
-size_t ed_decode_fused_ws_bytes(int B, int V);
-int ed_decode_fused_frame(int dtype, const void* E1t, long long e_row_stride, int B, int J, const void* W1d,
-                          long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                          const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                          const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                          const void* Wp, const float* bp, float* h_state, float* c_state, void* dec_out, int blank,
-                          int unk, int32_t* tokens_out, long long tok_stride, int t, float* score, void* hid, void* parts,
-                          int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, hipStream_t s);
-int ed_decode_fused_beam_step(int dtype, const void* E1t, long long e_row_stride, int B, int J, const void* W1d,
-                              long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                              const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                              const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                              const void* Wp, const float* bp, const float* h_state, const float* c_state,
-                              const int32_t* pred, void* dec_new, void* hid, float* logits, float* h_new, float* c_new,
-                              void* Y0, void* Y1, hipStream_t s);
-bool ed_decode_fused_lm_ok(int dtype, int emb_dtype, int V, int E, int H);
-int ed_decode_fused_lm_step(int dtype, int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                            const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                            const void* Wo, const float* bo, const float* h_state, const float* c_state,
-                            const int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, float* logits,
-                            hipStream_t s);
 
 namespace {
 
@@ -135,30 +111,66 @@ __global__ void commit_kernel(const int32_t* __restrict__ pred, int blank, T* __
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+// One step of an LstmNet composed from the general kernels: the embedding of pred[b], per layer the input product and
+// the LSTM cell from (h_state, c_state) [L, B, H] into u.h_new / u.c_new, then out [B, O] (out_dtype) = y_L Wo^T + bo
+int composed_lstm_step(int dtype, int B, const LstmNet& n, const int32_t* pred, const float* h_state,
+                       const float* c_state, const StepBufs& u, int out_dtype, void* out, hipStream_t s) {
+    const int H = n.H;
+    int rc;
+    if ((rc = edgedict_embedding_fwd(dtype, n.emb_dtype, pred, 1, n.emb, u.x, B, 1, n.E, n.V, 0, 0, s))) return rc;
+    const void* xin = u.x;
+    int xin_dim = n.E;
+    for (int k = 0; k < n.L; ++k) {
+        if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, n.w_ih[k], xin_dim, 1, u.G, 4 * H, B, 4 * H, xin_dim,
+                                n.b_ih[k], n.b_hh[k], 0, 1, s)))
+            return rc;
+        if ((rc = edgedict_lstm_forward(dtype, u.G, u.Hprev, u.Y[k & 1], u.Cst, n.w_hh[k], nullptr,
+                                        h_state + (size_t)k * B * H, c_state + (size_t)k * B * H,
+                                        u.h_new + (size_t)k * B * H, u.c_new + (size_t)k * B * H, B, 1, H, nullptr, s)))
+            return rc;
+        xin = u.Y[k & 1];
+        xin_dim = H;
+    }
+    return edgedict_gemm(dtype, out_dtype, xin, H, 1, n.Wo, H, 1, out, n.O, B, n.O, H, n.bo, nullptr, 0, 1, s);
+}
 
-struct Ws {
-    size_t D1, hid, logits, pred, x, G, Hprev, Y0, Y1, Cst, h_new, c_new, dec_new, total;
-};
-inline Ws ws_layout(int esz, int B, int J, int V, int E, int L, int H, int P2) {
-    Ws w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
-    w.D1 = take((size_t)B * J * esz);
-    w.hid = take((size_t)B * J * esz);
-    w.logits = take((size_t)B * V * 4);
-    w.pred = take((size_t)B * 4);
-    w.x = take((size_t)B * E * esz);
-    w.G = take((size_t)B * 4 * H * esz);
-    w.Hprev = take((size_t)B * H * esz);
-    w.Y0 = take((size_t)B * H * esz);
-    w.Y1 = take((size_t)B * H * esz);
-    w.Cst = take((size_t)B * H * 4);
-    w.h_new = take((size_t)L * B * H * 4);
-    w.c_new = take((size_t)L * B * H * 4);
-    w.dec_new = take((size_t)B * P2 * esz);
-    w.total = o;
-    return w;
+// The joint on the frame e1t composed from the general kernels, for the prediction-network output `dec` [B, P2]:
+// D1 = dec W1d^T + b1;  hid = tanh(E1[:, t] + D1);  logits (fp32)
+int composed_joint(const SearchNet& net, const char* e1t, const void* dec, const StepBufs& u, hipStream_t s) {
+    const int dtype = net.dtype, B = net.B, J = net.J;
+    int rc;
+    if ((rc = edgedict_gemm(dtype, dtype, dec, net.P2, 1, net.W1d, net.ldw1, 1, u.D1, J, B, J, net.P2, net.b1, nullptr, 0,
+                            1, s)))
+        return rc;
+    dispatch(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(add_tanh_rows<T>, dim3(ed_grid_for((long long)B * J, 256)), dim3(256), 0, s, (const T*)e1t,
+                           net.e_row_stride, (const T*)u.D1, (T*)u.hid, B, J);
+    });
+    return edgedict_gemm(dtype, ED_F32, u.hid, J, 1, net.W2, J, 1, u.logits, net.V, B, net.V, J, net.b2, nullptr, 0, 1, s);
+}
+
+// The argument checks the searches share, in the order they have always run: dtype, shape, null pointers, and for the
+// beam searches blank / bos.  shape_ok / ptrs_ok carry the caller's own conditions, shape_note the tail of its message.
+int check_net(const SearchNet& n, const char* what, bool shape_ok, const char* shape_note, bool ptrs_ok, bool beam) {
+    const LstmNet& p = n.pred;
+    ED_CHECK_ARG(n.dtype == ED_F32 || n.dtype == ED_BF16, "%s: bad dtype", what);
+    ED_CHECK_ARG(shape_ok && n.B > 0 && n.J > 0 && n.V > 0 && p.L > 0 && p.H > 0 && n.P2 > 0 && p.E > 0, "%s: bad shape%s",
+                 what, shape_note);
+    ED_CHECK_ARG(ptrs_ok && n.W1d && n.b1 && n.W2 && n.b2 && p.emb && p.w_ih && p.w_hh && p.b_ih && p.b_hh && p.Wo && p.bo,
+                 "%s: null pointer", what);
+    ED_CHECK_ARG(!beam || (n.blank >= 0 && n.blank < n.V && n.bos >= 0 && n.bos < n.V),
+                 "%s: blank/bos outside the vocabulary", what);
+    return ED_OK;
+}
+
+// the shapes alone, for the size queries
+SearchNet net_dims(int dtype, int B, int J, int V, int E, int L, int H, int P2) {
+    SearchNet n{};
+    n.dtype = dtype; n.esz = dtype == ED_F32 ? 4 : 2;
+    n.B = B; n.J = J; n.V = V; n.P2 = P2;
+    n.pred.V = V; n.pred.E = E; n.pred.L = L; n.pred.H = H; n.pred.O = P2;
+    return n;
 }
 
 }  // namespace
@@ -166,7 +178,7 @@ inline Ws ws_layout(int esz, int B, int J, int V, int E, int L, int H, int P2) {
 extern "C" size_t edgedict_greedy_workspace_bytes(int dtype, int B, int J, int V, int E, int L,
                                                   int H, int P2) {
     if (B <= 0) return 0;
-    return ws_layout(dtype == ED_F32 ? 4 : 2, B, J, V, E, L, H, P2).total;
+    return ws_layout(net_dims(dtype, B, J, V, E, L, H, P2)).total;
 }
 
 extern "C" int edgedict_greedy_decode(
@@ -177,28 +189,12 @@ extern "C" int edgedict_greedy_decode(
     const float* const* b_hh, int H, const void* Wp, const float* bp, float* h_state,
     float* c_state, void* dec_out, int blank, int unk, int32_t* tokens_out, int tok_stride,
     float* score, void* workspace, void* stream_) {
-    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "greedy_decode: bad dtype");
-    ED_CHECK_ARG(B > 0 && T >= 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0,
-                 "greedy_decode: bad shape");
-    ED_CHECK_ARG(E1 && W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp && bp &&
-                     h_state && c_state && dec_out && workspace,
-                 "greedy_decode: null pointer");
+    const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V,
+                        {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, 0, 0, 0, 0};
+    if (int rc = check_net(net, "greedy_decode", T >= 0, "", E1 && h_state && c_state && dec_out && workspace, false))
+        return rc;
     hipStream_t s = (hipStream_t)stream_;
-    const int esz = dtype == ED_F32 ? 4 : 2;
-    const Ws w = ws_layout(esz, B, J, V, E, L, H, P2);
-    char* p = (char*)workspace;
-    void* D1 = p + w.D1;
-    void* hid = p + w.hid;
-    float* logits = (float*)(p + w.logits);
-    int32_t* pred = (int32_t*)(p + w.pred);
-    void* x = p + w.x;
-    void* G = p + w.G;
-    void* Hprev = p + w.Hprev;
-    void* Y[2] = {p + w.Y0, p + w.Y1};
-    float* Cst = (float*)(p + w.Cst);
-    float* h_new = (float*)(p + w.h_new);
-    float* c_new = (float*)(p + w.c_new);
-    void* dec_new = p + w.dec_new;
+    const StepBufs u = bind((char*)workspace, ws_layout(net));
 
     // a frame is five fused launches (decode_fused.hip; the slice partials live in the logits buffer, which the fused
     // frame never fills); odd shapes: composed from the general kernels below
@@ -206,62 +202,25 @@ extern "C" int edgedict_greedy_decode(
                        align256((size_t)B * V * 4) >= ed_decode_fused_ws_bytes(B, V);
     for (int t = 0; t < T; ++t) {
         int rc;
+        const char* e1t = net.frame(t);
         if (fused) {
-            const char* e1f = (const char*)E1 + (size_t)t * e_frame_stride * esz;
-            if ((rc = ed_decode_fused_frame(dtype, e1f, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype, E, L,
-                                            w_ih, w_hh, b_ih, b_hh, H, Wp, bp, h_state, c_state, dec_out, blank, unk,
-                                            tokens_out, tok_stride, t, score, hid, logits, pred, h_new, c_new, Y[0],
-                                            Y[1], s)))
+            if ((rc = ed_decode_fused_frame(net, e1t, h_state, c_state, dec_out, {unk, tokens_out, tok_stride, t, score}, u,
+                                            s)))
                 return rc;
             continue;
         }
-        // joint on frame t:  D1 = dec_out W1d^T + b1;  hid = tanh(E1[:,t] + D1);  logits (fp32)
-        if ((rc = edgedict_gemm(dtype, dtype, dec_out, P2, 1, W1d, ldw1, 1, D1, J, B, J, P2, b1,
-                                nullptr, 0, 1, s)))
-            return rc;
-        const char* e1t = (const char*)E1 + (size_t)t * e_frame_stride * esz;
-        if (dtype == ED_F32)
-            hipLaunchKernelGGL(add_tanh_rows<float>, dim3(ed_grid_for((long long)B * J, 256)),
-                               dim3(256), 0, s, (const float*)e1t, e_row_stride, (const float*)D1,
-                               (float*)hid, B, J);
-        else
-            hipLaunchKernelGGL(add_tanh_rows<bf16_t>, dim3(ed_grid_for((long long)B * J, 256)),
-                               dim3(256), 0, s, (const bf16_t*)e1t, e_row_stride,
-                               (const bf16_t*)D1, (bf16_t*)hid, B, J);
-        if ((rc = edgedict_gemm(dtype, ED_F32, hid, J, 1, W2, J, 1, logits, V, B, V, J, b2, nullptr,
-                                0, 1, s)))
-            return rc;
-        hipLaunchKernelGGL(pick_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, B, V, unk, pred,
-                           tokens_out, tok_stride, t, score, blank);
+        // joint on frame t, then the pick
+        if ((rc = composed_joint(net, e1t, dec_out, u, s))) return rc;
+        hipLaunchKernelGGL(pick_kernel, dim3((B + 3) / 4), dim3(256), 0, s, u.logits, B, V, unk, u.pred, tokens_out,
+                           tok_stride, t, score, blank);
         // prediction network step on the picked symbols (for every row, committed where != blank)
-        if ((rc = edgedict_embedding_fwd(dtype, emb_dtype, pred, 1, emb, x, B, 1, E, V, 0, 0, s)))
-            return rc;
-        const void* xin = x;
-        int xin_dim = E;
-        for (int k = 0; k < L; ++k) {
-            if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, w_ih[k], xin_dim, 1, G, 4 * H, B,
-                                    4 * H, xin_dim, b_ih[k], b_hh[k], 0, 1, s)))
-                return rc;
-            if ((rc = edgedict_lstm_forward(dtype, G, Hprev, Y[k & 1], Cst, w_hh[k], nullptr,
-                                            h_state + (size_t)k * B * H, c_state + (size_t)k * B * H,
-                                            h_new + (size_t)k * B * H, c_new + (size_t)k * B * H, B,
-                                            1, H, nullptr, s)))
-                return rc;
-            xin = Y[k & 1];
-            xin_dim = H;
-        }
-        if ((rc = edgedict_gemm(dtype, dtype, xin, H, 1, Wp, H, 1, dec_new, P2, B, P2, H, bp,
-                                nullptr, 0, 1, s)))
-            return rc;
+        if ((rc = composed_lstm_step(dtype, B, net.pred, u.pred, h_state, c_state, u, dtype, u.dec_new, s))) return rc;
         const long long n = (long long)B * P2 + (long long)L * B * H;
-        if (dtype == ED_F32)
-            hipLaunchKernelGGL(commit_kernel<float>, dim3(ed_grid_for(n, 256)), dim3(256), 0, s,
-                               pred, blank, (float*)dec_out, (const float*)dec_new, P2, h_state,
-                               h_new, c_state, c_new, L, B, H);
-        else
-            hipLaunchKernelGGL(commit_kernel<bf16_t>, dim3(ed_grid_for(n, 256)), dim3(256), 0, s,
-                               pred, blank, (bf16_t*)dec_out, (const bf16_t*)dec_new, P2, h_state,
-                               h_new, c_state, c_new, L, B, H);
+        dispatch(dtype, [&](auto tag) {
+            using ET = decltype(tag);
+            hipLaunchKernelGGL(commit_kernel<ET>, dim3(ed_grid_for(n, 256)), dim3(256), 0, s, u.pred, blank, (ET*)dec_out,
+                               (const ET*)u.dec_new, P2, h_state, u.h_new, c_state, u.c_new, L, B, H);
+        });
     }
     ED_CHECK_LAUNCH("greedy_decode");
     return ED_OK;
@@ -270,7 +229,7 @@ extern "C" int edgedict_greedy_decode(
 
 // =====================================================================================
 // Beam search (Graves 2012) as the reference's legacy Transducer.beam_search runs it
-// (/root/reference/models.py:121-202, prefix=False), for a batch of utterances in lockstep.
+// (models.py:121-202, prefix=False), for a batch of utterances in lockstep.
 //
 // Per utterance and frame the reference keeps two Python lists: A (hypotheses still to expand) and
 // B (hypotheses that emitted blank in this frame).  Here A is a score POOL in list order:
@@ -713,51 +672,74 @@ __global__ __launch_bounds__(256) void beam_query_logp(const float* __restrict__
 }
 constexpr int BEAM_QMAX = 1024;      // queries per batch of the prefix branch
 
+template <typename T>
+inline T* at(char* base, size_t off) { return (T*)(base + off); }
+
+// The survivors of the previous frame (the list B) and the token tree: in the per-call workspace (offline search) or in
+// the persistent state of the streams
+struct SurvivorOffs {
+    size_t bp_logp, bp_node, n_bp, bp_h0, bp_c0, nodes, n_nodes;
+};
+
+// per-call workspace of both beam searches
 struct BeamWs {
     Ws step;   // the greedy loop's per-iteration buffers (prediction-network step + joint)
     size_t h_state, c_state;
-    size_t pool, bp_logp, bp_node, n_bp, bp_h0, bp_h1, bp_c0, bp_c1, bn_logp, bn_node, bn_ref, n_b, max_b, blk_max, blk_arg,
-        exp_node, exp_ref, exp_logp, e_count, f_h, f_c, nodes, n_nodes, open, lens, flags, total_exp, total;
+    SurvivorOffs sv;                                                                   // offline only
+    size_t pool, bp_h1, bp_c1, bn_logp, bn_node, bn_ref, n_b, max_b, blk_max, blk_arg, exp_node, exp_ref, exp_logp, e_count,
+        f_h, f_c, open, lens, flags, total_exp;
+    size_t c_old, c_mark, commit, n_commit;                                            // streaming only: compaction scratch
     size_t node_pred, q_row, q_node, q_tok, q_pred, q_D1, q_hid, q_logits, q_out;      // prefix = 1 only
+    size_t total;
 };
-inline BeamWs beam_layout(int esz, int B, int T, int J, int V, int E, int L, int H, int P2, int W, int EM, int prefix) {
-    BeamWs w;
-    w.step = ws_layout(esz, B, J, V, E, L, H, P2);
+// nodes = token-tree capacity per utterance.  stream: the survivors and the tree live in the state
+// (beam_stream_state_layout) and the compaction scratch is appended.  The order of the take() calls IS the layout callers
+// have sized their buffers for (tests/golden/search_sizes.json): leave it alone.
+inline BeamWs beam_layout(const SearchNet& n, size_t nodes, int prefix, bool stream) {
+    BeamWs w{};
+    w.step = ws_layout(n);
     size_t o = w.step.total;
     auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
-    const size_t LH = (size_t)L * H, NODES = (size_t)T * EM + 1;
-    w.h_state = take((size_t)B * LH * 4);
-    w.c_state = take((size_t)B * LH * 4);
-    w.pool = take((size_t)B * (W + (size_t)EM * V) * 8);
-    w.bp_logp = take((size_t)B * W * 8);
-    w.bp_node = take((size_t)B * W * 4);
-    w.n_bp = take((size_t)B * 4);
-    w.bp_h0 = take((size_t)B * W * LH * 4);
-    w.bp_h1 = take((size_t)B * W * LH * 4);
-    w.bp_c0 = take((size_t)B * W * LH * 4);
-    w.bp_c1 = take((size_t)B * W * LH * 4);
-    w.bn_logp = take((size_t)B * W * 8);
-    w.bn_node = take((size_t)B * W * 4);
-    w.bn_ref = take((size_t)B * W * 4);
-    w.n_b = take((size_t)B * 4);
-    w.max_b = take((size_t)B * 8);
-    w.blk_max = take((size_t)B * (EM + 1) * 8);
-    w.blk_arg = take((size_t)B * (EM + 1) * 4);
-    w.exp_node = take((size_t)B * EM * 4);
-    w.exp_ref = take((size_t)B * EM * 4);
-    w.exp_logp = take((size_t)B * EM * 8);
-    w.e_count = take((size_t)B * 4);
-    w.f_h = take((size_t)B * EM * LH * 4);
-    w.f_c = take((size_t)B * EM * LH * 4);
-    w.nodes = take((size_t)B * NODES * 8);
-    w.n_nodes = take((size_t)B * 4);
-    w.open = take((size_t)B * 4);
-    w.lens = take((size_t)B * 4);
+    auto own = [&](size_t bytes) { return stream ? (size_t)0 : take(bytes); };
+    const size_t B = n.B, W = n.W, EM = n.EM, V = n.V, LH = (size_t)n.pred.L * n.pred.H;
+    w.h_state = take(B * LH * 4);
+    w.c_state = take(B * LH * 4);
+    w.pool = take(B * (W + EM * V) * 8);
+    w.sv.bp_logp = own(B * W * 8);
+    w.sv.bp_node = own(B * W * 4);
+    w.sv.n_bp = own(B * 4);
+    w.sv.bp_h0 = own(B * W * LH * 4);
+    w.bp_h1 = take(B * W * LH * 4);
+    w.sv.bp_c0 = own(B * W * LH * 4);
+    w.bp_c1 = take(B * W * LH * 4);
+    w.bn_logp = take(B * W * 8);
+    w.bn_node = take(B * W * 4);
+    w.bn_ref = take(B * W * 4);
+    w.n_b = take(B * 4);
+    w.max_b = take(B * 8);
+    w.blk_max = take(B * (EM + 1) * 8);
+    w.blk_arg = take(B * (EM + 1) * 4);
+    w.exp_node = take(B * EM * 4);
+    w.exp_ref = take(B * EM * 4);
+    w.exp_logp = take(B * EM * 8);
+    w.e_count = take(B * 4);
+    w.f_h = take(B * EM * LH * 4);
+    w.f_c = take(B * EM * LH * 4);
+    w.sv.nodes = own(B * nodes * 8);
+    w.sv.n_nodes = own(B * 4);
+    w.open = take(B * 4);
+    w.lens = take(B * 4);
     w.flags = take(8);
     w.total_exp = take(8);
-    w.node_pred = w.q_row = w.q_node = w.q_tok = w.q_pred = w.q_D1 = w.q_hid = w.q_logits = w.q_out = 0;
+    if (stream) {
+        w.c_old = take(B * nodes * 8);
+        w.c_mark = take(B * nodes * 4);
+        w.commit = take(B * nodes * 4);
+        w.n_commit = take(B * 4);
+    }
     if (prefix) {
-        w.node_pred = take((size_t)B * (NODES + 1) * P2 * esz);
+        const size_t esz = n.esz, J = n.J, P2 = n.P2;
+        w.node_pred = take(B * (nodes + 1) * P2 * esz);
         w.q_row = take((size_t)BEAM_QMAX * 4);
         w.q_node = take((size_t)BEAM_QMAX * 4);
         w.q_tok = take((size_t)BEAM_QMAX * 4);
@@ -771,78 +753,151 @@ inline BeamWs beam_layout(int esz, int B, int T, int J, int V, int E, int L, int
     return w;
 }
 
-// LM shallow fusion: the LM step's buffers and the LM state pools, appended behind a search's workspace (offsets from
-// `base`, a multiple of 256).  with_bp0: the survivors' buffer [0] lives here too (offline); the streaming search
-// keeps it in its persistent state (beam_stream_lm_state_layout).
-struct LmWs {
-    size_t pred, h_state, c_state, h_new, c_new, x, G, Hprev, Y0, Y1, Cst, logits, bp_h0, bp_c0, bp_h1, bp_c1, f_h, f_c,
-        total;
+// persistent state, per stream; with an LM the survivors' LM (h, c) [S][W][lm_L][lm_H] are appended behind the plain
+// state (so that edgedict_beam_stream_read serves both forms)
+struct BeamStreamState {
+    SurvivorOffs sv;
+    size_t root_tok, n_committed, n_exp, lm_bp_h, lm_bp_c, total;
 };
-inline LmWs lm_ws_layout(size_t base, int esz, int B, int V, int L, int E, int H, int W, int EM, bool with_bp0) {
-    LmWs w;
-    size_t o = base;
+inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int NC, const edgedict_beam_lm_t* lm) {
+    BeamStreamState w{};
+    size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
     const size_t LH = (size_t)L * H;
-    w.pred = take((size_t)B * 4);
-    w.h_state = take((size_t)B * LH * 4);
-    w.c_state = take((size_t)B * LH * 4);
-    w.h_new = take((size_t)B * LH * 4);
-    w.c_new = take((size_t)B * LH * 4);
-    w.x = take((size_t)B * E * esz);
-    w.G = take((size_t)B * 4 * H * esz);
-    w.Hprev = take((size_t)B * H * esz);
-    w.Y0 = take((size_t)B * H * esz);
-    w.Y1 = take((size_t)B * H * esz);
-    w.Cst = take((size_t)B * H * 4);
-    w.logits = take((size_t)B * V * 4);
-    w.bp_h0 = w.bp_c0 = 0;
-    if (with_bp0) {
-        w.bp_h0 = take((size_t)B * W * LH * 4);
-        w.bp_c0 = take((size_t)B * W * LH * 4);
+    w.sv.bp_logp = take((size_t)S * W * 8);
+    w.sv.bp_node = take((size_t)S * W * 4);
+    w.sv.n_bp = take((size_t)S * 4);
+    w.sv.bp_h0 = take((size_t)S * W * LH * 4);
+    w.sv.bp_c0 = take((size_t)S * W * LH * 4);
+    w.sv.nodes = take((size_t)S * NC * 8);
+    w.sv.n_nodes = take((size_t)S * 4);
+    w.root_tok = take((size_t)S * 4);
+    w.n_committed = take((size_t)S * 8);
+    w.n_exp = take((size_t)S * 8);
+    if (lm) {
+        w.lm_bp_h = take((size_t)S * W * lm->L * lm->H * 4);
+        w.lm_bp_c = take((size_t)S * W * lm->L * lm->H * 4);
     }
-    w.bp_h1 = take((size_t)B * W * LH * 4);
-    w.bp_c1 = take((size_t)B * W * LH * 4);
-    w.f_h = take((size_t)B * EM * LH * 4);
-    w.f_c = take((size_t)B * EM * LH * 4);
     w.total = o;
     return w;
 }
 
-// the LM's buffers of one search call (null when there is no LM)
-struct LmBufs {
-    const edgedict_beam_lm_t* lm;
-    float *h_new, *c_new, *Cst, *logits;
-    void *x, *G, *Hprev, *Y[2];
+// LM shallow fusion: the LM step's buffers and the LM state pools, appended behind a search's workspace (offsets from
+// `base`, a multiple of 256).  with_bp0: the survivors' buffer [0] lives here too (offline); the streaming search
+// keeps it in its persistent state.
+struct LmWs {
+    size_t pred, h_state, c_state, h_new, c_new, x, G, Hprev, Y0, Y1, Cst, logits, bp_h0, bp_c0, bp_h1, bp_c1, f_h, f_c,
+        total;
 };
-inline LmBufs lm_bufs(const edgedict_beam_lm_t* lm, char* p, const LmWs& w) {
-    LmBufs u{};
-    u.lm = lm;
-    if (!lm) return u;
-    u.h_new = (float*)(p + w.h_new);
-    u.c_new = (float*)(p + w.c_new);
-    u.Cst = (float*)(p + w.Cst);
-    u.logits = (float*)(p + w.logits);
-    u.x = p + w.x;
-    u.G = p + w.G;
-    u.Hprev = p + w.Hprev;
-    u.Y[0] = p + w.Y0;
-    u.Y[1] = p + w.Y1;
-    return u;
+inline LmWs lm_ws_layout(size_t base, const SearchNet& n, const edgedict_beam_lm_t& lm, bool with_bp0) {
+    LmWs w;
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    const size_t B = n.B, W = n.W, EM = n.EM, esz = n.esz, H = lm.H, LH = (size_t)lm.L * lm.H;
+    w.pred = take(B * 4);
+    w.h_state = take(B * LH * 4);
+    w.c_state = take(B * LH * 4);
+    w.h_new = take(B * LH * 4);
+    w.c_new = take(B * LH * 4);
+    w.x = take(B * lm.E * esz);
+    w.G = take(B * 4 * H * esz);
+    w.Hprev = take(B * H * esz);
+    w.Y0 = take(B * H * esz);
+    w.Y1 = take(B * H * esz);
+    w.Cst = take(B * H * 4);
+    w.logits = take(B * n.V * 4);
+    w.bp_h0 = w.bp_c0 = 0;
+    if (with_bp0) {
+        w.bp_h0 = take(B * W * LH * 4);
+        w.bp_c0 = take(B * W * LH * 4);
+    }
+    w.bp_h1 = take(B * W * LH * 4);
+    w.bp_c1 = take(B * W * LH * 4);
+    w.f_h = take(B * EM * LH * 4);
+    w.f_c = take(B * EM * LH * 4);
+    w.total = o;
+    return w;
 }
-// the LM fields of the pointer bundle that live in the workspace (the survivors' buffer [0] is set by the caller)
-inline void lm_ptrs(BeamPtrs& q, const edgedict_beam_lm_t* lm, char* p, const LmWs& w) {
-    if (!lm) return;
-    q.lm_bp_h[1] = (float*)(p + w.bp_h1);
-    q.lm_bp_c[1] = (float*)(p + w.bp_c1);
-    q.lm_f_h = (float*)(p + w.f_h);
-    q.lm_f_c = (float*)(p + w.f_c);
-    q.lm_pred = (int32_t*)(p + w.pred);
-    q.lm_h_state = (float*)(p + w.h_state);
-    q.lm_c_state = (float*)(p + w.c_state);
+
+// Everything one beam-search call points at: the kernels' bundle, the host-side step buffers, and the LM's
+struct BeamBufs {
+    BeamPtrs q;
+    StepBufs u;                      // prediction-network step + joint
+    float *h_state, *c_state;        // [L][B][H] state of the popped hypotheses
+    void* node_pred;                 // prefix = 1: the prediction stored per token-tree node (else null)
+    const edgedict_beam_lm_t* lm;    // null: no LM
+    LstmNet lm_net;
+    StepBufs lmu;                    // the LM step's buffers (its symbol and state are q.lm_pred, q.lm_h/c_state)
+};
+// p / w: workspace and its layout (null: only the state is bound - reset);  st / a: the streams' persistent state (null:
+// offline, the survivors live in the workspace);  lm / lw: the LM and its part of the workspace
+BeamBufs bind_beam_ptrs(char* p, const BeamWs* w, char* st, const BeamStreamState* a, const edgedict_beam_lm_t* lm,
+                        const LmWs* lw) {
+    BeamBufs bb{};
+    BeamPtrs& q = bb.q;
+    if (p) {
+        bb.u = bind(p, w->step);
+        bb.h_state = at<float>(p, w->h_state);
+        bb.c_state = at<float>(p, w->c_state);
+        if (w->node_pred) bb.node_pred = p + w->node_pred;
+        q.pool = at<double>(p, w->pool);
+        q.bp_h[1] = at<float>(p, w->bp_h1);
+        q.bp_c[1] = at<float>(p, w->bp_c1);
+        q.bn_logp = at<double>(p, w->bn_logp);
+        q.bn_node = at<int32_t>(p, w->bn_node);
+        q.bn_ref = at<int32_t>(p, w->bn_ref);
+        q.n_b = at<int32_t>(p, w->n_b);
+        q.max_b = at<double>(p, w->max_b);
+        q.blk_max = at<double>(p, w->blk_max);
+        q.blk_arg = at<int32_t>(p, w->blk_arg);
+        q.exp_node = at<int32_t>(p, w->exp_node);
+        q.exp_ref = at<int32_t>(p, w->exp_ref);
+        q.exp_logp = at<double>(p, w->exp_logp);
+        q.e_count = at<int32_t>(p, w->e_count);
+        q.f_h = at<float>(p, w->f_h);
+        q.f_c = at<float>(p, w->f_c);
+        q.open = at<int32_t>(p, w->open);
+        q.lens = at<int32_t>(p, w->lens);
+        q.flags = at<int32_t>(p, w->flags);
+        q.total_exp = at<long long>(p, w->total_exp);
+    }
+    char* home = st ? st : p;
+    const SurvivorOffs& v = st ? a->sv : w->sv;
+    q.bp_logp = at<double>(home, v.bp_logp);
+    q.bp_node = at<int32_t>(home, v.bp_node);
+    q.n_bp = at<int32_t>(home, v.n_bp);
+    q.bp_h[0] = at<float>(home, v.bp_h0);
+    q.bp_c[0] = at<float>(home, v.bp_c0);
+    q.nodes = at<int2>(home, v.nodes);
+    q.n_nodes = at<int32_t>(home, v.n_nodes);
+    if (st) {       // (offline: the root's token is BOS, nothing is committed, expansions are counted per call only)
+        q.root_tok = at<int32_t>(st, a->root_tok);
+        q.stream_exp = at<long long>(st, a->n_exp);
+        q.n_committed = at<long long>(st, a->n_committed);
+    }
+    bb.lm = lm;
+    if (!lm) return bb;
+    bb.lm_net = LstmNet{lm->emb, lm->emb_dtype, lm->V, lm->E, lm->L, lm->w_ih, lm->w_hh, lm->b_ih, lm->b_hh, lm->H, lm->Wo,
+                        lm->bo, lm->V};
     q.lm_L = lm->L;
     q.lm_H = lm->H;
     q.lm_bos = lm->bos;
+    q.lm_bp_h[0] = st ? at<float>(st, a->lm_bp_h) : at<float>(p, lw->bp_h0);
+    q.lm_bp_c[0] = st ? at<float>(st, a->lm_bp_c) : at<float>(p, lw->bp_c0);
+    if (!p) return bb;
+    q.lm_bp_h[1] = at<float>(p, lw->bp_h1);
+    q.lm_bp_c[1] = at<float>(p, lw->bp_c1);
+    q.lm_f_h = at<float>(p, lw->f_h);
+    q.lm_f_c = at<float>(p, lw->f_c);
+    q.lm_pred = at<int32_t>(p, lw->pred);
+    q.lm_h_state = at<float>(p, lw->h_state);
+    q.lm_c_state = at<float>(p, lw->c_state);
+    bb.lmu = StepBufs{nullptr, nullptr, at<float>(p, lw->logits), q.lm_pred, p + lw->x, p + lw->G, p + lw->Hprev,
+                      {p + lw->Y0, p + lw->Y1}, at<float>(p, lw->Cst), at<float>(p, lw->h_new), at<float>(p, lw->c_new),
+                      nullptr};
+    return bb;
 }
+
 // an LM that the search can use: status code and message, or ED_OK
 int lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what) {
     if (!lm) return ED_OK;
@@ -860,322 +915,48 @@ int lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what) 
     return ED_OK;
 }
 
-// one LM step for every row: token lm_pred[b] from (lm_h_state, lm_c_state) -> new state, fp32 logits [B, V]
-int lm_step(int dtype, int B, const edgedict_beam_lm_t& lm, const BeamPtrs& q, const LmBufs& u, hipStream_t s) {
-    const int L = lm.L, E = lm.E, H = lm.H, V = lm.V;
-    if (ed_decode_fused_lm_ok(dtype, lm.emb_dtype, V, E, H))
-        return ed_decode_fused_lm_step(dtype, B, V, lm.emb, lm.emb_dtype, E, L, lm.w_ih, lm.w_hh, lm.b_ih, lm.b_hh, H,
-                                       lm.Wo, lm.bo, q.lm_h_state, q.lm_c_state, q.lm_pred, u.h_new, u.c_new, u.Y[0],
-                                       u.Y[1], u.logits, s);
-    int rc;
-    if ((rc = edgedict_embedding_fwd(dtype, lm.emb_dtype, q.lm_pred, 1, lm.emb, u.x, B, 1, E, V, 0, 0, s))) return rc;
-    const void* xin = u.x;
-    int xin_dim = E;
-    for (int k = 0; k < L; ++k) {
-        if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, lm.w_ih[k], xin_dim, 1, u.G, 4 * H, B, 4 * H, xin_dim,
-                                lm.b_ih[k], lm.b_hh[k], 0, 1, s)))
-            return rc;
-        if ((rc = edgedict_lstm_forward(dtype, u.G, u.Hprev, u.Y[k & 1], u.Cst, lm.w_hh[k], nullptr,
-                                        q.lm_h_state + (size_t)k * B * H, q.lm_c_state + (size_t)k * B * H,
-                                        u.h_new + (size_t)k * B * H, u.c_new + (size_t)k * B * H, B, 1, H, nullptr, s)))
-            return rc;
-        xin = u.Y[k & 1];
-        xin_dim = H;
-    }
-    return edgedict_gemm(dtype, ED_F32, xin, H, 1, lm.Wo, H, 1, u.logits, V, B, V, H, lm.bo, nullptr, 0, 1, s);
+// Sequence.g of the children (models.py:183): this expansion's prediction, kept per token-tree node
+void store_pred(const SearchNet& net, const BeamBufs& bb, hipStream_t s) {
+    dispatch(net.dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(beam_store_pred<T>, dim3(net.B), dim3(64), 0, s, bb.q, (const T*)bb.u.dec_new,
+                           (T*)bb.node_pred, net.EM, net.NODES, net.P2);
+    });
 }
 
-
-// The arguments of one search call: weights and shapes as edgedict_beam_search takes them ...
-struct BeamNet {
-    int dtype, esz;
-    const void* E1;
-    long long e_row_stride, e_frame_stride;
-    int B, J;
-    const void* W1d;
-    long long ldw1;
-    const float* b1;
-    int P2;
-    const void* W2;
-    const float* b2;
-    int V;
-    const void* emb;
-    int emb_dtype, E, L;
-    const void* const* w_ih;
-    const void* const* w_hh;
-    const float* const* b_ih;
-    const float* const* b_hh;
-    int H;
-    const void* Wp;
-    const float* bp;
-    int blank, bos, W, EM, NODES;
-};
-// ... and the per-iteration buffers of the prediction-network step and the joint
-struct BeamBufs {
-    void *D1, *hid;
-    float* logits;
-    int32_t* pred;
-    void *x, *G, *Hprev, *Y[2];
-    float *Cst, *h_new, *c_new;
-    void* dec_new;
-    float *h_state, *c_state;
-    void* node_pred;
-};
-
-// The frame loop shared by the offline search and the streaming one: frames [0, maxlen), utterance b taking part in
-// frames t < lens[b]; per frame: frame begin -> lockstep pop / step / expand iterations -> frame end.  The survivors'
-// states alternate between bp_h/bp_c[0] and [1], starting in [0]: after the loop utterance b's are in [lens[b] & 1].
-// prefix = 1: `prefix_merge(t, E1 of frame t)` runs the host list logic before every frame after the first.
-// lmu.lm != null: every iteration also runs the LM step, and beam_expand_lm replaces beam_expand (prefix must be 0).
-int beam_frame_loop(const BeamNet& net, const BeamBufs& u, const BeamPtrs& q, const LmBufs& lmu, int maxlen, int prefix,
-                    const std::function<int(int, const char*)>& prefix_merge, hipStream_t s) {
-    const int dtype = net.dtype, esz = net.esz, B = net.B, J = net.J, P2 = net.P2, V = net.V, emb_dtype = net.emb_dtype,
-              E = net.E, L = net.L, H = net.H, blank = net.blank, bos = net.bos, W = net.W, EM = net.EM,
-              NODES = net.NODES;
-    const void* E1 = net.E1;
-    const long long e_row_stride = net.e_row_stride, e_frame_stride = net.e_frame_stride, ldw1 = net.ldw1;
-    const void *W1d = net.W1d, *W2 = net.W2, *emb = net.emb, *Wp = net.Wp;
-    const float *b1 = net.b1, *b2 = net.b2, *bp = net.bp;
-    const void* const* w_ih = net.w_ih;
-    const void* const* w_hh = net.w_hh;
-    const float* const* b_ih = net.b_ih;
-    const float* const* b_hh = net.b_hh;
-    void *D1 = u.D1, *hid = u.hid, *x = u.x, *G = u.G, *Hprev = u.Hprev, *dec_new = u.dec_new, *node_pred = u.node_pred;
-    void* const* Y = u.Y;
-    float *logits = u.logits, *Cst = u.Cst, *h_new = u.h_new, *c_new = u.c_new, *h_state = u.h_state,
-          *c_state = u.c_state;
-    int32_t* pred = u.pred;
-    std::vector<int32_t> open_h(B);
-    const bool fused_step = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
-    auto expand = [&]() {
-        if (lmu.lm)
-            hipLaunchKernelGGL(beam_expand_lm, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, lmu.logits, lmu.h_new,
-                               lmu.c_new, lmu.lm->weight, lmu.lm->length_bonus, W, V, EM, L, H, B, blank);
-        else
-            hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, logits, h_new, c_new, W, V, EM, L, H, B,
-                               blank);
-    };
-    int cur = 0;
-    for (int t = 0; t < maxlen; ++t) {
-        const char* e1t = (const char*)E1 + (size_t)t * e_frame_stride * esz;
-        if (prefix && t > 0) {
-            const int rc = prefix_merge(t, e1t);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, EM, V);
-        for (int it = 0;; ++it) {
-            int rc;
-            hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, V, EM, L, H, B, NODES,
-                               bos, pred, h_state, c_state);
-            // the LM's step on y*'s last token from y*'s LM state (its logits are only read by beam_expand_lm)
-            if (lmu.lm && (rc = lm_step(dtype, B, *lmu.lm, q, lmu, s))) return rc;
-            if (fused_step) {
-                // prediction-network step + projection + joint hidden + logits as 3 + L fused launches (decode_fused.hip)
-                if ((rc = ed_decode_fused_beam_step(dtype, e1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
-                                                    emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, h_state, c_state,
-                                                    pred, dec_new, hid, logits, h_new, c_new, Y[0], Y[1], s)))
-                    return rc;
-                if (prefix) {
-                    if (dtype == ED_F32)
-                        hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
-                                           (float*)node_pred, EM, NODES, P2);
-                    else
-                        hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
-                                           (bf16_t*)node_pred, EM, NODES, P2);
-                }
-                expand();
-            } else {
-            // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132)
-            if ((rc = edgedict_embedding_fwd(dtype, emb_dtype, pred, 1, emb, x, B, 1, E, V, 0, 0, s)))
-                return rc;
-            const void* xin = x;
-            int xin_dim = E;
-            for (int k = 0; k < L; ++k) {
-                if ((rc = edgedict_gemm(dtype, dtype, xin, xin_dim, 1, w_ih[k], xin_dim, 1, G, 4 * H,
-                                        B, 4 * H, xin_dim, b_ih[k], b_hh[k], 0, 1, s)))
-                    return rc;
-                if ((rc = edgedict_lstm_forward(dtype, G, Hprev, Y[k & 1], Cst, w_hh[k], nullptr,
-                                                h_state + (size_t)k * B * H, c_state + (size_t)k * B * H,
-                                                h_new + (size_t)k * B * H, c_new + (size_t)k * B * H,
-                                                B, 1, H, nullptr, s)))
-                    return rc;
-                xin = Y[k & 1];
-                xin_dim = H;
-            }
-            if ((rc = edgedict_gemm(dtype, dtype, xin, H, 1, Wp, H, 1, dec_new, P2, B, P2, H, bp,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            if (prefix) {        // Sequence.g of the children (models.py:183): this expansion's prediction, kept per node
-                if (dtype == ED_F32)
-                    hipLaunchKernelGGL(beam_store_pred<float>, dim3(B), dim3(64), 0, s, q, (const float*)dec_new,
-                                       (float*)node_pred, EM, NODES, P2);
-                else
-                    hipLaunchKernelGGL(beam_store_pred<bf16_t>, dim3(B), dim3(64), 0, s, q, (const bf16_t*)dec_new,
-                                       (bf16_t*)node_pred, EM, NODES, P2);
-            }
-            // joint(x_t, pred) (models.py:165): D1 = pred W1d^T + b1; hid = tanh(E1[:,t] + D1); logits
-            if ((rc = edgedict_gemm(dtype, dtype, dec_new, P2, 1, W1d, ldw1, 1, D1, J, B, J, P2, b1,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            if (dtype == ED_F32)
-                hipLaunchKernelGGL(add_tanh_rows<float>, dim3(ed_grid_for((long long)B * J, 256)),
-                                   dim3(256), 0, s, (const float*)e1t, e_row_stride,
-                                   (const float*)D1, (float*)hid, B, J);
-            else
-                hipLaunchKernelGGL(add_tanh_rows<bf16_t>, dim3(ed_grid_for((long long)B * J, 256)),
-                                   dim3(256), 0, s, (const bf16_t*)e1t, e_row_stride,
-                                   (const bf16_t*)D1, (bf16_t*)hid, B, J);
-            if ((rc = edgedict_gemm(dtype, ED_F32, hid, J, 1, W2, J, 1, logits, V, B, V, J, b2,
-                                    nullptr, 0, 1, s)))
-                return rc;
-            expand();
-            }
-            if (it + 1 >= W) {   // B cannot hold W hypotheses before W expansions
-                ED_CHECK_HIP(hipMemcpyAsync(open_h.data(), q.open, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-                ED_CHECK_HIP(hipStreamSynchronize(s));
-                int any = 0;
-                for (int b = 0; b < B; ++b) any |= open_h[b];
-                if (!any) break;
-            }
-        }
-        hipLaunchKernelGGL(beam_frame_end, dim3(B), dim3(256), 0, s, q, t, cur, W, EM, L, H);
-        cur ^= 1;
-    }
-    return ED_OK;
-}
-}  // namespace
-
-extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
-
-extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
-    if (B <= 0 || W <= 0 || max_expansions <= 0) return 0;
-    const int esz = dtype == ED_F32 ? 4 : 2;
-    const size_t base = beam_layout(esz, B, T < 0 ? 0 : T, J, V, E, L, H, P2, W, max_expansions, prefix).total;
-    if (!lm) return base;
-    return lm_ws_layout(base, esz, B, V, lm->L, lm->E, lm->H, W, max_expansions, true).total;
-}
-
-extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
-                                                int H, int P2, int W, int max_expansions, int prefix) {
-    return edgedict_beam_workspace_bytes_lm(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, nullptr);
-}
-
-extern "C" int edgedict_beam_search_lm(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
-    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "beam_search: bad dtype");
-    ED_CHECK_ARG(B > 0 && T >= 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0 && W > 0 &&
-                     max_expansions >= W && max_tokens >= 0,
-                 "beam_search: bad shape (max_expansions must be >= W)");
-    ED_CHECK_ARG((T == 0 || E1) && W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh &&
-                     Wp && bp && lens_host && tokens_host && ntokens_host && score_host && workspace,
-                 "beam_search: null pointer");
-    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "beam_search: blank/bos outside the vocabulary");
-    for (int b = 0; b < B; ++b)
-        ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "beam_search: lens[%d] = %d outside [0, %d]", b, lens_host[b], T);
-    {
-        const int rc = lm_check(lm, V, prefix, "beam_search");
-        if (rc) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream_;
-    const int esz = dtype == ED_F32 ? 4 : 2, EM = max_expansions;
-    const int NODES = T * EM + 1;
-    const BeamWs w = beam_layout(esz, B, T, J, V, E, L, H, P2, W, EM, prefix);
-    char* p = (char*)workspace;
-    void* D1 = p + w.step.D1;
-    void* hid = p + w.step.hid;
-    float* logits = (float*)(p + w.step.logits);
-    int32_t* pred = (int32_t*)(p + w.step.pred);
-    void* x = p + w.step.x;
-    void* G = p + w.step.G;
-    void* Hprev = p + w.step.Hprev;
-    void* Y[2] = {p + w.step.Y0, p + w.step.Y1};
-    float* Cst = (float*)(p + w.step.Cst);
-    float* h_new = (float*)(p + w.step.h_new);
-    float* c_new = (float*)(p + w.step.c_new);
-    void* dec_new = p + w.step.dec_new;
-    float* h_state = (float*)(p + w.h_state);
-    float* c_state = (float*)(p + w.c_state);
-    BeamPtrs q{};
-    q.pool = (double*)(p + w.pool);
-    q.bp_logp = (double*)(p + w.bp_logp);
-    q.bp_node = (int32_t*)(p + w.bp_node);
-    q.n_bp = (int32_t*)(p + w.n_bp);
-    q.bp_h[0] = (float*)(p + w.bp_h0); q.bp_h[1] = (float*)(p + w.bp_h1);
-    q.bp_c[0] = (float*)(p + w.bp_c0); q.bp_c[1] = (float*)(p + w.bp_c1);
-    q.bn_logp = (double*)(p + w.bn_logp);
-    q.bn_node = (int32_t*)(p + w.bn_node);
-    q.bn_ref = (int32_t*)(p + w.bn_ref);
-    q.n_b = (int32_t*)(p + w.n_b);
-    q.max_b = (double*)(p + w.max_b);
-    q.blk_max = (double*)(p + w.blk_max);
-    q.blk_arg = (int32_t*)(p + w.blk_arg);
-    q.exp_node = (int32_t*)(p + w.exp_node);
-    q.exp_ref = (int32_t*)(p + w.exp_ref);
-    q.exp_logp = (double*)(p + w.exp_logp);
-    q.e_count = (int32_t*)(p + w.e_count);
-    q.f_h = (float*)(p + w.f_h);
-    q.f_c = (float*)(p + w.f_c);
-    q.nodes = (int2*)(p + w.nodes);
-    q.n_nodes = (int32_t*)(p + w.n_nodes);
-    q.open = (int32_t*)(p + w.open);
-    q.lens = (int32_t*)(p + w.lens);
-    q.flags = (int32_t*)(p + w.flags);
-    q.total_exp = (long long*)(p + w.total_exp);
-    q.root_tok = nullptr;
-    q.stream_exp = nullptr;
-
-    const size_t LH = (size_t)L * H;
-    ED_CHECK_HIP(hipMemcpyAsync(q.lens, lens_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    // the empty hypothesis' state is zero (Decoder.forward(empty, None), rnnt/models.py:150-153)
-    ED_CHECK_HIP(hipMemsetAsync(q.bp_h[0], 0, (size_t)B * W * LH * 4, s));
-    ED_CHECK_HIP(hipMemsetAsync(q.bp_c[0], 0, (size_t)B * W * LH * 4, s));
-    // rows of finished / not yet popped utterances flow through the step kernels: keep them finite
-    ED_CHECK_HIP(hipMemsetAsync(h_state, 0, (size_t)B * LH * 4, s));
-    ED_CHECK_HIP(hipMemsetAsync(c_state, 0, (size_t)B * LH * 4, s));
-    ED_CHECK_HIP(hipMemsetAsync(pred, 0, (size_t)B * 4, s));
-    LmWs lw{};
-    if (lm) {
-        lw = lm_ws_layout(w.total, esz, B, V, lm->L, lm->E, lm->H, W, EM, true);
-        lm_ptrs(q, lm, p, lw);
-        q.lm_bp_h[0] = (float*)(p + lw.bp_h0);
-        q.lm_bp_c[0] = (float*)(p + lw.bp_c0);
-        const size_t LHl = (size_t)lm->L * lm->H;
-        // the LM's initial state is zero (LMModel.init_hidden, models.py:255-261); idle rows stay finite
-        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_h[0], 0, (size_t)B * W * LHl * 4, s));
-        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_c[0], 0, (size_t)B * W * LHl * 4, s));
-        ED_CHECK_HIP(hipMemsetAsync(q.lm_h_state, 0, (size_t)B * LHl * 4, s));
-        ED_CHECK_HIP(hipMemsetAsync(q.lm_c_state, 0, (size_t)B * LHl * 4, s));
-        ED_CHECK_HIP(hipMemsetAsync(q.lm_pred, 0, (size_t)B * 4, s));
-    }
-    const LmBufs lmu = lm_bufs(lm, p, lw);
-    hipLaunchKernelGGL(beam_init, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W);
-    int maxlen = 0;
-    for (int b = 0; b < B; ++b) maxlen = lens_host[b] > maxlen ? lens_host[b] : maxlen;
-
-    // ---- prefix = 1: host mirrors for the list logic of models.py:145-161
-    long long prefix_steps = 0;                 // prediction-network steps the reference spends in that branch
+// prefix = 1: the host list logic of models.py:145-161, run before every frame after the first.  Host mirrors of the
+// survivors and of the token tree are members, so that their storage is reused from frame to frame.
+struct PrefixMerge {
+    const SearchNet& net;
+    const BeamPtrs q;
+    const int32_t* lens_host;
+    hipStream_t s;
+    const void* node_pred;
+    int32_t *d_row, *d_node, *d_tok;            // one batch of (utterance, node, token) queries on the device ...
+    void *d_pred, *d_D1, *d_hid;                // ... their stored predictions and joint buffers
+    float *d_logits, *d_out;
+    long long steps = 0;                        // prediction-network steps the reference spends in this branch
     std::vector<int32_t> nbp_h, node_h, nn_h, qrow, qnode, qtok;
     std::vector<double> logp_h;
-    std::vector<int2> nodes_h;
     std::vector<float> qout;
     // the token tree is APPEND-ONLY (beam_expand writes node n_nodes[b]++ and nothing else): the host keeps a mirror and
     // fetches, per frame, only the node columns that are new since its last fetch - one strided copy of
     // [B] x [min_b mirrored[b], max_b n_nodes[b]) instead of the whole B x NODES tree (O(T^2 EM B) bytes per utterance
     // batch)
+    std::vector<int2> nodes_h;
     std::vector<int32_t> mirrored;
     struct Pair { int b, j, i, q0, nq; };
     std::vector<Pair> pairs;
-    std::vector<std::vector<int>> paths;                          // per list entry: its nodes, last token first
-    if (prefix) { nodes_h.resize((size_t)B * NODES); mirrored.assign(B, 0); paths.resize(W); }
-    void* node_pred = prefix ? (void*)(p + w.node_pred) : nullptr;
-    auto prefix_merge = [&](int t, const char* e1t) -> int {
+    std::vector<std::vector<int>> paths;        // per list entry: its nodes, last token first
+
+    PrefixMerge(const SearchNet& net_, const BeamBufs& bb, char* p, const BeamWs& w, const int32_t* lens, hipStream_t s_)
+        : net(net_), q(bb.q), lens_host(lens), s(s_), node_pred(bb.node_pred), d_row(at<int32_t>(p, w.q_row)),
+          d_node(at<int32_t>(p, w.q_node)), d_tok(at<int32_t>(p, w.q_tok)), d_pred(p + w.q_pred), d_D1(p + w.q_D1),
+          d_hid(p + w.q_hid), d_logits(at<float>(p, w.q_logits)), d_out(at<float>(p, w.q_out)),
+          nodes_h((size_t)net_.B * net_.NODES), mirrored(net_.B, 0), paths(net_.W) {}
+
+    int operator()(int t, const char* e1t) {
+        const int B = net.B, W = net.W, NODES = net.NODES;
         nbp_h.resize(B); node_h.resize((size_t)B * W); logp_h.resize((size_t)B * W); nn_h.resize(B);
         ED_CHECK_HIP(hipMemcpyAsync(nbp_h.data(), q.n_bp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
         ED_CHECK_HIP(hipMemcpyAsync(nn_h.data(), q.n_nodes, (size_t)B * 4, hipMemcpyDeviceToHost, s));
@@ -1231,37 +1012,29 @@ extern "C" int edgedict_beam_search_lm(
         if (pairs.empty()) return ED_OK;
         const int NQ = (int)qrow.size();
         qout.resize(NQ);
-        int32_t* d_row = (int32_t*)(p + w.q_row);
-        int32_t* d_node = (int32_t*)(p + w.q_node);
-        int32_t* d_tok = (int32_t*)(p + w.q_tok);
-        void* d_pred = p + w.q_pred;
-        void* d_D1 = p + w.q_D1;
-        void* d_hid = p + w.q_hid;
-        float* d_logits = (float*)(p + w.q_logits);
-        float* d_out = (float*)(p + w.q_out);
         for (int q0 = 0; q0 < NQ; q0 += BEAM_QMAX) {
             const int nq = std::min(BEAM_QMAX, NQ - q0);
             int rc;
             ED_CHECK_HIP(hipMemcpyAsync(d_row, qrow.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
             ED_CHECK_HIP(hipMemcpyAsync(d_node, qnode.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
             ED_CHECK_HIP(hipMemcpyAsync(d_tok, qtok.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-            if (dtype == ED_F32)
-                hipLaunchKernelGGL(beam_query_gather<float>, dim3(nq), dim3(64), 0, s, (const float*)node_pred, d_row,
-                                   d_node, (float*)d_pred, NODES, P2);
-            else
-                hipLaunchKernelGGL(beam_query_gather<bf16_t>, dim3(nq), dim3(64), 0, s, (const bf16_t*)node_pred, d_row,
-                                   d_node, (bf16_t*)d_pred, NODES, P2);
-            if ((rc = edgedict_gemm(dtype, dtype, d_pred, P2, 1, W1d, ldw1, 1, d_D1, J, nq, J, P2, b1, nullptr, 0, 1, s)))
+            dispatch(net.dtype, [&](auto tag) {
+                using T = decltype(tag);
+                hipLaunchKernelGGL(beam_query_gather<T>, dim3(nq), dim3(64), 0, s, (const T*)node_pred, d_row, d_node,
+                                   (T*)d_pred, NODES, net.P2);
+            });
+            if ((rc = edgedict_gemm(net.dtype, net.dtype, d_pred, net.P2, 1, net.W1d, net.ldw1, 1, d_D1, net.J, nq, net.J,
+                                    net.P2, net.b1, nullptr, 0, 1, s)))
                 return rc;
-            if (dtype == ED_F32)
-                hipLaunchKernelGGL(beam_query_hidden<float>, dim3(nq), dim3(128), 0, s, (const float*)e1t, e_row_stride,
-                                   d_row, (const float*)d_D1, (float*)d_hid, J);
-            else
-                hipLaunchKernelGGL(beam_query_hidden<bf16_t>, dim3(nq), dim3(128), 0, s, (const bf16_t*)e1t, e_row_stride,
-                                   d_row, (const bf16_t*)d_D1, (bf16_t*)d_hid, J);
-            if ((rc = edgedict_gemm(dtype, ED_F32, d_hid, J, 1, W2, J, 1, d_logits, V, nq, V, J, b2, nullptr, 0, 1, s)))
+            dispatch(net.dtype, [&](auto tag) {
+                using T = decltype(tag);
+                hipLaunchKernelGGL(beam_query_hidden<T>, dim3(nq), dim3(128), 0, s, (const T*)e1t, net.e_row_stride, d_row,
+                                   (const T*)d_D1, (T*)d_hid, net.J);
+            });
+            if ((rc = edgedict_gemm(net.dtype, ED_F32, d_hid, net.J, 1, net.W2, net.J, 1, d_logits, net.V, nq, net.V, net.J,
+                                    net.b2, nullptr, 0, 1, s)))
                 return rc;
-            hipLaunchKernelGGL(beam_query_logp, dim3(nq), dim3(256), 0, s, d_logits, d_tok, d_out, V);
+            hipLaunchKernelGGL(beam_query_logp, dim3(nq), dim3(256), 0, s, d_logits, d_tok, d_out, net.V);
             ED_CHECK_HIP(hipMemcpyAsync(qout.data() + q0, d_out, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
             ED_CHECK_HIP(hipStreamSynchronize(s));
         }
@@ -1273,23 +1046,167 @@ extern "C" int edgedict_beam_search_lm(
             double& a = logp_h[(size_t)pr.b * W + pr.j];
             const double hi = a > cur ? a : cur;
             a = hi + log1p(exp(-fabs(a - cur)));
-            ++prefix_steps;
+            ++steps;
         }
         ED_CHECK_HIP(hipMemcpyAsync(q.bp_logp, logp_h.data(), logp_h.size() * 8, hipMemcpyHostToDevice, s));
         ED_CHECK_HIP(hipStreamSynchronize(s));       // (logp_h is reused by the next frame)
         return ED_OK;
-    };
-
-    const BeamNet net{dtype, esz, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype,
-                      E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, EM, NODES};
-    const BeamBufs bufs{D1, hid, logits, pred, x, G, Hprev, {Y[0], Y[1]}, Cst, h_new, c_new, dec_new, h_state, c_state,
-                        node_pred};
-    {
-        const int rc = beam_frame_loop(net, bufs, q, lmu, maxlen, prefix, prefix_merge, s);
-        if (rc) return rc;
     }
+};
+
+// one LM step for every row: token lm_pred[b] from (lm_h_state, lm_c_state) -> new state, fp32 logits [B, V]
+int lm_step(int dtype, int B, const BeamBufs& bb, hipStream_t s) {
+    const LstmNet& n = bb.lm_net;
+    const BeamPtrs& q = bb.q;
+    if (ed_decode_fused_lm_ok(dtype, n.emb_dtype, n.V, n.E, n.H))
+        return ed_decode_fused_lm_step(dtype, B, n, q.lm_h_state, q.lm_c_state, bb.lmu, s);
+    return composed_lstm_step(dtype, B, n, q.lm_pred, q.lm_h_state, q.lm_c_state, bb.lmu, ED_F32, bb.lmu.logits, s);
+}
+
+// The frame loop shared by the offline search and the streaming one: frames [0, maxlen), utterance b taking part in
+// frames t < lens[b]; per frame: frame begin -> lockstep pop / step / expand iterations -> frame end.  The survivors'
+// states alternate between bp_h/bp_c[0] and [1], starting in [0]: after the loop utterance b's are in [lens[b] & 1].
+// prefix_merge != null (prefix = 1): it runs the host list logic before every frame after the first, and every
+// expansion's prediction is kept per node.
+// bb.lm != null: every iteration also runs the LM step, and beam_expand_lm replaces beam_expand (no prefix_merge then).
+int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, PrefixMerge* prefix_merge, hipStream_t s) {
+    const BeamPtrs& q = bb.q;
+    const StepBufs& u = bb.u;
+    const LstmNet& pn = net.pred;
+    const int B = net.B, W = net.W;
+    std::vector<int32_t> open_h(B);
+    const bool fused_step = ed_decode_fused_ok(net.dtype, pn.emb_dtype, net.J, net.V, pn.E, pn.H, net.P2);
+    int cur = 0;
+    for (int t = 0; t < maxlen; ++t) {
+        const char* e1t = net.frame(t);
+        if (prefix_merge && t > 0) {
+            const int rc = (*prefix_merge)(t, e1t);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, net.EM, net.V);
+        for (int it = 0;; ++it) {
+            int rc;
+            hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B, net.NODES,
+                               net.bos, u.pred, bb.h_state, bb.c_state);
+            // the LM's step on y*'s last token from y*'s LM state (its logits are only read by beam_expand_lm)
+            if (bb.lm && (rc = lm_step(net.dtype, B, bb, s))) return rc;
+            // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132), then joint(x_t, pred)
+            // (models.py:165): 3 + L fused launches (decode_fused.hip), or composed from the general kernels
+            if (fused_step) rc = ed_decode_fused_beam_step(net, e1t, bb.h_state, bb.c_state, u, s);
+            else rc = composed_lstm_step(net.dtype, B, pn, u.pred, bb.h_state, bb.c_state, u, net.dtype, u.dec_new, s);
+            if (rc) return rc;
+            if (prefix_merge) store_pred(net, bb, s);
+            if (!fused_step && (rc = composed_joint(net, e1t, u.dec_new, u, s))) return rc;
+            if (bb.lm)
+                hipLaunchKernelGGL(beam_expand_lm, dim3(B), dim3(256), 0, s, q, u.logits, u.h_new, u.c_new, bb.lmu.logits,
+                                   bb.lmu.h_new, bb.lmu.c_new, bb.lm->weight, bb.lm->length_bonus, W, net.V, net.EM, pn.L,
+                                   pn.H, B, net.blank);
+            else
+                hipLaunchKernelGGL(beam_expand, dim3(B), dim3(256), 0, s, q, u.logits, u.h_new, u.c_new, W, net.V, net.EM,
+                                   pn.L, pn.H, B, net.blank);
+            if (it + 1 >= W) {   // B cannot hold W hypotheses before W expansions
+                ED_CHECK_HIP(hipMemcpyAsync(open_h.data(), q.open, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+                ED_CHECK_HIP(hipStreamSynchronize(s));
+                int any = 0;
+                for (int b = 0; b < B; ++b) any |= open_h[b];
+                if (!any) break;
+            }
+        }
+        hipLaunchKernelGGL(beam_frame_end, dim3(B), dim3(256), 0, s, q, t, cur, W, net.EM, pn.L, pn.H);
+        cur ^= 1;
+    }
+    return ED_OK;
+}
+
+// Per utterance the tokens of its first survivor (node[b * W], score -logp[b * W]): the token tree (row b of `nodes`,
+// `stride` nodes apart) walked from that node to the root.  `what` opens the message of a path beyond max_tokens.
+int read_best_path(int B, int W, const int32_t* node, const double* logp, const int2* nodes, size_t stride,
+                   const char* what, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host, double* score_host) {
+    std::vector<int32_t> rev;
+    for (int b = 0; b < B; ++b) {
+        rev.clear();
+        for (int n = node[(size_t)b * W]; n >= 0; n = nodes[(size_t)b * stride + n].x)
+            rev.push_back(nodes[(size_t)b * stride + n].y);
+        const int len = (int)rev.size();
+        ntokens_host[b] = len;
+        ED_CHECK_ARG(len <= max_tokens, "%s of %d tokens exceeds max_tokens = %d", what, len, max_tokens);
+        for (int i = 0; i < len; ++i) tokens_host[(size_t)b * max_tokens + i] = rev[len - 1 - i];
+        score_host[b] = -logp[(size_t)b * W];
+    }
+    return ED_OK;
+}
+}  // namespace
+
+extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
+
+extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
+                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
+    if (B <= 0 || W <= 0 || max_expansions <= 0) return 0;
+    SearchNet n = net_dims(dtype, B, J, V, E, L, H, P2);
+    n.W = W;
+    n.EM = max_expansions;
+    const size_t base = beam_layout(n, (size_t)(T < 0 ? 0 : T) * n.EM + 1, prefix, false).total;
+    return lm ? lm_ws_layout(base, n, *lm, true).total : base;
+}
+
+extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
+                                                int H, int P2, int W, int max_expansions, int prefix) {
+    return edgedict_beam_workspace_bytes_lm(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, nullptr);
+}
+
+extern "C" int edgedict_beam_search_lm(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
+    const int EM = max_expansions;
+    const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V,
+                        {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, T * EM + 1};
+    if (int rc = check_net(net, "beam_search", T >= 0 && W > 0 && EM >= W && max_tokens >= 0,
+                           " (max_expansions must be >= W)",
+                           (T == 0 || E1) && lens_host && tokens_host && ntokens_host && score_host && workspace, true))
+        return rc;
+    for (int b = 0; b < B; ++b)
+        ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "beam_search: lens[%d] = %d outside [0, %d]", b, lens_host[b], T);
+    if (int rc = lm_check(lm, V, prefix, "beam_search")) return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    char* p = (char*)workspace;
+    const BeamWs w = beam_layout(net, (size_t)T * EM + 1, prefix, false);
+    LmWs lw{};
+    if (lm) lw = lm_ws_layout(w.total, net, *lm, true);
+    const BeamBufs bufs = bind_beam_ptrs(p, &w, nullptr, nullptr, lm, &lw);
+    const BeamPtrs& q = bufs.q;
+
+    const size_t LH = (size_t)L * H;
+    ED_CHECK_HIP(hipMemcpyAsync(q.lens, lens_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    // the empty hypothesis' state is zero (Decoder.forward(empty, None), rnnt/models.py:150-153)
+    ED_CHECK_HIP(hipMemsetAsync(q.bp_h[0], 0, (size_t)B * W * LH * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(q.bp_c[0], 0, (size_t)B * W * LH * 4, s));
+    // rows of finished / not yet popped utterances flow through the step kernels: keep them finite
+    ED_CHECK_HIP(hipMemsetAsync(bufs.h_state, 0, (size_t)B * LH * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(bufs.c_state, 0, (size_t)B * LH * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(bufs.u.pred, 0, (size_t)B * 4, s));
+    if (lm) {
+        const size_t LHl = (size_t)lm->L * lm->H;
+        // the LM's initial state is zero (LMModel.init_hidden, models.py:255-261); idle rows stay finite
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_h[0], 0, (size_t)B * W * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_bp_c[0], 0, (size_t)B * W * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_h_state, 0, (size_t)B * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_c_state, 0, (size_t)B * LHl * 4, s));
+        ED_CHECK_HIP(hipMemsetAsync(q.lm_pred, 0, (size_t)B * 4, s));
+    }
+    hipLaunchKernelGGL(beam_init, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W);
+    int maxlen = 0;
+    for (int b = 0; b < B; ++b) maxlen = lens_host[b] > maxlen ? lens_host[b] : maxlen;
+    std::optional<PrefixMerge> merge;
+    if (prefix) merge.emplace(net, bufs, p, w, lens_host, s);
+    if (int rc = beam_frame_loop(net, bufs, maxlen, merge ? &*merge : nullptr, s)) return rc;
     ED_CHECK_LAUNCH("beam_search");
     // results: B[0] of the last frame (models.py:201-202), token tree walked on the host
+    const int NODES = net.NODES;
     std::vector<double> logp((size_t)B * W);
     std::vector<int32_t> node((size_t)B * W), nn(B);
     std::vector<int2> nodes((size_t)B * NODES);
@@ -1304,19 +1221,9 @@ extern "C" int edgedict_beam_search_lm(
     ED_CHECK_HIP(hipStreamSynchronize(s));
     ED_CHECK_ARG(!flags[0], "beam_search: an utterance needed more than max_expansions = %d expansions in one frame", EM);
     ED_CHECK_ARG(!flags[1], "beam_search: token tree overflow");
-    if (expansions_host) *expansions_host = total + prefix_steps;
-    std::vector<int32_t> rev;
-    for (int b = 0; b < B; ++b) {
-        rev.clear();
-        for (int n = node[(size_t)b * W]; n >= 0; n = nodes[(size_t)b * NODES + n].x)
-            rev.push_back(nodes[(size_t)b * NODES + n].y);
-        const int len = (int)rev.size();
-        ntokens_host[b] = len;
-        ED_CHECK_ARG(len <= max_tokens, "beam_search: hypothesis of %d tokens exceeds max_tokens = %d", len, max_tokens);
-        for (int i = 0; i < len; ++i) tokens_host[(size_t)b * max_tokens + i] = rev[len - 1 - i];
-        score_host[b] = -logp[(size_t)b * W];
-    }
-    return ED_OK;
+    if (expansions_host) *expansions_host = total + (merge ? merge->steps : 0);
+    return read_best_path(B, W, node.data(), logp.data(), nodes.data(), (size_t)NODES, "beam_search: hypothesis",
+                          tokens_host, max_tokens, ntokens_host, score_host);
 }
 
 extern "C" int edgedict_beam_search(
@@ -1343,122 +1250,6 @@ extern "C" int edgedict_beam_search(
 // in root_tok).  The tree then holds only the part where the survivors still differ.
 // =====================================================================================
 namespace {
-
-// persistent state, per stream
-struct BeamStreamState {
-    size_t bp_logp, bp_node, n_bp, bp_h, bp_c, nodes, n_nodes, root_tok, n_committed, n_exp, total;
-};
-inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int NC) {
-    BeamStreamState w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
-    const size_t LH = (size_t)L * H;
-    w.bp_logp = take((size_t)S * W * 8);
-    w.bp_node = take((size_t)S * W * 4);
-    w.n_bp = take((size_t)S * 4);
-    w.bp_h = take((size_t)S * W * LH * 4);
-    w.bp_c = take((size_t)S * W * LH * 4);
-    w.nodes = take((size_t)S * NC * 8);
-    w.n_nodes = take((size_t)S * 4);
-    w.root_tok = take((size_t)S * 4);
-    w.n_committed = take((size_t)S * 8);
-    w.n_exp = take((size_t)S * 8);
-    w.total = o;
-    return w;
-}
-
-// per-call workspace: the frame loop's buffers (BeamWs without the state) and the compaction's scratch
-struct BeamStreamWs {
-    Ws step;
-    size_t h_state, c_state;
-    size_t pool, bp_h1, bp_c1, bn_logp, bn_node, bn_ref, n_b, max_b, blk_max, blk_arg, exp_node, exp_ref, exp_logp,
-        e_count, f_h, f_c, open, lens, flags, total_exp, c_old, c_mark, commit, n_commit, total;
-};
-inline BeamStreamWs beam_stream_ws_layout(int esz, int S, int J, int V, int E, int L, int H, int P2, int W, int EM,
-                                          int NC) {
-    BeamStreamWs w;
-    w.step = ws_layout(esz, S, J, V, E, L, H, P2);
-    size_t o = w.step.total;
-    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
-    const size_t LH = (size_t)L * H;
-    w.h_state = take((size_t)S * LH * 4);
-    w.c_state = take((size_t)S * LH * 4);
-    w.pool = take((size_t)S * (W + (size_t)EM * V) * 8);
-    w.bp_h1 = take((size_t)S * W * LH * 4);
-    w.bp_c1 = take((size_t)S * W * LH * 4);
-    w.bn_logp = take((size_t)S * W * 8);
-    w.bn_node = take((size_t)S * W * 4);
-    w.bn_ref = take((size_t)S * W * 4);
-    w.n_b = take((size_t)S * 4);
-    w.max_b = take((size_t)S * 8);
-    w.blk_max = take((size_t)S * (EM + 1) * 8);
-    w.blk_arg = take((size_t)S * (EM + 1) * 4);
-    w.exp_node = take((size_t)S * EM * 4);
-    w.exp_ref = take((size_t)S * EM * 4);
-    w.exp_logp = take((size_t)S * EM * 8);
-    w.e_count = take((size_t)S * 4);
-    w.f_h = take((size_t)S * EM * LH * 4);
-    w.f_c = take((size_t)S * EM * LH * 4);
-    w.open = take((size_t)S * 4);
-    w.lens = take((size_t)S * 4);
-    w.flags = take(8);
-    w.total_exp = take(8);
-    w.c_old = take((size_t)S * NC * 8);
-    w.c_mark = take((size_t)S * NC * 4);
-    w.commit = take((size_t)S * NC * 4);
-    w.n_commit = take((size_t)S * 4);
-    w.total = o;
-    return w;
-}
-
-// LM shallow fusion: the survivors' LM (h, c) [S][W][lm_L][lm_H], appended behind the plain state (so that
-// edgedict_beam_stream_read serves both forms)
-struct BeamStreamLmState {
-    size_t bp_h, bp_c, total;
-};
-inline BeamStreamLmState beam_stream_lm_state_layout(size_t base, int S, int W, const edgedict_beam_lm_t& lm) {
-    BeamStreamLmState w;
-    size_t o = base;
-    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
-    w.bp_h = take((size_t)S * W * lm.L * lm.H * 4);
-    w.bp_c = take((size_t)S * W * lm.L * lm.H * 4);
-    w.total = o;
-    return w;
-}
-
-BeamPtrs beam_stream_ptrs(char* st, const BeamStreamState& a, char* ws, const BeamStreamWs& w) {
-    BeamPtrs q{};
-    q.pool = (double*)(ws + w.pool);
-    q.bp_logp = (double*)(st + a.bp_logp);
-    q.bp_node = (int32_t*)(st + a.bp_node);
-    q.n_bp = (int32_t*)(st + a.n_bp);
-    q.bp_h[0] = (float*)(st + a.bp_h); q.bp_h[1] = (float*)(ws + w.bp_h1);
-    q.bp_c[0] = (float*)(st + a.bp_c); q.bp_c[1] = (float*)(ws + w.bp_c1);
-    q.bn_logp = (double*)(ws + w.bn_logp);
-    q.bn_node = (int32_t*)(ws + w.bn_node);
-    q.bn_ref = (int32_t*)(ws + w.bn_ref);
-    q.n_b = (int32_t*)(ws + w.n_b);
-    q.max_b = (double*)(ws + w.max_b);
-    q.blk_max = (double*)(ws + w.blk_max);
-    q.blk_arg = (int32_t*)(ws + w.blk_arg);
-    q.exp_node = (int32_t*)(ws + w.exp_node);
-    q.exp_ref = (int32_t*)(ws + w.exp_ref);
-    q.exp_logp = (double*)(ws + w.exp_logp);
-    q.e_count = (int32_t*)(ws + w.e_count);
-    q.f_h = (float*)(ws + w.f_h);
-    q.f_c = (float*)(ws + w.f_c);
-    q.nodes = (int2*)(st + a.nodes);
-    q.n_nodes = (int32_t*)(st + a.n_nodes);
-    q.open = (int32_t*)(ws + w.open);
-    q.lens = (int32_t*)(ws + w.lens);
-    q.flags = (int32_t*)(ws + w.flags);
-    q.total_exp = (long long*)(ws + w.total_exp);
-    q.root_tok = (int32_t*)(st + a.root_tok);
-    q.stream_exp = (long long*)(st + a.n_exp);
-    q.n_committed = (const long long*)(st + a.n_committed);
-    return q;
-}
-
 // streams [b0, b0 + n) with mask[b] != 0 (mask null: all) -> B = [empty hypothesis]: one survivor, logp 0, node -1
 // with BOS as its last token, zero prediction-network state; empty tree and committed log
 __global__ __launch_bounds__(256) void beam_stream_reset_kernel(BeamPtrs p, long long* n_committed,
@@ -1600,8 +1391,7 @@ extern "C" size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, i
                                                       const edgedict_beam_lm_t* lm) {
     (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
     if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
-    const size_t base = beam_stream_state_layout(S, L, H, W, node_capacity).total;
-    return lm ? beam_stream_lm_state_layout(base, S, W, *lm).total : base;
+    return beam_stream_state_layout(S, L, H, W, node_capacity, lm).total;
 }
 
 extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
@@ -1613,9 +1403,11 @@ extern "C" size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int 
                                                           int W, int max_expansions, int node_capacity,
                                                           const edgedict_beam_lm_t* lm) {
     if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
-    const int esz = dtype == ED_F32 ? 4 : 2;
-    const size_t base = beam_stream_ws_layout(esz, S, J, V, E, L, H, P2, W, max_expansions, node_capacity).total;
-    return lm ? lm_ws_layout(base, esz, S, V, lm->L, lm->E, lm->H, W, max_expansions, false).total : base;
+    SearchNet n = net_dims(dtype, S, J, V, E, L, H, P2);
+    n.W = W;
+    n.EM = max_expansions;
+    const size_t base = beam_layout(n, (size_t)node_capacity, 0, true).total;
+    return lm ? lm_ws_layout(base, n, *lm, false).total : base;
 }
 
 extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
@@ -1631,25 +1423,10 @@ extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int nod
     ED_CHECK_ARG(state, "beam_stream_reset: null state");
     ED_CHECK_ARG(!lm || (lm->L > 0 && lm->H > 0), "beam_stream_reset: bad LM shape");
     hipStream_t s = (hipStream_t)stream_;
-    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity);
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity, lm);
     char* st = (char*)state;
-    BeamPtrs q{};
-    q.bp_logp = (double*)(st + a.bp_logp);
-    q.bp_node = (int32_t*)(st + a.bp_node);
-    q.n_bp = (int32_t*)(st + a.n_bp);
-    q.bp_h[0] = (float*)(st + a.bp_h);
-    q.bp_c[0] = (float*)(st + a.bp_c);
-    q.n_nodes = (int32_t*)(st + a.n_nodes);
-    q.root_tok = (int32_t*)(st + a.root_tok);
-    q.stream_exp = (long long*)(st + a.n_exp);
-    if (lm) {
-        const BeamStreamLmState la = beam_stream_lm_state_layout(a.total, S, W, *lm);
-        q.lm_bp_h[0] = (float*)(st + la.bp_h);
-        q.lm_bp_c[0] = (float*)(st + la.bp_c);
-        q.lm_L = lm->L;
-        q.lm_H = lm->H;
-    }
-    long long* n_committed = (long long*)(st + a.n_committed);
+    const BeamPtrs q = bind_beam_ptrs(nullptr, nullptr, st, &a, lm, nullptr).q;
+    long long* n_committed = at<long long>(st, a.n_committed);
     if (!mask || !mask_on_host) {
         hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, n_committed, mask, 0, W, L, H, bos);
     } else {            // host mask: one launch per run of selected streams
@@ -1678,18 +1455,13 @@ extern "C" int edgedict_beam_stream_advance_lm(
     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
     int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
     long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
-    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "beam_stream_advance: bad dtype");
-    ED_CHECK_ARG(S > 0 && J > 0 && V > 0 && L > 0 && H > 0 && P2 > 0 && E > 0 && W > 0 && max_expansions >= W &&
-                     node_capacity > 0,
-                 "beam_stream_advance: bad shape (max_expansions must be >= W)");
-    ED_CHECK_ARG(W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp && bp && n_frames_host &&
-                     commit_host && ncommit_host && state && workspace,
-                 "beam_stream_advance: null pointer");
-    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "beam_stream_advance: blank/bos outside the vocabulary");
-    {
-        const int rc = lm_check(lm, V, 0, "beam_stream_advance");
-        if (rc) return rc;
-    }
+    const int EM = max_expansions, NC = node_capacity;
+    const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V,
+                        {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, NC};
+    if (int rc = check_net(net, "beam_stream_advance", W > 0 && EM >= W && NC > 0, " (max_expansions must be >= W)",
+                           n_frames_host && commit_host && ncommit_host && state && workspace, true))
+        return rc;
+    if (int rc = lm_check(lm, V, 0, "beam_stream_advance")) return rc;
     int maxlen = 0;
     for (int b = 0; b < S; ++b) {
         ED_CHECK_ARG(n_frames_host[b] >= 0, "beam_stream_advance: n_frames[%d] = %d < 0", b, n_frames_host[b]);
@@ -1697,21 +1469,14 @@ extern "C" int edgedict_beam_stream_advance_lm(
     }
     ED_CHECK_ARG(maxlen == 0 || E1, "beam_stream_advance: null E1");
     hipStream_t s = (hipStream_t)stream_;
-    const int esz = dtype == ED_F32 ? 4 : 2, EM = max_expansions, NC = node_capacity;
-    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC);
-    const BeamStreamWs w = beam_stream_ws_layout(esz, S, J, V, E, L, H, P2, W, EM, NC);
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC, lm);
+    const BeamWs w = beam_layout(net, (size_t)NC, 0, true);
     char* st = (char*)state;
     char* p = (char*)workspace;
-    BeamPtrs q = beam_stream_ptrs(st, a, p, w);
     LmWs lw{};
-    if (lm) {
-        const BeamStreamLmState la = beam_stream_lm_state_layout(a.total, S, W, *lm);
-        lw = lm_ws_layout(w.total, esz, S, V, lm->L, lm->E, lm->H, W, EM, false);
-        lm_ptrs(q, lm, p, lw);
-        q.lm_bp_h[0] = (float*)(st + la.bp_h);
-        q.lm_bp_c[0] = (float*)(st + la.bp_c);
-    }
-    const LmBufs lmu = lm_bufs(lm, p, lw);
+    if (lm) lw = lm_ws_layout(w.total, net, *lm, false);
+    const BeamBufs bufs = bind_beam_ptrs(p, &w, st, &a, lm, &lw);
+    const BeamPtrs& q = bufs.q;
     for (int b = 0; b < S; ++b) ncommit_host[b] = 0;
     if (expansions_host) *expansions_host = 0;
     if (maxlen == 0) return ED_OK;
@@ -1728,16 +1493,12 @@ extern "C" int edgedict_beam_stream_advance_lm(
                      b, need, nn[b], n_frames_host[b], EM, NC);
     }
 
-    const BeamBufs bufs{p + w.step.D1, p + w.step.hid, (float*)(p + w.step.logits), (int32_t*)(p + w.step.pred),
-                        p + w.step.x, p + w.step.G, p + w.step.Hprev, {p + w.step.Y0, p + w.step.Y1},
-                        (float*)(p + w.step.Cst), (float*)(p + w.step.h_new), (float*)(p + w.step.c_new),
-                        p + w.step.dec_new, (float*)(p + w.h_state), (float*)(p + w.c_state), nullptr};
     const size_t LH = (size_t)L * H;
     ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
     // rows of finished / not yet popped streams flow through the step kernels: keep them finite
     ED_CHECK_HIP(hipMemsetAsync(bufs.h_state, 0, (size_t)S * LH * 4, s));
     ED_CHECK_HIP(hipMemsetAsync(bufs.c_state, 0, (size_t)S * LH * 4, s));
-    ED_CHECK_HIP(hipMemsetAsync(bufs.pred, 0, (size_t)S * 4, s));
+    ED_CHECK_HIP(hipMemsetAsync(bufs.u.pred, 0, (size_t)S * 4, s));
     if (lm) {
         const size_t LHl = (size_t)lm->L * lm->H;
         ED_CHECK_HIP(hipMemsetAsync(q.lm_h_state, 0, (size_t)S * LHl * 4, s));
@@ -1746,19 +1507,14 @@ extern "C" int edgedict_beam_stream_advance_lm(
     }
     ED_CHECK_HIP(hipMemsetAsync(q.flags, 0, 8, s));
     ED_CHECK_HIP(hipMemsetAsync(q.total_exp, 0, 8, s));
-    const BeamNet net{dtype, esz, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype,
-                      E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, EM, NC};
-    {
-        const int rc = beam_frame_loop(net, bufs, q, lmu, maxlen, 0, [](int, const char*) { return (int)ED_OK; }, s);
-        if (rc) return rc;
-    }
+    if (int rc = beam_frame_loop(net, bufs, maxlen, nullptr, s)) return rc;
     hipLaunchKernelGGL(beam_stream_settle, dim3(S), dim3(256), 0, s, q, W, L, H);
     const int use_lds = NC <= BEAM_COMPACT_LDS_NODES;
-    int32_t* commit = (int32_t*)(p + w.commit);
-    int32_t* n_commit = (int32_t*)(p + w.n_commit);
+    int32_t* commit = at<int32_t>(p, w.commit);
+    int32_t* n_commit = at<int32_t>(p, w.n_commit);
     hipLaunchKernelGGL(beam_compact, dim3(S), dim3(256), use_lds ? (size_t)NC * 8 : 0, s, q, W, NC, use_lds,
-                       (int2*)(p + w.c_old), (int32_t*)(p + w.c_mark), commit, n_commit,
-                       (long long*)(st + a.n_committed));
+                       at<int2>(p, w.c_old), at<int32_t>(p, w.c_mark), commit, n_commit,
+                       at<long long>(st, a.n_committed));
     ED_CHECK_LAUNCH("beam_stream_advance");
     int32_t flags[2];
     long long total = 0;
@@ -1802,14 +1558,14 @@ extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_ca
     ED_CHECK_ARG(state && tokens_host && ntokens_host && score_host, "beam_stream_read: null pointer");
     hipStream_t s = (hipStream_t)stream_;
     const int NC = node_capacity;
-    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC);
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC, nullptr);
     const char* st = (const char*)state;
     std::vector<double> logp((size_t)S * W);
     std::vector<int32_t> node((size_t)S * W), nn(S);
     std::vector<long long> ncom(S), nexp(S);
-    ED_CHECK_HIP(hipMemcpyAsync(logp.data(), st + a.bp_logp, logp.size() * 8, hipMemcpyDeviceToHost, s));
-    ED_CHECK_HIP(hipMemcpyAsync(node.data(), st + a.bp_node, node.size() * 4, hipMemcpyDeviceToHost, s));
-    ED_CHECK_HIP(hipMemcpyAsync(nn.data(), st + a.n_nodes, nn.size() * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(logp.data(), st + a.sv.bp_logp, logp.size() * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(node.data(), st + a.sv.bp_node, node.size() * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(nn.data(), st + a.sv.n_nodes, nn.size() * 4, hipMemcpyDeviceToHost, s));
     ED_CHECK_HIP(hipMemcpyAsync(ncom.data(), st + a.n_committed, ncom.size() * 8, hipMemcpyDeviceToHost, s));
     ED_CHECK_HIP(hipMemcpyAsync(nexp.data(), st + a.n_exp, nexp.size() * 8, hipMemcpyDeviceToHost, s));
     ED_CHECK_HIP(hipStreamSynchronize(s));
@@ -1817,23 +1573,14 @@ extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_ca
     for (int b = 0; b < S; ++b) maxnn = std::max(maxnn, nn[b]);
     std::vector<int2> nodes((size_t)S * std::max(maxnn, 1));
     if (maxnn > 0) {
-        ED_CHECK_HIP(hipMemcpy2DAsync(nodes.data(), (size_t)maxnn * 8, st + a.nodes, (size_t)NC * 8, (size_t)maxnn * 8,
+        ED_CHECK_HIP(hipMemcpy2DAsync(nodes.data(), (size_t)maxnn * 8, st + a.sv.nodes, (size_t)NC * 8, (size_t)maxnn * 8,
                                       (size_t)S, hipMemcpyDeviceToHost, s));
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
-    std::vector<int32_t> rev;
     for (int b = 0; b < S; ++b) {
-        rev.clear();
-        for (int n = node[(size_t)b * W]; n >= 0; n = nodes[(size_t)b * maxnn + n].x)
-            rev.push_back(nodes[(size_t)b * maxnn + n].y);
-        const int len = (int)rev.size();
-        ntokens_host[b] = len;
-        ED_CHECK_ARG(len <= max_tokens, "beam_stream_read: hypothesis tail of %d tokens exceeds max_tokens = %d", len,
-                     max_tokens);
-        for (int i = 0; i < len; ++i) tokens_host[(size_t)b * max_tokens + i] = rev[len - 1 - i];
-        score_host[b] = -logp[(size_t)b * W];
         if (ncommitted_host) ncommitted_host[b] = ncom[b];
         if (expansions_host) expansions_host[b] = nexp[b];
     }
-    return ED_OK;
+    return read_best_path(S, W, node.data(), logp.data(), nodes.data(), (size_t)maxnn, "beam_stream_read: hypothesis tail",
+                          tokens_host, max_tokens, ntokens_host, score_host);
 }

@@ -24,7 +24,7 @@
 //         = 4 k that feed FOUR MFMA steps (the same k permutation on both operands - see lstm.hip f32_product16).
 // Rows are independent and a row's arithmetic does not depend on its position in the batch, so S concurrent streams
 // equal S single-stream decoders bit for bit (tests/test_stream_gpu.py).
-#include "common.hpp"
+#include "decode_net.hpp"
 
 namespace {
 
@@ -610,8 +610,6 @@ __global__ __launch_bounds__(256, 2) void enc_lstm_tile(const bf16_t* __restrict
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace
 
 // ---- C ABI: the streaming encoder step (rnnt/stream.py:93-100: `self.encoder(xs, (enc_h, enc_c))` on a chunk of a
@@ -705,145 +703,98 @@ size_t ed_decode_fused_ws_bytes(int B, int V) {
 
 namespace {
 
+const GreedyOut NO_PICK{-1, nullptr, 0, 0, nullptr};
+
+// one dec_lstm_step launch per layer of `n`: (h_state, c_state) [L, B, H] -> u.h_new / u.c_new, layer outputs ping-pong
+// through u.Y.  first_mode 1: the first layer finishes the pick from `parts` (u.pred out; blank and `out` say what to do
+// with it); 2: the symbol is u.pred[b] (parts null, blank -1, NO_PICK)
 template <typename ET>
-void launch_lstm_steps(int first_mode, const PickPart* parts, int NS, int unk, int blank, int32_t* pred, int32_t* tokens,
-                       long long tok_stride, int t, float* score, const void* emb, int emb_dtype, int E, int L,
-                       const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-                       const float* const* b_hh, int H, const float* h_state, const float* c_state, float* h_new,
-                       float* c_new, void* const* Y, int B, int V, hipStream_t s) {
-    const int RB = (B + 15) / 16;
-    for (int k = 0; k < L; ++k) {
+void launch_lstm_steps(int first_mode, const LstmNet& n, const PickPart* parts, int blank, const GreedyOut& out,
+                       const float* h_state, const float* c_state, const StepBufs& u, int B, hipStream_t s) {
+    const int RB = (B + 15) / 16, H = n.H;
+    for (int k = 0; k < n.L; ++k) {
         LstmStepArgs<ET> A;
-        A.V = V;
-        A.parts = parts; A.nslices = NS; A.unk = unk; A.blank = blank;
-        A.pred = pred; A.tokens = tokens; A.tok_stride = tok_stride; A.t = t; A.score = score;
-        A.emb = emb; A.emb_f32 = emb_dtype == ED_F32 ? 1 : 0; A.E = E;
-        A.x_prev = k > 0 ? (const ET*)Y[(k - 1) & 1] : nullptr;
-        A.w_ih = (const ET*)w_ih[k]; A.w_hh = (const ET*)w_hh[k]; A.b_ih = b_ih[k]; A.b_hh = b_hh[k];
+        A.V = n.V;
+        A.parts = parts; A.nslices = parts ? (n.V + 63) / 64 : 0; A.unk = out.unk; A.blank = blank;
+        A.pred = u.pred; A.tokens = out.tokens; A.tok_stride = out.tok_stride; A.t = out.t; A.score = out.score;
+        A.emb = n.emb; A.emb_f32 = n.emb_dtype == ED_F32 ? 1 : 0; A.E = n.E;
+        A.x_prev = k > 0 ? (const ET*)u.Y[(k - 1) & 1] : nullptr;
+        A.w_ih = (const ET*)n.w_ih[k]; A.w_hh = (const ET*)n.w_hh[k]; A.b_ih = n.b_ih[k]; A.b_hh = n.b_hh[k];
         A.h_in = h_state + (size_t)k * B * H; A.c_in = c_state + (size_t)k * B * H;
-        A.h_out = h_new + (size_t)k * B * H; A.c_out = c_new + (size_t)k * B * H;
-        A.y_out = (ET*)Y[k & 1];
-        A.B = B; A.H = H; A.Kx = k == 0 ? E : H;
+        A.h_out = u.h_new + (size_t)k * B * H; A.c_out = u.c_new + (size_t)k * B * H;
+        A.y_out = (ET*)u.Y[k & 1];
+        A.B = B; A.H = H; A.Kx = k == 0 ? n.E : H;
         hipLaunchKernelGGL(dec_lstm_step<ET>, dim3(RB, H / 16), dim3(256), 0, s, A, k == 0 ? first_mode : 0);
     }
 }
 
-template <typename ET>
-int beam_step_t(const void* E1t, long long e_row_stride, int B, int J, const void* W1d, long long ldw1, const float* b1,
-                int P2, const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-                const void* const* w_ih, const void* const* w_hh, const float* const* b_ih, const float* const* b_hh,
-                int H, const void* Wp, const float* bp, const float* h_state, const float* c_state, const int32_t* pred,
-                void* dec_new, void* hid, float* logits, float* h_new, float* c_new, void* Y0, void* Y1, hipStream_t s) {
-    const int RB = (B + 15) / 16;
-    void* Y[2] = {Y0, Y1};
-    launch_lstm_steps<ET>(2, nullptr, 0, -1, -1, const_cast<int32_t*>(pred), nullptr, 0, 0, nullptr, emb, emb_dtype, E, L,
-                          w_ih, w_hh, b_ih, b_hh, H, h_state, c_state, h_new, c_new, Y, B, V, s);
-    hipLaunchKernelGGL(dec_proj_commit<ET>, dim3(RB, (P2 + 63) / 64), dim3(256), 0, s, (const ET*)Y[(L - 1) & 1], H,
-                       (const ET*)Wp, bp, P2, (const int32_t*)nullptr, 0, (ET*)dec_new, (float*)nullptr,
-                       (const float*)nullptr, (float*)nullptr, (const float*)nullptr, L, B);
-    hipLaunchKernelGGL(dec_joint_hidden<ET>, dim3(RB, (J + 63) / 64), dim3(256), 0, s, (const ET*)E1t, e_row_stride,
-                       (const ET*)dec_new, P2, (const ET*)W1d, ldw1, b1, (ET*)hid, B, J);
-    hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, (V + 63) / 64), dim3(256), 0, s, (const ET*)hid, J, (const ET*)W2,
-                       b2, V, -1, 0, (PickPart*)nullptr, logits, B);
-    return ED_OK;
-}
-
-template <typename ET>
-int frame_t(const void* E1t, long long e_row_stride, int B, int J, const void* W1d, long long ldw1, const float* b1,
-            int P2, const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-            const void* const* w_ih, const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-            const void* Wp, const float* bp, float* h_state, float* c_state, void* dec_out, int blank, int unk,
-            int32_t* tokens_out, long long tok_stride, int t, float* score, void* hid, void* parts, int32_t* pred,
-            float* h_new, float* c_new, void* Y0, void* Y1, hipStream_t s) {
-    const int RB = (B + 15) / 16, NS = (V + 63) / 64;
-    hipLaunchKernelGGL(dec_joint_hidden<ET>, dim3(RB, (J + 63) / 64), dim3(256), 0, s, (const ET*)E1t, e_row_stride,
-                       (const ET*)dec_out, P2, (const ET*)W1d, ldw1, b1, (ET*)hid, B, J);
-    hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, NS), dim3(256), 0, s, (const ET*)hid, J, (const ET*)W2, b2, V,
-                       unk, score ? 1 : 0, (PickPart*)parts, (float*)nullptr, B);
-    void* Y[2] = {Y0, Y1};
-    launch_lstm_steps<ET>(1, (const PickPart*)parts, NS, unk, blank, pred, tokens_out, tok_stride, t, score, emb, emb_dtype,
-                          E, L, w_ih, w_hh, b_ih, b_hh, H, h_state, c_state, h_new, c_new, Y, B, V, s);
-    hipLaunchKernelGGL(dec_proj_commit<ET>, dim3(RB, (P2 + 63) / 64), dim3(256), 0, s, (const ET*)Y[(L - 1) & 1], H,
-                       (const ET*)Wp, bp, P2, pred, blank, (ET*)dec_out, h_state, h_new, c_state, c_new, L, B);
-    return ED_OK;
-}
-
 }  // namespace
 
-// beam search (decode.hip): prediction-network step on pred[b] from (h_state, c_state) -> h_new / c_new, dec_new, the
-// joint's hidden vector of frame t and the logits (fp32 [B, V]) of every row - 3 + L launches instead of 5 + 2 L
-int ed_decode_fused_beam_step(int dtype, const void* E1t, long long e_row_stride, int B, int J, const void* W1d,
-                              long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                              const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                              const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                              const void* Wp, const float* bp, const float* h_state, const float* c_state,
-                              const int32_t* pred, void* dec_new, void* hid, float* logits, float* h_new, float* c_new,
-                              void* Y0, void* Y1, hipStream_t s) {
-    if (dtype == ED_F32)
-        beam_step_t<float>(E1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih,
-                           b_hh, H, Wp, bp, h_state, c_state, pred, dec_new, hid, logits, h_new, c_new, Y0, Y1, s);
-    else
-        beam_step_t<bf16_t>(E1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih,
-                            b_hh, H, Wp, bp, h_state, c_state, pred, dec_new, hid, logits, h_new, c_new, Y0, Y1, s);
+// beam search (decode.hip): prediction-network step on u.pred[b] from (h_state, c_state) -> u.h_new / u.c_new, u.dec_new,
+// the joint's hidden vector of the frame E1t (u.hid) and the logits (u.logits, fp32 [B, V]) of every row - 3 + L launches
+// instead of 5 + 2 L
+int ed_decode_fused_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                              const StepBufs& u, hipStream_t s) {
+    const LstmNet& pn = net.pred;
+    const int B = net.B, RB = (B + 15) / 16;
+    dispatch(net.dtype, [&](auto tag) {
+        using ET = decltype(tag);
+        launch_lstm_steps<ET>(2, pn, nullptr, -1, NO_PICK, h_state, c_state, u, B, s);
+        hipLaunchKernelGGL(dec_proj_commit<ET>, dim3(RB, (net.P2 + 63) / 64), dim3(256), 0, s,
+                           (const ET*)u.Y[(pn.L - 1) & 1], pn.H, (const ET*)pn.Wo, pn.bo, net.P2, (const int32_t*)nullptr, 0,
+                           (ET*)u.dec_new, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
+                           pn.L, B);
+        hipLaunchKernelGGL(dec_joint_hidden<ET>, dim3(RB, (net.J + 63) / 64), dim3(256), 0, s, (const ET*)E1t,
+                           net.e_row_stride, (const ET*)u.dec_new, net.P2, (const ET*)net.W1d, net.ldw1, net.b1,
+                           (ET*)u.hid, B, net.J);
+        hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, (net.V + 63) / 64), dim3(256), 0, s, (const ET*)u.hid, net.J,
+                           (const ET*)net.W2, net.b2, net.V, -1, 0, (PickPart*)nullptr, u.logits, B);
+    });
     ED_CHECK_LAUNCH("decode_fused_beam_step");
     return ED_OK;
 }
 
-// one frame of the search: see the file header.  hid [B, J], parts = ed_decode_fused_ws_bytes(B, V) bytes,
-// h_new / c_new [L, B, H] fp32, Y [2][B, H] (ping-pong between layers); pred [B] out
-int ed_decode_fused_frame(int dtype, const void* E1t, long long e_row_stride, int B, int J, const void* W1d,
-                          long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                          const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                          const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                          const void* Wp, const float* bp, float* h_state, float* c_state, void* dec_out, int blank,
-                          int unk, int32_t* tokens_out, long long tok_stride, int t, float* score, void* hid, void* parts,
-                          int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, hipStream_t s) {
-    if (dtype == ED_F32)
-        frame_t<float>(E1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh,
-                       H, Wp, bp, h_state, c_state, dec_out, blank, unk, tokens_out, tok_stride, t, score, hid, parts,
-                       pred, h_new, c_new, Y0, Y1, s);
-    else
-        frame_t<bf16_t>(E1t, e_row_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh,
-                        H, Wp, bp, h_state, c_state, dec_out, blank, unk, tokens_out, tok_stride, t, score, hid, parts,
-                        pred, h_new, c_new, Y0, Y1, s);
+// one frame of the greedy / streaming search: see the file header.  The slice partials (ed_decode_fused_ws_bytes(B, V)
+// bytes) go where the composed path keeps its logits; u.pred [B] out
+int ed_decode_fused_frame(const SearchNet& net, const void* E1t, float* h_state, float* c_state, void* dec_out,
+                          const GreedyOut& out, const StepBufs& u, hipStream_t s) {
+    const LstmNet& pn = net.pred;
+    const int B = net.B, RB = (B + 15) / 16, NS = (net.V + 63) / 64;
+    PickPart* parts = (PickPart*)u.logits;
+    dispatch(net.dtype, [&](auto tag) {
+        using ET = decltype(tag);
+        hipLaunchKernelGGL(dec_joint_hidden<ET>, dim3(RB, (net.J + 63) / 64), dim3(256), 0, s, (const ET*)E1t,
+                           net.e_row_stride, (const ET*)dec_out, net.P2, (const ET*)net.W1d, net.ldw1, net.b1,
+                           (ET*)u.hid, B, net.J);
+        hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, NS), dim3(256), 0, s, (const ET*)u.hid, net.J,
+                           (const ET*)net.W2, net.b2, net.V, out.unk, out.score ? 1 : 0, parts, (float*)nullptr, B);
+        launch_lstm_steps<ET>(1, pn, parts, net.blank, out, h_state, c_state, u, B, s);
+        hipLaunchKernelGGL(dec_proj_commit<ET>, dim3(RB, (net.P2 + 63) / 64), dim3(256), 0, s,
+                           (const ET*)u.Y[(pn.L - 1) & 1], pn.H, (const ET*)pn.Wo, pn.bo, net.P2,
+                           (const int32_t*)u.pred, net.blank, (ET*)dec_out, h_state, (const float*)u.h_new, c_state,
+                           (const float*)u.c_new, pn.L, B);
+    });
     ED_CHECK_LAUNCH("decode_fused_frame");
     return ED_OK;
 }
 
-// LM shallow fusion of the beam search (decode.hip lm_step): the same rule as the search frame, for an LSTM LM with no
-// joint or projection (E, H multiples of 32, V % 4 == 0)
+// LM shallow fusion of the beam search (decode.hip): the same rule as the search frame, for an LSTM LM with no joint or
+// projection (E, H multiples of 32, V % 4 == 0)
 bool ed_decode_fused_lm_ok(int dtype, int emb_dtype, int V, int E, int H) {
     return ed_decode_fused_ok(dtype, emb_dtype, 32, V, E, H, 32);
 }
 
-namespace {
-template <typename ET>
-void lm_step_t(int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-               const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wo,
-               const float* bo, const float* h_state, const float* c_state, const int32_t* pred, float* h_new,
-               float* c_new, void* Y0, void* Y1, float* logits, hipStream_t s) {
-    const int RB = (B + 15) / 16;
-    void* Y[2] = {Y0, Y1};
-    launch_lstm_steps<ET>(2, nullptr, 0, -1, -1, const_cast<int32_t*>(pred), nullptr, 0, 0, nullptr, emb, emb_dtype, E, L,
-                          w_ih, w_hh, b_ih, b_hh, H, h_state, c_state, h_new, c_new, Y, B, V, s);
-    hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, (V + 63) / 64), dim3(256), 0, s, (const ET*)Y[(L - 1) & 1], H,
-                       (const ET*)Wo, bo, V, -1, 0, (PickPart*)nullptr, logits, B);
-}
-}  // namespace
-
-// one LM step for B rows: token pred[b] from (h_state, c_state) [L, B, H] fp32 -> h_new / c_new, logits fp32 [B, V]
-// = y_L Wo^T + bo; L + 1 launches (dec_lstm_step per layer, dec_logits_pick in its logits-out form)
-int ed_decode_fused_lm_step(int dtype, int B, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                            const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H,
-                            const void* Wo, const float* bo, const float* h_state, const float* c_state,
-                            const int32_t* pred, float* h_new, float* c_new, void* Y0, void* Y1, float* logits,
-                            hipStream_t s) {
-    if (dtype == ED_F32)
-        lm_step_t<float>(B, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wo, bo, h_state, c_state, pred, h_new,
-                         c_new, Y0, Y1, logits, s);
-    else
-        lm_step_t<bf16_t>(B, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wo, bo, h_state, c_state, pred, h_new,
-                          c_new, Y0, Y1, logits, s);
+// one LM step for B rows: token u.pred[b] from (h_state, c_state) [L, B, H] fp32 -> u.h_new / u.c_new, u.logits fp32
+// [B, V] = y_L Wo^T + bo; L + 1 launches (dec_lstm_step per layer, dec_logits_pick in its logits-out form)
+int ed_decode_fused_lm_step(int dtype, int B, const LstmNet& lm, const float* h_state, const float* c_state,
+                            const StepBufs& u, hipStream_t s) {
+    dispatch(dtype, [&](auto tag) {
+        using ET = decltype(tag);
+        launch_lstm_steps<ET>(2, lm, nullptr, -1, NO_PICK, h_state, c_state, u, B, s);
+        hipLaunchKernelGGL(dec_logits_pick<ET>, dim3((B + 15) / 16, (lm.V + 63) / 64), dim3(256), 0, s,
+                           (const ET*)u.Y[(lm.L - 1) & 1], lm.H, (const ET*)lm.Wo, lm.bo, lm.V, -1, 0, (PickPart*)nullptr,
+                           u.logits, B);
+    });
     ED_CHECK_LAUNCH("decode_fused_lm_step");
     return ED_OK;
 }

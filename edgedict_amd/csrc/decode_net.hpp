@@ -1,0 +1,105 @@
+// The search network and the buffers of one search step, stated once for decode.hip (the search loops, a step composed
+// from the general kernels) and decode_fused.hip (the same step as fused launches).  Host-side only.
+#pragma once
+#include "common.hpp"
+
+static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+// f(ET{}) with ET = the element type of `dtype`: the one place a kernel template is picked from a dtype code
+template <typename F>
+static inline void dispatch(int dtype, F&& f) {
+    if (dtype == ED_F32) f(float{});
+    else f(bf16_t{});
+}
+
+// Embedding -> L LSTM layers -> Linear.  The transducer's prediction network (Wo = its projection, O = P2) and the
+// fusion LM (edgedict_beam_lm_t: Wo = its decoder, O = V) are both one.
+struct LstmNet {
+    const void* emb;                 // [V, E] in emb_dtype
+    int emb_dtype, V, E, L;
+    const void* const* w_ih;         // HOST arrays [L] of DEVICE pointers: [4H, E or H], [4H, H] in the search's dtype,
+    const void* const* w_hh;         // fp32 [4H]
+    const float* const* b_ih;
+    const float* const* b_hh;
+    int H;
+    const void* Wo;                  // [O, H] in the search's dtype
+    const float* bo;                 // fp32 [O]
+    int O;
+};
+
+// Weights and shapes of one search call, as the extern "C" searches take them (include/edgedict_hip.h)
+struct SearchNet {
+    int dtype, esz;
+    const void* E1;                  // the joint's encoder rows; row b of frame t at (b * e_row_stride + t * e_frame_stride)
+    long long e_row_stride, e_frame_stride;
+    int B, J;
+    const void* W1d;                 // joint: hid = tanh(E1 + pred W1d^T + b1), logits = hid W2^T + b2
+    long long ldw1;
+    const float* b1;
+    int P2;
+    const void* W2;
+    const float* b2;
+    int V;
+    LstmNet pred;                    // the prediction network
+    int blank;
+    int bos, W, EM, NODES;           // beam searches only: width, expansions per frame, token-tree capacity per utterance
+    const char* frame(int t) const { return (const char*)E1 + (size_t)t * e_frame_stride * esz; }
+};
+
+// Per-iteration buffers of the prediction-network step and the joint: offsets into a workspace ...
+struct Ws {
+    size_t D1, hid, logits, pred, x, G, Hprev, Y0, Y1, Cst, h_new, c_new, dec_new, total;
+};
+static inline Ws ws_layout(const SearchNet& n) {
+    const int esz = n.esz, B = n.B, J = n.J, V = n.V, E = n.pred.E, L = n.pred.L, H = n.pred.H, P2 = n.P2;
+    Ws w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    w.D1 = take((size_t)B * J * esz);
+    w.hid = take((size_t)B * J * esz);
+    w.logits = take((size_t)B * V * 4);
+    w.pred = take((size_t)B * 4);
+    w.x = take((size_t)B * E * esz);
+    w.G = take((size_t)B * 4 * H * esz);
+    w.Hprev = take((size_t)B * H * esz);
+    w.Y0 = take((size_t)B * H * esz);
+    w.Y1 = take((size_t)B * H * esz);
+    w.Cst = take((size_t)B * H * 4);
+    w.h_new = take((size_t)L * B * H * 4);
+    w.c_new = take((size_t)L * B * H * 4);
+    w.dec_new = take((size_t)B * P2 * esz);
+    w.total = o;
+    return w;
+}
+// ... and the pointers.  An LM's step uses the same bundle (no D1 / hid / dec_new; logits = its output).
+struct StepBufs {
+    void *D1, *hid;                  // [B, J]
+    float* logits;                   // fp32 [B, V]; the fused greedy frame keeps its slice partials here instead
+    int32_t* pred;                   // [B] the symbol the network consumes
+    void *x, *G, *Hprev, *Y[2];      // embedding rows, gate pre-activations, LSTM scratch, layer outputs (ping-pong)
+    float *Cst, *h_new, *c_new;      // h_new / c_new: [L, B, H] candidates
+    void* dec_new;                   // [B, P2]
+};
+static inline StepBufs bind(char* p, const Ws& w) {
+    return {p + w.D1, p + w.hid, (float*)(p + w.logits), (int32_t*)(p + w.pred), p + w.x, p + w.G, p + w.Hprev,
+            {p + w.Y0, p + w.Y1}, (float*)(p + w.Cst), (float*)(p + w.h_new), (float*)(p + w.c_new), p + w.dec_new};
+}
+
+// decode_fused.hip: a step as fused launches, for the shapes *_ok accepts (otherwise decode.hip composes it)
+bool ed_decode_fused_ok(int dtype, int emb_dtype, int J, int V, int E, int H, int P2);
+bool ed_decode_fused_lm_ok(int dtype, int emb_dtype, int V, int E, int H);
+size_t ed_decode_fused_ws_bytes(int B, int V);
+// what the greedy frame does with its pick (the beam search's steps take their symbol from u.pred instead)
+struct GreedyOut {
+    int unk;
+    int32_t* tokens;
+    long long tok_stride;
+    int t;
+    float* score;
+};
+int ed_decode_fused_frame(const SearchNet& net, const void* E1t, float* h_state, float* c_state, void* dec_out,
+                          const GreedyOut& out, const StepBufs& u, hipStream_t s);
+int ed_decode_fused_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                              const StepBufs& u, hipStream_t s);
+int ed_decode_fused_lm_step(int dtype, int B, const LstmNet& lm, const float* h_state, const float* c_state,
+                            const StepBufs& u, hipStream_t s);

@@ -55,38 +55,19 @@ def init_search_state(model, batch):
 def run_search(model, enc_out, state, unk=-1, want_score=True):
     """Advance ``state`` over all frames of ``enc_out`` [B, T, P_enc] (compute dtype).
     Returns (tokens int32 [B, T] on device, score fp32 [B] or None)."""
-    from .models import WEIGHTS
     cd = enc_out.dtype
     B, T, P = enc_out.shape
-    dec = model.decoder
-    l1, l2 = model.joint.joint[0], model.joint.joint[2]
-    J, V = l1.weight.shape[0], l2.weight.shape[0]
-    P2 = dec.proj.weight.shape[0]
-    L, H = dec.lstm.num_layers, dec.lstm.hidden_size
-    E = dec.embed.weight.shape[1]
-    w1c = WEIGHTS.get(l1.weight, cd)
-    w2c = WEIGHTS.get(l2.weight, cd)
-    wpc = WEIGHTS.get(dec.proj.weight, cd)
-    # encoder half of the joint's first Linear for all frames at once
-    E1 = ops.gemm(enc_out.reshape(B * T, P), w1c[:, :P]) if T > 0 else enc_out.new_empty(0, J)
-    w_ih = [WEIGHTS.get(dec.lstm.layer(k)[0], cd) for k in range(L)]
-    w_hh = [WEIGHTS.get(dec.lstm.layer(k)[1], cd) for k in range(L)]
-    b_ih = [dec.lstm.layer(k)[2].detach() for k in range(L)]
-    b_hh = [dec.lstm.layer(k)[3].detach() for k in range(L)]
+    net = _SearchNet(model, cd)
+    E1 = net.e1(enc_out)
     lib = _lib.load()
     dev = enc_out.device
-    nbytes = lib.edgedict_greedy_workspace_bytes(dtype_code(cd), B, J, V, E, L, H, P2)
+    nbytes = lib.edgedict_greedy_workspace_bytes(dtype_code(cd), B, net.J, net.V, net.E, net.L, net.H, net.P2)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     tokens = torch.empty(B, max(T, 1), dtype=torch.int32, device=dev)
     score = torch.zeros(B, dtype=torch.float32, device=dev) if want_score else None
-    w1d = w1c[:, P:]
-    keep = (E1, w1c, w2c, wpc, w_ih, w_hh, b_ih, b_hh, ws)   # alive until the stream is done
+    keep = (E1, net, ws)   # alive until the stream is done
     rc = lib.edgedict_greedy_decode(
-        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * J), ctypes.c_longlong(J), B, T, J,
-        _lib.ptr(w1d), ctypes.c_longlong(w1c.stride(0)), _lib.ptr(l1.bias.detach()), P2,
-        _lib.ptr(w2c), _lib.ptr(l2.bias.detach()), V, _lib.ptr(dec.embed.weight.detach()),
-        dtype_code(dec.embed.weight.dtype), E, L, _ptr_array(w_ih), _ptr_array(w_hh),
-        _ptr_array(b_ih), _ptr_array(b_hh), H, _lib.ptr(wpc), _lib.ptr(dec.proj.bias.detach()),
+        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, *net.args(P),
         _lib.ptr(state.h), _lib.ptr(state.c), _lib.ptr(state.dec_out), int(model.blank), int(unk),
         _lib.ptr(tokens), tokens.stride(0), _lib.ptr(score), _lib.ptr(ws), _lib.stream_ptr())
     _lib.check(rc, "greedy_decode")
@@ -144,9 +125,9 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
                            length_bonus=length_bonus, lm_bos=lm_bos)
 
 
-class _BeamNet:
+class _SearchNet:
     """The prediction network's and the joint's weights in the compute dtype ``cd`` (converted once through
-    ``WEIGHTS``) with the shapes and ctypes arguments the native beam searches take."""
+    ``WEIGHTS``) with the shapes and ctypes arguments the native searches take."""
 
     def __init__(self, model, cd):
         from .models import WEIGHTS
@@ -181,10 +162,19 @@ class _BeamNet:
                 _ptr_array(self.b_hh), self.H, _lib.ptr(self.wpc), _lib.ptr(self.bp))
 
 
+def _native(name, flm, *args, tail=()):
+    """``edgedict_<name>(*args, *tail)``, or with a fusion LM ``edgedict_<name>_lm(*args, lm, *tail)``: the ``_lm`` entry
+    points take the plain ones' arguments with the LM in front of the trailing state / workspace / stream."""
+    lib = _lib.load()
+    if flm is None:
+        return getattr(lib, "edgedict_" + name)(*args, *tail)
+    return getattr(lib, "edgedict_" + name + "_lm")(*args, flm.ref(), *tail)
+
+
 def joint_rows(model, enc_out):
     """E1 = enc_out [B, T, P] times the encoder half of the joint's first Linear, [B * T, J] in the compute dtype: the
     rows both beam searches read (``beam_search_rows``, ``StreamingBeamSearch.advance``)."""
-    return _BeamNet(model, enc_out.dtype).e1(enc_out.contiguous())
+    return _SearchNet(model, enc_out.dtype).e1(enc_out.contiguous())
 
 
 def beam_search_enc(model, enc_out, lens=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
@@ -210,15 +200,10 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     cd = E1.dtype
     lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
     EM = int(max_expansions) if max_expansions else max(16, 8 * W)
-    net = _BeamNet(model, cd)
-    lib = _lib.load()
+    net = _SearchNet(model, cd)
     flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
-    if flm is None:
-        nbytes = lib.edgedict_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W,
-                                                   EM, int(bool(prefix)))
-    else:
-        nbytes = lib.edgedict_beam_workspace_bytes_lm(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2,
-                                                      W, EM, int(bool(prefix)), flm.ref())
+    nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
+                     int(bool(prefix)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=E1.device)
     max_tokens = T * EM + 1
     tokens = np.zeros((B, max_tokens), dtype=np.int32)
@@ -230,10 +215,7 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
             lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM,
             int(bool(prefix)), tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
             score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-    if flm is None:
-        rc = lib.edgedict_beam_search(*args, _lib.ptr(ws), _lib.stream_ptr())
-    else:
-        rc = lib.edgedict_beam_search_lm(*args, flm.ref(), _lib.ptr(ws), _lib.stream_ptr())
+    rc = _native("beam_search", flm, *args, tail=(_lib.ptr(ws), _lib.stream_ptr()))
     _lib.check(rc, "beam_search")
     beam_search_batch.last_expansions = int(nexp.value)
     seqs = [tokens[b, :ntok[b]].astype(np.int64) for b in range(B)]
@@ -285,14 +267,9 @@ class StreamingBeamSearch:
         self._lm_args = (lm_weight, length_bonus, lm_bos)
         net = self._weights()
         flm = self._fusion()
-        lib = _lib.load()
         dims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.EM, self.NC)
-        if flm is None:
-            sbytes = lib.edgedict_beam_stream_state_bytes(*dims)
-            wbytes = lib.edgedict_beam_stream_workspace_bytes(*dims)
-        else:
-            sbytes = lib.edgedict_beam_stream_state_bytes_lm(*dims, flm.ref())
-            wbytes = lib.edgedict_beam_stream_workspace_bytes_lm(*dims, flm.ref())
+        sbytes = _native("beam_stream_state_bytes", flm, *dims)
+        wbytes = _native("beam_stream_workspace_bytes", flm, *dims)
         self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
         self._commit_buf = np.zeros((self.S, self.NC), dtype=np.int32)
@@ -302,7 +279,7 @@ class StreamingBeamSearch:
 
     def _weights(self):
         # converted once per parameter version by WEIGHTS (as run_search does); only the pointer bundle is rebuilt
-        return _BeamNet(self.model, self.cd)
+        return _SearchNet(self.model, self.cd)
 
     def _fusion(self):
         from .lm import FusionLM
@@ -312,8 +289,6 @@ class StreamingBeamSearch:
         """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log."""
         from .tokenizer import BOS
         net = self._weights()
-        flm = self._fusion()
-        lib = _lib.load()
         if mask is None:
             sel = np.ones(self.S, dtype=bool)
             mh, on_host = None, 0
@@ -322,12 +297,8 @@ class StreamingBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
         mp = None if mh is None else mh.ctypes.data_as(ctypes.c_void_p)
-        if flm is None:
-            rc = lib.edgedict_beam_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
-                                                _lib.ptr(self._state), _lib.stream_ptr())
-        else:
-            rc = lib.edgedict_beam_stream_reset_lm(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
-                                                   flm.ref(), _lib.ptr(self._state), _lib.stream_ptr())
+        rc = _native("beam_stream_reset", self._fusion(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
+                     tail=(_lib.ptr(self._state), _lib.stream_ptr()))
         _lib.check(rc, "beam_stream_reset")
         if not hasattr(self, "_committed"):
             self._committed = [[] for _ in range(self.S)]
@@ -374,18 +345,13 @@ class StreamingBeamSearch:
 
     def _advance(self, net, E1, T, P, nf):
         from .tokenizer import BOS
-        lib = _lib.load()
         nexp = ctypes.c_longlong(0)
         args = (dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S,
                 nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
                 self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p),
                 self._ncommit.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-        flm = self._fusion()
-        if flm is None:
-            rc = lib.edgedict_beam_stream_advance(*args, _lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
-        else:
-            rc = lib.edgedict_beam_stream_advance_lm(*args, flm.ref(), _lib.ptr(self._state), _lib.ptr(self._ws),
-                                                     _lib.stream_ptr())
+        rc = _native("beam_stream_advance", self._fusion(), *args,
+                     tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()))
         _lib.check(rc, "beam_stream_advance")
         self.last_expansions = int(nexp.value)
         for s in np.nonzero(self._ncommit)[0]:
