@@ -15,6 +15,7 @@
 //                                                                              latency-bound.
 //   3. rnnt_grad       : one wave64 per row again; reads logits once, writes grads once. HBM-bound.
 #include "common.hpp"
+#include <cfloat>
 
 namespace {
 
@@ -212,7 +213,10 @@ __device__ __forceinline__ double log_add64(double a, double b) {
 // trip each: 0.17 -> 0.03 ms).  Per cell the arithmetic and its operand order are those of the barrier kernel it
 // replaces (fp64 carry, fp32 correction term of log_add64 above): alphas, betas and the likelihoods are bit-identical
 // to that kernel built with the same log_add64 (the correction term itself changed in rounds 4 and 5).
-template <int C>
+// VIT = true is the Viterbi walk of the forced aligner: ONE wave per utterance (blockIdx.x = b, direction 0 only), max
+// in place of the log-add, v(t,u) written where the alphas go and the best path's score into ll[2 b].  The VIT = false
+// instantiation is the kernel as it was.
+template <int C, bool VIT = false>
 __global__ __launch_bounds__(64) void rnnt_alpha_beta(const float* __restrict__ lpb, const float* __restrict__ lpl,
                                                       const int32_t* __restrict__ act_lens,
                                                       const int32_t* __restrict__ label_lens, int Tm, int U1,
@@ -221,8 +225,8 @@ __global__ __launch_bounds__(64) void rnnt_alpha_beta(const float* __restrict__ 
     // log-probabilities are requested D steps ahead of their use (a step is ~0.3 us of dependent arithmetic, an L2
     // round trip ~1 us: one step ahead the recurrence waited for its loads on every row - 0.30 instead of 0.17 ms)
     constexpr int D = C <= 2 ? 8 : (C <= 4 ? 4 : (C <= 8 ? 2 : 1));
-    const int b = blockIdx.x >> 1;
-    const int dir = blockIdx.x & 1;
+    const int b = VIT ? blockIdx.x : blockIdx.x >> 1;
+    const int dir = VIT ? 0 : blockIdx.x & 1;
     const int lane = threadIdx.x;
     // clamped exactly as rnnt_lse_gather / rnnt_grad clamp them: malformed lengths (the Python shim
     // rejects them, a raw C-ABI caller may not) cannot index past the [Tm, U1] slab; an empty utterance
@@ -285,7 +289,7 @@ __global__ __launch_bounds__(64) void rnnt_alpha_beta(const float* __restrict__ 
                     const long long idx = base + (long long)t * U1 + u;
                     if (dir == 0) {
                         // a(t,u) = lse(a(t-1,u) + lpb(t-1,u), a(t,u-1) + lpl(t,u-1))
-                        const double a = (t == 0 && u == 0) ? 0.0 : log_add64(keep[c], side);
+                        const double a = (t == 0 && u == 0) ? 0.0 : (VIT ? fmax(keep[c], side) : log_add64(keep[c], side));
                         alphas[idx] = a;
                         keep[c] = a + cb[c];
                         side = (u < Ub) ? a + cl[c] : NEG;
@@ -331,18 +335,68 @@ __global__ __launch_bounds__(256) void rnnt_costs(const double* __restrict__ ll,
     if (threadIdx.x == 0 && reduced) reduced[0] = reduce_scale * (part[0] + part[1] + part[2] + part[3]);
 }
 
+// Back-trace of the Viterbi walk (rnnt_alpha_beta<C, true>): one wave per utterance.  Lane 0 walks from (T_b - 1, U_b)
+// to (0, 0) and re-forms, with the operations of the forward walk (double + (double)float), the two candidates of which
+// v(t,u) is the maximum - one of them is v(t,u) bit for bit, no back-pointers are stored.  TIE RULE: equal candidates
+// take the blank predecessor (come from t - 1).  frames[b][u] = frame on which label u is emitted (the step
+// (t,u) -> (t,u+1)); the other lanes write the -1 padding behind U_b.  T_b + U_b - 1 dependent steps of four loads.
+__global__ __launch_bounds__(64) void rnnt_viterbi_backtrace(const float* __restrict__ lpb, const float* __restrict__ lpl,
+                                                             const double* __restrict__ v, const double* __restrict__ ll,
+                                                             const int32_t* __restrict__ act_lens,
+                                                             const int32_t* __restrict__ label_lens, int Tm, int U1,
+                                                             int32_t* __restrict__ frames, float* __restrict__ scores) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U1 - 1));   // as rnnt_alpha_beta
+    int32_t* fr = frames + (long long)b * (U1 - 1);
+    for (int u = (Tb > 0 ? Ub : 0) + lane; u < U1 - 1; u += 64) fr[u] = -1;
+    if (lane != 0) return;
+    scores[b] = (float)ll[2 * b];                    // -inf for an empty utterance
+    if (Tb == 0) return;
+    const long long base = (long long)b * Tm * U1;
+    int t = Tb - 1, u = Ub;
+    while (u > 0) {
+        bool from_label = (t == 0);
+        if (!from_label) {
+            const long long up = base + (long long)(t - 1) * U1 + u, left = base + (long long)t * U1 + u - 1;
+            const double via_blank = v[up] + (double)lpb[up];
+            const double via_label = v[left] + (double)lpl[left];
+            from_label = via_label > via_blank;
+        }
+        if (from_label) {
+            fr[u - 1] = t;
+            --u;
+        } else {
+            --t;
+        }
+    }
+}
+
+// log(1 + lambda exp(d)), d <= 0 up to rounding: FastEmit's correction of c_all, on the hardware transcendental units
+// with the series of log_add64 below 1e-2 (the term lies in [0, log(1 + lambda)])
+__device__ __forceinline__ float fastemit_log1p(float lambda, float d) {
+    const float x = lambda * __expf(d);
+    return x < 1e-2f ? x * (1.f - x * (0.5f - x * (1.f / 3.f))) : __logf(1.f + x);
+}
+
 // ------------------------------------------------------------------ kernel 3
+// FastEmit (Yu et al. 2021), FE = true: the gradient through the label emissions is scaled by 1 + lambda,
+//   grad(t,u,k) = softmax_k (wb + (1 + lambda) wl) - [k == blank] wb - [k == y] (1 + lambda) wl,
+//   wb = exp(a + lpb + beta(t+1,u) - L), wl = exp(a + lpl + beta(t,u+1) - L), wb + wl = exp(a + beta(t,u) - L):
+// c_label grows by log1p(lambda) (fe_log1p, formed on the host) and c_all by log(1 + lambda wl / (wb + wl)), the
+// exponent lpl + beta(t,u+1) - beta(t,u) formed in fp64 - one read of the lpl plane per CELL.  FE = false is the
+// kernel as it was: the three extra arguments are not touched.
 #ifndef ED_GRAD_OCC
 #define ED_GRAD_OCC 1
 #endif
-template <typename T>
+template <typename T, bool FE>
 __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
     const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int B, int Tm,
     int U1, int V, int blank, const float* __restrict__ denom, const double* __restrict__ alphas,
     const double* __restrict__ betas, const double* __restrict__ ll, float scale_host,
     const float* __restrict__ scale_dev, int scale_stride, int vec_ok,
-    const long long* __restrict__ pk_off, int b0) {
+    const long long* __restrict__ pk_off, int b0, const float* __restrict__ lpl, float fe_lambda, float fe_log1p) {
     constexpr int VEC = ElemIO<T>::VEC;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -383,7 +437,12 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
                 c_blank = (float)(a - L) - lse;
             if (u < Ub) {
                 y = labels[(long long)b * (U1 - 1) + u];
-                c_label = (float)(a + betas[row + 1] - L) - lse;
+                const double bl = betas[row + 1];
+                c_label = (float)(a + bl - L) - lse;
+                if (FE) {
+                    c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
+                    c_label += fe_log1p;
+                }
             }
         }
         if (vec_ok) {
@@ -436,14 +495,14 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
 // row - VEC accumulators per lane with static indices, four loads in flight as before.  (Tried first: one row per wave
 // with 4 x VEC register accumulators, 1.09 instead of 0.88 ms; LDS ds_add_f32 accumulators, 5.8 ms.)
 // Needs 16-byte aligned rows and V <= 4 * 64 * VEC (2048 in bf16, 1024 in f32); arithmetic per cell as in rnnt_grad.
-template <typename T>
+template <typename T, bool FE>
 __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
     const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int B, int Tm,
     int U1, int V, int blank, const float* __restrict__ denom, const double* __restrict__ alphas,
     const double* __restrict__ betas, const double* __restrict__ ll, float scale_host,
     const float* __restrict__ scale_dev, int scale_stride, const long long* __restrict__ pk_off,
-    float* __restrict__ colsum_parts) {
+    float* __restrict__ colsum_parts, const float* __restrict__ lpl, float fe_lambda, float fe_log1p) {
     constexpr int VEC = ElemIO<T>::VEC;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -470,7 +529,7 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
             const long long row = ((long long)b * Tm + t) * U1 + u;
             const double a = alphas[row], bt_ = betas[row];
             const float lse = denom[row];
-            const float c_all = (float)(a + bt_ - L) - lse;
+            float c_all = (float)(a + bt_ - L) - lse;
             float c_blank = -INFINITY, c_label = -INFINITY;
             int y = -1;
             if (t < Tb - 1)
@@ -479,7 +538,12 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
                 c_blank = (float)(a - L) - lse;
             if (u < Ub) {
                 y = labels[(long long)b * (U1 - 1) + u];
-                c_label = (float)(a + betas[row + 1] - L) - lse;
+                const double bl = betas[row + 1];
+                c_label = (float)(a + bl - L) - lse;
+                if (FE) {
+                    c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
+                    c_label += fe_log1p;
+                }
             }
             if (col_live) {
                 float x[VEC], o[VEC];
@@ -537,10 +601,14 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
                         const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U1,
                         int V, int blank, float* costs, float* reduced, float reduce_scale,
                         void* workspace, const long long* pk_off, void* stream_,
-                        const float* lse_parts = nullptr, int lse_slots = 0) {
+                        const float* lse_parts = nullptr, int lse_slots = 0,
+                        int32_t* al_frames = nullptr, float* al_scores = nullptr) {
+    // al_scores set: the forced aligner (edgedict_rnnt_align*): same first stage, then the Viterbi walk and its
+    // back-trace in place of the two lattice walks and the costs
     if (int rc = check_common(B, T, U1, V, blank, acts_dtype)) return rc;
-    ED_CHECK_ARG(acts && (labels || U1 == 1) && act_lens && label_lens && costs && workspace,
+    ED_CHECK_ARG(acts && (labels || U1 == 1) && act_lens && label_lens && (costs || al_scores) && workspace,
                  "rnnt_loss_forward: null pointer argument");
+    ED_CHECK_ARG(!al_scores || al_frames || U1 == 1, "rnnt_align: null frames");
     ED_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "rnnt_loss_forward: workspace must be 16-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
     const WsLayout w = ws_layout(B, T, U1);
@@ -575,8 +643,15 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
 
     // one wave per (utterance, direction), C = ceil(U1 / 64) label columns per lane (rounded up to a power of two)
     ED_CHECK_ARG(U1 <= 64 * 32, "rnnt_loss_forward: more than 2047 labels per utterance (U1 = %d)", U1);
-#define ED_AB_LAUNCH(CC) hipLaunchKernelGGL(rnnt_alpha_beta<CC>, dim3(2 * B), dim3(64), 0, stream, lpb, lpl, act_lens, \
-                                            label_lens, T, U1, alphas, betas, ll)
+#define ED_AB_LAUNCH(CC)                                                                                              \
+    do {                                                                                                              \
+        if (al_scores)                                                                                                \
+            hipLaunchKernelGGL((rnnt_alpha_beta<CC, true>), dim3(B), dim3(64), 0, stream, lpb, lpl, act_lens,         \
+                               label_lens, T, U1, alphas, betas, ll);                                                 \
+        else                                                                                                          \
+            hipLaunchKernelGGL(rnnt_alpha_beta<CC>, dim3(2 * B), dim3(64), 0, stream, lpb, lpl, act_lens, label_lens, \
+                               T, U1, alphas, betas, ll);                                                             \
+    } while (0)
     const int cols = (U1 + 63) / 64;
     if (cols <= 1) ED_AB_LAUNCH(1);
     else if (cols <= 2) ED_AB_LAUNCH(2);
@@ -586,6 +661,12 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
     else ED_AB_LAUNCH(32);
 #undef ED_AB_LAUNCH
     ED_CHECK_LAUNCH("rnnt_alpha_beta");
+    if (al_scores) {
+        hipLaunchKernelGGL(rnnt_viterbi_backtrace, dim3(B), dim3(64), 0, stream, lpb, lpl, alphas, ll, act_lens,
+                           label_lens, T, U1, al_frames, al_scores);
+        ED_CHECK_LAUNCH("rnnt_viterbi_backtrace");
+        return ED_OK;
+    }
     hipLaunchKernelGGL(rnnt_costs, dim3(1), dim3(256), 0, stream, ll, costs, B, reduced,
                        reduce_scale);
     ED_CHECK_LAUNCH("rnnt_costs");
@@ -634,7 +715,10 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
                          int V, int blank, const void* workspace, float grad_scale_host,
                          const float* grad_scale_dev, int grad_scale_stride,
                          const long long* pk_off, void* stream_, int b0 = 0, int nb = -1,
-                         float* colsum_parts = nullptr) {
+                         float* colsum_parts = nullptr, float fe_lambda = 0.f) {
+    // (first: a bad lambda is refused whatever else the call holds, before any launch)
+    ED_CHECK_ARG(fe_lambda >= 0.f && fe_lambda <= FLT_MAX, "rnnt_loss_backward: fastemit_lambda must be finite and >= 0 (got %g)",
+                 (double)fe_lambda);
     if (int rc = check_common(B, T, U1, V, blank, acts_dtype)) return rc;
     if (nb < 0) nb = B - b0;
     ED_CHECK_ARG(b0 >= 0 && nb >= 0 && b0 + nb <= B, "rnnt_loss_backward: utterance range [%d, %d) outside the batch of %d", b0, b0 + nb, B);
@@ -648,6 +732,10 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
     const double* alphas = (const double*)(p + w.off_alpha);
     const double* betas = (const double*)(p + w.off_beta);
     const double* ll = (const double*)(p + w.off_ll);
+    const float* lpl = (const float*)(p + w.off_lpl);
+    // FastEmit is a template parameter of the gradient kernels: lambda == 0 launches the instantiation without it
+    const bool fe = fe_lambda > 0.f;
+    const float fe_log1p = log1pf(fe_lambda);
     const size_t esz = acts_dtype == ED_F32 ? 4 : 2;
     const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)acts & 15) == 0) &&
                        (((uintptr_t)grads & 15) == 0);
@@ -657,27 +745,33 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
         ED_CHECK_ARG(vec_ok && V <= cs_width && pk_off && b0 == 0 && nb == B,
                      "rnnt_loss_backward: fused column sums need the packed lattice, 16-byte aligned rows and V <= %d (got V = %d)",
                      cs_width, V);
-        if (acts_dtype == ED_F32)
-            hipLaunchKernelGGL(rnnt_grad_cs<float>, grid, dim3(256), 0, stream, (const float*)acts, (float*)grads, labels,
-                               act_lens, label_lens, B, T, U1, V, blank, denom, alphas, betas, ll, grad_scale_host,
-                               grad_scale_dev, grad_scale_stride, pk_off, colsum_parts);
-        else
-            hipLaunchKernelGGL(rnnt_grad_cs<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)acts, (bf16_t*)grads,
-                               labels, act_lens, label_lens, B, T, U1, V, blank, denom, alphas, betas, ll,
-                               grad_scale_host, grad_scale_dev, grad_scale_stride, pk_off, colsum_parts);
+#define ED_CS_LAUNCH(TT, FE)                                                                                           \
+    hipLaunchKernelGGL((rnnt_grad_cs<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
+                       label_lens, B, T, U1, V, blank, denom, alphas, betas, ll, grad_scale_host, grad_scale_dev,        \
+                       grad_scale_stride, pk_off, colsum_parts, lpl, fe_lambda, fe_log1p)
+        if (acts_dtype == ED_F32) {
+            if (fe) ED_CS_LAUNCH(float, true);
+            else ED_CS_LAUNCH(float, false);
+        } else {
+            if (fe) ED_CS_LAUNCH(bf16_t, true);
+            else ED_CS_LAUNCH(bf16_t, false);
+        }
+#undef ED_CS_LAUNCH
         ED_CHECK_LAUNCH("rnnt_grad_cs");
         return ED_OK;
     }
-    if (acts_dtype == ED_F32)
-        hipLaunchKernelGGL(rnnt_grad<float>, grid, dim3(256), 0, stream, (const float*)acts,
-                           (float*)grads, labels, act_lens, label_lens, B, T, U1, V, blank, denom,
-                           alphas, betas, ll, grad_scale_host, grad_scale_dev, grad_scale_stride,
-                           vec_ok, pk_off, b0);
-    else
-        hipLaunchKernelGGL(rnnt_grad<bf16_t>, grid, dim3(256), 0, stream,
-                           (const bf16_t*)acts, (bf16_t*)grads, labels, act_lens, label_lens, B, T,
-                           U1, V, blank, denom, alphas, betas, ll, grad_scale_host, grad_scale_dev,
-                           grad_scale_stride, vec_ok, pk_off, b0);
+#define ED_GRAD_LAUNCH(TT, FE)                                                                                         \
+    hipLaunchKernelGGL((rnnt_grad<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
+                       label_lens, B, T, U1, V, blank, denom, alphas, betas, ll, grad_scale_host, grad_scale_dev,     \
+                       grad_scale_stride, vec_ok, pk_off, b0, lpl, fe_lambda, fe_log1p)
+    if (acts_dtype == ED_F32) {
+        if (fe) ED_GRAD_LAUNCH(float, true);
+        else ED_GRAD_LAUNCH(float, false);
+    } else {
+        if (fe) ED_GRAD_LAUNCH(bf16_t, true);
+        else ED_GRAD_LAUNCH(bf16_t, false);
+    }
+#undef ED_GRAD_LAUNCH
     ED_CHECK_LAUNCH("rnnt_grad");
     return ED_OK;
 }
@@ -736,4 +830,92 @@ extern "C" int edgedict_rnnt_loss_backward_packed_range(const void* acts, int ac
     return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank,
                          workspace, grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets,
                          stream_, b0, nb);
+}
+
+// ---------------------------------------------------------------------------------------------- FastEmit entry points
+// the plain entry points above with `fastemit_lambda` (>= 0, finite): only the gradient changes, the costs the forward
+// call returned stay the plain negative log-likelihood.  lambda == 0 runs the kernels of the plain entry points.
+extern "C" int edgedict_rnnt_loss_backward_fe(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                              const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U1,
+                                              int V, int blank, const void* workspace, float grad_scale_host,
+                                              const float* grad_scale_dev, int grad_scale_stride,
+                                              float fastemit_lambda, void* stream_) {
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, nullptr, stream_, 0, -1, nullptr,
+                         fastemit_lambda);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_fe(const void* acts, int acts_dtype, void* grads,
+                                                     const int32_t* labels, const int32_t* act_lens,
+                                                     const int32_t* label_lens, const long long* row_offsets, int B,
+                                                     int T, int U1, int V, int blank, const void* workspace,
+                                                     float grad_scale_host, const float* grad_scale_dev,
+                                                     int grad_scale_stride, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_fe: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets, "rnnt_loss_backward_packed_fe: null row_offsets");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, 0, -1, nullptr,
+                         fastemit_lambda);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_colsum_fe(const void* acts, int acts_dtype, void* grads,
+                                                            const int32_t* labels, const int32_t* act_lens,
+                                                            const int32_t* label_lens, const long long* row_offsets,
+                                                            int B, int T, int U1, int V, int blank,
+                                                            const void* workspace, float grad_scale_host,
+                                                            const float* grad_scale_dev, int grad_scale_stride,
+                                                            float* colsum_parts, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_colsum_fe: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets && colsum_parts, "rnnt_loss_backward_packed_colsum_fe: null pointer");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, 0, -1, colsum_parts,
+                         fastemit_lambda);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_range_fe(const void* acts, int acts_dtype, void* grads,
+                                                           const int32_t* labels, const int32_t* act_lens,
+                                                           const int32_t* label_lens, const long long* row_offsets,
+                                                           int B, int T, int U1, int V, int blank,
+                                                           const void* workspace, float grad_scale_host,
+                                                           const float* grad_scale_dev, int grad_scale_stride, int b0,
+                                                           int nb, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_range_fe: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets, "rnnt_loss_backward_packed_range_fe: null row_offsets");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, b0, nb, nullptr,
+                         fastemit_lambda);
+}
+
+// ---------------------------------------------------------------------------------------------------- forced alignment
+// Viterbi over the lattice of the loss: v(t,u) = max(v(t-1,u) + lpb(t-1,u), v(t,u-1) + lpl(t,u-1)),
+// score = v(T_b-1,U_b) + lpb(T_b-1,U_b).  Arguments as the forward entry points', frames [B][U1-1] (frame on which
+// label u is emitted, -1 behind U_b) and scores [B] in place of costs / reduced.  Ties take the blank predecessor.
+extern "C" int edgedict_rnnt_align(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                                   const int32_t* label_lens, int B, int T, int U1, int V, int blank, int32_t* frames,
+                                   float* scores, void* workspace, void* stream_) {
+    ED_CHECK_ARG(scores, "rnnt_align: null scores");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, nullptr, stream_, nullptr, 0, frames, scores);
+}
+
+extern "C" int edgedict_rnnt_align_packed(const void* acts, int acts_dtype, const int32_t* labels,
+                                          const int32_t* act_lens, const int32_t* label_lens,
+                                          const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                          int32_t* frames, float* scores, void* workspace, void* stream_) {
+    ED_CHECK_ARG(row_offsets && scores, "rnnt_align_packed: null pointer");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, row_offsets, stream_, nullptr, 0, frames, scores);
+}
+
+extern "C" int edgedict_rnnt_align_packed_parts(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                                const int32_t* label_lens, const long long* row_offsets, int B, int T,
+                                                int U1, int V, int blank, int32_t* frames, float* scores,
+                                                void* workspace, const float* lse_parts, int lse_slots, void* stream_) {
+    ED_CHECK_ARG(row_offsets && lse_parts && scores, "rnnt_align_packed_parts: null pointer");
+    ED_CHECK_ARG(lse_slots == (V + 63) / 64, "rnnt_align_packed_parts: lse_slots must be ceil(V / 64)");
+    return loss_forward(acts, ED_BF16, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, row_offsets, stream_, lse_parts, lse_slots, frames, scores);
 }

@@ -391,3 +391,15 @@ class StreamingBeamSearch:
     def expansions(self):
         """int64 [S]: prediction-network steps (pops) of every stream since its reset."""
         return self._read()[3]
+
+
+def emission_times(frames, flags, time_reduction=2):
+    """Seconds (float64 tensor, shape of ``frames``) at which the encoder frames of ``Transducer.align`` /
+    ``loss.rnnt_align`` START: one encoder frame covers ``flags.hop_length * flags.downsample * time_reduction`` samples
+    (feature hop x frame stacking, as ``stream.chunk_geometry`` counts a chunk's hop, x the encoder's time reductions:
+    2 per reduced layer, ``enc_time_reductions=[1]`` by default -> 2).  The -1 padding behind an utterance's labels
+    becomes NaN.  The frame's END is one such step later; a causal model cannot have seen the token's audio before."""
+    frames = torch.as_tensor(frames)
+    step = flags.hop_length * max(1, flags.downsample) * int(time_reduction) / float(getattr(flags, "sample_rate", 16000))
+    out = frames.to(torch.float64) * step
+    return torch.where(frames < 0, torch.full_like(out, float("nan")), out)

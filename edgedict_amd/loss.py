@@ -15,7 +15,14 @@ Difference from upstream that is deliberate: upstream computes the full gradient
 ``forward`` and rescales it by ``grad_output`` in ``backward`` (a second pass over
 ``B*T*(U+1)*V`` elements).  Here ``forward`` only fills the small alpha/beta workspace and
 ``backward`` writes the already-scaled gradient once.
+
+``fastemit_lambda`` (FastEmit, Yu et al. 2021; the argument of the same name of the warp-transducer
+forks) scales the gradient that flows through the label emissions by ``1 + lambda``.  The returned
+costs stay the plain negative log-likelihood: only the gradient changes.  ``rnnt_align`` is the forced
+aligner over the same lattice (the frames on which a known transcript is emitted).
 """
+import math
+
 import torch
 
 from . import _lib
@@ -54,9 +61,17 @@ def _certify_inputs(acts, labels, act_lens, label_lens, check_lengths):
             raise ValueError("Output length mismatch")
 
 
+def check_fastemit_lambda(value):
+    """``float(value)``; ValueError unless it is finite and >= 0."""
+    lam = float(value)
+    if not (lam >= 0.0 and math.isfinite(lam)):
+        raise ValueError("fastemit_lambda must be finite and >= 0, got %r" % (value,))
+    return lam
+
+
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction):
+    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda=0.0):
         _lib.require_cuda(acts, labels, act_lens, label_lens)
         B, T, U1, V = acts.shape
         lib = _lib.load()
@@ -70,6 +85,7 @@ class _RNNTLossFn(torch.autograd.Function):
         ctx.save_for_backward(acts, labels, act_lens, label_lens, ws)
         ctx.blank = int(blank)
         ctx.reduction = reduction
+        ctx.fastemit_lambda = float(fastemit_lambda)
         ctx.costs = costs
         return costs if reduction == "none" else reduced
 
@@ -81,9 +97,14 @@ class _RNNTLossFn(torch.autograd.Function):
         go = grad_output.contiguous().float()
         host_scale = 1.0 / B if ctx.reduction == "mean" else 1.0
         stride = 1 if ctx.reduction == "none" else 0
-        _lib.call("rnnt_loss_backward", acts, _lib.dtype_code(acts.dtype), grads, labels,
-                  act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride)
-        return grads, None, None, None, None, None
+        if ctx.fastemit_lambda == 0.0:
+            _lib.call("rnnt_loss_backward", acts, _lib.dtype_code(acts.dtype), grads, labels,
+                      act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride)
+        else:
+            _lib.call("rnnt_loss_backward_fe", acts, _lib.dtype_code(acts.dtype), grads, labels,
+                      act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride,
+                      ctx.fastemit_lambda)
+        return grads, None, None, None, None, None, None
 
 
 class RNNTLoss(torch.nn.Module):
@@ -91,19 +112,45 @@ class RNNTLoss(torch.nn.Module):
 
     ``reduction``: ``'mean'`` (default; ``sum_b cost_b / B`` with shape ``(1,)``), ``'sum'``
     (shape ``(1,)``) or ``'none'`` (shape ``(B,)``).
+
+    ``fastemit_lambda`` >= 0 (default 0: the plain loss, bit for bit): FastEmit regularisation.  The
+    gradient through the label emissions is scaled by ``1 + lambda``; the returned value stays the plain
+    negative log-likelihood, so losses are comparable across lambdas.
     """
 
-    def __init__(self, blank=0, reduction="mean", check_lengths=True):
+    def __init__(self, blank=0, reduction="mean", check_lengths=True, fastemit_lambda=0.0):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+        self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
         self.blank = blank
         self.reduction = reduction
         self.check_lengths = check_lengths
 
     def forward(self, acts, labels, act_lens, label_lens):
         _certify_inputs(acts, labels, act_lens, label_lens, self.check_lengths)
-        return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, self.blank, self.reduction)
+        return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, self.blank, self.reduction,
+                                 self.fastemit_lambda)
+
+
+@torch.no_grad()
+def rnnt_align(acts, labels, act_lens, label_lens, blank=0):
+    """Forced alignment: the single most probable alignment of the transcripts ``labels`` (Viterbi over
+    the lattice of the loss).  Arguments as ``RNNTLoss.forward`` (validated the same way).  Returns
+    ``(frames, scores)``: ``frames`` int32 ``[B, U]``, ``frames[b, u]`` the frame on which label ``u`` of
+    utterance ``b`` is emitted (non-decreasing in ``u``; -1 for ``u >= label_lens[b]``), and ``scores``
+    float32 ``[B]``, the log-probability of that alignment (``<= -cost``).  Where two alignments score
+    equal, the one that waits (takes the blank predecessor) wins."""
+    _certify_inputs(acts, labels, act_lens, label_lens, True)
+    _lib.require_cuda(acts, labels, act_lens, label_lens)
+    B, T, U1, V = acts.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=acts.device)
+    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=acts.device)
+    scores = torch.empty(B, dtype=torch.float32, device=acts.device)
+    _lib.call("rnnt_align", acts.detach(), _lib.dtype_code(acts.dtype), labels, act_lens, label_lens, B, T, U1, V,
+              int(blank), frames, scores, ws)
+    return frames, scores
 
 
 def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0):

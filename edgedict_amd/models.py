@@ -419,10 +419,12 @@ class _JointLossFn(torch.autograd.Function):
     their gradients are [M_valid, .] matrices (row of (b,t,u) = off[b] + t (U_b+1) + u).  Cells
     outside the box have zero gradient and no influence on the loss, so nothing changes
     numerically; the two big products and the loss kernels just do not touch padding
-    (35 % of the rows on the bench batch).  Needs the lengths on the HOST (they size M_valid)."""
+    (35 % of the rows on the bench batch).  Needs the lengths on the HOST (they size M_valid).
+    ``fastemit_lambda`` > 0 scales the gradient through the label emissions by 1 + lambda (loss.py);
+    the returned loss stays the plain negative log-likelihood."""
 
     @staticmethod
-    def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd):
+    def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd, fastemit_lambda=0.0):
         from ._staging import to_device
         B, T, P = enc.shape
         U1, P2 = dec.shape[1], dec.shape[2]
@@ -478,6 +480,7 @@ class _JointLossFn(torch.autograd.Function):
         ctx.save_for_backward(enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, off_d, ws)
         ctx.b1, ctx.b2 = b1, b2
         ctx.cfg = (cd, B, T, U1, P, P2, J, V, M, int(blank))
+        ctx.fastemit_lambda = float(fastemit_lambda)
         return reduced
 
     @staticmethod
@@ -497,8 +500,16 @@ class _JointLossFn(torch.autograd.Function):
         # partial rows (a few MB) instead of a second pass over dl beside the encoder's BPTT (0.4 ms per step)
         cs_rows = _lib.load().edgedict_rnnt_grad_colsum_rows(_lib.dtype_code(cd), B, T, U1, V) if config.FUSED_DB2 else 0
         db2_parts = torch.empty(cs_rows, V, dtype=F32, device=dl.device) if cs_rows > 0 else None
+        lam = ctx.fastemit_lambda
         with ops.timed("rnnt_grad"):
-            if db2_parts is not None:
+            if lam != 0.0:
+                if db2_parts is not None:
+                    _lib.call("rnnt_loss_backward_packed_colsum_fe", logits, _lib.dtype_code(cd), dl, labels, al_d,
+                              ll_d, off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, lam)
+                else:
+                    _lib.call("rnnt_loss_backward_packed_fe", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
+                              off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, lam)
+            elif db2_parts is not None:
                 _lib.call("rnnt_loss_backward_packed_colsum", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
                           off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts)
             else:
@@ -522,7 +533,7 @@ class _JointLossFn(torch.autograd.Function):
             wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
             wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return (denc, ddec, *wg.grads, None, None, None, None, None)
+        return (denc, ddec, *wg.grads, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -853,9 +864,13 @@ class Transducer(nn.Module):
                  enc_hidden_size, enc_layers, enc_dropout, enc_proj_size,
                  dec_hidden_size, dec_layers, dec_dropout, dec_proj_size,
                  joint_size, enc_time_reductions=[1],
-                 blank=NUL, module_type='LSTM', output_loss=True):
+                 blank=NUL, module_type='LSTM', output_loss=True, *, fastemit_lambda=0.0):
         super().__init__()
         self.blank = blank
+        # FastEmit (loss.py): a plain attribute - no parameter, no buffer, the state dict's keys do not change.  Scales
+        # the gradient through the label emissions by 1 + lambda; the loss forward() returns stays the plain one.
+        from .loss import check_fastemit_lambda
+        self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
         if module_type not in ['GRU', 'LSTM']:
             raise ValueError('Unsupported module type')
         self.encoder = Encoder(input_size=input_size, hidden_size=enc_hidden_size,
@@ -928,7 +943,7 @@ class Transducer(nn.Module):
             # output with only xs uploaded) is moved, as Decoder.forward does for its own copy
             labels = ys.to(device=h_enc.device, dtype=torch.int32).contiguous()
             loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias,
-                                      l2.weight, l2.bias, labels, act, ylen, self.blank, cd)
+                                      l2.weight, l2.bias, labels, act, ylen, self.blank, cd, self.fastemit_lambda)
             ops.mark("joint:exit")
             return loss
         logits = self.joint(h_enc, h_dec)
@@ -941,9 +956,74 @@ class Transducer(nn.Module):
                 logits, labels,
                 xlen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
                 ylen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
-                self.blank, "mean")
+                self.blank, "mean", self.fastemit_lambda)
             return loss
         return logits
+
+    @torch.no_grad()
+    def align(self, xs, ys, xlen, ylen):
+        """Forced alignment of the transcripts ``ys`` (``loss.rnnt_align`` on this model's joint logits): returns
+        ``(frames, scores)``, ``frames`` int32 ``[B, U]`` with the ENCODER frame (after the time reductions, as
+        ``scale_length`` counts them) on which each label is emitted, -1 behind ``ylen[b]``; ``scores`` float32 ``[B]``, the
+        log-probability of the best alignment.  ``decode.emission_times`` turns the frames into seconds.  Arguments as
+        ``forward``; with host-side lengths the joint runs on the packed lattice as the training path does (the dense
+        logits are never formed).  Leaves no state behind: run it in ``eval()`` mode, or dropout takes part."""
+        from ._staging import to_device
+        xs = xs[:, :xlen.max()].contiguous()
+        ys = ys[:, :ylen.max()].contiguous()
+        if xs.is_cuda and not ys.is_cuda:
+            ys = ys.to(xs.device)
+        h_enc, _ = self.encoder(xs)
+        h_dec, _ = self.decoder(ys)
+        act = self.scale_length(h_enc, xlen)
+        dev = h_enc.device
+        labels = ys.to(device=dev, dtype=torch.int32).contiguous()
+        if not (config.PACKED_LATTICE and not xlen.is_cuda and not ylen.is_cuda and h_enc.is_cuda):
+            from .loss import rnnt_align
+            return rnnt_align(self.joint(h_enc, h_dec).contiguous(), labels,
+                              act.to(device=dev, dtype=torch.int32).contiguous(),
+                              ylen.to(device=dev, dtype=torch.int32).contiguous(), self.blank)
+        cd = self.compute_dtype
+        l1, l2 = self.joint.joint[0], self.joint.joint[2]
+        enc, dec = _to_cd(h_enc, cd), _to_cd(h_dec, cd)
+        B, T, P = enc.shape
+        U1, P2 = dec.shape[1], dec.shape[2]
+        J, V = l1.weight.shape[0], l2.weight.shape[0]
+        al = act.to(torch.int64).cpu()
+        ll = ylen.to(torch.int64).cpu()
+        if int(al.max()) != T or int(ll.max()) != U1 - 1 or int(al.min()) < 1 or int(ll.min()) < 0:
+            raise ValueError("Input length mismatch")
+        rows = al * (ll + 1)
+        off = torch.zeros(B, dtype=torch.int64)
+        off[1:] = torch.cumsum(rows, 0)[:-1]
+        M = int(rows.sum())
+        off_d = to_device(off, dev)
+        al_d = to_device(al.to(torch.int32), dev)
+        ll_d = to_device(ll.to(torch.int32), dev)
+        w1c = WEIGHTS.get(l1.weight, cd)
+        w2c = WEIGHTS.get(l2.weight, cd)
+        E1 = ops.gemm(enc.reshape(B * T, P), w1c[:, :P])
+        D1 = ops.gemm(dec.reshape(B * U1, P2), w1c[:, P:], bias=l1.bias.detach())
+        hid = torch.empty(M, J, dtype=cd, device=dev)
+        _lib.call("joint_hidden_fwd_packed", _lib.dtype_code(cd), E1, D1, hid, al_d, ll_d, off_d, B, T, U1, J)
+        ws = torch.empty(_lib.load().edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=dev)
+        frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, dtype=F32, device=dev)
+        if config.FUSED_LSE and cd == torch.bfloat16 and J >= 128 and J % 64 == 0 and V % 8 == 0 and M >= 256:
+            slots = (V + 63) // 64
+            parts = torch.empty(M, slots, 2, dtype=F32, device=dev)
+            logits = torch.empty(M, V, dtype=cd, device=dev)
+            _lib.call("gemm_nt_lse", hid, ops._ll(J), w2c, ops._ll(J), logits, ops._ll(V), M, V, J,
+                      l2.bias.detach(), parts)
+            with ops.timed("rnnt_align"):
+                _lib.call("rnnt_align_packed_parts", logits, labels, al_d, ll_d, off_d, B, T, U1, V, int(self.blank),
+                          frames, scores, ws, parts, slots)
+        else:
+            logits = ops.gemm(hid, w2c, bias=l2.bias.detach())
+            with ops.timed("rnnt_align"):
+                _lib.call("rnnt_align_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d, B, T, U1, V,
+                          int(self.blank), frames, scores, ws)
+        return frames, scores
 
     @torch.no_grad()
     def greedy_decode(self, xs, xlen):

@@ -50,6 +50,9 @@ class TrainEngine:
             self.spec_augment = SpecAugment(getattr(flags, "T_mask", 0), getattr(flags, "T_num_mask", 0),
                                             getattr(flags, "F_mask", 0), getattr(flags, "F_num_mask", 0))
         self.model = Transducer(**model_kwargs(flags, vocab_size=vocab_size))
+        # FastEmit (loss.py): a flag of the training run, not of the model's shape - model_kwargs does not carry it
+        from .loss import check_fastemit_lambda
+        self.model.fastemit_lambda = check_fastemit_lambda(getattr(flags, "fastemit_lambda", 0.0))
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
         self.model.to(self.device)

@@ -125,6 +125,55 @@ int edgedict_rnnt_loss_backward_packed_range(const void* acts, int acts_dtype, v
                                              int B, int T, int U1, int V, int blank, const void* workspace,
                                              float grad_scale_host, const float* grad_scale_dev,
                                              int grad_scale_stride, int b0, int nb, void* stream);
+/* FastEmit (Yu et al. 2021): the four backward entry points above with `fastemit_lambda` behind their own arguments.
+ * The gradient that flows through the label emissions is scaled by 1 + lambda:
+ *   wb = exp(alpha + lp_blank + beta(t+1,u) - L),  wl = exp(alpha + lp_label + beta(t,u+1) - L)
+ *   grad(t,u,k) = softmax_k (wb + (1 + lambda) wl) - [k == blank] wb - [k == labels[u]] (1 + lambda) wl
+ * The COSTS of the forward call stay the plain negative log-likelihood (validation losses stay comparable across
+ * lambdas); the workspace is the one any forward entry point filled.  lambda == 0 launches the kernels of the plain
+ * entry points (bit-identical gradients and column sums); lambda < 0, NaN or infinite is ED_ERR_INVALID, reported
+ * before anything is launched. */
+int edgedict_rnnt_loss_backward_fe(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                   const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U1, int V,
+                                   int blank, const void* workspace, float grad_scale_host,
+                                   const float* grad_scale_dev, int grad_scale_stride, float fastemit_lambda,
+                                   void* stream);
+int edgedict_rnnt_loss_backward_packed_fe(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                          const int32_t* act_lens, const int32_t* label_lens,
+                                          const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                          const void* workspace, float grad_scale_host, const float* grad_scale_dev,
+                                          int grad_scale_stride, float fastemit_lambda, void* stream);
+int edgedict_rnnt_loss_backward_packed_colsum_fe(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                                 const int32_t* act_lens, const int32_t* label_lens,
+                                                 const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                                 const void* workspace, float grad_scale_host,
+                                                 const float* grad_scale_dev, int grad_scale_stride,
+                                                 float* colsum_parts, float fastemit_lambda, void* stream);
+int edgedict_rnnt_loss_backward_packed_range_fe(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                                const int32_t* act_lens, const int32_t* label_lens,
+                                                const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                                const void* workspace, float grad_scale_host,
+                                                const float* grad_scale_dev, int grad_scale_stride, int b0, int nb,
+                                                float fastemit_lambda, void* stream);
+/* Forced alignment: the single best alignment of a KNOWN transcript (Viterbi over the lattice of the loss),
+ *   v(t,u) = max(v(t-1,u) + lp_blank(t-1,u), v(t,u-1) + lp_label(t,u-1)),  score = v(T_b-1,U_b) + lp_blank(T_b-1,U_b).
+ * Arguments as the forward entry points' (dense; packed; packed bf16 with the log-sum-exp partials), with
+ *   frames  [B, U1-1] int32  out: frames[b][u] = frame on which label u of utterance b is emitted, -1 for u >= label_lens[b]
+ *   scores  [B] fp32         out: log-probability of that alignment (<= -cost); -inf for an empty utterance (T_b <= 0,
+ *                            whose frames are all -1)
+ * in place of costs / reduced.  Lengths are clamped as the loss clamps them.  TIE RULE: where both predecessors of a
+ * cell score equal, the path comes from the blank one (t - 1).  The workspace (same size and layout as the loss's) is
+ * scratch: v lies where the alphas go, the beta plane is not written. */
+int edgedict_rnnt_align(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                        const int32_t* label_lens, int B, int T, int U1, int V, int blank, int32_t* frames,
+                        float* scores, void* workspace, void* stream);
+int edgedict_rnnt_align_packed(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                               const int32_t* label_lens, const long long* row_offsets, int B, int T, int U1, int V,
+                               int blank, int32_t* frames, float* scores, void* workspace, void* stream);
+int edgedict_rnnt_align_packed_parts(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                     const int32_t* label_lens, const long long* row_offsets, int B, int T, int U1,
+                                     int V, int blank, int32_t* frames, float* scores, void* workspace,
+                                     const float* lse_parts, int lse_slots, void* stream);
 /* debug / test accessors into a filled workspace (device pointers):
  * which: 0 = log-softmax denominators f32[B,T,U1], 1 = alphas f64[B,T,U1], 2 = betas f64,
  * 3 = log-likelihoods f64[B,2] (alpha-side, beta-side), 4 = lp_blank f32[B,T,U1], 5 = lp_label */
