@@ -287,6 +287,11 @@ struct BeamPtrs {
     float* lm_c_state;
     const long long* n_committed;   // [B] committed tokens per stream, or null (offline: nothing committed)
     int lm_L, lm_H, lm_bos;
+    // detail per token-tree node, beside `nodes` (both null: not kept - the plain searches): the encoder frame on which
+    // the expansion that produced the node's token ran, and the token's score increment
+    int32_t* nd_frame;   // [B][NODES]
+    double* nd_logp;     // [B][NODES]
+    const long long* frames_done;   // [B] frames of the stream since its reset, before this advance; null: 0 (offline)
 };
 
 // (max, first position) of a workgroup's per-thread candidates: butterfly inside a wave, the four waves through LDS.
@@ -357,10 +362,13 @@ __global__ __launch_bounds__(64) void beam_frame_begin(BeamPtrs p, int t, int W,
 }
 
 // y* = max(A) (first on ties), removed from A; its last token -> pred, its state -> h/c_state
-__global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int V, int EM, int L,
-                                                int H, int B, int NODES, int bos,
-                                                int32_t* __restrict__ pred, float* __restrict__ h_state,
-                                                float* __restrict__ c_state) {
+// DETAIL: a node created here also records its frame (t, counted from the stream's reset) and its token's increment
+//   score(child in the pool) - score(popped parent) = pool[idx] - exp_logp[ep]      (fp64)
+// which with an LM is the fused increment lp_rnnt + (lm_weight lp_lm + length_bonus).
+template <bool DETAIL>
+__device__ __forceinline__ void beam_pop_body(BeamPtrs& p, int cur, int W, int V, int EM, int L, int H, int B, int NODES,
+                                              int bos, int32_t* __restrict__ pred, float* __restrict__ h_state,
+                                              float* __restrict__ c_state, int t) {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (!p.open[b]) return;
     double* pool = p.pool + (size_t)b * (W + (size_t)EM * V);
@@ -409,6 +417,10 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
             int nn = p.n_nodes[b];
             if (nn >= NODES) { p.flags[1] = 1; nn = NODES - 1; }
             p.nodes[(size_t)b * NODES + nn] = make_int2(p.exp_node[b * EM + ep], k);
+            if constexpr (DETAIL) {
+                p.nd_frame[(size_t)b * NODES + nn] = (int32_t)((p.frames_done ? p.frames_done[b] : 0ll) + t);
+                p.nd_logp[(size_t)b * NODES + nn] = __dsub_rn(popped, p.exp_logp[b * EM + ep]);
+            }
             p.n_nodes[b] = nn + 1;
             node = nn;
             ref = W + ep;
@@ -445,6 +457,20 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
             p.lm_c_state[((size_t)l * B + b) * HL + j] = lc[i];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int V, int EM, int L,
+                                                int H, int B, int NODES, int bos,
+                                                int32_t* __restrict__ pred, float* __restrict__ h_state,
+                                                float* __restrict__ c_state) {
+    beam_pop_body<false>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, 0);
+}
+
+// beam_pop that keeps the detail per node; t = the frame of this advance
+__global__ __launch_bounds__(256) void beam_pop_detail(BeamPtrs p, int cur, int W, int V, int EM, int L, int H, int B,
+                                                       int NODES, int bos, int32_t* __restrict__ pred,
+                                                       float* __restrict__ h_state, float* __restrict__ c_state, int t) {
+    beam_pop_body<true>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, t);
 }
 
 // log-softmax of the joint's logits; children into the pool, the blank child into B, the new
@@ -1069,6 +1095,7 @@ int lm_step(int dtype, int B, const BeamBufs& bb, hipStream_t s) {
 // prefix_merge != null (prefix = 1): it runs the host list logic before every frame after the first, and every
 // expansion's prediction is kept per node.
 // bb.lm != null: every iteration also runs the LM step, and beam_expand_lm replaces beam_expand (no prefix_merge then).
+// bb.q.nd_frame != null: beam_pop_detail replaces beam_pop.
 int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, PrefixMerge* prefix_merge, hipStream_t s) {
     const BeamPtrs& q = bb.q;
     const StepBufs& u = bb.u;
@@ -1086,8 +1113,12 @@ int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, Prefix
         hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, net.EM, net.V);
         for (int it = 0;; ++it) {
             int rc;
-            hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B, net.NODES,
-                               net.bos, u.pred, bb.h_state, bb.c_state);
+            if (q.nd_frame)
+                hipLaunchKernelGGL(beam_pop_detail, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B,
+                                   net.NODES, net.bos, u.pred, bb.h_state, bb.c_state, t);
+            else
+                hipLaunchKernelGGL(beam_pop, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B, net.NODES,
+                                   net.bos, u.pred, bb.h_state, bb.c_state);
             // the LM's step on y*'s last token from y*'s LM state (its logits are only read by beam_expand_lm)
             if (bb.lm && (rc = lm_step(net.dtype, B, bb, s))) return rc;
             // prediction-network step on y*'s last token from y*'s state (models.py:164,126-132), then joint(x_t, pred)
@@ -1135,6 +1166,113 @@ int read_best_path(int B, int W, const int32_t* node, const double* logp, const 
     }
     return ED_OK;
 }
+
+// ---- N-best read-out with detail.  One thread per survivor path: depth first, then the tokens, frames and increments
+// written root to leaf into the dense result rows [b][j][0, max_tokens).  A path deeper than max_tokens writes its
+// length only (the host reports it); a walk never takes more than NODES steps.
+struct NBestRes {
+    size_t len, tok, frame, lp, total;
+};
+inline NBestRes nbest_result_layout(size_t B, size_t W, size_t MT) {
+    NBestRes r{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t x = o; o += align256(bytes); return x; };
+    r.len = take(B * W * 4);
+    r.tok = take(B * W * MT * 4);
+    r.frame = take(B * W * MT * 4);
+    r.lp = take(B * W * MT * 8);
+    r.total = o;
+    return r;
+}
+
+__global__ __launch_bounds__(64) void beam_read_paths(BeamPtrs p, int W, int NODES, int MT, int32_t* __restrict__ r_len,
+                                                      int32_t* __restrict__ r_tok, int32_t* __restrict__ r_frame,
+                                                      double* __restrict__ r_lp) {
+    const int b = blockIdx.x;
+    const int nb = min(p.n_bp[b], W);
+    const int2* tree = p.nodes + (size_t)b * NODES;
+    const int32_t* fr = p.nd_frame + (size_t)b * NODES;
+    const double* lp = p.nd_logp + (size_t)b * NODES;
+    for (int j = threadIdx.x; j < W; j += 64) {
+        const size_t row = (size_t)b * W + j;
+        if (j >= nb) { r_len[row] = 0; continue; }
+        const int leaf = p.bp_node[row];
+        int d = 0;
+        for (int n = leaf; n >= 0 && n < NODES && d <= NODES; n = tree[n].x) ++d;
+        r_len[row] = d;
+        if (d > MT) continue;
+        int k = d;
+        for (int n = leaf; n >= 0 && n < NODES && k > 0; n = tree[n].x) {
+            --k;
+            r_tok[row * MT + k] = tree[n].y;
+            r_frame[row * MT + k] = fr[n];
+            r_lp[row * MT + k] = lp[n];
+        }
+    }
+}
+
+// where an N-best read puts its results (all HOST)
+struct NBestHost {
+    int32_t *tokens, *frames;    // [B][W][max_tokens]
+    double* token_logp;          // [B][W][max_tokens]
+    int32_t* ntokens;            // [B][W]
+    int32_t* nhyp;               // [B]
+    double* logp;                // [B][W]
+};
+
+// The list B of every utterance from the device: the read-out kernel over the tree q points at, then only the lengths,
+// the scores and the used columns of the result cross to the host.
+int read_nbest(const BeamPtrs& q, int B, int W, int NODES, int max_tokens, void* result, const NBestHost& o,
+               const char* what, hipStream_t s) {
+    const NBestRes r = nbest_result_layout(B, W, max_tokens);
+    char* rp = (char*)result;
+    hipLaunchKernelGGL(beam_read_paths, dim3(B), dim3(64), 0, s, q, W, NODES, max_tokens, at<int32_t>(rp, r.len),
+                       at<int32_t>(rp, r.tok), at<int32_t>(rp, r.frame), at<double>(rp, r.lp));
+    ED_CHECK_LAUNCH(what);
+    ED_CHECK_HIP(hipMemcpyAsync(o.nhyp, q.n_bp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(o.logp, q.bp_logp, (size_t)B * W * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(o.ntokens, rp + r.len, (size_t)B * W * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    int maxlen = 0;
+    for (int b = 0; b < B; ++b) {
+        o.nhyp[b] = std::min(o.nhyp[b], W);
+        for (int j = 0; j < o.nhyp[b]; ++j) {
+            const int len = o.ntokens[(size_t)b * W + j];
+            ED_CHECK_ARG(len <= max_tokens, "%s of %d tokens exceeds max_tokens = %d", what, len, max_tokens);
+            maxlen = std::max(maxlen, len);
+        }
+    }
+    if (maxlen > 0) {
+        const size_t MT = (size_t)max_tokens, rows = (size_t)B * W;
+        ED_CHECK_HIP(hipMemcpy2DAsync(o.tokens, MT * 4, rp + r.tok, MT * 4, (size_t)maxlen * 4, rows,
+                                      hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipMemcpy2DAsync(o.frames, MT * 4, rp + r.frame, MT * 4, (size_t)maxlen * 4, rows,
+                                      hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipMemcpy2DAsync(o.token_logp, MT * 8, rp + r.lp, MT * 8, (size_t)maxlen * 8, rows,
+                                      hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    return ED_OK;
+}
+
+// the detail per node of the offline search's tree: its own buffer beside the workspace
+struct DetailOffs {
+    size_t nd_frame, nd_logp, total;
+};
+inline DetailOffs beam_detail_layout(size_t B, size_t nodes) {
+    DetailOffs d{};
+    d.nd_frame = 0;
+    d.nd_logp = align256(B * nodes * 4);
+    d.total = d.nd_logp + align256(B * nodes * 8);
+    return d;
+}
+
+// what the detail-enabled offline search adds to the plain call
+struct NBestOut {
+    void* detail;        // device, edgedict_beam_detail_bytes
+    void* result;        // device, edgedict_beam_nbest_result_bytes
+    NBestHost host;
+};
 }  // namespace
 
 extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
@@ -1154,15 +1292,28 @@ extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, 
     return edgedict_beam_workspace_bytes_lm(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, nullptr);
 }
 
-extern "C" int edgedict_beam_search_lm(
+namespace {
+// Both offline searches.  nb == null: edgedict_beam_search[_lm], B[0] through tokens_host / ntokens_host / score_host;
+// else edgedict_beam_search_nbest: the detail is kept per node and the whole list B is read through nb.
+int beam_search_run(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
     const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
     const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
     const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
     const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
     int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, const NBestOut* nb,
+    void* stream_) {
     const int EM = max_expansions;
+    ED_CHECK_ARG(!nb || !prefix,
+                 "beam_search_nbest: prefix = 1 is not supported (the prefix merge changes a hypothesis' score at frame "
+                 "starts, so the per-token increments would no longer add up to it)");
+    if (nb) {       // the plain call's outputs are not used: stand-ins for its null-pointer check
+        const NBestHost& o = nb->host;
+        ED_CHECK_ARG(nb->detail && nb->result && o.tokens && o.frames && o.token_logp && o.ntokens && o.nhyp && o.logp,
+                     "beam_search_nbest: null pointer");
+        tokens_host = o.tokens; ntokens_host = o.ntokens; score_host = o.logp;
+    }
     const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V,
                         {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, T * EM + 1};
     if (int rc = check_net(net, "beam_search", T >= 0 && W > 0 && EM >= W && max_tokens >= 0,
@@ -1177,7 +1328,12 @@ extern "C" int edgedict_beam_search_lm(
     const BeamWs w = beam_layout(net, (size_t)T * EM + 1, prefix, false);
     LmWs lw{};
     if (lm) lw = lm_ws_layout(w.total, net, *lm, true);
-    const BeamBufs bufs = bind_beam_ptrs(p, &w, nullptr, nullptr, lm, &lw);
+    BeamBufs bufs = bind_beam_ptrs(p, &w, nullptr, nullptr, lm, &lw);
+    if (nb) {
+        const DetailOffs d = beam_detail_layout(B, (size_t)T * EM + 1);
+        bufs.q.nd_frame = at<int32_t>((char*)nb->detail, d.nd_frame);
+        bufs.q.nd_logp = at<double>((char*)nb->detail, d.nd_logp);
+    }
     const BeamPtrs& q = bufs.q;
 
     const size_t LH = (size_t)L * H;
@@ -1205,8 +1361,20 @@ extern "C" int edgedict_beam_search_lm(
     if (prefix) merge.emplace(net, bufs, p, w, lens_host, s);
     if (int rc = beam_frame_loop(net, bufs, maxlen, merge ? &*merge : nullptr, s)) return rc;
     ED_CHECK_LAUNCH("beam_search");
-    // results: B[0] of the last frame (models.py:201-202), token tree walked on the host
     const int NODES = net.NODES;
+    if (nb) {       // results: the whole list B of the last frame, its paths walked on the device
+        int32_t flags[2];
+        long long total = 0;
+        ED_CHECK_HIP(hipMemcpyAsync(flags, q.flags, 8, hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipMemcpyAsync(&total, q.total_exp, 8, hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipStreamSynchronize(s));
+        ED_CHECK_ARG(!flags[0], "beam_search: an utterance needed more than max_expansions = %d expansions in one frame",
+                     EM);
+        ED_CHECK_ARG(!flags[1], "beam_search: token tree overflow");
+        if (expansions_host) *expansions_host = total;
+        return read_nbest(q, B, W, NODES, max_tokens, nb->result, nb->host, "beam_search: hypothesis", s);
+    }
+    // results: B[0] of the last frame (models.py:201-202), token tree walked on the host
     std::vector<double> logp((size_t)B * W);
     std::vector<int32_t> node((size_t)B * W), nn(B);
     std::vector<int2> nodes((size_t)B * NODES);
@@ -1224,6 +1392,46 @@ extern "C" int edgedict_beam_search_lm(
     if (expansions_host) *expansions_host = total + (merge ? merge->steps : 0);
     return read_best_path(B, W, node.data(), logp.data(), nodes.data(), (size_t)NODES, "beam_search: hypothesis",
                           tokens_host, max_tokens, ntokens_host, score_host);
+}
+}  // namespace
+
+extern "C" int edgedict_beam_search_lm(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
+    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
+                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
+                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, workspace, nullptr,
+                           stream_);
+}
+
+extern "C" size_t edgedict_beam_detail_bytes(int B, int T, int max_expansions) {
+    if (B <= 0 || max_expansions <= 0) return 0;
+    return beam_detail_layout(B, (size_t)(T < 0 ? 0 : T) * max_expansions + 1).total;
+}
+
+extern "C" size_t edgedict_beam_nbest_result_bytes(int B, int W, int max_tokens) {
+    if (B <= 0 || W <= 0 || max_tokens < 0) return 0;
+    return nbest_result_layout(B, W, max_tokens).total;
+}
+
+extern "C" int edgedict_beam_search_nbest(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
+    int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host, long long* expansions_host,
+    const edgedict_beam_lm_t* lm, void* workspace, void* detail, void* result, void* stream_) {
+    const NBestOut nb{detail, result, {tokens_host, frames_host, token_logp_host, ntokens_host, nhyp_host, logp_host}};
+    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
+                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
+                           nullptr, max_tokens, nullptr, nullptr, expansions_host, lm, workspace, &nb, stream_);
 }
 
 extern "C" int edgedict_beam_search(
@@ -1309,9 +1517,21 @@ constexpr int BEAM_COMPACT_LDS_NODES = 4096;    // trees up to this capacity wal
 //  3. the path root .. LCA is appended to the committed log (commit[b][0, n_commit[b])) and the LCA becomes the root;
 //  4. the nodes below the LCA that are marked are renumbered by an exclusive scan (order kept, so parents still precede
 //     their children), written back with rewritten parent links, and the survivors' node ids remapped.
-__global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, int use_lds, int2* __restrict__ c_old,
-                                                    int32_t* __restrict__ c_mark, int32_t* __restrict__ commit,
-                                                    int32_t* __restrict__ n_commit, long long* __restrict__ n_committed) {
+// DETAIL: the nodes' frames and increments (p.nd_frame / p.nd_logp) move with them - copied aside with the old tree,
+// written back under the new ids, and those of the path root .. LCA written next to its tokens - and the stream's count
+// of frames done grows by this advance's frames.
+struct CompactDetail {
+    int32_t* old_frame;      // [S][NC] scratch
+    double* old_logp;
+    int32_t* commit_frame;   // [S][NC] beside commit
+    double* commit_logp;
+    long long* frames_done;  // [S] (state)
+};
+template <bool DETAIL>
+__device__ __forceinline__ void beam_compact_body(BeamPtrs& p, int W, int NC, int use_lds, int2* __restrict__ c_old,
+                                                  int32_t* __restrict__ c_mark, int32_t* __restrict__ commit,
+                                                  int32_t* __restrict__ n_commit, long long* __restrict__ n_committed,
+                                                  const CompactDetail& cd) {
     const int b = blockIdx.x, tid = threadIdx.x;
     extern __shared__ int s_dyn[];
     __shared__ int s_scan[256];
@@ -1330,6 +1550,10 @@ __global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, i
         old[i] = v;
         mark[i] = 0;
         if (use_lds) spar[i] = v.x;
+        if constexpr (DETAIL) {
+            cd.old_frame[(size_t)b * NC + i] = p.nd_frame[(size_t)b * NC + i];
+            cd.old_logp[(size_t)b * NC + i] = p.nd_logp[(size_t)b * NC + i];
+        }
     }
     __syncthreads();
     const int nb = p.n_bp[b];
@@ -1347,7 +1571,14 @@ __global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, i
         int d = 0;
         for (int x = lca; x >= 0; x = use_lds ? spar[x] : old[x].x) ++d;
         int k = d;
-        for (int x = lca; x >= 0; x = use_lds ? spar[x] : old[x].x) commit[(size_t)b * NC + --k] = old[x].y;
+        for (int x = lca; x >= 0; x = use_lds ? spar[x] : old[x].x) {
+            commit[(size_t)b * NC + --k] = old[x].y;
+            if constexpr (DETAIL) {
+                cd.commit_frame[(size_t)b * NC + k] = cd.old_frame[(size_t)b * NC + x];
+                cd.commit_logp[(size_t)b * NC + k] = cd.old_logp[(size_t)b * NC + x];
+            }
+        }
+        if constexpr (DETAIL) cd.frames_done[b] += p.lens[b];
         n_commit[b] = d;
         n_committed[b] += d;
         if (lca >= 0) p.root_tok[b] = old[lca].y;
@@ -1376,6 +1607,10 @@ __global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, i
         if (ni < 0) continue;
         const int2 v = old[i];
         tree[ni] = make_int2(v.x == lca ? -1 : mark[v.x], v.y);
+        if constexpr (DETAIL) {
+            p.nd_frame[(size_t)b * NC + ni] = cd.old_frame[(size_t)b * NC + i];
+            p.nd_logp[(size_t)b * NC + ni] = cd.old_logp[(size_t)b * NC + i];
+        }
     }
     if (tid < nb) {
         const int x = p.bp_node[(size_t)b * W + tid];
@@ -1383,6 +1618,71 @@ __global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, i
     }
     if (tid == 0) p.n_nodes[b] = kept;
 }
+
+__global__ __launch_bounds__(256) void beam_compact(BeamPtrs p, int W, int NC, int use_lds, int2* __restrict__ c_old,
+                                                    int32_t* __restrict__ c_mark, int32_t* __restrict__ commit,
+                                                    int32_t* __restrict__ n_commit, long long* __restrict__ n_committed) {
+    beam_compact_body<false>(p, W, NC, use_lds, c_old, c_mark, commit, n_commit, n_committed, CompactDetail{});
+}
+
+__global__ __launch_bounds__(256) void beam_compact_detail(BeamPtrs p, int W, int NC, int use_lds,
+                                                           int2* __restrict__ c_old, int32_t* __restrict__ c_mark,
+                                                           int32_t* __restrict__ commit, int32_t* __restrict__ n_commit,
+                                                           long long* __restrict__ n_committed, CompactDetail cd) {
+    beam_compact_body<true>(p, W, NC, use_lds, c_old, c_mark, commit, n_commit, n_committed, cd);
+}
+
+// the detail-enabled streams' count of frames done -> 0, for streams [b0, b0 + n) with mask[b] != 0 (mask null: all)
+__global__ void beam_detail_reset_kernel(long long* __restrict__ frames_done, const int32_t* __restrict__ mask, int b0,
+                                         int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (mask && !mask[b0 + i]) return;
+    frames_done[b0 + i] = 0;
+}
+
+// detail of the streams' trees: persistent (beside the state) and per call (beside the workspace)
+struct StreamDetailState {
+    size_t nd_frame, nd_logp, frames_done, total;
+};
+inline StreamDetailState stream_detail_state_layout(size_t S, size_t NC) {
+    StreamDetailState d{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    d.nd_frame = take(S * NC * 4);
+    d.nd_logp = take(S * NC * 8);
+    d.frames_done = take(S * 8);
+    d.total = o;
+    return d;
+}
+struct StreamDetailWs {
+    size_t old_frame, old_logp, commit_frame, commit_logp, total;
+};
+inline StreamDetailWs stream_detail_ws_layout(size_t S, size_t NC) {
+    StreamDetailWs d{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    d.old_frame = take(S * NC * 4);
+    d.old_logp = take(S * NC * 8);
+    d.commit_frame = take(S * NC * 4);
+    d.commit_logp = take(S * NC * 8);
+    d.total = o;
+    return d;
+}
+void bind_stream_detail(BeamPtrs& q, char* dstate, int S, int NC) {
+    const StreamDetailState d = stream_detail_state_layout(S, NC);
+    q.nd_frame = at<int32_t>(dstate, d.nd_frame);
+    q.nd_logp = at<double>(dstate, d.nd_logp);
+    q.frames_done = at<long long>(dstate, d.frames_done);
+}
+
+// what the detail-enabled advance adds to the plain call
+struct StreamDetailArgs {
+    void* dstate;                    // device, edgedict_beam_stream_detail_state_bytes
+    void* dws;                       // device, edgedict_beam_stream_detail_workspace_bytes
+    int32_t* commit_frame_host;      // HOST [S, node_capacity]
+    double* commit_logp_host;        // HOST [S, node_capacity]
+};
 
 }  // namespace
 
@@ -1448,14 +1748,19 @@ extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_c
     return edgedict_beam_stream_reset_lm(S, L, H, W, node_capacity, bos, mask, mask_on_host, nullptr, state, stream_);
 }
 
-extern "C" int edgedict_beam_stream_advance_lm(
+namespace {
+// Both advances.  dt == null: edgedict_beam_stream_advance[_lm]; else edgedict_beam_stream_advance_detail.
+int beam_stream_advance_run(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
     int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
     const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
     int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
+    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, const StreamDetailArgs* dt,
+    void* stream_) {
     const int EM = max_expansions, NC = node_capacity;
+    ED_CHECK_ARG(!dt || (dt->dstate && dt->dws && dt->commit_frame_host && dt->commit_logp_host),
+                 "beam_stream_advance_detail: null pointer");
     const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V,
                         {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, NC};
     if (int rc = check_net(net, "beam_stream_advance", W > 0 && EM >= W && NC > 0, " (max_expansions must be >= W)",
@@ -1475,7 +1780,8 @@ extern "C" int edgedict_beam_stream_advance_lm(
     char* p = (char*)workspace;
     LmWs lw{};
     if (lm) lw = lm_ws_layout(w.total, net, *lm, false);
-    const BeamBufs bufs = bind_beam_ptrs(p, &w, st, &a, lm, &lw);
+    BeamBufs bufs = bind_beam_ptrs(p, &w, st, &a, lm, &lw);
+    if (dt) bind_stream_detail(bufs.q, (char*)dt->dstate, S, NC);
     const BeamPtrs& q = bufs.q;
     for (int b = 0; b < S; ++b) ncommit_host[b] = 0;
     if (expansions_host) *expansions_host = 0;
@@ -1512,9 +1818,21 @@ extern "C" int edgedict_beam_stream_advance_lm(
     const int use_lds = NC <= BEAM_COMPACT_LDS_NODES;
     int32_t* commit = at<int32_t>(p, w.commit);
     int32_t* n_commit = at<int32_t>(p, w.n_commit);
-    hipLaunchKernelGGL(beam_compact, dim3(S), dim3(256), use_lds ? (size_t)NC * 8 : 0, s, q, W, NC, use_lds,
-                       at<int2>(p, w.c_old), at<int32_t>(p, w.c_mark), commit, n_commit,
-                       at<long long>(st, a.n_committed));
+    CompactDetail cd{};
+    if (dt) {
+        const StreamDetailWs dw = stream_detail_ws_layout(S, NC);
+        char* dp = (char*)dt->dws;
+        cd = CompactDetail{at<int32_t>(dp, dw.old_frame), at<double>(dp, dw.old_logp), at<int32_t>(dp, dw.commit_frame),
+                           at<double>(dp, dw.commit_logp),
+                           at<long long>((char*)dt->dstate, stream_detail_state_layout(S, NC).frames_done)};
+        hipLaunchKernelGGL(beam_compact_detail, dim3(S), dim3(256), use_lds ? (size_t)NC * 8 : 0, s, q, W, NC, use_lds,
+                           at<int2>(p, w.c_old), at<int32_t>(p, w.c_mark), commit, n_commit,
+                           at<long long>(st, a.n_committed), cd);
+    } else {
+        hipLaunchKernelGGL(beam_compact, dim3(S), dim3(256), use_lds ? (size_t)NC * 8 : 0, s, q, W, NC, use_lds,
+                           at<int2>(p, w.c_old), at<int32_t>(p, w.c_mark), commit, n_commit,
+                           at<long long>(st, a.n_committed));
+    }
     ED_CHECK_LAUNCH("beam_stream_advance");
     int32_t flags[2];
     long long total = 0;
@@ -1531,9 +1849,78 @@ extern "C" int edgedict_beam_stream_advance_lm(
     if (maxc > 0) {
         ED_CHECK_HIP(hipMemcpy2DAsync(commit_host, (size_t)NC * 4, commit, (size_t)NC * 4, (size_t)maxc * 4, (size_t)S,
                                       hipMemcpyDeviceToHost, s));
+        if (dt) {
+            ED_CHECK_HIP(hipMemcpy2DAsync(dt->commit_frame_host, (size_t)NC * 4, cd.commit_frame, (size_t)NC * 4,
+                                          (size_t)maxc * 4, (size_t)S, hipMemcpyDeviceToHost, s));
+            ED_CHECK_HIP(hipMemcpy2DAsync(dt->commit_logp_host, (size_t)NC * 8, cd.commit_logp, (size_t)NC * 8,
+                                          (size_t)maxc * 8, (size_t)S, hipMemcpyDeviceToHost, s));
+        }
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;
+}
+}  // namespace
+
+extern "C" int edgedict_beam_stream_advance_lm(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
+    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
+                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
+                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, state,
+                                   workspace, nullptr, stream_);
+}
+
+extern "C" size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capacity) {
+    if (S <= 0 || node_capacity <= 0) return 0;
+    return stream_detail_state_layout(S, node_capacity).total;
+}
+
+extern "C" size_t edgedict_beam_stream_detail_workspace_bytes(int S, int node_capacity) {
+    if (S <= 0 || node_capacity <= 0) return 0;
+    return stream_detail_ws_layout(S, node_capacity).total;
+}
+
+extern "C" int edgedict_beam_stream_reset_detail(int S, int L, int H, int W, int node_capacity, int bos,
+                                                 const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
+                                                 void* state, void* detail_state, void* stream_) {
+    ED_CHECK_ARG(detail_state, "beam_stream_reset_detail: null detail state");
+    if (int rc = edgedict_beam_stream_reset_lm(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, state, stream_))
+        return rc;
+    hipStream_t s = (hipStream_t)stream_;
+    long long* fd = at<long long>((char*)detail_state, stream_detail_state_layout(S, node_capacity).frames_done);
+    if (!mask || !mask_on_host) {
+        hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((S + 63) / 64), dim3(64), 0, s, fd, mask, 0, S);
+    } else {
+        for (int b = 0; b < S;) {
+            if (!mask[b]) { ++b; continue; }
+            int e = b;
+            while (e < S && mask[e]) ++e;
+            hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((e - b + 63) / 64), dim3(64), 0, s, fd,
+                               (const int32_t*)nullptr, b, e - b);
+            b = e;
+        }
+    }
+    ED_CHECK_LAUNCH("beam_stream_reset_detail");
+    return ED_OK;
+}
+
+extern "C" int edgedict_beam_stream_advance_detail(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* commit_frame_host,
+    double* commit_logp_host, int32_t* ncommit_host, long long* expansions_host, const edgedict_beam_lm_t* lm,
+    void* state, void* workspace, void* detail_state, void* detail_workspace, void* stream_) {
+    const StreamDetailArgs dt{detail_state, detail_workspace, commit_frame_host, commit_logp_host};
+    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
+                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
+                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, state,
+                                   workspace, &dt, stream_);
 }
 
 extern "C" int edgedict_beam_stream_advance(
@@ -1583,4 +1970,30 @@ extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_ca
     }
     return read_best_path(S, W, node.data(), logp.data(), nodes.data(), (size_t)maxnn, "beam_stream_read: hypothesis tail",
                           tokens_host, max_tokens, ntokens_host, score_host);
+}
+
+extern "C" int edgedict_beam_stream_read_nbest(int S, int L, int H, int W, int node_capacity, const void* state,
+                                               const void* detail_state, void* result, int32_t* tokens_host,
+                                               int32_t* frames_host, double* token_logp_host, int max_tokens,
+                                               int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                               long long* ncommitted_host, long long* expansions_host,
+                                               long long* frames_done_host, void* stream_) {
+    ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0 && max_tokens >= 0,
+                 "beam_stream_read_nbest: bad shape");
+    ED_CHECK_ARG(state && detail_state && result && tokens_host && frames_host && token_logp_host && ntokens_host &&
+                     nhyp_host && logp_host,
+                 "beam_stream_read_nbest: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    const int NC = node_capacity;
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC, nullptr);
+    BeamPtrs q = bind_beam_ptrs(nullptr, nullptr, (char*)state, &a, nullptr, nullptr).q;
+    bind_stream_detail(q, (char*)detail_state, S, NC);
+    if (ncommitted_host)
+        ED_CHECK_HIP(hipMemcpyAsync(ncommitted_host, q.n_committed, (size_t)S * 8, hipMemcpyDeviceToHost, s));
+    if (expansions_host)
+        ED_CHECK_HIP(hipMemcpyAsync(expansions_host, q.stream_exp, (size_t)S * 8, hipMemcpyDeviceToHost, s));
+    if (frames_done_host)
+        ED_CHECK_HIP(hipMemcpyAsync(frames_done_host, q.frames_done, (size_t)S * 8, hipMemcpyDeviceToHost, s));
+    const NBestHost o{tokens_host, frames_host, token_logp_host, ntokens_host, nhyp_host, logp_host};
+    return read_nbest(q, S, W, NC, max_tokens, result, o, "beam_stream_read_nbest: hypothesis tail", s);
 }

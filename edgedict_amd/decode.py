@@ -21,6 +21,10 @@ log p).  The LM's root token is ``lm_bos`` (default 1, the start token ``cli/tra
 or, when streaming, the last committed token once a stream has committed one.  ``lm_weight = length_bonus = 0`` gives
 tokens, scores and expansion counts bit-equal to the search without an LM.  A positive ``length_bonus`` can raise the
 pops per frame; hitting ``max_expansions`` stays an error.
+
+``beam_search_nbest`` (``_enc``, ``_rows``; ``StreamingBeamSearch(..., detail=True).nbest()``) runs the same search and
+returns the WHOLE list B of the last frame as ``NBestResult`` objects: every hypothesis with the encoder frame on which
+each of its tokens was emitted and the token's score increment (csrc/decode.hip keeps both per token-tree node).
 """
 import ctypes
 
@@ -222,6 +226,153 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     return seqs, torch.from_numpy(score)
 
 
+class NBestResult:
+    """The list B of one utterance's last frame: ``n <= W`` hypotheses **in B's own order, which is insertion order**
+    (the order in which the hypotheses emitted blank on the last frame - the reference's ``sorted`` calls discard their
+    result, so neither it nor the search here ever ranks B; entry 0 is what ``beam_search_batch`` returns).  Ranking is
+    therefore a separate step: ``ranked()``.
+
+    ``tokens[i]``      int64 array: the hypothesis' tokens, no blanks
+    ``frames[i]``      int32 array, same length: the encoder frame on which each token was emitted (offline: index into
+                       the utterance; streaming: counted since the stream's reset); ``emission_times`` turns them into
+                       seconds
+    ``token_logp[i]``  float64 array, same length: the increment each token added to the hypothesis' score (with an LM
+                       the fused increment ``lp_rnnt + (lm_weight lp_lm + length_bonus)``); ``logp[i]`` minus their sum
+                       is what the hypothesis' blanks contributed
+    ``logp``           float64 [n]: log p per hypothesis (fused log p with an LM)
+    """
+
+    def __init__(self, tokens, frames, token_logp, logp):
+        self.tokens = list(tokens)
+        self.frames = list(frames)
+        self.token_logp = list(token_logp)
+        self.logp = np.asarray(logp, dtype=np.float64)
+        if not (len(self.tokens) == len(self.frames) == len(self.token_logp) == self.logp.shape[0]):
+            raise ValueError("NBestResult: fields of different lengths")
+
+    def __len__(self):
+        return len(self.tokens)
+
+    def ranked(self, merge=True):
+        """A new ``NBestResult`` sorted by ``logp`` descending, stably (ties keep B's order).  ``merge=True`` first folds
+        entries with identical token sequences into one with log-add (the legacy search keeps them apart: the same
+        sequence can be in B twice, reached with different emission frames); the folded entry keeps the frames and
+        increments of its most probable member (the first one on ties) and stands at that member's place in B."""
+        idx = list(range(len(self)))
+        logp = self.logp.copy()
+        if merge:
+            groups = {}
+            for i in idx:
+                groups.setdefault(tuple(int(t) for t in self.tokens[i]), []).append(i)
+            idx = []
+            for members in groups.values():
+                best = max(members, key=lambda i: (self.logp[i], -i))
+                vals = self.logp[members]
+                m = vals.max()
+                logp[best] = m + np.log(np.exp(vals - m).sum()) if np.isfinite(m) else m
+                idx.append(best)
+            idx.sort()
+        order = sorted(idx, key=lambda i: -logp[i])          # sorted() is stable
+        return NBestResult([self.tokens[i] for i in order], [self.frames[i] for i in order],
+                           [self.token_logp[i] for i in order], logp[order] if order else np.zeros(0))
+
+
+def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
+    """Host arrays of a native N-best read -> one ``NBestResult`` per row; ``prefix[b]`` = (tokens, frames, increments)
+    lists prepended to every hypothesis of row b (the streams' committed log)."""
+    out = []
+    for b in range(len(nhyp)):
+        ts, fs, ls = [], [], []
+        for j in range(int(nhyp[b])):
+            n = int(ntok[b, j])
+            t, f, l = tokens[b, j, :n].astype(np.int64), frames[b, j, :n].astype(np.int32), tlogp[b, j, :n].copy()
+            if prefix is not None:
+                t = np.concatenate([np.asarray(prefix[b][0], dtype=np.int64), t])
+                f = np.concatenate([np.asarray(prefix[b][1], dtype=np.int32), f])
+                l = np.concatenate([np.asarray(prefix[b][2], dtype=np.float64), l])
+            ts.append(t); fs.append(f); ls.append(l)
+        out.append(NBestResult(ts, fs, ls, logp[b, :int(nhyp[b])].copy()))
+    return out
+
+
+def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
+                      lm_bos=1):
+    """``beam_search_batch`` (``prefix=False``) returning, per utterance, an ``NBestResult``: all ``n <= W`` hypotheses
+    of the last frame's list B in B's order, each with its tokens, the encoder frame every token was emitted on and the
+    score increment every token added, and ``logp`` (log p, not negated).  Entry 0 is exactly what ``beam_search_batch``
+    returns (same tokens, ``logp[0] == -score`` bit for bit), and ``beam_search_batch.last_expansions`` is set as there.
+    An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.  The prefix-sum variant is not available
+    here: its merge changes a score at frame starts, so the increments would no longer add up."""
+    from .lm import check_fusion_args
+    check_fusion_args(lm, lm_weight, _vocab(model), False)
+    _lib.require_cuda(xs)
+    if W < 1:
+        raise ValueError("beam width must be >= 1")
+    enc_out, _ = model.encoder(xs)
+    enc_out = enc_out.contiguous()
+    if xlen is None:
+        lens = None
+    else:
+        xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
+        lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
+    return beam_search_nbest_enc(model, enc_out, lens, W, max_expansions, lm=lm, lm_weight=lm_weight,
+                                 length_bonus=length_bonus, lm_bos=lm_bos)
+
+
+def beam_search_nbest_enc(model, enc_out, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
+                          length_bonus=0.0, lm_bos=1, prefix=False):
+    """``beam_search_nbest`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
+    encoder frames per utterance; None: all T)."""
+    enc_out = enc_out.contiguous()
+    B, T, P = enc_out.shape
+    return beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, lm=lm,
+                                  lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, prefix=prefix)
+
+
+def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
+                           length_bonus=0.0, lm_bos=1, prefix=False, max_tokens=None):
+    """``beam_search_nbest_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output
+    of width P.  ``prefix=True`` raises ``ValueError`` (see ``beam_search_nbest``).  ``max_tokens`` bounds a hypothesis'
+    length (default: what the token tree can hold, T x max_expansions + 1); a longer one raises, it is never cut."""
+    from .lm import FusionLM, check_fusion_args
+    if prefix:
+        raise ValueError("beam_search_nbest: prefix=True is not supported with token detail (the prefix merge changes a "
+                         "hypothesis' score at frame starts, so the per-token increments would no longer add up)")
+    check_fusion_args(lm, lm_weight, _vocab(model), False)
+    if W < 1:
+        raise ValueError("beam width must be >= 1")
+    cd = E1.dtype
+    lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    EM = int(max_expansions) if max_expansions else max(16, 8 * W)
+    net = _SearchNet(model, cd)
+    flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
+    lib = _lib.load()
+    nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
+                     0)
+    MT = T * EM + 1 if max_tokens is None else int(max_tokens)
+    dev = E1.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    detail = torch.empty(lib.edgedict_beam_detail_bytes(B, T, EM), dtype=torch.uint8, device=dev)
+    result = torch.empty(lib.edgedict_beam_nbest_result_bytes(B, W, MT), dtype=torch.uint8, device=dev)
+    tokens = np.empty((B, W, MT), dtype=np.int32)       # (only the used columns are written and read)
+    frames = np.empty((B, W, MT), dtype=np.int32)
+    tlogp = np.empty((B, W, MT), dtype=np.float64)
+    ntok = np.zeros((B, W), dtype=np.int32)
+    nhyp = np.zeros(B, dtype=np.int32)
+    logp = np.zeros((B, W), dtype=np.float64)
+    nexp = ctypes.c_longlong(0)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    from .tokenizer import BOS
+    rc = lib.edgedict_beam_search_nbest(
+        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
+        *net.args(P), int(model.blank), int(BOS), int(W), EM, 0, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok),
+        vp(nhyp), vp(logp), ctypes.byref(nexp), flm.ref() if flm is not None else None, _lib.ptr(ws), _lib.ptr(detail),
+        _lib.ptr(result), _lib.stream_ptr())
+    _lib.check(rc, "beam_search_nbest")
+    beam_search_batch.last_expansions = int(nexp.value)
+    return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
+
+
 class StreamingBeamSearch:
     """The beam search of ``beam_search_batch`` for S streams whose encoder output arrives chunk by chunk.
 
@@ -243,10 +394,15 @@ class StreamingBeamSearch:
     ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion as in ``beam_search_batch`` (module
     docstring).  The survivors' LM states are carried in the device state beside the prediction network's; the LM's
     root token is ``lm_bos`` until a stream has committed a token, then its last committed token.
+
+    ``detail=True`` keeps, per token, the encoder frame it was emitted on (counted since the stream's reset) and its
+    score increment, through compaction and in the committed log: ``nbest()`` then returns the whole list B as
+    ``NBestResult`` objects and ``committed_detail()`` the committed log with frames and increments.  Without it both
+    raise; ``best()``, ``committed()`` and ``expansions()`` are the same either way.
     """
 
     def __init__(self, model, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False, *, lm=None,
-                 lm_weight=None, length_bonus=0.0, lm_bos=1):
+                 lm_weight=None, length_bonus=0.0, lm_bos=1, detail=False):
         from .lm import check_fusion_args
         check_fusion_args(lm, lm_weight, _vocab(model), prefix)
         if prefix:
@@ -274,6 +430,16 @@ class StreamingBeamSearch:
         self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
         self._commit_buf = np.zeros((self.S, self.NC), dtype=np.int32)
         self._ncommit = np.zeros(self.S, dtype=np.int32)
+        self.detail = bool(detail)
+        if self.detail:
+            lib = _lib.load()
+            self._dstate = torch.empty(lib.edgedict_beam_stream_detail_state_bytes(self.S, self.NC), dtype=torch.uint8,
+                                       device=self.device)
+            self._dws = torch.empty(lib.edgedict_beam_stream_detail_workspace_bytes(self.S, self.NC), dtype=torch.uint8,
+                                    device=self.device)
+            self._commit_frame_buf = np.zeros((self.S, self.NC), dtype=np.int32)
+            self._commit_logp_buf = np.zeros((self.S, self.NC), dtype=np.float64)
+            self._result = None
         self.last_expansions = 0
         self.reset()
 
@@ -297,13 +463,23 @@ class StreamingBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
         mp = None if mh is None else mh.ctypes.data_as(ctypes.c_void_p)
-        rc = _native("beam_stream_reset", self._fusion(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
-                     tail=(_lib.ptr(self._state), _lib.stream_ptr()))
+        if self.detail:
+            flm = self._fusion()
+            rc = _lib.load().edgedict_beam_stream_reset_detail(
+                self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, flm.ref() if flm is not None else None,
+                _lib.ptr(self._state), _lib.ptr(self._dstate), _lib.stream_ptr())
+        else:
+            rc = _native("beam_stream_reset", self._fusion(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp,
+                         on_host, tail=(_lib.ptr(self._state), _lib.stream_ptr()))
         _lib.check(rc, "beam_stream_reset")
         if not hasattr(self, "_committed"):
             self._committed = [[] for _ in range(self.S)]
+            self._committed_frames = [[] for _ in range(self.S)]
+            self._committed_logp = [[] for _ in range(self.S)]
         for s in np.nonzero(sel)[0]:
             self._committed[s] = []
+            self._committed_frames[s] = []
+            self._committed_logp[s] = []
 
     def joint_rows(self, enc_out):
         """The rows ``advance`` reads for ``enc_out`` [S, T, P]: see ``joint_rows``."""
@@ -350,12 +526,23 @@ class StreamingBeamSearch:
                 nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
                 self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p),
                 self._ncommit.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-        rc = _native("beam_stream_advance", self._fusion(), *args,
-                     tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()))
+        if self.detail:
+            flm = self._fusion()
+            vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+            rc = _lib.load().edgedict_beam_stream_advance_detail(
+                *args[:-2], vp(self._commit_frame_buf), vp(self._commit_logp_buf), *args[-2:],
+                flm.ref() if flm is not None else None, _lib.ptr(self._state), _lib.ptr(self._ws),
+                _lib.ptr(self._dstate), _lib.ptr(self._dws), _lib.stream_ptr())
+        else:
+            rc = _native("beam_stream_advance", self._fusion(), *args,
+                         tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()))
         _lib.check(rc, "beam_stream_advance")
         self.last_expansions = int(nexp.value)
         for s in np.nonzero(self._ncommit)[0]:
             self._committed[s].extend(self._commit_buf[s, :self._ncommit[s]].tolist())
+            if self.detail:
+                self._committed_frames[s].extend(self._commit_frame_buf[s, :self._ncommit[s]].tolist())
+                self._committed_logp[s].extend(self._commit_logp_buf[s, :self._ncommit[s]].tolist())
 
     def _read(self):
         net = self._weights()
@@ -392,10 +579,53 @@ class StreamingBeamSearch:
         """int64 [S]: prediction-network steps (pops) of every stream since its reset."""
         return self._read()[3]
 
+    def _need_detail(self, what):
+        if not self.detail:
+            raise RuntimeError("StreamingBeamSearch.%s() needs a search built with detail=True" % what)
+
+    def nbest(self):
+        """Per stream an ``NBestResult``: the current list B, as ``beam_search_nbest`` over the stream's frames since
+        its reset returns it; every hypothesis is the committed log followed by its uncommitted tail, in tokens, frames
+        and increments alike.  Needs ``detail=True``."""
+        self._need_detail("nbest")
+        net = self._weights()
+        lib = _lib.load()
+        S, W, MT = self.S, self.W, self.NC
+        if self._result is None:
+            self._result = torch.empty(lib.edgedict_beam_nbest_result_bytes(S, W, MT), dtype=torch.uint8,
+                                       device=self.device)
+        tokens = np.empty((S, W, MT), dtype=np.int32)
+        frames = np.empty((S, W, MT), dtype=np.int32)
+        tlogp = np.empty((S, W, MT), dtype=np.float64)
+        ntok = np.zeros((S, W), dtype=np.int32)
+        nhyp = np.zeros(S, dtype=np.int32)
+        logp = np.zeros((S, W), dtype=np.float64)
+        ncom = np.zeros(S, dtype=np.int64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = lib.edgedict_beam_stream_read_nbest(S, net.L, net.H, W, self.NC, _lib.ptr(self._state),
+                                                 _lib.ptr(self._dstate), _lib.ptr(self._result), vp(tokens), vp(frames),
+                                                 vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp), vp(ncom), None, None,
+                                                 _lib.stream_ptr())
+        _lib.check(rc, "beam_stream_read_nbest")
+        for s in range(S):
+            if ncom[s] != len(self._committed[s]):
+                raise RuntimeError("beam_stream_read_nbest: stream %d has %d committed tokens on the device, %d in the "
+                                   "log" % (s, ncom[s], len(self._committed[s])))
+        prefix = list(zip(self._committed, self._committed_frames, self._committed_logp))
+        return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix)
+
+    def committed_detail(self):
+        """Per stream ``(tokens int64, frames int32, token_logp float64)`` of the committed log: a prefix of every
+        hypothesis of ``nbest()`` that no later frame can change.  Needs ``detail=True``."""
+        self._need_detail("committed_detail")
+        return [(np.asarray(t, dtype=np.int64), np.asarray(f, dtype=np.int32), np.asarray(l, dtype=np.float64))
+                for t, f, l in zip(self._committed, self._committed_frames, self._committed_logp)]
+
 
 def emission_times(frames, flags, time_reduction=2):
     """Seconds (float64 tensor, shape of ``frames``) at which the encoder frames of ``Transducer.align`` /
-    ``loss.rnnt_align`` START: one encoder frame covers ``flags.hop_length * flags.downsample * time_reduction`` samples
+    ``loss.rnnt_align`` - or the decoder's own, ``NBestResult.frames`` of ``beam_search_nbest`` / ``nbest()`` (counted
+    from the utterance's start, or from the stream's reset) - START: one encoder frame covers ``flags.hop_length * flags.downsample * time_reduction`` samples
     (feature hop x frame stacking, as ``stream.chunk_geometry`` counts a chunk's hop, x the encoder's time reductions:
     2 per reduced layer, ``enc_time_reductions=[1]`` by default -> 2).  The -1 padding behind an utterance's labels
     becomes NaN.  The frame's END is one such step later; a causal model cannot have seen the token's audio before."""

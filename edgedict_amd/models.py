@@ -1042,6 +1042,16 @@ class Transducer(nn.Module):
         return beam_search_batch(self, xs, xlen, W, max_expansions, prefix=prefix, lm=lm, lm_weight=lm_weight,
                                  length_bonus=length_bonus, lm_bos=lm_bos)
 
+    def beam_search_nbest(self, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
+                          lm_bos=1):
+        """``beam_search`` (``prefix=False``) returning per utterance a ``decode.NBestResult``: the whole list B of the
+        last frame in B's order, every hypothesis with its tokens, the encoder frame each token was emitted on, each
+        token's score increment, and its log p; entry 0 is what ``beam_search`` returns.  See
+        ``decode.beam_search_nbest``."""
+        from .decode import beam_search_nbest
+        return beam_search_nbest(self, xs, xlen, W, max_expansions, lm=lm, lm_weight=lm_weight,
+                                 length_bonus=length_bonus, lm_bos=lm_bos)
+
 
 class _CausalConvFn(torch.autograd.Function):
     """Conv1d(C_in, C_out, k, stride s, padding k-1) followed by dropping the last k-1 frames

@@ -818,6 +818,87 @@ int edgedict_beam_stream_advance_lm(int dtype, const void* E1, long long e_row_s
                                     void* state, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * N-best lists with token frames and log-probs from both beam searches.  The *_nbest / *_detail entry
+ * points run the searches above (same frame loop, same pops, same scores) and keep, beside every
+ * token-tree node, a DETAIL:
+ *   frame   the encoder frame on which the expansion that produced the node's token ran (offline: the
+ *           index into the utterance; streaming: counted since the stream's last reset)
+ *   logp    the token's score increment, score(child in the pool) - score(popped parent), an fp64
+ *           difference; with an LM the fused increment lp_rnnt + (weight * lp_lm + length_bonus)
+ * and return the WHOLE list B of the last frame (n <= W hypotheses, in B's insertion order; entry 0 is
+ * what the plain calls return, logp[.][0] = -score bit for bit), each hypothesis root to leaf with its
+ * tokens, frames and increments.  The paths are walked by a kernel into a dense device result
+ * [B][W][max_tokens]; only the lengths, the scores and the used columns of it are copied to the host.
+ * The plain entry points are unchanged and run the kernels they ran before; the detail lives in
+ * buffers of its own with their own size queries:
+ *   beam_detail_bytes(B, T, max_expansions)            device bytes of the offline search's detail
+ *   beam_nbest_result_bytes(B, W, max_tokens)          device bytes of the read-out's result
+ *   beam_stream_detail_state_bytes(S, node_capacity)   persistent, beside the streams' state: the
+ *                                                      nodes' detail and the frames done per stream
+ *   beam_stream_detail_workspace_bytes(S, node_capacity) per call, beside beam_stream_advance's
+ *                                                      workspace (compaction moves the detail too)
+ * beam_search_nbest            operands as edgedict_beam_search_lm (lm nullable; workspace sized by
+ *                              edgedict_beam_workspace_bytes[_lm] with prefix = 0), with the outputs
+ *                                tokens_host / frames_host  HOST int32 [B, W, max_tokens]
+ *                                token_logp_host            HOST fp64  [B, W, max_tokens]
+ *                                ntokens_host HOST int32 [B, W];  nhyp_host HOST int32 [B] (= n)
+ *                                logp_host    HOST fp64  [B, W] = log p (fused with an LM)
+ *                              Entries behind n / behind a hypothesis' length are not written.  An
+ *                              utterance of 0 frames has one empty hypothesis with logp 0.  prefix = 1
+ *                              is refused (-1) before anything runs: the prefix merge changes a score
+ *                              at frame starts, so the increments would no longer add up to it.  A
+ *                              hypothesis longer than max_tokens is an error, never a truncation.
+ * beam_stream_reset_detail     edgedict_beam_stream_reset_lm, and the selected streams' frame count -> 0
+ * beam_stream_advance_detail   edgedict_beam_stream_advance_lm; additionally commit_frame_host HOST int32
+ *                              / commit_logp_host HOST fp64 [S, node_capacity]: frames and increments of
+ *                              the tokens committed by this advance, next to commit_host
+ * beam_stream_read_nbest       per stream the uncommitted tails of every entry of B as above (the full
+ *                              hypothesis is the committed log followed by the tail); ncommitted_host,
+ *                              expansions_host as edgedict_beam_stream_read; frames_done_host HOST int64
+ *                              [S], nullable: frames since the stream's reset.  Synchronises the stream.
+ * A state advanced with the detail form must always be reset, advanced and read with it.
+ */
+size_t edgedict_beam_detail_bytes(int B, int T, int max_expansions);
+size_t edgedict_beam_nbest_result_bytes(int B, int W, int max_tokens);
+int edgedict_beam_search_nbest(int dtype, const void* E1, long long e_row_stride,
+                               long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
+                               const void* W1d, long long ldw1, const float* b1, int P2,
+                               const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
+                               int E, int L, const void* const* w_ih, const void* const* w_hh,
+                               const float* const* b_ih, const float* const* b_hh, int H,
+                               const void* Wp, const float* bp, int blank, int bos, int W,
+                               int max_expansions, int prefix, int32_t* tokens_host,
+                               int32_t* frames_host, double* token_logp_host, int max_tokens,
+                               int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                               long long* expansions_host, const edgedict_beam_lm_t* lm,
+                               void* workspace, void* detail, void* result, void* stream);
+size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capacity);
+size_t edgedict_beam_stream_detail_workspace_bytes(int S, int node_capacity);
+int edgedict_beam_stream_reset_detail(int S, int L, int H, int W, int node_capacity, int bos,
+                                      const int32_t* mask, int mask_on_host,
+                                      const edgedict_beam_lm_t* lm, void* state, void* detail_state,
+                                      void* stream);
+int edgedict_beam_stream_advance_detail(int dtype, const void* E1, long long e_row_stride,
+                                        long long e_frame_stride, int S, const int32_t* n_frames_host,
+                                        int J, const void* W1d, long long ldw1, const float* b1,
+                                        int P2, const void* W2, const float* b2, int V,
+                                        const void* emb, int emb_dtype, int E, int L,
+                                        const void* const* w_ih, const void* const* w_hh,
+                                        const float* const* b_ih, const float* const* b_hh, int H,
+                                        const void* Wp, const float* bp, int blank, int bos, int W,
+                                        int max_expansions, int node_capacity, int32_t* commit_host,
+                                        int32_t* commit_frame_host, double* commit_logp_host,
+                                        int32_t* ncommit_host, long long* expansions_host,
+                                        const edgedict_beam_lm_t* lm, void* state, void* workspace,
+                                        void* detail_state, void* detail_workspace, void* stream);
+int edgedict_beam_stream_read_nbest(int S, int L, int H, int W, int node_capacity, const void* state,
+                                    const void* detail_state, void* result, int32_t* tokens_host,
+                                    int32_t* frames_host, double* token_logp_host, int max_tokens,
+                                    int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                    long long* ncommitted_host, long long* expansions_host,
+                                    long long* frames_done_host, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Row log-softmax (LMModel.forward's F.log_softmax(decoded, dim=-1), models.py:251):
  *   x fp32 or bf16 (x_dtype) [M, N] rows of leading dimension ldx;  y fp32 [M, N] contiguous.
  *   y = (x - max) - log(sum exp(x - max)) per row, fp32 arithmetic.
