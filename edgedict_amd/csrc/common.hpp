@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <math.h>
 
 #include "edgedict_hip.h"
@@ -143,6 +144,27 @@ __device__ __forceinline__ bool ed_drop_keep(unsigned seed, long long i, unsigne
     return ed_drop_hash(seed ^ ed_drop_hash((unsigned)i * 0x9e3779b9U + (unsigned)(i >> 32))) >= thresh;
 }
 __host__ __device__ static inline unsigned ed_drop_thresh(float p) { return (unsigned)((double)p * 4294967296.0); }
+
+// Compute units of the current device, queried once per process (256, the MI355X's count, where there is no device:
+// the dry-run exports edgedict_stack_schedule and edgedict_gemm_plan)
+inline int ed_device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            n = 0;
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+
+// Integer environment switches: atoi of the value, `dflt` when the variable is unset.  ed_env_now reads at every call
+// (a test flips the switch inside one process), ed_env_once reads once per process and call site.
+static inline int ed_env_now(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+#define ed_env_once(name, dflt) ([] { static const int v = ed_env_now(name, dflt); return v; }())
 
 static inline int ed_grid_for(long long work_items, int per_block, int max_blocks = 256 * 8) {
     long long g = (work_items + per_block - 1) / per_block;

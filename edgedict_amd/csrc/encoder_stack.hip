@@ -672,11 +672,7 @@ namespace {
 
 long long* g_wsr_trace = nullptr;   // debug: device buffer registered by edgedict_stack_wsr_set_trace (tools/lpw_trace.py, tools/sk_trace.py)
 
-int device_cus() {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-    return n;
-}
+int device_cus() { return ed_device_cus(); }
 bool lpw_data_poll() {
     // default: no counter on the dependency chain - the images are filled before the pass and the readers validate what
     // they gather; 0: the readers poll the arrival counters (round 3's protocol: 7.9 instead of 7.1 us per step)
@@ -724,11 +720,7 @@ int forward_lpw(const edgedict_stack_desc_t* d, const std::vector<Geom>& g, Stre
     if (split >= L) split = (L + 1) / 2;
     auto side = [&](int l) -> hipStream_t { return (st.serial || l < split) ? st.S[0] : st.C; };
     const int WGS = (H >> 4) * ((B + 63) >> 6);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n;
-    }();
+    const int n_cu = ed_device_cus();
     const int max_slots = max(1, min(ED_STACK_MAX_SLOTS, (g_trace ? 256 : n_cu) / WGS));
     const char* e_m = getenv("EDGEDICT_LPW_MARGIN");
     const int margin = (e_m && atoi(e_m) > 0) ? atoi(e_m) : 2;
@@ -1508,11 +1500,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
         // ---- macro-steps: launch w carries, for every runnable layer, its next <= sk_ns BPTT steps (descending t,
         // never across a chunk boundary); the schedule is the one below in units of macro-steps
         const int WGS = (H >> 6) * 4;
-        static const int n_cu = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-            return n;
-        }();
+        const int n_cu = ed_device_cus();
         const int max_slots = max(1, min(ED_STACK_MAX_SLOTS, (g_trace ? 256 : n_cu) / WGS));
         const char* e_m = getenv("EDGEDICT_LPW_MARGIN_B");
         margin = (e_m && atoi(e_m) > 0) ? atoi(e_m) : 2;

@@ -16,10 +16,8 @@
 // tile's global loads issued before the current tile's MFMAs.
 // split_k > 1 partitions K over workgroups (XCD-aware: one K slice per XCD) and combines with fp32
 // atomics (gradient "+=").
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "gemm_nt.hpp"
+#include "gemm_plan.hpp"
 #include "blaslt.hpp"
 
 namespace {
@@ -398,17 +396,6 @@ int launch2(const GemmArgs& g, int a_km, int b_km, dim3 grid, hipStream_t s, int
     ED_CHECK_LAUNCH("gemm");
     return ED_OK;
 }
-template <typename TI, typename TO>
-int launch(const GemmArgs& g, int a_km, int b_km, dim3 grid, hipStream_t s, int pad) {
-    // FAST: both operands 16-byte aligned with a leading dimension that is a multiple of the
-    // vector width, and the contiguous extent of each operand a multiple of it as well
-    constexpr int VEC = Cfg<TI>::VEC;
-    const bool a_ext = a_km ? (g.K % VEC == 0) : (g.M % VEC == 0);
-    const bool b_ext = b_km ? (g.K % VEC == 0) : (g.N % VEC == 0);
-    if (g.a_vec && g.b_vec && a_ext && b_ext) return launch2<TI, TO, true>(g, a_km, b_km, grid, s, pad);
-    return launch2<TI, TO, false>(g, a_km, b_km, grid, s, pad);
-}
-
 // C[m][n] (+)= sum_s part[s][m][n]
 __global__ void reduce_partials_kernel(const float* __restrict__ part, long long stride, int S,
                                        float* __restrict__ C, long long ldc, long long M, int N,
@@ -432,195 +419,272 @@ __global__ void zero_f32(float* p, long long rows, long long cols, long long ld)
 
 }  // namespace
 
-static int gemm_impl(int dtype_in, int dtype_out, const void* A, long long lda, int a_kmajor,
-                     const void* B, long long ldb, int b_kmajor, void* C, long long ldc, int M, int N,
-                     int K, const float* bias1, const float* bias2, int accumulate, int split_k,
-                     void* stream_, int max_wg_per_cu, float* partials = nullptr, bool reduce = true) {
-    ED_CHECK_ARG(dtype_in == ED_F32 || dtype_in == ED_BF16, "gemm: bad input dtype %d", dtype_in);
-    ED_CHECK_ARG(dtype_out == ED_F32 || dtype_out == ED_BF16, "gemm: bad output dtype %d", dtype_out);
-    ED_CHECK_ARG(!(dtype_in == ED_F32 && dtype_out == ED_BF16), "gemm: fp32 inputs with bf16 output is not supported");
-    ED_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "gemm: negative dimension");
-    ED_CHECK_ARG(split_k >= 1, "gemm: split_k must be >= 1");
-    ED_CHECK_ARG(split_k == 1 || dtype_out == ED_F32, "gemm: split_k > 1 needs an fp32 output (atomic +=)");
+// ---------------------------------------------------------------- the plan: which kernel, which grid, how many slices
+static int pow2_slices(int split_k) {   // quiet slices: the next power of two >= split_k, at most 8
+    int p2 = 1;
+    while (p2 < split_k && p2 < 8) p2 *= 2;
+    return p2;
+}
+static bool vec16(const void* p, long long ld, int vec) { return (uintptr_t)p % 16 == 0 && ld % vec == 0; }
+// what the direct-to-LDS bf16 NT kernels (gemm_nt.hip, gemm_nt256.hip, gemm_nt256r.hip) take
+static bool nt_ok(const GemmCall& c) {
+    if ((uintptr_t)c.bias1 % 16 != 0 || (uintptr_t)c.bias2 % 16 != 0) return false;   // float4 bias loads
+    return c.dtype_in == ED_BF16 && c.dtype_out == ED_BF16 && c.a_kmajor && c.b_kmajor && c.split_k == 1 && c.M > 0 &&
+           c.N > 0 && c.K >= 64 && c.K % 64 == 0 && c.lda % 8 == 0 && c.ldb % 8 == 0 && c.ldc % 8 == 0 && c.N % 8 == 0 &&
+           (uintptr_t)c.A % 16 == 0 && (uintptr_t)c.B % 16 == 0 && (uintptr_t)c.C % 16 == 0;
+}
+static bool nt256_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K >= 128 && K % 64 == 0; }
+static bool tn256_ok(const GemmCall& c) {
+    return ed_env_once("EDGEDICT_GEMM_TN256", 1) && c.M >= 8 && c.N >= 8 && c.K >= 1 && c.M % 8 == 0 && c.N % 8 == 0 &&
+           c.lda % 8 == 0 && c.ldb % 8 == 0 && (uintptr_t)c.A % 16 == 0 && (uintptr_t)c.B % 16 == 0;
+}
+
+int ed_gemm_plan(const GemmCall& c, GemmPlan& p) {
+    p = GemmPlan{};
+    const int M = c.M, N = c.N, K = c.K, n_cu = ed_device_cus();
     if (M == 0 || N == 0) return ED_OK;
-    ED_CHECK_ARG(A && B && C, "gemm: null operand");
-    hipStream_t stream = (hipStream_t)stream_;
-    // bf16 NT products with K % 64 == 0 take the direct-to-LDS kernel (gemm_nt.hip)
-    static const bool nt_enabled = [] {
-        const char* e = getenv("EDGEDICT_GEMM_NT");
-        return !(e && e[0] == '0');
-    }();
-    // large bf16 NT products: the 256 x 256-tile kernel (gemm_nt256.hip), ahead of the vendor route
-    if (nt_enabled && max_wg_per_cu == 0 && ed_gemm_nt256_ok(M, N, K, accumulate) &&
-        ed_gemm_nt_ok(dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, split_k, bias1, bias2))
-        return ed_gemm_nt256_launch(A, lda, B, ldb, C, ldc, M, N, K, bias1, bias2, stream);
-    // the one plain product that is large AND output-heavy (short K: the joint's logits) goes to the
-    // vendor library when it is there (blaslt.cpp says why); everything else runs here
-    if (dtype_in == ED_BF16 && dtype_out == ED_BF16 && a_kmajor && b_kmajor && !accumulate && !bias2 &&
-        split_k == 1 && max_wg_per_cu == 0 && K <= 1024 && N >= 1024 && (long long)M * N >= (1ll << 28) &&
-        lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
-        ed_blaslt_nt_bf16(A, lda, B, ldb, C, ldc, M, N, K, bias1, 0, stream))
+    p.split = 1;
+    const bool has_bias = c.bias1 || c.bias2;
+    // bf16 NT products with K % 64 == 0 take the direct-to-LDS kernels
+    const bool nt = ed_env_once("EDGEDICT_GEMM_NT", 1) && c.max_wg_per_cu == 0 && nt_ok(c);
+    // large ones (worth it from ~2 tiles per CU on; the 128 x 128 kernel keeps the small and the accumulating products)
+    // and the log-sum-exp entry: 256 x 256 tiles, ahead of the vendor route
+    const long long tiles256 = (long long)((M + 255) / 256) * ((N + 255) / 256);
+    if (c.lse_part || (nt && ed_env_once("EDGEDICT_GEMM_NT256", 1) && !c.accumulate && nt256_shape_ok(M, N, K) &&
+                       tiles256 >= 512)) {
+        ED_CHECK_ARG(tiles256 < (1ll << 31), "gemm: too many tiles");
+        // the persistent ring kernel: one workgroup per CU walks the tiles.  A workgroup keeps ONE bias fragment, so with
+        // a bias all of its tiles must lie in the same column tile; else one tile per workgroup (gemm_nt256.hip).
+        // (EDGEDICT_GEMM_NT256R is read at every call: tests/test_gemm_gpu.py compares both kernels in one process)
+        const int n_tiles = (N + 255) / 256, cus = n_cu - n_cu % 8;
+        const int grid = (int)(tiles256 < cus ? tiles256 : cus);
+        const bool ring = ed_env_now("EDGEDICT_GEMM_NT256R", 1) &&
+                          !(has_bias && tiles256 > grid && ((grid / 8) % n_tiles != 0 || grid % 8 != 0));
+        p.kernel = !ring ? ED_K_NT256 : c.lse_part ? ED_K_NT256R_LSE : ED_K_NT256R;
+        p.grid = ring ? grid : (unsigned)tiles256;
+        p.block = 512;
+        p.lds = ring ? ED_NT256R_LDS_BYTES : ED_NT256_LDS_BYTES;
         return ED_OK;
-    // ... and the long-K, few-tiles products of the encoder stack's backward chain (dX of a chunk:
-    // [768..1536 x 1024 x 4096], 19-23 us there vs 32 us here, tools/blas_probe2.py)
-    static const bool small_vendor = [] {
-        const char* e = getenv("EDGEDICT_BLASLT_SMALL");   // measured: step 27.17 -> 27.01 ms
-        return !(e && e[0] == '0');
-    }();
-    if (small_vendor && dtype_in == ED_BF16 && dtype_out == ED_BF16 && a_kmajor && b_kmajor && !bias1 && !bias2 &&
-        split_k == 1 && max_wg_per_cu == 0 && K >= 2048 && M <= 4096 && N <= 2048 && M >= 256 &&
-        lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
-        ed_blaslt_nt_bf16(A, lda, B, ldb, C, ldc, M, N, K, nullptr, accumulate, stream))
+    }
+    // the one plain product that is large AND output-heavy (short K: the joint's logits) goes to the vendor library
+    // when it is there (blaslt.cpp says why), and so do the long-K, few-tiles products of the encoder stack's backward
+    // chain (dX of a chunk: [768..1536 x 1024 x 4096], 19-23 us there vs 32 us here, tools/blas_probe2.py;
+    // EDGEDICT_BLASLT_SMALL measured: step 27.17 -> 27.01 ms); everything else runs here
+    const bool plain_nt = c.dtype_in == ED_BF16 && c.dtype_out == ED_BF16 && c.a_kmajor && c.b_kmajor && c.split_k == 1 &&
+                          c.max_wg_per_cu == 0 && c.lda % 8 == 0 && c.ldb % 8 == 0 && c.ldc % 8 == 0;
+    if (plain_nt && !c.accumulate && !c.bias2 && K <= 1024 && N >= 1024 && (long long)M * N >= (1ll << 28))
+        p.vendor = ED_VENDOR_NT_LOGITS;
+    else if (plain_nt && !has_bias && K >= 2048 && M <= 4096 && N <= 2048 && M >= 256 &&
+             ed_env_once("EDGEDICT_BLASLT_SMALL", 1))
+        p.vendor = ED_VENDOR_NT_SMALL;
+    if (nt) {
+        // small problem: spread it out over 64 x 64 tiles (<256,128,64> measured slower everywhere; kept for
+        // re-measurement), and those with a long K onto the ring kernel
+        const int force = ed_env_once("EDGEDICT_GEMM_NT_TILE", 0);
+        int tm = 128, tn = 128;
+        if (force == 64 || (!force && (long long)((M + 127) / 128) * ((N + 127) / 128) <= 128)) tm = tn = 64;
+        else if (force == 256) tm = 256;
+        const long long tiles = (long long)((M + tm - 1) / tm) * ((N + tn - 1) / tn);
+        ED_CHECK_ARG(tiles < (1ll << 31), "gemm: too many tiles");
+        p.kernel = tm == 256 ? ED_K_NT_256X128 : tm == 128 ? ED_K_NT_128 :
+                   ed_env_once("EDGEDICT_GEMM_NT_RING", 1) && K >= 1024 && !ed_env_once("EDGEDICT_GEMM_NT_DEBUG", 0)
+                       ? ED_K_NT_RING64 : ED_K_NT_64;   // (the probe bits exist in gemm_nt_kernel only)
+        p.grid = (unsigned)tiles;
+        p.block = tm == 256 ? 512 : 256;
         return ED_OK;
-    if (nt_enabled && max_wg_per_cu == 0 &&
-        ed_gemm_nt_ok(dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, split_k, bias1, bias2))
-        return ed_gemm_nt_launch(A, lda, B, ldb, C, ldc, M, N, K, bias1, bias2, accumulate, 0, stream);
-    const int esz = dtype_in == ED_F32 ? 4 : 2;
-    const int vec = 16 / esz;
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias1 = bias1; g.bias2 = bias2;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.a_vec = ((uintptr_t)A % 16 == 0) && (lda % vec == 0);
-    g.b_vec = ((uintptr_t)B % 16 == 0) && (ldb % vec == 0);
-    g.c_vec = (dtype_out == ED_BF16) && ((uintptr_t)C % 16 == 0) && (ldc % 8 == 0) && (N % 8 == 0);
-    g.accumulate = accumulate;
-    const int bk = dtype_in == ED_F32 ? 16 : 64;
-    int ktiles = (K + bk - 1) / bk;
-    if (partials) {
-        // quiet mode: few long-lived slices (power of two <= 8 keeps slice <-> XCD set fixed)
-        int p2 = 1;
-        while (p2 < split_k && p2 < 8) p2 *= 2;
-        split_k = p2;
-    } else if (split_k > 1) {
-        split_k = (split_k + 7) / 8 * 8;   // whole K slices per XCD (see the kernel)
     }
-    if (split_k > ktiles) split_k = ktiles > 0 ? ktiles : 1;
-    g.split_k = split_k;
-    g.k_per_split = ((ktiles + split_k - 1) / split_k) * bk;
-    if (g.k_per_split == 0) g.k_per_split = bk;
-    g.partials = partials;
-    g.partial_stride = (long long)M * N;
-    if (split_k > 1 && !accumulate && !partials) {
-        // atomics need a defined starting value
-        const long long n = (long long)M * N;
-        hipLaunchKernelGGL(zero_f32, dim3(ed_grid_for(n, 256)), dim3(256), 0, stream, (float*)C,
-                           (long long)M, (long long)N, ldc);
-        ED_CHECK_LAUNCH("gemm zero");
+    // large bf16 weight gradients (both operands row-major over the reduction) from the background entries: 256-row tiles
+    // pull fewer bytes per flop through the CU fetch path that the recurrence beside them is bound by - with a partials
+    // buffer the own quiet kernel (gemm_tn256.hip) + the reduce pass, else the vendor's
+    const bool dw = c.dtype_in == ED_BF16 && c.dtype_out == ED_F32 && !c.a_kmajor && !c.b_kmajor &&
+                    (long long)M * N >= (1ll << 18);
+    if (dw && c.partials && K >= 1024 && tn256_ok(c)) {
+        // K slices that fill the chip with one workgroup per CU (96 KB LDS), at most slice_cap, at least 8 K stages each
+        const long long tiles = (long long)((M + 255) / 256) * ((N + 127) / 128);
+        long long s = n_cu / tiles < c.slice_cap ? n_cu / tiles : c.slice_cap;
+        while (s > 1 && s * 8 > (K + 31) / 32) --s;
+        if (s < 1) s = 1;
+        ED_CHECK_ARG(tiles * s < (1ll << 30), "gemm_tn256: too many tiles");
+        const int items = (int)(tiles * s);
+        int grid = n_cu < items ? n_cu : items;
+        if (grid > 8) grid = grid / 8 * 8;
+        const int per = (items + grid - 1) / grid;    // items a workgroup walks
+        p.kernel = ED_K_TN256;
+        p.grid = (items + per - 1) / per;
+        p.block = 512;
+        p.lds = ED_TN256_LDS_BYTES;
+        p.split = (int)s;
+        p.k_per_split = (int)(((K + s - 1) / s + 63) / 64 * 64);
+        p.reduce_after = !c.unreduced;
+        return ED_OK;
     }
+    if (dw && (c.max_wg_per_cu > 0 || c.partials) && !has_bias && K >= 4096 && c.lda % 8 == 0 && c.ldb % 8 == 0 &&
+        c.ldc % 4 == 0)
+        p.vendor = ED_VENDOR_TN_F32;
+    // ---- the generic kernel
+    const bool f32 = c.dtype_in == ED_F32;
+    const int bk = f32 ? 16 : 64, vec = f32 ? 4 : 8, ktiles = (K + bk - 1) / bk;
+    int split = c.split_k;
+    if (c.partials) split = pow2_slices(split);   // quiet: few long-lived slices (power of two keeps slice <-> XCD set fixed)
+    else if (split > 1) split = (split + 7) / 8 * 8;   // whole K slices per XCD (see the kernel)
+    if (split > ktiles) split = ktiles > 0 ? ktiles : 1;
+    p.split = split;
+    p.k_per_split = ktiles > 0 ? ((ktiles + split - 1) / split) * bk : bk;
+    p.zero_first = split > 1 && !c.accumulate && !c.partials;
+    p.reduce_after = c.partials && !c.unreduced;
     const long long tiles = (long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
     ED_CHECK_ARG(tiles < (1ll << 31), "gemm: too many tiles");
-    ED_CHECK_ARG(tiles * split_k < (1ll << 31), "gemm: too many workgroups");
-    g.items = (int)(tiles * split_k);
-    long long nwg = g.items;
-    if (max_wg_per_cu > 0) {
-        // background: only as many workgroups as are resident at once (see the kernel)
-        static const int n_cu = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-                n = 256;
-            return n > 0 ? n : 256;
-        }();
-        long long cap = (long long)max_wg_per_cu * n_cu;
-        if (split_k > 1) cap = cap / split_k * split_k;   // keep item % split_k fixed per workgroup
-        if (cap >= split_k && nwg > cap) nwg = cap;
+    ED_CHECK_ARG(tiles * split < (1ll << 31), "gemm: too many workgroups");
+    long long nwg = tiles * split;
+    if (c.max_wg_per_cu > 0) {
+        // background: only as many workgroups as are resident at once (see the kernel) ...
+        long long cap = (long long)c.max_wg_per_cu * n_cu;
+        if (split > 1) cap = cap / split * split;   // keep item % split_k fixed per workgroup
+        if (cap >= split && nwg > cap) nwg = cap;
+        // ... and each claims enough extra LDS that only max_wg_per_cu workgroups fit on a CU
+        const int stat = (BM + BN) * (f32 ? Cfg<float>::ROW * 4 : Cfg<bf16_t>::ROW * 2);
+        const int want = (160 * 1024) / (c.max_wg_per_cu + 1) + 1024;   // one more would not fit
+        if (want > stat) p.lds = (want - stat + 255) / 256 * 256;
     }
-    dim3 grid((unsigned)nwg, 1, 1);
-    // occupancy cap: claim enough extra LDS that only max_wg_per_cu workgroups fit on a CU
-    int pad = 0;
-    if (max_wg_per_cu > 0) {
-        const int stat = (BM + BN) * (dtype_in == ED_F32 ? Cfg<float>::ROW * 4 : Cfg<bf16_t>::ROW * 2);
-        const int want = (160 * 1024) / (max_wg_per_cu + 1) + 1024;   // one more would not fit
-        if (want > stat) pad = (want - stat + 255) / 256 * 256;
+    p.grid = (unsigned)nwg;
+    p.block = THREADS;
+    // FAST: both operands 16-byte aligned with a leading dimension that is a multiple of the vector width, and the
+    // contiguous extent of each operand a multiple of it as well
+    const bool fast = vec16(c.A, c.lda, vec) && vec16(c.B, c.ldb, vec) && (c.a_kmajor ? K : M) % vec == 0 &&
+                      (c.b_kmajor ? K : N) % vec == 0;
+    p.kernel = (f32 ? ED_K_GENERIC_F32_F32 : c.dtype_out == ED_F32 ? ED_K_GENERIC_BF16_F32 : ED_K_GENERIC_BF16_BF16) + fast;
+    return ED_OK;
+}
+
+static int generic_launch(const GemmCall& c, const GemmPlan& p, hipStream_t s) {
+    const int vec = c.dtype_in == ED_F32 ? 4 : 8;
+    GemmArgs g;
+    g.A = c.A; g.B = c.B; g.C = c.C; g.bias1 = c.bias1; g.bias2 = c.bias2;
+    g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.M = c.M; g.N = c.N; g.K = c.K;
+    g.a_vec = vec16(c.A, c.lda, vec);
+    g.b_vec = vec16(c.B, c.ldb, vec);
+    g.c_vec = c.dtype_out == ED_BF16 && vec16(c.C, c.ldc, 8) && c.N % 8 == 0;
+    g.accumulate = c.accumulate;
+    g.split_k = p.split;
+    g.k_per_split = p.k_per_split;
+    g.items = (int)((long long)((c.M + BM - 1) / BM) * ((c.N + BN - 1) / BN) * p.split);
+    g.partials = c.partials;
+    g.partial_stride = (long long)c.M * c.N;
+    const dim3 grid(p.grid, 1, 1);
+    switch (p.kernel) {
+    case ED_K_GENERIC_BF16_BF16_FAST: return launch2<bf16_t, bf16_t, true>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
+    case ED_K_GENERIC_BF16_BF16: return launch2<bf16_t, bf16_t, false>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
+    case ED_K_GENERIC_BF16_F32_FAST: return launch2<bf16_t, float, true>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
+    case ED_K_GENERIC_BF16_F32: return launch2<bf16_t, float, false>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
+    case ED_K_GENERIC_F32_F32_FAST: return launch2<float, float, true>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
+    default: return launch2<float, float, false>(g, c.a_kmajor, c.b_kmajor, grid, s, p.lds);
     }
-    int rc;
-    if (dtype_in == ED_BF16 && dtype_out == ED_BF16) rc = launch<bf16_t, bf16_t>(g, a_kmajor, b_kmajor, grid, stream, pad);
-    else if (dtype_in == ED_BF16 && dtype_out == ED_F32) rc = launch<bf16_t, float>(g, a_kmajor, b_kmajor, grid, stream, pad);
-    else rc = launch<float, float>(g, a_kmajor, b_kmajor, grid, stream, pad);
-    if (rc != ED_OK || !partials || !reduce) return rc;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ed_grid_for((long long)M * N, 256, 2048)), dim3(256), 0,
-                       stream, partials, g.partial_stride, g.split_k, (float*)C, ldc, (long long)M, N,
-                       accumulate);
+}
+
+int ed_gemm_run(const GemmCall& c, const GemmPlan& p, hipStream_t s, int* slices) {
+    if (slices) *slices = p.split;
+    if (p.kernel == ED_K_NONE) return ED_OK;
+    if (p.vendor == ED_VENDOR_TN_F32
+            ? ed_blaslt_tn_f32(c.A, c.lda, c.B, c.ldb, (float*)c.C, c.ldc, c.M, c.N, c.K, c.accumulate, s)
+            : p.vendor && ed_blaslt_nt_bf16(c.A, c.lda, c.B, c.ldb, c.C, c.ldc, c.M, c.N, c.K, c.bias1, c.accumulate, s)) {
+        if (slices) *slices = 1;
+        return ED_OK;
+    }
+    if (p.zero_first) {
+        hipLaunchKernelGGL(zero_f32, dim3(ed_grid_for((long long)c.M * c.N, 256)), dim3(256), 0, s, (float*)c.C,
+                           (long long)c.M, (long long)c.N, c.ldc);
+        ED_CHECK_LAUNCH("gemm zero");
+    }
+    const int rc = p.kernel == ED_K_TN256 ? ed_gemm_tn256_launch(c, p, s)
+                 : p.kernel >= ED_K_NT256R ? ed_gemm_nt256r_launch(c, p, s)
+                 : p.kernel == ED_K_NT256 ? ed_gemm_nt256_launch(c, p, s)
+                 : p.kernel >= ED_K_NT_64 ? ed_gemm_nt_launch(c, p, s) : generic_launch(c, p, s);
+    if (rc != ED_OK || !p.reduce_after) return rc;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ed_grid_for((long long)c.M * c.N, 256, 2048)), dim3(256), 0, s,
+                       c.partials, (long long)c.M * c.N, p.split, (float*)c.C, c.ldc, (long long)c.M, c.N, c.accumulate);
     ED_CHECK_LAUNCH("gemm reduce_partials");
     return ED_OK;
 }
 
-// internal (encoder_stack.hip): quiet background product that leaves the slices UNREDUCED in
-// `partials`; returns the number of slices written through *slices
+// ---------------------------------------------------------------- entry points: validate, describe, plan, run
+static int gemm_validate(const GemmCall& c, bool bg) {
+    if (c.lse_part) {
+        ED_CHECK_ARG(nt256_shape_ok(c.M, c.N, c.K) && nt_ok(c),
+                     "gemm_nt_lse: needs bf16 K-contiguous operands, K %% 64 == 0, K >= 128, N %% 8 == 0, "
+                     "16-byte aligned pointers and leading dimensions (M=%d N=%d K=%d)", c.M, c.N, c.K);
+        return ED_OK;
+    }
+    ED_CHECK_ARG(!bg || (c.max_wg_per_cu >= 1 && c.max_wg_per_cu <= 8), "gemm_bg: max_wg_per_cu must be 1..8");
+    ED_CHECK_ARG(!c.partials || c.dtype_out == ED_F32, "gemm_bg: the quiet (partials) form needs an fp32 output");
+    ED_CHECK_ARG(!c.partials || (!c.bias1 && !c.bias2), "gemm_bg: the quiet (partials) form takes no bias");
+    ED_CHECK_ARG(c.dtype_in == ED_F32 || c.dtype_in == ED_BF16, "gemm: bad input dtype %d", c.dtype_in);
+    ED_CHECK_ARG(c.dtype_out == ED_F32 || c.dtype_out == ED_BF16, "gemm: bad output dtype %d", c.dtype_out);
+    ED_CHECK_ARG(!(c.dtype_in == ED_F32 && c.dtype_out == ED_BF16), "gemm: fp32 inputs with bf16 output is not supported");
+    ED_CHECK_ARG(c.M >= 0 && c.N >= 0 && c.K >= 0, "gemm: negative dimension");
+    ED_CHECK_ARG(c.split_k >= 1, "gemm: split_k must be >= 1");
+    ED_CHECK_ARG(c.split_k == 1 || c.dtype_out == ED_F32, "gemm: split_k > 1 needs an fp32 output (atomic +=)");
+    ED_CHECK_ARG(c.M == 0 || c.N == 0 || (c.A && c.B && c.C), "gemm: null operand");
+    return ED_OK;
+}
+static int gemm_go(const GemmCall& c, bool bg, void* stream, int* slices = nullptr) {
+    GemmPlan p;
+    int rc = gemm_validate(c, bg);
+    if (rc == ED_OK) rc = ed_gemm_plan(c, p);
+    return rc == ED_OK ? ed_gemm_run(c, p, (hipStream_t)stream, slices) : rc;
+}
+
+// internal (encoder_stack.hip): quiet background product that leaves the slices UNREDUCED in `partials`; returns the
+// number of slices written through *slices (every caller's partials buffer holds 8 slices: encoder_stack.hip tmpW)
 int ed_gemm_quiet_partials(int dtype_in, const void* A, long long lda, int a_kmajor, const void* B,
                            long long ldb, int b_kmajor, int M, int N, int K, int split_k,
                            int max_wg_per_cu, float* partials, int* slices, hipStream_t stream) {
-    int p2 = 1;
-    while (p2 < split_k && p2 < 8) p2 *= 2;
-    // large bf16 weight-gradient products: 256-row tiles pull fewer bytes per flop through the CU fetch
-    // path that the recurrence beside them is bound by - the own kernel (gemm_tn256.hip), else the vendor's
-    if (dtype_in == ED_BF16 && !a_kmajor && !b_kmajor && (long long)M * N >= (1ll << 18) && K >= 1024 &&
-        ed_gemm_tn256_ok(A, lda, B, ldb, M, N, K)) {
-        // (every caller's partials buffer holds 8 slices: encoder_stack.hip tmpW)
-        const int S = ed_gemm_tn256_slices(M, N, K, 8);
-        *slices = S;
-        return ed_gemm_tn256_partials(A, lda, B, ldb, partials, M, N, K, S, 0, stream);
-    }
-    if (dtype_in == ED_BF16 && !a_kmajor && !b_kmajor && (long long)M * N >= (1ll << 18) && K >= 4096 &&
-        lda % 8 == 0 && ldb % 8 == 0 && N % 4 == 0 &&
-        ed_blaslt_tn_f32(A, lda, B, ldb, partials, N, M, N, K, 0, stream)) {
-        *slices = 1;
-        return ED_OK;
-    }
-    const int bk = dtype_in == ED_F32 ? 16 : 64;
-    const int ktiles = (K + bk - 1) / bk;
-    if (p2 > ktiles) p2 = ktiles > 0 ? ktiles : 1;
-    *slices = p2;
-    return gemm_impl(dtype_in, ED_F32, A, lda, a_kmajor, B, ldb, b_kmajor, partials, N, M, N, K, nullptr,
-                     nullptr, 0, p2, (void*)stream, max_wg_per_cu, partials, false);
+    ED_CHECK_ARG(partials, "gemm: quiet product without a partials buffer");
+    return gemm_go({dtype_in, ED_F32, A, lda, a_kmajor, B, ldb, b_kmajor, partials, N, M, N, K, nullptr, nullptr, 0, split_k,
+                    max_wg_per_cu, partials, 8, true, nullptr}, false, stream, slices);
 }
 
 extern "C" int edgedict_gemm(int dtype_in, int dtype_out, const void* A, long long lda, int a_kmajor,
                              const void* B, long long ldb, int b_kmajor, void* C, long long ldc,
                              int M, int N, int K, const float* bias1, const float* bias2,
-                             int accumulate, int split_k, void* stream_) {
-    return gemm_impl(dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, bias1,
-                     bias2, accumulate, split_k, stream_, 0);
+                             int accumulate, int split_k, void* stream) {
+    return gemm_go({dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, bias1, bias2, accumulate,
+                    split_k, 0, nullptr, 0, false, nullptr}, false, stream);
 }
 
 extern "C" int edgedict_gemm_nt_lse(const void* A, long long lda, const void* B, long long ldb, void* C,
                                     long long ldc, int M, int N, int K, const float* bias,
-                                    float* lse_part, void* stream_) {
+                                    float* lse_part, void* stream) {
     ED_CHECK_ARG(A && B && C && lse_part, "gemm_nt_lse: null pointer");
-    ED_CHECK_ARG(ed_gemm_nt256_shape_ok(M, N, K) &&
-                 ed_gemm_nt_ok(ED_BF16, ED_BF16, A, lda, 1, B, ldb, 1, C, ldc, M, N, K, 1, bias, nullptr),
-                 "gemm_nt_lse: needs bf16 K-contiguous operands, K %% 64 == 0, K >= 128, N %% 8 == 0, "
-                 "16-byte aligned pointers and leading dimensions (M=%d N=%d K=%d)", M, N, K);
-    return ed_gemm_nt256_launch(A, lda, B, ldb, C, ldc, M, N, K, bias, nullptr, (hipStream_t)stream_, lse_part);
+    return gemm_go({ED_BF16, ED_BF16, A, lda, 1, B, ldb, 1, C, ldc, M, N, K, bias, nullptr, 0, 1, 0, nullptr, 0, false,
+                    lse_part}, false, stream);
 }
 
+// (the caller's partials buffer holds the next power of two >= split_k, at most 8, slices)
 extern "C" int edgedict_gemm_bg(int dtype_in, int dtype_out, const void* A, long long lda,
                                 int a_kmajor, const void* B, long long ldb, int b_kmajor, void* C,
                                 long long ldc, int M, int N, int K, const float* bias1,
                                 const float* bias2, int accumulate, int split_k,
-                                int max_wg_per_cu, float* partials, void* stream_) {
-    ED_CHECK_ARG(max_wg_per_cu >= 1 && max_wg_per_cu <= 8, "gemm_bg: max_wg_per_cu must be 1..8");
-    ED_CHECK_ARG(!partials || dtype_out == ED_F32, "gemm_bg: the quiet (partials) form needs an fp32 output");
-    ED_CHECK_ARG(!partials || (!bias1 && !bias2), "gemm_bg: the quiet (partials) form takes no bias");
-    // weight gradients (both operands row-major over the reduction) with a partials buffer: own 256 x 128
-    // quiet kernel + the reduce pass
-    if (partials && dtype_in == ED_BF16 && dtype_out == ED_F32 && !a_kmajor && !b_kmajor && A && B && C &&
-        (long long)M * N >= (1ll << 18) && K >= 1024 && ed_gemm_tn256_ok(A, lda, B, ldb, M, N, K)) {
-        int p2 = 1;      // the caller's buffer holds the next power of two >= split_k (<= 8) slices
-        while (p2 < split_k && p2 < 8) p2 *= 2;
-        p2 = ed_gemm_tn256_slices(M, N, K, p2);
-        const int rc = ed_gemm_tn256_partials(A, lda, B, ldb, partials, M, N, K, p2, 0, (hipStream_t)stream_);
-        if (rc != ED_OK) return rc;
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(ed_grid_for((long long)M * N, 256, 2048)), dim3(256), 0,
-                           (hipStream_t)stream_, partials, (long long)M * N, p2, (float*)C, ldc, (long long)M, N,
-                           accumulate);
-        ED_CHECK_LAUNCH("gemm reduce_partials");
-        return ED_OK;
-    }
-    if (dtype_in == ED_BF16 && dtype_out == ED_F32 && !a_kmajor && !b_kmajor && !bias1 && !bias2 && A && B && C &&
-        (long long)M * N >= (1ll << 18) && K >= 4096 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 &&
-        ed_blaslt_tn_f32(A, lda, B, ldb, (float*)C, ldc, M, N, K, accumulate, (hipStream_t)stream_))
-        return ED_OK;
-    return gemm_impl(dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, bias1,
-                     bias2, accumulate, split_k, stream_, max_wg_per_cu, partials, true);
+                                int max_wg_per_cu, float* partials, void* stream) {
+    return gemm_go({dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, bias1, bias2, accumulate,
+                    split_k, max_wg_per_cu, partials, pow2_slices(split_k), false, nullptr}, true, stream);
+}
+
+extern "C" int edgedict_gemm_plan(int dtype_in, int dtype_out, const void* A, long long lda, int a_kmajor,
+                                  const void* B, long long ldb, int b_kmajor, void* C, long long ldc, int M,
+                                  int N, int K, const float* bias1, const float* bias2, int accumulate,
+                                  int split_k, int max_wg_per_cu, float* partials, int lse, int unreduced,
+                                  int32_t* record) {
+    static float lse_dummy[2];
+    ED_CHECK_ARG(record, "gemm_plan: null record");
+    const GemmCall c = {dtype_in, dtype_out, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, bias1, bias2, accumulate,
+                        split_k, max_wg_per_cu, partials, unreduced ? 8 : pow2_slices(split_k), unreduced != 0,
+                        lse ? lse_dummy : nullptr};
+    GemmPlan p;
+    int rc = gemm_validate(c, max_wg_per_cu != 0 && !unreduced);
+    if (rc == ED_OK) rc = ed_gemm_plan(c, p);
+    if (rc != ED_OK) return rc;
+    const int32_t r[ED_GEMM_PLAN_WORDS] = {p.kernel, (int32_t)p.grid, p.block, p.lds, p.split, p.k_per_split,
+                                           p.zero_first, p.reduce_after, p.vendor};
+    for (int i = 0; i < ED_GEMM_PLAN_WORDS; ++i) record[i] = r[i];
+    return ED_OK;
 }

@@ -15,10 +15,8 @@
 // (2 workgroups per CU: one's epilogue stores overlap the other's main loop).
 // Requirements (else gemm.hip's kernel runs): K % 64 == 0, lda/ldb % 8 == 0, 16-byte aligned
 // operands, bf16 output with ldc % 8 == 0 and N % 8 == 0, split_k == 1.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "gemm_nt.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -324,42 +322,22 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_ring64_kernel(NtArgs g) {
 
 }  // namespace
 
-bool ed_gemm_nt_ok(int dtype_in, int dtype_out, const void* A, long long lda, int a_kmajor,
-                   const void* B, long long ldb, int b_kmajor, const void* C, long long ldc, int M,
-                   int N, int K, int split_k, const float* bias1, const float* bias2) {
-    if ((uintptr_t)bias1 % 16 != 0 || (uintptr_t)bias2 % 16 != 0) return false;   // float4 bias loads
-    return dtype_in == ED_BF16 && dtype_out == ED_BF16 && a_kmajor && b_kmajor && split_k == 1 &&
-           M > 0 && N > 0 && K >= 64 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
-           N % 8 == 0 && (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0 && (uintptr_t)C % 16 == 0;
-}
-
-int ed_gemm_nt_launch(const void* A, long long lda, const void* B, long long ldb, void* C,
-                      long long ldc, int M, int N, int K, const float* bias1, const float* bias2,
-                      int accumulate, int lds_pad, hipStream_t s) {
+int ed_gemm_nt_launch(const GemmCall& c, const GemmPlan& p, hipStream_t s) {
+    const int tn = (p.kernel == ED_K_NT_64 || p.kernel == ED_K_NT_RING64) ? 64 : 128;
     NtArgs g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = (bf16_t*)C;
-    g.bias1 = bias1; g.bias2 = bias2;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K;
-    g.accumulate = accumulate;
-    static const int dbg = [] { const char* e = getenv("EDGEDICT_GEMM_NT_DEBUG"); return e ? atoi(e) : 0; }();
-    g.debug = dbg;
-    static const int force_t = [] { const char* e = getenv("EDGEDICT_GEMM_NT_TILE"); return e ? atoi(e) : 0; }();
-    const long long tiles128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
-    // small problem: spread it out
-    int tm = 128, tn = 128;
-    if (force_t == 64 || (!force_t && tiles128 <= 128)) tm = tn = 64;
-    else if (force_t == 256) tm = 256;   // measured slower everywhere; kept for re-measurement
-    g.n_tiles = (N + tn - 1) / tn;
-    const long long tiles = (long long)((M + tm - 1) / tm) * g.n_tiles;
-    ED_CHECK_ARG(tiles < (1ll << 31), "gemm: too many tiles");
-    g.tiles = (int)tiles;
-    static const int ring = [] { const char* e = getenv("EDGEDICT_GEMM_NT_RING"); return e ? atoi(e) : 1; }();
-    if (tm == 64 && ring && K >= 1024 && lds_pad == 0 && !g.debug)
-        hipLaunchKernelGGL(gemm_nt_ring64_kernel, dim3((unsigned)tiles), dim3(256), 0, s, g);
-    else if (tm == 64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 32>), dim3((unsigned)tiles), dim3(256), lds_pad, s, g);
-    else if (tm == 256) hipLaunchKernelGGL((gemm_nt_kernel<256, 128, 64>), dim3((unsigned)tiles), dim3(512), lds_pad, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<128, 128, 64>), dim3((unsigned)tiles), dim3(256), lds_pad, s, g);
+    g.A = (const bf16_t*)c.A; g.B = (const bf16_t*)c.B; g.C = (bf16_t*)c.C;
+    g.bias1 = c.bias1; g.bias2 = c.bias2;
+    g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc;
+    g.M = c.M; g.N = c.N; g.K = c.K;
+    g.accumulate = c.accumulate;
+    g.debug = ed_env_once("EDGEDICT_GEMM_NT_DEBUG", 0);
+    g.n_tiles = (c.N + tn - 1) / tn;
+    g.tiles = (int)p.grid;
+    const dim3 grid(p.grid), block(p.block);
+    if (p.kernel == ED_K_NT_RING64) hipLaunchKernelGGL(gemm_nt_ring64_kernel, grid, block, 0, s, g);
+    else if (p.kernel == ED_K_NT_64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 32>), grid, block, 0, s, g);
+    else if (p.kernel == ED_K_NT_256X128) hipLaunchKernelGGL((gemm_nt_kernel<256, 128, 64>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel<128, 128, 64>), grid, block, 0, s, g);
     ED_CHECK_LAUNCH("gemm_nt");
     return ED_OK;
 }

@@ -22,10 +22,8 @@
 //
 // Requirements (else gemm_nt.hip / gemm.hip run): K % 64 == 0, K >= 128, lda/ldb/ldc % 8 == 0,
 // N % 8 == 0, 16-byte aligned operands, no accumulate.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "gemm_nt.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -36,6 +34,7 @@ constexpr int TM = 256, TN = 256, BK = 64;
 constexpr int HT = 256 * 32 * 2;          // one half-tile: 256 rows x 32 k bf16 = 16 KB
 constexpr int BUF = 4 * HT;               // A.k0 | A.k1 | B.k0 | B.k1
 constexpr int LDS_BYTES = 2 * BUF;        // 128 KB
+static_assert(LDS_BYTES == ED_NT256_LDS_BYTES, "the plan launches with this much");
 
 struct Nt256Args {
     const bf16_t* A;
@@ -257,38 +256,19 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256_kernel(Nt256Args g) {
 
 }  // namespace
 
-bool ed_gemm_nt256_shape_ok(int M, int N, int K) {
-    return M > 0 && N > 0 && K >= 128 && K % 64 == 0;
-}
-
-bool ed_gemm_nt256_ok(int M, int N, int K, int accumulate) {
-    static const int on = [] { const char* e = getenv("EDGEDICT_GEMM_NT256"); return e ? atoi(e) : 1; }();
-    // worth it from ~2 tiles per CU on; the 128 x 128 kernel keeps the small and the accumulating products
-    return on && !accumulate && ed_gemm_nt256_shape_ok(M, N, K) &&
-           (long long)((M + 255) / 256) * ((N + 255) / 256) >= 512;
-}
-
-int ed_gemm_nt256_launch(const void* A, long long lda, const void* B, long long ldb, void* C,
-                         long long ldc, int M, int N, int K, const float* bias1, const float* bias2,
-                         hipStream_t s, float* lse_part) {
-    if (ed_gemm_nt256r_ok(M, N, K, bias1 || bias2))
-        return ed_gemm_nt256r_launch(A, lda, B, ldb, C, ldc, M, N, K, bias1, bias2, s, lse_part);
+int ed_gemm_nt256_launch(const GemmCall& c, const GemmPlan& p, hipStream_t s) {
     Nt256Args g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = (bf16_t*)C;
-    g.bias1 = bias1; g.bias2 = bias2;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K;
-    g.lse_part = (float2*)lse_part;
-    static const int dbg = [] { const char* e = getenv("EDGEDICT_NT256_DEBUG"); return e ? atoi(e) : 0; }();
-    g.dbg = dbg;
-    g.lse_slots = (N + 63) / 64;
-    g.n_tiles = (N + TN - 1) / TN;
-    const long long tiles = (long long)((M + TM - 1) / TM) * g.n_tiles;
-    ED_CHECK_ARG(tiles < (1ll << 31), "gemm: too many tiles");
-    g.tiles = (int)tiles;
-    ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_nt256_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    hipLaunchKernelGGL(gemm_nt256_kernel, dim3((unsigned)tiles), dim3(512), LDS_BYTES, s, g);
+    g.A = (const bf16_t*)c.A; g.B = (const bf16_t*)c.B; g.C = (bf16_t*)c.C;
+    g.bias1 = c.bias1; g.bias2 = c.bias2;
+    g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc;
+    g.M = c.M; g.N = c.N; g.K = c.K;
+    g.lse_part = (float2*)c.lse_part;
+    g.dbg = ed_env_once("EDGEDICT_NT256_DEBUG", 0);
+    g.lse_slots = (c.N + 63) / 64;
+    g.n_tiles = (c.N + TN - 1) / TN;
+    g.tiles = (int)p.grid;
+    ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_nt256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    hipLaunchKernelGGL(gemm_nt256_kernel, dim3(p.grid), dim3(p.block), p.lds, s, g);
     ED_CHECK_LAUNCH("gemm_nt256");
     return ED_OK;
 }

@@ -34,10 +34,8 @@
 // == 0, N % 8 == 0, 16-byte aligned operands, no accumulate; with a bias, a workgroup's tiles must share
 // their column tile (workgroups per XCD % column tiles == 0, or one tile per workgroup): the pre-added bias
 // fragment stays in 16 registers for the workgroup's lifetime.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "gemm_nt.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -49,6 +47,7 @@ constexpr int TM = 256, TN = 256, BK = 64;
 constexpr int HT = 128 * 128;             // half-tile: 128 rows x 64 k bf16 = 16 KB
 constexpr int RING_BYTES = 8 * HT;        // [K-tile parity][A0 A1 B0 B1]
 constexpr int LDS_BYTES = RING_BYTES + TN * 4;   // + the workgroup's bias slice (fp32, pre-added)
+static_assert(LDS_BYTES == ED_NT256R_LDS_BYTES, "the plan launches with this much");
 
 struct Nt256rArgs {
     const bf16_t* A;
@@ -335,51 +334,21 @@ __global__ __launch_bounds__(512, 1) void gemm_nt256r_kernel(Nt256rArgs g) {
 
 }  // namespace
 
-bool ed_gemm_nt256r_ok(int M, int N, int K, bool has_bias, int* grid_out) {
-    // (read at every call: tests/test_gemm_gpu.py compares both kernels in one process)
-    const char* e = getenv("EDGEDICT_GEMM_NT256R");
-    if ((e && atoi(e) == 0) || !ed_gemm_nt256_shape_ok(M, N, K)) return false;
-    const int n_tiles = (N + TN - 1) / TN;
-    const long long tiles = (long long)((M + TM - 1) / TM) * n_tiles;
-    if (tiles >= (1ll << 31)) return false;
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n > 0 ? n - n % 8 : 256;
-    }();
-    const int grid = (int)(tiles < cus ? tiles : cus);
-    // a workgroup keeps ONE bias fragment: all of its tiles must lie in the same column tile
-    if (has_bias && tiles > grid && ((grid / 8) % n_tiles != 0 || grid % 8 != 0)) return false;
-    if (grid_out) *grid_out = grid;
-    return true;
-}
-
-int ed_gemm_nt256r_launch(const void* A, long long lda, const void* B, long long ldb, void* C, long long ldc, int M,
-                          int N, int K, const float* bias1, const float* bias2, hipStream_t s, float* lse_part) {
-    int grid = 0;
-    ED_CHECK_ARG(ed_gemm_nt256r_ok(M, N, K, bias1 || bias2, &grid), "gemm_nt256r: shape not covered");
+int ed_gemm_nt256r_launch(const GemmCall& c, const GemmPlan& p, hipStream_t s) {
     Nt256rArgs g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = (bf16_t*)C;
-    g.bias1 = bias1; g.bias2 = bias2;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K;
-    g.lse_part = (float2*)lse_part;
-    g.lse_slots = (N + 63) / 64;
-    g.n_tiles = (N + TN - 1) / TN;
-    g.tiles = ((M + TM - 1) / TM) * g.n_tiles;
-    static const int dbg = [] { const char* e = getenv("EDGEDICT_NT256_DEBUG"); return e ? atoi(e) : 0; }();
-    g.dbg = dbg;
-    if (lse_part) {
-        ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_nt256r_kernel<true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        hipLaunchKernelGGL(gemm_nt256r_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_BYTES, s, g);
-    } else {
-        ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_nt256r_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        hipLaunchKernelGGL(gemm_nt256r_kernel<false>, dim3((unsigned)grid), dim3(512), LDS_BYTES, s, g);
-    }
+    g.A = (const bf16_t*)c.A; g.B = (const bf16_t*)c.B; g.C = (bf16_t*)c.C;
+    g.bias1 = c.bias1; g.bias2 = c.bias2;
+    g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc;
+    g.M = c.M; g.N = c.N; g.K = c.K;
+    g.lse_part = (float2*)c.lse_part;
+    g.lse_slots = (c.N + 63) / 64;
+    g.n_tiles = (c.N + TN - 1) / TN;
+    g.tiles = ((c.M + TM - 1) / TM) * g.n_tiles;
+    g.dbg = ed_env_once("EDGEDICT_NT256_DEBUG", 0);
+    const void* k = p.kernel == ED_K_NT256R_LSE ? (const void*)gemm_nt256r_kernel<true> : (const void*)gemm_nt256r_kernel<false>;
+    ED_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    if (p.kernel == ED_K_NT256R_LSE) hipLaunchKernelGGL(gemm_nt256r_kernel<true>, dim3(p.grid), dim3(p.block), p.lds, s, g);
+    else hipLaunchKernelGGL(gemm_nt256r_kernel<false>, dim3(p.grid), dim3(p.block), p.lds, s, g);
     ED_CHECK_LAUNCH("gemm_nt256r");
     return ED_OK;
 }

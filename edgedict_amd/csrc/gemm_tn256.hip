@@ -31,10 +31,8 @@
 //
 // Requirements (else gemm.hip runs): M % 8 == 0, N % 8 == 0, lda % 8 == 0, ldb % 8 == 0, 16-byte aligned
 // operands.  K is arbitrary: rows past the end of a slice are read from a zero line.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "gemm_nt.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -49,6 +47,7 @@ constexpr int B_ST = BK * TN * 2;             // B stage: 8 KB (2 panels)
 constexpr int STAGE = A_ST + B_ST;            // 24 KB
 constexpr int NSTAGE = 4;                     // ring: one stage being read, up to three in flight
 constexpr int LDS_BYTES = NSTAGE * STAGE;     // 96 KB
+static_assert(LDS_BYTES == ED_TN256_LDS_BYTES, "the plan launches with this much");
 
 __device__ uint4 g_zero_line[4];              // 64 zero bytes: the source of K rows past a slice's end
 
@@ -191,56 +190,19 @@ __global__ __launch_bounds__(512, 2) void gemm_tn256_kernel(Tn256Args g) {
 
 }  // namespace
 
-bool ed_gemm_tn256_ok(const void* A, long long lda, const void* B, long long ldb, int M, int N, int K) {
-    static const int on = [] { const char* e = getenv("EDGEDICT_GEMM_TN256"); return e ? atoi(e) : 1; }();
-    return on && A && B && M >= 8 && N >= 8 && K >= 1 && M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-           (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0;
-}
-
-// K slices that fill the chip with one workgroup per CU (at most max_slices, at least 8 K stages each)
-int ed_gemm_tn256_slices(int M, int N, int K, int max_slices) {
-    const long long tiles = (long long)((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-    int n_cu = 256, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-        n_cu = 256;
-    long long s = n_cu / (tiles > 0 ? tiles : 1);
-    if (s > max_slices) s = max_slices;
-    const int stages = (K + BK - 1) / BK;
-    while (s > 1 && s * 8 > stages) --s;
-    return s < 1 ? 1 : (int)s;
-}
-
-int ed_gemm_tn256_partials(const void* A, long long lda, const void* B, long long ldb, float* partials, int M,
-                           int N, int K, int slices, int max_wgs, hipStream_t s) {
-    ED_CHECK_ARG(partials && slices >= 1 && slices <= 64, "gemm_tn256: bad partials / slices");
+int ed_gemm_tn256_launch(const GemmCall& c, const GemmPlan& p, hipStream_t s) {
     Tn256Args g;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.P = partials;
-    g.lda = lda; g.ldb = ldb; g.pstride = (long long)M * N;
-    g.M = M; g.N = N; g.K = K;
-    g.n_tiles = (N + TN - 1) / TN;
-    const long long tiles = (long long)((M + TM - 1) / TM) * g.n_tiles;
-    ED_CHECK_ARG(tiles * slices < (1ll << 30), "gemm_tn256: too many tiles");
-    g.tiles = (int)tiles;
-    g.slices = slices;
-    g.k_per = ((K + slices - 1) / slices + 63) / 64 * 64;
-    g.items = g.tiles * slices;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 256;
-        return n > 0 ? n : 256;
-    }();
-    int grid = n_cu;                     // one workgroup per CU is resident (96 KB LDS)
-    if (max_wgs > 0 && max_wgs < grid) grid = max_wgs;
-    if (grid > g.items) grid = g.items;
-    if (grid > 8) grid = grid / 8 * 8;
-    g.per = (g.items + grid - 1) / grid;
-    grid = (g.items + g.per - 1) / g.per;
-    ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn256_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    hipLaunchKernelGGL(gemm_tn256_kernel, dim3((unsigned)grid), dim3(512), LDS_BYTES, s, g);
+    g.A = (const bf16_t*)c.A; g.B = (const bf16_t*)c.B; g.P = c.partials;
+    g.lda = c.lda; g.ldb = c.ldb; g.pstride = (long long)c.M * c.N;
+    g.M = c.M; g.N = c.N; g.K = c.K;
+    g.n_tiles = (c.N + TN - 1) / TN;
+    g.tiles = ((c.M + TM - 1) / TM) * g.n_tiles;
+    g.slices = p.split;
+    g.k_per = p.k_per_split;
+    g.items = g.tiles * p.split;
+    g.per = (g.items + (int)p.grid - 1) / (int)p.grid;    // the plan's grid is ceil(items / per)
+    ED_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    hipLaunchKernelGGL(gemm_tn256_kernel, dim3(p.grid), dim3(p.block), p.lds, s, g);
     ED_CHECK_LAUNCH("gemm_tn256");
     return ED_OK;
 }

@@ -455,11 +455,7 @@ bool f32_lpw_ok(int B, int Tn, int H) {
     if (e && atoi(e) == 0) return false;
     if (!(H == 256 || H == 512 || H == 1024) || Tn < 2) return false;
     if ((unsigned long long)B * Tn * H * 4ull >= (1ull << 32)) return false;      // one 32-bit buffer descriptor
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n;
-    }();
+    const int n_cu = ed_device_cus();
     return (long long)(H / 16) * ((B + 15) / 16) <= n_cu;      // every workgroup (16 rows x 16 units) resident at once
 }
 

@@ -220,6 +220,31 @@ int edgedict_gemm_nt_lse(const void* A, long long lda, const void* B, long long 
                          long long ldc, int M, int N, int K, const float* bias, float* lse_part,
                          void* stream);
 
+/* DRY RUN of the three entry points above (and of the encoder stack's internal quiet products): which kernel a product
+ * would run, with which launch - nothing is launched, no pointer is dereferenced (only alignment and nullness count) and
+ * no device is needed (without one the plan assumes 256 compute units).  Arguments as edgedict_gemm_bg, with
+ *   max_wg_per_cu = 0 : the plan of edgedict_gemm
+ *   lse != 0          : the plan of edgedict_gemm_nt_lse (bf16 K-contiguous operands, bias1 = its bias)
+ *   unreduced != 0    : the internal quiet form that leaves its K slices in `partials` (C = partials, ldc = N)
+ * record [ED_GEMM_PLAN_WORDS] int32 out:
+ *   [0] kernel id   0 none (empty product)
+ *                   1 / 2 gemm_kernel<bf16, bf16> plain / FAST (vector loads without guards), 3 / 4 <bf16, f32>,
+ *                   5 / 6 <f32, f32> (gemm.hip; the layout pair of the call picks one of four instantiations)
+ *                   7 gemm_nt_kernel<64,64,32>, 8 <128,128,64>, 9 <256,128,64>, 10 gemm_nt_ring64_kernel (gemm_nt.hip)
+ *                   11 gemm_nt256_kernel, 12 gemm_nt256r_kernel<false>, 13 gemm_nt256r_kernel<true> (log-sum-exp)
+ *                   14 gemm_tn256_kernel
+ *   [1] grid (workgroups)   [2] block (threads)   [3] dynamic LDS bytes
+ *   [4] K slices that run (1: K is not split)      [5] K per slice (0 for the kernels that never split K)
+ *   [6] 1: a zero pass precedes (atomic split-K into a fresh C)   [7] 1: the reduce pass over `partials` follows
+ *   [8] vendor route tried first where the library has the bridge (the kernel above runs when it declines):
+ *       0 none, 1 large short-K bf16 NT (the joint's logits), 2 small long-K bf16 NT, 3 bf16 TN with fp32 output
+ * Returns what the entry point would return for arguments it rejects. */
+#define ED_GEMM_PLAN_WORDS 9
+int edgedict_gemm_plan(int dtype_in, int dtype_out, const void* A, long long lda, int a_kmajor,
+                       const void* B, long long ldb, int b_kmajor, void* C, long long ldc, int M, int N,
+                       int K, const float* bias1, const float* bias2, int accumulate, int split_k,
+                       int max_wg_per_cu, float* partials, int lse, int unreduced, int32_t* record);
+
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm fused with the residual add and the encoder's TimeReduction.

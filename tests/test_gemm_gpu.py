@@ -234,3 +234,31 @@ def test_gemm_nt_small_long_k_ring_path(hip_lib, M, N, K):
     ops.gemm(a, b, out=acc, accumulate=True)
     want = c0.double() + out.double()         # the kernel adds its bf16-rounded tile to the bf16 C
     assert ((acc.double() - want).abs() <= 2.0 ** -6 * want.abs() + 1e-2).all()
+
+
+def test_gemm_nt256_one_tile_per_workgroup_kernel_with_bias_by_default_routing(hip_lib):
+    """N = 768 is three column tiles: with a bias and more tiles (258) than the ring kernel's 256 workgroups, a
+    workgroup's tiles would not share their column tile, so the product runs the one-tile-per-workgroup kernel of
+    gemm_nt256.hip (kernel id 11 of edgedict_gemm_plan) - without any switch.  Against the fp32 product."""
+    import ctypes
+    from edgedict_amd import _lib
+    from edgedict_amd.ops import _ll
+    M, N, K = 256 * 86, 768, 128
+    a = _mk((M, K), torch.bfloat16, 61)
+    b = _mk((N, K), torch.bfloat16, 62)
+    bv = torch.randn(N, generator=torch.Generator().manual_seed(7)).cuda()
+    c = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device="cuda")
+    parts = torch.full((M, N // 64, 2), float("nan"), device="cuda")
+    rec = (ctypes.c_int32 * 9)()
+    assert hip_lib.edgedict_gemm_plan(1, 1, _lib.ptr(a), _ll(K), 1, _lib.ptr(b), _ll(K), 1, _lib.ptr(c), _ll(N), M, N, K,
+                                      _lib.ptr(bv), None, 0, 1, 0, None, 1, 0, rec) == 0
+    assert list(rec)[:4] == [11, 258, 512, 128 * 1024]
+    _lib.call("gemm_nt_lse", a, _ll(K), b, _ll(K), c, _ll(N), M, N, K, bv, parts)
+    ref = a.float() @ b.float().t() + bv
+    err = (c.float() - ref).abs()
+    assert (err <= 2.0 ** -7 * ref.abs() + 1e-3 * (K ** 0.5)).all()
+    cf = c.double()
+    mx, sm = parts[..., 0].double(), parts[..., 1].double()
+    top = mx.max(dim=1, keepdim=True).values
+    got = top[:, 0] + torch.log((sm * torch.exp(mx - top)).sum(1))
+    assert (got - torch.logsumexp(cf, dim=1)).abs().max().item() < 1e-4
