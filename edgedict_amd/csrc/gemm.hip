@@ -472,7 +472,7 @@ int ed_gemm_plan(const GemmCall& c, GemmPlan& p) {
     // EDGEDICT_BLASLT_SMALL measured: step 27.17 -> 27.01 ms); everything else runs here
     const bool plain_nt = c.dtype_in == ED_BF16 && c.dtype_out == ED_BF16 && c.a_kmajor && c.b_kmajor && c.split_k == 1 &&
                           c.max_wg_per_cu == 0 && c.lda % 8 == 0 && c.ldb % 8 == 0 && c.ldc % 8 == 0;
-    if (plain_nt && !c.accumulate && !c.bias2 && K <= 1024 && N >= 1024 && (long long)M * N >= (1ll << 28))
+    if (plain_nt && !c.accumulate && !c.bias2 && K >= 1 && K <= 1024 && N >= 1024 && (long long)M * N >= (1ll << 28))
         p.vendor = ED_VENDOR_NT_LOGITS;
     else if (plain_nt && !has_bias && K >= 2048 && M <= 4096 && N <= 2048 && M >= 256 &&
              ed_env_once("EDGEDICT_BLASLT_SMALL", 1))
@@ -623,7 +623,8 @@ static int gemm_validate(const GemmCall& c, bool bg) {
     ED_CHECK_ARG(c.M >= 0 && c.N >= 0 && c.K >= 0, "gemm: negative dimension");
     ED_CHECK_ARG(c.split_k >= 1, "gemm: split_k must be >= 1");
     ED_CHECK_ARG(c.split_k == 1 || c.dtype_out == ED_F32, "gemm: split_k > 1 needs an fp32 output (atomic +=)");
-    ED_CHECK_ARG(c.M == 0 || c.N == 0 || (c.A && c.B && c.C), "gemm: null operand");
+    // (K == 0: the operands are empty and never read - an empty tensor has no address -, C still gets the bias)
+    ED_CHECK_ARG(c.M == 0 || c.N == 0 || (c.C && (c.K == 0 || (c.A && c.B))), "gemm: null operand");
     return ED_OK;
 }
 static int gemm_go(const GemmCall& c, bool bg, void* stream, int* slices = nullptr) {

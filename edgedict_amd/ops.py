@@ -119,11 +119,11 @@ def _operand(t):
     raise ValueError("gemm operand must have a unit stride in one dimension")
 
 
-def gemm(a, b, out=None, bias=None, bias2=None, accumulate=False, split_k=1,
-         out_dtype=None, max_wg_per_cu=0):
-    """out[M,N] (+)= a[M,K] @ b[N,K]^T (+ bias).  ``a`` / ``b`` may be transposed *views*
-    (``x.t()``): the kernel reads them in place, nothing is materialised."""
-    require_cuda(a, b)
+def _gemm_args(a, b, out, bias, bias2, accumulate, split_k, out_dtype, max_wg_per_cu, dry=False):
+    """What ``gemm`` hands to the library and ``gemm_plan`` to its dry run: ``(out, args, nslice)``.  ``args`` is the
+    argument tuple shared by edgedict_gemm / _gemm_bg / _gemm_plan up to ``split_k`` (tensors still as tensors);
+    ``nslice`` > 0 is the number of [M, N] fp32 slices of the quiet background form's partials buffer.  ``dry``: a
+    missing ``out`` is described (a meta tensor), not allocated."""
     if a.dtype != b.dtype:
         raise TypeError("gemm: operand dtypes differ (%s vs %s)" % (a.dtype, b.dtype))
     M, K = a.shape
@@ -131,7 +131,7 @@ def gemm(a, b, out=None, bias=None, bias2=None, accumulate=False, split_k=1,
     if K != K2:
         raise ValueError("gemm: inner dimensions differ (%d vs %d)" % (K, K2))
     if out is None:
-        out = torch.empty(M, N, dtype=out_dtype or a.dtype, device=a.device)
+        out = torch.empty(M, N, dtype=out_dtype or a.dtype, device="meta" if dry else a.device)
         if accumulate:
             raise ValueError("gemm: accumulate needs an existing out tensor")
     if out.shape != (M, N) or out.stride(1) != 1:
@@ -144,17 +144,61 @@ def gemm(a, b, out=None, bias=None, bias2=None, accumulate=False, split_k=1,
     args = (dtype_code(a.dtype), dtype_code(out.dtype), a_, _ll(lda), akm, b_, _ll(ldb), bkm,
             out, _ll(out.stride(0) if M > 1 else max(out.stride(0), N)), M, N, K, bias, bias2,
             int(bool(accumulate)), int(split_k))
-    if max_wg_per_cu:     # background product on a side stream: capped CU residency, quiet split-K
-        part = None
-        if out.dtype == torch.float32 and bias is None and bias2 is None:
-            nslice = 1
-            while nslice < int(split_k) and nslice < 8:
-                nslice *= 2
-            part = torch.empty(nslice, M, N, dtype=torch.float32, device=out.device)
+    nslice = 0
+    # background product on a side stream: capped CU residency, quiet split-K where the output allows it
+    if max_wg_per_cu and out.dtype == torch.float32 and bias is None and bias2 is None:
+        nslice = 1
+        while nslice < int(split_k) and nslice < 8:
+            nslice *= 2
+    return out, args, nslice
+
+
+def gemm(a, b, out=None, bias=None, bias2=None, accumulate=False, split_k=1,
+         out_dtype=None, max_wg_per_cu=0):
+    """out[M,N] (+)= a[M,K] @ b[N,K]^T (+ bias).  ``a`` / ``b`` may be transposed *views*
+    (``x.t()``): the kernel reads them in place, nothing is materialised."""
+    require_cuda(a, b)
+    out, args, nslice = _gemm_args(a, b, out, bias, bias2, accumulate, split_k, out_dtype, max_wg_per_cu)
+    if max_wg_per_cu:
+        M, N = out.shape
+        part = torch.empty(nslice, M, N, dtype=torch.float32, device=out.device) if nslice else None
         call("gemm_bg", *args, int(max_wg_per_cu), part)
     else:
         call("gemm", *args)
     return out
+
+
+_PLAN_BASE = 1 << 40    # made-up, 4 KiB aligned: what a fresh allocation looks like to the planner
+GEMM_PLAN_WORDS = 9
+
+
+def _plan_addr(t):
+    """The address the planner sees for ``t``: the real one on the device, else a made-up aligned base plus the view's
+    offset into its storage (the plan reads nullness and alignment only).  Empty tensors have no address, as on the
+    device."""
+    if t is None or t.numel() == 0:
+        return ctypes.c_void_p(0)
+    if t.is_cuda:
+        return ctypes.c_void_p(t.data_ptr())
+    return ctypes.c_void_p(_PLAN_BASE + t.storage_offset() * t.element_size())
+
+
+def _gemm_plan_record(args, max_wg_per_cu, nslice, lse=0):
+    rec = (ctypes.c_int32 * GEMM_PLAN_WORDS)()
+    cargs = [_plan_addr(x) if x is None or isinstance(x, torch.Tensor) else x for x in args]
+    part = ctypes.c_void_p(_PLAN_BASE if nslice else 0)
+    lib = _lib.load()
+    _lib.check(lib.edgedict_gemm_plan(*cargs, int(max_wg_per_cu), part, int(lse), 0, rec), "gemm_plan")
+    return list(rec)
+
+
+def gemm_plan(a, b, out=None, bias=None, bias2=None, accumulate=False, split_k=1,
+              out_dtype=None, max_wg_per_cu=0):
+    """DRY run of ``gemm`` with the same arguments: the record of edgedict_gemm_plan (include/edgedict_hip.h:
+    [kernel id, grid, block, dynamic LDS bytes, K slices, K per slice, zero pass, reduce pass, vendor route]).
+    Nothing is launched or allocated; the tensors may live on any device (``meta`` included)."""
+    _, args, nslice = _gemm_args(a, b, out, bias, bias2, accumulate, split_k, out_dtype, max_wg_per_cu, dry=True)
+    return _gemm_plan_record(args, max_wg_per_cu, nslice)
 
 
 def cast(x, dtype):
