@@ -64,6 +64,10 @@ def load():
         lib.edgedict_beam_workspace_bytes_lm.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_state_bytes_lm.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_workspace_bytes_lm.restype = ctypes.c_size_t
+        lib.edgedict_beam_bias_struct_bytes.restype = ctypes.c_size_t
+        lib.edgedict_beam_workspace_bytes_bias.restype = ctypes.c_size_t
+        lib.edgedict_beam_stream_state_bytes_bias.restype = ctypes.c_size_t
+        lib.edgedict_beam_stream_workspace_bytes_bias.restype = ctypes.c_size_t
         lib.edgedict_beam_detail_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_nbest_result_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_detail_state_bytes.restype = ctypes.c_size_t

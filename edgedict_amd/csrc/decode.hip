@@ -292,7 +292,34 @@ struct BeamPtrs {
     int32_t* nd_frame;   // [B][NODES]
     double* nd_logp;     // [B][NODES]
     const long long* frames_done;   // [B] frames of the stream since its reset, before this advance; null: 0 (offline)
+    // contextual biasing (all null without a bias list): one phrase-automaton state per hypothesis, under the same state
+    // references as (h, c) - the state BEFORE the hypothesis' last token - and the automaton's tables (edgedict_beam_bias_t)
+    int32_t* bias_bp[2]; // [B][W] double-buffered per frame
+    int32_t* bias_f;     // [B][EM] states made in this frame: goto(carried state, last token) of the e-th popped hypothesis
+    const int32_t* bias_root_next;  // [V]
+    const double* bias_held;        // [S]
+    const double* bias_pend;        // [S]
+    const int32_t* bias_row_ptr;    // [S + 1]
+    const int32_t* bias_exc_tok;    // [n_exc] sorted inside a row
+    const int32_t* bias_exc_next;   // [n_exc]
+    int bias_S;                     // states of the automaton: every state read from a table or a pool is clamped to it
 };
+
+// a state as the tables may be indexed with it (a stale or foreign state must not read out of range)
+__device__ __forceinline__ int bias_state(const BeamPtrs& p, int s) { return min(max(s, 0), p.bias_S - 1); }
+
+// goto(s, k) of the phrase automaton: the exception row of s (binary search), else the root's transition
+__device__ __forceinline__ int bias_goto(const BeamPtrs& p, int s, int k) {
+    s = bias_state(p, s);
+    int lo = p.bias_row_ptr[s], hi = p.bias_row_ptr[s + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int t = p.bias_exc_tok[mid];
+        if (t == k) return bias_state(p, p.bias_exc_next[mid]);
+        if (t < k) lo = mid + 1; else hi = mid;
+    }
+    return bias_state(p, p.bias_root_next[k]);
+}
 
 // (max, first position) of a workgroup's per-thread candidates: butterfly inside a wave, the four waves through LDS.
 // Ties go to the lower position, -inf candidates carry INT_MAX.  Every thread gets the result.
@@ -364,8 +391,10 @@ __global__ __launch_bounds__(64) void beam_frame_begin(BeamPtrs p, int t, int W,
 // y* = max(A) (first on ties), removed from A; its last token -> pred, its state -> h/c_state
 // DETAIL: a node created here also records its frame (t, counted from the stream's reset) and its token's increment
 //   score(child in the pool) - score(popped parent) = pool[idx] - exp_logp[ep]      (fp64)
-// which with an LM is the fused increment lp_rnnt + (lm_weight lp_lm + length_bonus).
-template <bool DETAIL>
+// which with an LM is the fused increment lp_rnnt + (lm_weight lp_lm + length_bonus), and with a bias list includes D.
+// BIAS: y*'s automaton state s = goto(carried state, last token) goes under the expansion's slot (bias_f), where
+// beam_expand reads it and a child's pop finds it as its carried state.
+template <bool DETAIL, bool BIAS>
 __device__ __forceinline__ void beam_pop_body(BeamPtrs& p, int cur, int W, int V, int EM, int L, int H, int B, int NODES,
                                               int bos, int32_t* __restrict__ pred, float* __restrict__ h_state,
                                               float* __restrict__ c_state, int t) {
@@ -434,6 +463,10 @@ __device__ __forceinline__ void beam_pop_body(BeamPtrs& p, int cur, int W, int V
         // the LM's root token: lm_bos until the stream has committed a token, then the last committed one (root_tok)
         if (p.lm_pred)
             p.lm_pred[b] = node >= 0 ? tok : (p.n_committed && p.n_committed[b] > 0 ? p.root_tok[b] : p.lm_bos);
+        if constexpr (BIAS) {
+            const int s0 = ref < W ? p.bias_bp[cur][b * W + ref] : p.bias_f[b * EM + (ref - W)];
+            p.bias_f[b * EM + e] = tok >= 0 && tok < V ? bias_goto(p, s0, tok) : 0;
+        }
         s_ref = ref;
     }
     __syncthreads();
@@ -463,14 +496,28 @@ __global__ __launch_bounds__(256) void beam_pop(BeamPtrs p, int cur, int W, int 
                                                 int H, int B, int NODES, int bos,
                                                 int32_t* __restrict__ pred, float* __restrict__ h_state,
                                                 float* __restrict__ c_state) {
-    beam_pop_body<false>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, 0);
+    beam_pop_body<false, false>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, 0);
 }
 
 // beam_pop that keeps the detail per node; t = the frame of this advance
 __global__ __launch_bounds__(256) void beam_pop_detail(BeamPtrs p, int cur, int W, int V, int EM, int L, int H, int B,
                                                        int NODES, int bos, int32_t* __restrict__ pred,
                                                        float* __restrict__ h_state, float* __restrict__ c_state, int t) {
-    beam_pop_body<true>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, t);
+    beam_pop_body<true, false>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, t);
+}
+
+// the two pops with a bias list
+__global__ __launch_bounds__(256) void beam_pop_bias(BeamPtrs p, int cur, int W, int V, int EM, int L, int H, int B,
+                                                     int NODES, int bos, int32_t* __restrict__ pred,
+                                                     float* __restrict__ h_state, float* __restrict__ c_state) {
+    beam_pop_body<false, true>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, 0);
+}
+
+__global__ __launch_bounds__(256) void beam_pop_detail_bias(BeamPtrs p, int cur, int W, int V, int EM, int L, int H,
+                                                            int B, int NODES, int bos, int32_t* __restrict__ pred,
+                                                            float* __restrict__ h_state, float* __restrict__ c_state,
+                                                            int t) {
+    beam_pop_body<true, true>(p, cur, W, V, EM, L, H, B, NODES, bos, pred, h_state, c_state, t);
 }
 
 // log-softmax of the joint's logits; children into the pool, the blank child into B, the new
@@ -478,7 +525,11 @@ __global__ __launch_bounds__(256) void beam_pop_detail(BeamPtrs p, int cur, int 
 // LM: the LM's logits get the same log-softmax, and a non-blank child k scores
 //   base + (double)lp_rnnt[k] + (lm_w * (double)lp_lm[k] + lm_b)      (fp64, this order, no contraction)
 // the blank child keeps base + lp_rnnt[blank]; the LM's new state goes into its frame pool under the same slot.
-template <bool LM>
+// BIAS: with s = bias_f[slot] (written by the pop) a non-blank child k scores
+//   (that score) + (held[goto(s, k)] - pend[s])                       (fp64, this order, no contraction)
+// The segment is filled with the root's transition goto(0, k) for every k, then - after a barrier - the few tokens of
+// s's exception row are rewritten with their own target, and only then is the segment's (max, first position) taken.
+template <bool LM, bool BIAS>
 __device__ __forceinline__ void beam_expand_body(BeamPtrs& p, const float* __restrict__ logits,
                                                  const float* __restrict__ h_new, const float* __restrict__ c_new,
                                                  const float* __restrict__ lm_logits,
@@ -516,16 +567,36 @@ __device__ __forceinline__ void beam_expand_body(BeamPtrs& p, const float* __res
     double* seg = pool + lo;
     double best = -INFINITY;
     int arg = 0x7fffffff;
-    for (int v = tid; v < V; v += 256) {
-        double c;
+    // child v's score before the bias term
+    auto child = [&](int v) -> double {
         if constexpr (LM)
-            c = v == blank ? -INFINITY
-                           : base + (double)((z[v] - m) - logs) +
-                                 __dadd_rn(__dmul_rn(lm_w, (double)((zl[v] - ml) - logsl)), lm_b);
+            return base + (double)((z[v] - m) - logs) + __dadd_rn(__dmul_rn(lm_w, (double)((zl[v] - ml) - logsl)), lm_b);
         else
-            c = v == blank ? -INFINITY : base + (double)((z[v] - m) - logs);
-        seg[v] = c;
-        if (c > best) { best = c; arg = lo + v; }
+            return base + (double)((z[v] - m) - logs);
+    };
+    if constexpr (BIAS) {
+        const int st = bias_state(p, p.bias_f[b * EM + e]);
+        const double pend_s = p.bias_pend[st];
+        for (int v = tid; v < V; v += 256)
+            seg[v] = v == blank ? -INFINITY : __dadd_rn(child(v), __dsub_rn(p.bias_held[bias_state(p, p.bias_root_next[v])], pend_s));
+        __syncthreads();
+        const int r0 = p.bias_row_ptr[st], r1 = p.bias_row_ptr[st + 1];
+        for (int i = r0 + tid; i < r1; i += 256) {
+            const int v = p.bias_exc_tok[i];
+            if (v != blank && v >= 0 && v < V)
+                seg[v] = __dadd_rn(child(v), __dsub_rn(p.bias_held[bias_state(p, p.bias_exc_next[i])], pend_s));
+        }
+        __syncthreads();
+        for (int v = tid; v < V; v += 256) {
+            const double c = seg[v];
+            if (c > best) { best = c; arg = lo + v; }
+        }
+    } else {
+        for (int v = tid; v < V; v += 256) {
+            const double c = v == blank ? -INFINITY : child(v);
+            seg[v] = c;
+            if (c > best) { best = c; arg = lo + v; }
+        }
     }
     const size_t LH = (size_t)L * H;
     float* dh = p.f_h + ((size_t)b * EM + e) * LH;
@@ -584,7 +655,8 @@ __global__ __launch_bounds__(256) void beam_expand(BeamPtrs p, const float* __re
                                                    const float* __restrict__ h_new,
                                                    const float* __restrict__ c_new, int W, int V,
                                                    int EM, int L, int H, int B, int blank) {
-    beam_expand_body<false>(p, logits, h_new, c_new, nullptr, nullptr, nullptr, 0.0, 0.0, W, V, EM, L, H, B, blank);
+    beam_expand_body<false, false>(p, logits, h_new, c_new, nullptr, nullptr, nullptr, 0.0, 0.0, W, V, EM, L, H, B,
+                                   blank);
 }
 
 // beam_expand with LM shallow fusion (one workgroup per utterance; both rows are V <= a few thousand floats, so this is
@@ -595,8 +667,27 @@ __global__ __launch_bounds__(256) void beam_expand_lm(BeamPtrs p, const float* _
                                                       const float* __restrict__ lm_h_new,
                                                       const float* __restrict__ lm_c_new, double lm_w, double lm_b,
                                                       int W, int V, int EM, int L, int H, int B, int blank) {
-    beam_expand_body<true>(p, logits, h_new, c_new, lm_logits, lm_h_new, lm_c_new, lm_w, lm_b, W, V, EM, L, H, B,
-                           blank);
+    beam_expand_body<true, false>(p, logits, h_new, c_new, lm_logits, lm_h_new, lm_c_new, lm_w, lm_b, W, V, EM, L, H, B,
+                                  blank);
+}
+
+// the two expansions with a bias list
+__global__ __launch_bounds__(256) void beam_expand_bias(BeamPtrs p, const float* __restrict__ logits,
+                                                        const float* __restrict__ h_new,
+                                                        const float* __restrict__ c_new, int W, int V, int EM, int L,
+                                                        int H, int B, int blank) {
+    beam_expand_body<false, true>(p, logits, h_new, c_new, nullptr, nullptr, nullptr, 0.0, 0.0, W, V, EM, L, H, B, blank);
+}
+
+__global__ __launch_bounds__(256) void beam_expand_lm_bias(BeamPtrs p, const float* __restrict__ logits,
+                                                           const float* __restrict__ h_new,
+                                                           const float* __restrict__ c_new,
+                                                           const float* __restrict__ lm_logits,
+                                                           const float* __restrict__ lm_h_new,
+                                                           const float* __restrict__ lm_c_new, double lm_w, double lm_b,
+                                                           int W, int V, int EM, int L, int H, int B, int blank) {
+    beam_expand_body<true, true>(p, logits, h_new, c_new, lm_logits, lm_h_new, lm_c_new, lm_w, lm_b, W, V, EM, L, H, B,
+                                 blank);
 }
 
 // B = B[:W] becomes the next frame's survivors (states gathered into the other buffer)
@@ -628,6 +719,11 @@ __global__ __launch_bounds__(256) void beam_frame_end(BeamPtrs p, int t, int cur
         p.bp_logp[b * W + tid] = p.bn_logp[b * W + tid];
         p.bp_node[b * W + tid] = p.bn_node[b * W + tid];
     }
+    if (p.bias_f)
+        for (int j = tid; j < n; j += 256) {
+            const int ref = p.bn_ref[b * W + j];
+            p.bias_bp[cur ^ 1][b * W + j] = ref < W ? p.bias_bp[cur][b * W + ref] : p.bias_f[b * EM + (ref - W)];
+        }
     if (tid == 0) p.n_bp[b] = n;
 }
 
@@ -639,6 +735,7 @@ __global__ void beam_init(BeamPtrs p, int B, int W) {
     p.bp_node[b * W] = -1;
     p.n_nodes[b] = 0;
     p.open[b] = 0;
+    if (p.bias_bp[0]) p.bias_bp[0][b * W] = 0;      // the empty hypothesis is at the automaton's root
     if (b == 0) { p.flags[0] = p.flags[1] = 0; *p.total_exp = 0; }
 }
 
@@ -780,12 +877,14 @@ inline BeamWs beam_layout(const SearchNet& n, size_t nodes, int prefix, bool str
 }
 
 // persistent state, per stream; with an LM the survivors' LM (h, c) [S][W][lm_L][lm_H] are appended behind the plain
-// state (so that edgedict_beam_stream_read serves both forms)
+// state (so that edgedict_beam_stream_read serves both forms), and with a bias list the survivors' automaton states
+// [S][W] behind those
 struct BeamStreamState {
     SurvivorOffs sv;
-    size_t root_tok, n_committed, n_exp, lm_bp_h, lm_bp_c, total;
+    size_t root_tok, n_committed, n_exp, lm_bp_h, lm_bp_c, bias_bp, total;
 };
-inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int NC, const edgedict_beam_lm_t* lm) {
+inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int NC, const edgedict_beam_lm_t* lm,
+                                                const edgedict_beam_bias_t* bias = nullptr) {
     BeamStreamState w{};
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
@@ -804,6 +903,7 @@ inline BeamStreamState beam_stream_state_layout(int S, int L, int H, int W, int 
         w.lm_bp_h = take((size_t)S * W * lm->L * lm->H * 4);
         w.lm_bp_c = take((size_t)S * W * lm->L * lm->H * 4);
     }
+    if (bias) w.bias_bp = take((size_t)S * W * 4);
     w.total = o;
     return w;
 }
@@ -845,6 +945,30 @@ inline LmWs lm_ws_layout(size_t base, const SearchNet& n, const edgedict_beam_lm
     return w;
 }
 
+// Contextual biasing: the automaton-state pools, appended behind a search's workspace and the LM's part of it (offsets
+// from `base`, a multiple of 256).  with_bp0 as in lm_ws_layout.
+struct BiasWs {
+    size_t bp0, bp1, f, total;
+};
+inline BiasWs bias_ws_layout(size_t base, const SearchNet& n, bool with_bp0) {
+    BiasWs w{};
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    const size_t B = n.B, W = n.W, EM = n.EM;
+    if (with_bp0) w.bp0 = take(B * W * 4);
+    w.bp1 = take(B * W * 4);
+    w.f = take(B * EM * 4);
+    w.total = o;
+    return w;
+}
+// workspace bytes behind the plain layout's `base`: the LM's part, then the bias list's
+inline size_t ws_total(size_t base, const SearchNet& n, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                       bool with_bp0) {
+    if (lm) base = lm_ws_layout(base, n, *lm, with_bp0).total;
+    if (bias) base = bias_ws_layout(base, n, with_bp0).total;
+    return base;
+}
+
 // Everything one beam-search call points at: the kernels' bundle, the host-side step buffers, and the LM's
 struct BeamBufs {
     BeamPtrs q;
@@ -852,15 +976,32 @@ struct BeamBufs {
     float *h_state, *c_state;        // [L][B][H] state of the popped hypotheses
     void* node_pred;                 // prefix = 1: the prediction stored per token-tree node (else null)
     const edgedict_beam_lm_t* lm;    // null: no LM
+    bool bias;                       // a bias list: the *_bias kernels run
     LstmNet lm_net;
     StepBufs lmu;                    // the LM step's buffers (its symbol and state are q.lm_pred, q.lm_h/c_state)
 };
 // p / w: workspace and its layout (null: only the state is bound - reset);  st / a: the streams' persistent state (null:
-// offline, the survivors live in the workspace);  lm / lw: the LM and its part of the workspace
+// offline, the survivors live in the workspace);  lm / lw: the LM and its part of the workspace;  bias / bw: the bias
+// list and its part
 BeamBufs bind_beam_ptrs(char* p, const BeamWs* w, char* st, const BeamStreamState* a, const edgedict_beam_lm_t* lm,
-                        const LmWs* lw) {
+                        const LmWs* lw, const edgedict_beam_bias_t* bias = nullptr, const BiasWs* bw = nullptr) {
     BeamBufs bb{};
     BeamPtrs& q = bb.q;
+    bb.bias = bias != nullptr;
+    if (bias) {
+        q.bias_S = bias->S;
+        q.bias_root_next = bias->root_next;
+        q.bias_held = bias->held;
+        q.bias_pend = bias->pend;
+        q.bias_row_ptr = bias->row_ptr;
+        q.bias_exc_tok = bias->exc_tok;
+        q.bias_exc_next = bias->exc_next;
+        q.bias_bp[0] = st ? at<int32_t>(st, a->bias_bp) : at<int32_t>(p, bw->bp0);
+        if (p) {
+            q.bias_bp[1] = at<int32_t>(p, bw->bp1);
+            q.bias_f = at<int32_t>(p, bw->f);
+        }
+    }
     if (p) {
         bb.u = bind(p, w->step);
         bb.h_state = at<float>(p, w->h_state);
@@ -938,6 +1079,20 @@ int lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what) 
     ED_CHECK_ARG(lm->bos >= 0 && lm->bos < V, "%s: LM bos = %d outside the vocabulary", what, lm->bos);
     ED_CHECK_ARG(lm->emb_dtype == ED_F32 || lm->emb_dtype == ED_BF16, "%s: bad LM embedding dtype", what);
     ED_CHECK_ARG(isfinite(lm->weight) && isfinite(lm->length_bonus), "%s: LM weight / length bonus not finite", what);
+    return ED_OK;
+}
+
+// a bias list that the search can use: status code and message, or ED_OK (the device tables themselves are trusted)
+int bias_check(const edgedict_beam_bias_t* bias, int V, int prefix, const char* what) {
+    if (!bias) return ED_OK;
+    ED_CHECK_ARG(!prefix, "%s: prefix = 1 with a bias list is not supported (the prefix merge joins hypotheses in "
+                          "different automaton states)", what);
+    ED_CHECK_ARG(bias->V == V, "%s: the bias list's vocabulary = %d differs from the transducer's V = %d", what, bias->V,
+                 V);
+    ED_CHECK_ARG(bias->S > 0 && bias->n_exc >= 0, "%s: bad bias automaton (S %d, exceptions %d)", what, bias->S,
+                 bias->n_exc);
+    ED_CHECK_ARG(bias->root_next && bias->held && bias->pend && bias->row_ptr && bias->exc_tok && bias->exc_next,
+                 "%s: null bias table pointer", what);
     return ED_OK;
 }
 
@@ -1096,6 +1251,7 @@ int lm_step(int dtype, int B, const BeamBufs& bb, hipStream_t s) {
 // expansion's prediction is kept per node.
 // bb.lm != null: every iteration also runs the LM step, and beam_expand_lm replaces beam_expand (no prefix_merge then).
 // bb.q.nd_frame != null: beam_pop_detail replaces beam_pop.
+// bb.bias: the *_bias instances of those four kernels run instead (no prefix_merge then).
 int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, PrefixMerge* prefix_merge, hipStream_t s) {
     const BeamPtrs& q = bb.q;
     const StepBufs& u = bb.u;
@@ -1113,7 +1269,13 @@ int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, Prefix
         hipLaunchKernelGGL(beam_frame_begin, dim3(B), dim3(64), 0, s, q, t, W, net.EM, net.V);
         for (int it = 0;; ++it) {
             int rc;
-            if (q.nd_frame)
+            if (bb.bias && q.nd_frame)
+                hipLaunchKernelGGL(beam_pop_detail_bias, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B,
+                                   net.NODES, net.bos, u.pred, bb.h_state, bb.c_state, t);
+            else if (bb.bias)
+                hipLaunchKernelGGL(beam_pop_bias, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B,
+                                   net.NODES, net.bos, u.pred, bb.h_state, bb.c_state);
+            else if (q.nd_frame)
                 hipLaunchKernelGGL(beam_pop_detail, dim3(B), dim3(256), 0, s, q, cur, W, net.V, net.EM, pn.L, pn.H, B,
                                    net.NODES, net.bos, u.pred, bb.h_state, bb.c_state, t);
             else
@@ -1128,7 +1290,14 @@ int beam_frame_loop(const SearchNet& net, const BeamBufs& bb, int maxlen, Prefix
             if (rc) return rc;
             if (prefix_merge) store_pred(net, bb, s);
             if (!fused_step && (rc = composed_joint(net, e1t, u.dec_new, u, s))) return rc;
-            if (bb.lm)
+            if (bb.bias && bb.lm)
+                hipLaunchKernelGGL(beam_expand_lm_bias, dim3(B), dim3(256), 0, s, q, u.logits, u.h_new, u.c_new,
+                                   bb.lmu.logits, bb.lmu.h_new, bb.lmu.c_new, bb.lm->weight, bb.lm->length_bonus, W, net.V,
+                                   net.EM, pn.L, pn.H, B, net.blank);
+            else if (bb.bias)
+                hipLaunchKernelGGL(beam_expand_bias, dim3(B), dim3(256), 0, s, q, u.logits, u.h_new, u.c_new, W, net.V,
+                                   net.EM, pn.L, pn.H, B, net.blank);
+            else if (bb.lm)
                 hipLaunchKernelGGL(beam_expand_lm, dim3(B), dim3(256), 0, s, q, u.logits, u.h_new, u.c_new, bb.lmu.logits,
                                    bb.lmu.h_new, bb.lmu.c_new, bb.lm->weight, bb.lm->length_bonus, W, net.V, net.EM, pn.L,
                                    pn.H, B, net.blank);
@@ -1276,15 +1445,22 @@ struct NBestOut {
 }  // namespace
 
 extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
+extern "C" size_t edgedict_beam_bias_struct_bytes(void) { return sizeof(edgedict_beam_bias_t); }
 
-extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
+extern "C" size_t edgedict_beam_workspace_bytes_bias(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
+                                                     int W, int max_expansions, int prefix,
+                                                     const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias) {
     if (B <= 0 || W <= 0 || max_expansions <= 0) return 0;
     SearchNet n = net_dims(dtype, B, J, V, E, L, H, P2);
     n.W = W;
     n.EM = max_expansions;
     const size_t base = beam_layout(n, (size_t)(T < 0 ? 0 : T) * n.EM + 1, prefix, false).total;
-    return lm ? lm_ws_layout(base, n, *lm, true).total : base;
+    return ws_total(base, n, lm, bias, true);
+}
+
+extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
+                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
+    return edgedict_beam_workspace_bytes_bias(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, lm, nullptr);
 }
 
 extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
@@ -1302,8 +1478,8 @@ int beam_search_run(
     const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
     const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
     int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, const NBestOut* nb,
-    void* stream_) {
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+    void* workspace, const NBestOut* nb, void* stream_) {
     const int EM = max_expansions;
     ED_CHECK_ARG(!nb || !prefix,
                  "beam_search_nbest: prefix = 1 is not supported (the prefix merge changes a hypothesis' score at frame "
@@ -1323,12 +1499,15 @@ int beam_search_run(
     for (int b = 0; b < B; ++b)
         ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "beam_search: lens[%d] = %d outside [0, %d]", b, lens_host[b], T);
     if (int rc = lm_check(lm, V, prefix, "beam_search")) return rc;
+    if (int rc = bias_check(bias, V, prefix, "beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     char* p = (char*)workspace;
     const BeamWs w = beam_layout(net, (size_t)T * EM + 1, prefix, false);
     LmWs lw{};
     if (lm) lw = lm_ws_layout(w.total, net, *lm, true);
-    BeamBufs bufs = bind_beam_ptrs(p, &w, nullptr, nullptr, lm, &lw);
+    BiasWs bw{};
+    if (bias) bw = bias_ws_layout(ws_total(w.total, net, lm, nullptr, true), net, true);
+    BeamBufs bufs = bind_beam_ptrs(p, &w, nullptr, nullptr, lm, &lw, bias, &bw);
     if (nb) {
         const DetailOffs d = beam_detail_layout(B, (size_t)T * EM + 1);
         bufs.q.nd_frame = at<int32_t>((char*)nb->detail, d.nd_frame);
@@ -1405,8 +1584,23 @@ extern "C" int edgedict_beam_search_lm(
     double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
     return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
                            emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
-                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, workspace, nullptr,
-                           stream_);
+                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, nullptr, workspace,
+                           nullptr, stream_);
+}
+
+extern "C" int edgedict_beam_search_bias(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
+    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+    void* workspace, void* stream_) {
+    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
+                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
+                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, bias, workspace,
+                           nullptr, stream_);
 }
 
 extern "C" size_t edgedict_beam_detail_bytes(int B, int T, int max_expansions) {
@@ -1428,10 +1622,27 @@ extern "C" int edgedict_beam_search_nbest(
     int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
     int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host, long long* expansions_host,
     const edgedict_beam_lm_t* lm, void* workspace, void* detail, void* result, void* stream_) {
+    return edgedict_beam_search_nbest_bias(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
+                                           W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
+                                           W, max_expansions, prefix, tokens_host, frames_host, token_logp_host,
+                                           max_tokens, ntokens_host, nhyp_host, logp_host, expansions_host, lm, nullptr,
+                                           workspace, detail, result, stream_);
+}
+
+extern "C" int edgedict_beam_search_nbest_bias(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
+    int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host, long long* expansions_host,
+    const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* workspace, void* detail, void* result,
+    void* stream_) {
     const NBestOut nb{detail, result, {tokens_host, frames_host, token_logp_host, ntokens_host, nhyp_host, logp_host}};
     return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
                            emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
-                           nullptr, max_tokens, nullptr, nullptr, expansions_host, lm, workspace, &nb, stream_);
+                           nullptr, max_tokens, nullptr, nullptr, expansions_host, lm, bias, workspace, &nb, stream_);
 }
 
 extern "C" int edgedict_beam_search(
@@ -1475,6 +1686,8 @@ __global__ __launch_bounds__(256) void beam_stream_reset_kernel(BeamPtrs p, long
         float* lc = p.lm_bp_c[0] + (size_t)b * nl;
         for (size_t i = tid; i < nl; i += 256) { lh[i] = 0.f; lc[i] = 0.f; }
     }
+    if (p.bias_bp[0])             // the automaton's root (state 0 of any bias list)
+        for (int i = tid; i < W; i += 256) p.bias_bp[0][(size_t)b * W + i] = 0;
     if (tid == 0) {
         p.n_bp[b] = 1;
         p.bp_logp[(size_t)b * W] = 0.0;
@@ -1503,6 +1716,8 @@ __global__ __launch_bounds__(256) void beam_stream_settle(BeamPtrs p, int W, int
             p.lm_bp_c[0][ol + i] = p.lm_bp_c[1][ol + i];
         }
     }
+    if (p.bias_f)
+        for (int i = tid; i < p.n_bp[b]; i += 256) p.bias_bp[0][(size_t)b * W + i] = p.bias_bp[1][(size_t)b * W + i];
 }
 
 constexpr int BEAM_COMPACT_LDS_NODES = 4096;    // trees up to this capacity walk their parent links in LDS (32 KiB)
@@ -1686,12 +1901,20 @@ struct StreamDetailArgs {
 
 }  // namespace
 
+extern "C" size_t edgedict_beam_stream_state_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                        int W, int max_expansions, int node_capacity,
+                                                        const edgedict_beam_lm_t* lm,
+                                                        const edgedict_beam_bias_t* bias) {
+    (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
+    if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
+    return beam_stream_state_layout(S, L, H, W, node_capacity, lm, bias).total;
+}
+
 extern "C" size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
                                                       int W, int max_expansions, int node_capacity,
                                                       const edgedict_beam_lm_t* lm) {
-    (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
-    if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
-    return beam_stream_state_layout(S, L, H, W, node_capacity, lm).total;
+    return edgedict_beam_stream_state_bytes_bias(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, lm,
+                                                 nullptr);
 }
 
 extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
@@ -1699,15 +1922,23 @@ extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int 
     return edgedict_beam_stream_state_bytes_lm(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, nullptr);
 }
 
-extern "C" size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                          int W, int max_expansions, int node_capacity,
-                                                          const edgedict_beam_lm_t* lm) {
+extern "C" size_t edgedict_beam_stream_workspace_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
+                                                            int P2, int W, int max_expansions, int node_capacity,
+                                                            const edgedict_beam_lm_t* lm,
+                                                            const edgedict_beam_bias_t* bias) {
     if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
     SearchNet n = net_dims(dtype, S, J, V, E, L, H, P2);
     n.W = W;
     n.EM = max_expansions;
     const size_t base = beam_layout(n, (size_t)node_capacity, 0, true).total;
-    return lm ? lm_ws_layout(base, n, *lm, false).total : base;
+    return ws_total(base, n, lm, bias, false);
+}
+
+extern "C" size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                          int W, int max_expansions, int node_capacity,
+                                                          const edgedict_beam_lm_t* lm) {
+    return edgedict_beam_stream_workspace_bytes_bias(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, lm,
+                                                     nullptr);
 }
 
 extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
@@ -1716,16 +1947,17 @@ extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, 
                                                    nullptr);
 }
 
-extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                             int mask_on_host, const edgedict_beam_lm_t* lm, void* state,
-                                             void* stream_) {
+namespace {
+// bias: only its presence matters here (the state then holds the survivors' automaton states; the root is state 0)
+int beam_stream_reset_run(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask, int mask_on_host,
+                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* stream_) {
     ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0, "beam_stream_reset: bad shape");
     ED_CHECK_ARG(state, "beam_stream_reset: null state");
     ED_CHECK_ARG(!lm || (lm->L > 0 && lm->H > 0), "beam_stream_reset: bad LM shape");
     hipStream_t s = (hipStream_t)stream_;
-    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity, lm);
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, node_capacity, lm, bias);
     char* st = (char*)state;
-    const BeamPtrs q = bind_beam_ptrs(nullptr, nullptr, st, &a, lm, nullptr).q;
+    const BeamPtrs q = bind_beam_ptrs(nullptr, nullptr, st, &a, lm, nullptr, bias, nullptr).q;
     long long* n_committed = at<long long>(st, a.n_committed);
     if (!mask || !mask_on_host) {
         hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, n_committed, mask, 0, W, L, H, bos);
@@ -1742,6 +1974,13 @@ extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int nod
     ED_CHECK_LAUNCH("beam_stream_reset");
     return ED_OK;
 }
+}  // namespace
+
+extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                             int mask_on_host, const edgedict_beam_lm_t* lm, void* state,
+                                             void* stream_) {
+    return beam_stream_reset_run(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, nullptr, state, stream_);
+}
 
 extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
                                           int mask_on_host, void* state, void* stream_) {
@@ -1756,8 +1995,8 @@ int beam_stream_advance_run(
     const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
     int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, const StreamDetailArgs* dt,
-    void* stream_) {
+    long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state,
+    void* workspace, const StreamDetailArgs* dt, void* stream_) {
     const int EM = max_expansions, NC = node_capacity;
     ED_CHECK_ARG(!dt || (dt->dstate && dt->dws && dt->commit_frame_host && dt->commit_logp_host),
                  "beam_stream_advance_detail: null pointer");
@@ -1767,6 +2006,7 @@ int beam_stream_advance_run(
                            n_frames_host && commit_host && ncommit_host && state && workspace, true))
         return rc;
     if (int rc = lm_check(lm, V, 0, "beam_stream_advance")) return rc;
+    if (int rc = bias_check(bias, V, 0, "beam_stream_advance")) return rc;
     int maxlen = 0;
     for (int b = 0; b < S; ++b) {
         ED_CHECK_ARG(n_frames_host[b] >= 0, "beam_stream_advance: n_frames[%d] = %d < 0", b, n_frames_host[b]);
@@ -1774,13 +2014,15 @@ int beam_stream_advance_run(
     }
     ED_CHECK_ARG(maxlen == 0 || E1, "beam_stream_advance: null E1");
     hipStream_t s = (hipStream_t)stream_;
-    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC, lm);
+    const BeamStreamState a = beam_stream_state_layout(S, L, H, W, NC, lm, bias);
     const BeamWs w = beam_layout(net, (size_t)NC, 0, true);
     char* st = (char*)state;
     char* p = (char*)workspace;
     LmWs lw{};
     if (lm) lw = lm_ws_layout(w.total, net, *lm, false);
-    BeamBufs bufs = bind_beam_ptrs(p, &w, st, &a, lm, &lw);
+    BiasWs bw{};
+    if (bias) bw = bias_ws_layout(ws_total(w.total, net, lm, nullptr, false), net, false);
+    BeamBufs bufs = bind_beam_ptrs(p, &w, st, &a, lm, &lw, bias, &bw);
     if (dt) bind_stream_detail(bufs.q, (char*)dt->dstate, S, NC);
     const BeamPtrs& q = bufs.q;
     for (int b = 0; b < S; ++b) ncommit_host[b] = 0;
@@ -1870,8 +2112,22 @@ extern "C" int edgedict_beam_stream_advance_lm(
     long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
     return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
                                    V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, state,
-                                   workspace, nullptr, stream_);
+                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, nullptr,
+                                   state, workspace, nullptr, stream_);
+}
+
+extern "C" int edgedict_beam_stream_advance_bias(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+    long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state,
+    void* workspace, void* stream_) {
+    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
+                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
+                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, bias,
+                                   state, workspace, nullptr, stream_);
 }
 
 extern "C" size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capacity) {
@@ -1888,8 +2144,17 @@ extern "C" int edgedict_beam_stream_reset_detail(int S, int L, int H, int W, int
                                                  const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
                                                  void* state, void* detail_state, void* stream_) {
     ED_CHECK_ARG(detail_state, "beam_stream_reset_detail: null detail state");
-    if (int rc = edgedict_beam_stream_reset_lm(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, state, stream_))
+    return edgedict_beam_stream_reset_bias(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, nullptr, state,
+                                           detail_state, stream_);
+}
+
+extern "C" int edgedict_beam_stream_reset_bias(int S, int L, int H, int W, int node_capacity, int bos,
+                                               const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
+                                               const edgedict_beam_bias_t* bias, void* state, void* detail_state,
+                                               void* stream_) {
+    if (int rc = beam_stream_reset_run(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, bias, state, stream_))
         return rc;
+    if (!detail_state) return ED_OK;
     hipStream_t s = (hipStream_t)stream_;
     long long* fd = at<long long>((char*)detail_state, stream_detail_state_layout(S, node_capacity).frames_done);
     if (!mask || !mask_on_host) {
@@ -1916,11 +2181,28 @@ extern "C" int edgedict_beam_stream_advance_detail(
     int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* commit_frame_host,
     double* commit_logp_host, int32_t* ncommit_host, long long* expansions_host, const edgedict_beam_lm_t* lm,
     void* state, void* workspace, void* detail_state, void* detail_workspace, void* stream_) {
+    return edgedict_beam_stream_advance_detail_bias(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1,
+                                                    b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp,
+                                                    bp, blank, bos, W, max_expansions, node_capacity, commit_host,
+                                                    commit_frame_host, commit_logp_host, ncommit_host, expansions_host,
+                                                    lm, nullptr, state, workspace, detail_state, detail_workspace,
+                                                    stream_);
+}
+
+extern "C" int edgedict_beam_stream_advance_detail_bias(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
+    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* commit_frame_host,
+    double* commit_logp_host, int32_t* ncommit_host, long long* expansions_host, const edgedict_beam_lm_t* lm,
+    const edgedict_beam_bias_t* bias, void* state, void* workspace, void* detail_state, void* detail_workspace,
+    void* stream_) {
     const StreamDetailArgs dt{detail_state, detail_workspace, commit_frame_host, commit_logp_host};
     return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
                                    V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, state,
-                                   workspace, &dt, stream_);
+                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, bias,
+                                   state, workspace, &dt, stream_);
 }
 
 extern "C" int edgedict_beam_stream_advance(

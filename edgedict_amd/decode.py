@@ -25,6 +25,18 @@ pops per frame; hitting ``max_expansions`` stays an error.
 ``beam_search_nbest`` (``_enc``, ``_rows``; ``StreamingBeamSearch(..., detail=True).nbest()``) runs the same search and
 returns the WHOLE list B of the last frame as ``NBestResult`` objects: every hypothesis with the encoder frame on which
 each of its tokens was emitted and the token's score increment (csrc/decode.hip keeps both per token-tree node).
+
+Every beam search also takes a contextual-biasing list (``bias=``, an ``edgedict_amd.bias.ContextGraph``: phrases to
+prefer, given at run time), alone or together with ``lm=``.  Every hypothesis then carries a state of the phrase
+automaton beside its prediction-network state, and a non-blank child k scores ``(base + lp_rnnt[k]) + D(s, k)``, with an
+LM ``((base + lp_rnnt[k]) + (lm_weight * lp_lm[k] + length_bonus)) + D(s, k)`` (fp64, in this order), where
+``D(s, k) = held[goto(s, k)] - pend[s]`` is the automaton's increment; the blank child is unchanged.  A partial match
+that breaks gives its bonus back, a completed phrase keeps it.  ``NBestResult.token_logp`` and ``logp`` include the
+bias increments.  Not in scope: output links (a phrase that occurs only inside a longer partial match that then breaks
+is not credited), an end-of-utterance retraction of a still-pending bonus, and the greedy search (not biased);
+``prefix=True`` with a bias list raises ``ValueError``, as with an LM.  ``bias=None``, an empty list and a list whose
+boosts are all 0 give tokens, scores and expansion counts bit-equal to the search without one (the first two run the
+plain kernels).  See ``edgedict_amd.bias``.
 """
 import ctypes
 
@@ -98,7 +110,7 @@ def _vocab(model):
 
 
 def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
-                      length_bonus=0.0, lm_bos=1):
+                      length_bonus=0.0, lm_bos=1, bias=None):
     """Graves (2012) beam search as the reference's legacy ``Transducer.beam_search`` runs it
     (models.py:121-202), batched: every utterance keeps its own A / B sets and all open utterances
     advance one expansion per lockstep iteration on the device.  ``prefix=True`` is the reference's
@@ -111,9 +123,14 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     (default 8 W, at least 16); hitting it raises instead of truncating the search.
 
     ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion, see the module docstring (``lm`` needs
-    ``lm_weight``; ``prefix=True`` with an LM and an LM of another vocabulary raise ``ValueError``)."""
+    ``lm_weight``; ``prefix=True`` with an LM and an LM of another vocabulary raise ``ValueError``).
+
+    ``bias``: a contextual-biasing list (``edgedict_amd.bias.ContextGraph``), see the module docstring; the same two
+    cases raise ``ValueError``."""
+    from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), prefix)
+    check_bias_args(bias, _vocab(model), prefix)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -126,7 +143,7 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
     return beam_search_enc(model, enc_out, lens, W, max_expansions, prefix, lm=lm, lm_weight=lm_weight,
-                           length_bonus=length_bonus, lm_bos=lm_bos)
+                           length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
 class _SearchNet:
@@ -166,10 +183,13 @@ class _SearchNet:
                 _ptr_array(self.b_hh), self.H, _lib.ptr(self.wpc), _lib.ptr(self.bp))
 
 
-def _native(name, flm, *args, tail=()):
+def _native(name, flm, *args, tail=(), bref=None):
     """``edgedict_<name>(*args, *tail)``, or with a fusion LM ``edgedict_<name>_lm(*args, lm, *tail)``: the ``_lm`` entry
-    points take the plain ones' arguments with the LM in front of the trailing state / workspace / stream."""
+    points take the plain ones' arguments with the LM in front of the trailing state / workspace / stream.  With a
+    bias list (``bref``, ``ContextGraph.ref``) ``edgedict_<name>_bias(*args, lm or NULL, bias, *tail)``."""
     lib = _lib.load()
+    if bref is not None:
+        return getattr(lib, "edgedict_" + name + "_bias")(*args, flm.ref() if flm is not None else None, bref, *tail)
     if flm is None:
         return getattr(lib, "edgedict_" + name)(*args, *tail)
     return getattr(lib, "edgedict_" + name + "_lm")(*args, flm.ref(), *tail)
@@ -182,23 +202,27 @@ def joint_rows(model, enc_out):
 
 
 def beam_search_enc(model, enc_out, lens=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
-                    length_bonus=0.0, lm_bos=1):
+                    length_bonus=0.0, lm_bos=1, bias=None):
     """``beam_search_batch`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
     encoder frames per utterance; None: all T)."""
+    from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), prefix)
+    check_bias_args(bias, _vocab(model), prefix)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
     return beam_search_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, prefix, lm=lm,
-                            lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos)
+                            lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
 def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, prefix=False, *, lm=None,
-                     lm_weight=None, length_bonus=0.0, lm_bos=1):
+                     lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
     width P."""
+    from .bias import active, check_bias_args
     from .lm import FusionLM, check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), prefix)
+    check_bias_args(bias, _vocab(model), prefix)
     if W < 1:
         raise ValueError("beam width must be >= 1")
     cd = E1.dtype
@@ -206,8 +230,12 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     EM = int(max_expansions) if max_expansions else max(16, 8 * W)
     net = _SearchNet(model, cd)
     flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
+    bref = None
+    if active(bias) is not None:
+        _lib.require_cuda(E1)
+        bref = active(bias).ref(E1.device)
     nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
-                     int(bool(prefix)))
+                     int(bool(prefix)), bref=bref)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=E1.device)
     max_tokens = T * EM + 1
     tokens = np.zeros((B, max_tokens), dtype=np.int32)
@@ -219,7 +247,7 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
             lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM,
             int(bool(prefix)), tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
             score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-    rc = _native("beam_search", flm, *args, tail=(_lib.ptr(ws), _lib.stream_ptr()))
+    rc = _native("beam_search", flm, *args, tail=(_lib.ptr(ws), _lib.stream_ptr()), bref=bref)
     _lib.check(rc, "beam_search")
     beam_search_batch.last_expansions = int(nexp.value)
     seqs = [tokens[b, :ntok[b]].astype(np.int64) for b in range(B)]
@@ -237,9 +265,10 @@ class NBestResult:
                        the utterance; streaming: counted since the stream's reset); ``emission_times`` turns them into
                        seconds
     ``token_logp[i]``  float64 array, same length: the increment each token added to the hypothesis' score (with an LM
-                       the fused increment ``lp_rnnt + (lm_weight lp_lm + length_bonus)``); ``logp[i]`` minus their sum
-                       is what the hypothesis' blanks contributed
-    ``logp``           float64 [n]: log p per hypothesis (fused log p with an LM)
+                       the fused increment ``lp_rnnt + (lm_weight lp_lm + length_bonus)``, with a bias list plus the
+                       automaton's increment ``D``); ``logp[i]`` minus their sum is what the hypothesis' blanks
+                       contributed
+    ``logp``           float64 [n]: log p per hypothesis (fused log p with an LM; plus the total bias with a list)
     """
 
     def __init__(self, tokens, frames, token_logp, logp):
@@ -296,15 +325,18 @@ def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
 
 
 def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                      lm_bos=1):
+                      lm_bos=1, bias=None):
     """``beam_search_batch`` (``prefix=False``) returning, per utterance, an ``NBestResult``: all ``n <= W`` hypotheses
     of the last frame's list B in B's order, each with its tokens, the encoder frame every token was emitted on and the
     score increment every token added, and ``logp`` (log p, not negated).  Entry 0 is exactly what ``beam_search_batch``
     returns (same tokens, ``logp[0] == -score`` bit for bit), and ``beam_search_batch.last_expansions`` is set as there.
     An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.  The prefix-sum variant is not available
-    here: its merge changes a score at frame starts, so the increments would no longer add up."""
+    here: its merge changes a score at frame starts, so the increments would no longer add up.  With ``bias`` (module
+    docstring) ``token_logp`` and ``logp`` include the bias increments."""
+    from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), False)
+    check_bias_args(bias, _vocab(model), False)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -316,29 +348,33 @@ def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=Non
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
     return beam_search_nbest_enc(model, enc_out, lens, W, max_expansions, lm=lm, lm_weight=lm_weight,
-                                 length_bonus=length_bonus, lm_bos=lm_bos)
+                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
 def beam_search_nbest_enc(model, enc_out, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
-                          length_bonus=0.0, lm_bos=1, prefix=False):
+                          length_bonus=0.0, lm_bos=1, prefix=False, bias=None):
     """``beam_search_nbest`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
     encoder frames per utterance; None: all T)."""
+    from .bias import check_bias_args
+    check_bias_args(bias, _vocab(model), prefix)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
     return beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, lm=lm,
-                                  lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, prefix=prefix)
+                                  lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, prefix=prefix, bias=bias)
 
 
 def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
-                           length_bonus=0.0, lm_bos=1, prefix=False, max_tokens=None):
+                           length_bonus=0.0, lm_bos=1, prefix=False, max_tokens=None, bias=None):
     """``beam_search_nbest_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output
     of width P.  ``prefix=True`` raises ``ValueError`` (see ``beam_search_nbest``).  ``max_tokens`` bounds a hypothesis'
     length (default: what the token tree can hold, T x max_expansions + 1); a longer one raises, it is never cut."""
+    from .bias import active, check_bias_args
     from .lm import FusionLM, check_fusion_args
     if prefix:
         raise ValueError("beam_search_nbest: prefix=True is not supported with token detail (the prefix merge changes a "
                          "hypothesis' score at frame starts, so the per-token increments would no longer add up)")
     check_fusion_args(lm, lm_weight, _vocab(model), False)
+    check_bias_args(bias, _vocab(model), False)
     if W < 1:
         raise ValueError("beam width must be >= 1")
     cd = E1.dtype
@@ -347,8 +383,12 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
     net = _SearchNet(model, cd)
     flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
     lib = _lib.load()
+    bref = None
+    if active(bias) is not None:
+        _lib.require_cuda(E1)
+        bref = active(bias).ref(E1.device)
     nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
-                     0)
+                     0, bref=bref)
     MT = T * EM + 1 if max_tokens is None else int(max_tokens)
     dev = E1.device
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -363,11 +403,14 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
     nexp = ctypes.c_longlong(0)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     from .tokenizer import BOS
-    rc = lib.edgedict_beam_search_nbest(
-        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
-        *net.args(P), int(model.blank), int(BOS), int(W), EM, 0, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok),
-        vp(nhyp), vp(logp), ctypes.byref(nexp), flm.ref() if flm is not None else None, _lib.ptr(ws), _lib.ptr(detail),
-        _lib.ptr(result), _lib.stream_ptr())
+    nb_args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
+               *net.args(P), int(model.blank), int(BOS), int(W), EM, 0, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok),
+               vp(nhyp), vp(logp), ctypes.byref(nexp), flm.ref() if flm is not None else None)
+    nb_tail = (_lib.ptr(ws), _lib.ptr(detail), _lib.ptr(result), _lib.stream_ptr())
+    if bref is not None:
+        rc = lib.edgedict_beam_search_nbest_bias(*nb_args, bref, *nb_tail)
+    else:
+        rc = lib.edgedict_beam_search_nbest(*nb_args, *nb_tail)
     _lib.check(rc, "beam_search_nbest")
     beam_search_batch.last_expansions = int(nexp.value)
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
@@ -399,12 +442,19 @@ class StreamingBeamSearch:
     score increment, through compaction and in the committed log: ``nbest()`` then returns the whole list B as
     ``NBestResult`` objects and ``committed_detail()`` the committed log with frames and increments.  Without it both
     raise; ``best()``, ``committed()`` and ``expansions()`` are the same either way.
+
+    ``bias``: a contextual-biasing list (``edgedict_amd.bias.ContextGraph``, module docstring) shared by all streams.
+    The survivors' automaton states are carried in the device state; the automaton reads a stream's root token as the
+    prediction network does, so commits change nothing.  ``set_bias`` swaps the list between utterances.  A search
+    built without a list (or with an empty one) runs the plain kernels until ``set_bias`` gives it one.
     """
 
     def __init__(self, model, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False, *, lm=None,
-                 lm_weight=None, length_bonus=0.0, lm_bos=1, detail=False):
+                 lm_weight=None, length_bonus=0.0, lm_bos=1, detail=False, bias=None):
+        from .bias import active, check_bias_args
         from .lm import check_fusion_args
         check_fusion_args(lm, lm_weight, _vocab(model), prefix)
+        check_bias_args(bias, _vocab(model), prefix)
         if prefix:
             raise ValueError("StreamingBeamSearch: prefix=True (the prefix-sum merge) is not supported when streaming")
         if W < 1:
@@ -421,13 +471,9 @@ class StreamingBeamSearch:
         self.device = model.decoder.embed.weight.device
         self.lm = lm
         self._lm_args = (lm_weight, length_bonus, lm_bos)
-        net = self._weights()
-        flm = self._fusion()
-        dims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.EM, self.NC)
-        sbytes = _native("beam_stream_state_bytes", flm, *dims)
-        wbytes = _native("beam_stream_workspace_bytes", flm, *dims)
-        self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
-        self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+        self.bias = active(bias)
+        self._frames = np.zeros(self.S, dtype=np.int64)      # frames per stream since its reset
+        self._alloc()
         self._commit_buf = np.zeros((self.S, self.NC), dtype=np.int32)
         self._ncommit = np.zeros(self.S, dtype=np.int32)
         self.detail = bool(detail)
@@ -442,6 +488,52 @@ class StreamingBeamSearch:
             self._result = None
         self.last_expansions = 0
         self.reset()
+
+    def _alloc(self):
+        """The persistent state and the workspace, sized for the current forms (LM, bias list)."""
+        net = self._weights()
+        flm = self._fusion()
+        dims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.EM, self.NC)
+        sbytes = _native("beam_stream_state_bytes", flm, *dims, bref=self._bref())
+        wbytes = _native("beam_stream_workspace_bytes", flm, *dims, bref=self._bref())
+        self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+
+    def _bref(self):
+        if self.bias is None:
+            return None
+        _lib.require_cuda(self.model.decoder.embed.weight)
+        return self.bias.ref(self.device)
+
+    def set_bias(self, graph, mask=None):
+        """Swap the bias list (a ``ContextGraph``, or None / an empty one for "no bias").  The list is shared by all
+        streams of the search and the survivors of a stream in mid-utterance hold states of the old automaton, so EVERY
+        stream must be fresh - no frames since its reset - or ``ValueError`` is raised.  ``mask`` (None: all) only
+        names the streams the caller swaps the list for: a stream in it that has frames is reported as such, one
+        outside it as being in the middle of an utterance.  Nothing is launched; the next ``advance`` reads the new
+        tables."""
+        from .bias import active, check_bias_args
+        check_bias_args(graph, _vocab(self.model), False)
+        if mask is None:
+            sel = np.ones(self.S, dtype=bool)
+        else:
+            m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+            sel = m.astype(bool).reshape(self.S)
+        busy = np.nonzero(self._frames > 0)[0]
+        for s in busy:
+            if sel[s]:
+                raise ValueError("set_bias: stream %d has advanced over %d frames since its reset (reset it first)"
+                                 % (s, self._frames[s]))
+        if len(busy):
+            raise ValueError("set_bias: the bias list is shared by all streams and stream %d, outside the mask, is in "
+                             "the middle of an utterance" % busy[0])
+        had = self.bias is not None
+        self.bias = active(graph)
+        if had != (self.bias is not None):
+            # the state gains / loses the survivors' automaton states: every stream is fresh, so a new state, reset
+            # (the committed logs are empty), is the old one
+            self._alloc()
+            self.reset()
 
     def _weights(self):
         # converted once per parameter version by WEIGHTS (as run_search does); only the pointer bundle is rebuilt
@@ -463,7 +555,12 @@ class StreamingBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
         mp = None if mh is None else mh.ctypes.data_as(ctypes.c_void_p)
-        if self.detail:
+        if self.bias is not None:
+            flm = self._fusion()
+            rc = _lib.load().edgedict_beam_stream_reset_bias(
+                self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, flm.ref() if flm is not None else None,
+                self._bref(), _lib.ptr(self._state), _lib.ptr(self._dstate) if self.detail else None, _lib.stream_ptr())
+        elif self.detail:
             flm = self._fusion()
             rc = _lib.load().edgedict_beam_stream_reset_detail(
                 self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, flm.ref() if flm is not None else None,
@@ -476,6 +573,7 @@ class StreamingBeamSearch:
             self._committed = [[] for _ in range(self.S)]
             self._committed_frames = [[] for _ in range(self.S)]
             self._committed_logp = [[] for _ in range(self.S)]
+        self._frames[sel] = 0
         for s in np.nonzero(sel)[0]:
             self._committed[s] = []
             self._committed_frames[s] = []
@@ -529,14 +627,19 @@ class StreamingBeamSearch:
         if self.detail:
             flm = self._fusion()
             vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-            rc = _lib.load().edgedict_beam_stream_advance_detail(
-                *args[:-2], vp(self._commit_frame_buf), vp(self._commit_logp_buf), *args[-2:],
-                flm.ref() if flm is not None else None, _lib.ptr(self._state), _lib.ptr(self._ws),
-                _lib.ptr(self._dstate), _lib.ptr(self._dws), _lib.stream_ptr())
+            dargs = (*args[:-2], vp(self._commit_frame_buf), vp(self._commit_logp_buf), *args[-2:],
+                     flm.ref() if flm is not None else None)
+            dtail = (_lib.ptr(self._state), _lib.ptr(self._ws), _lib.ptr(self._dstate), _lib.ptr(self._dws),
+                     _lib.stream_ptr())
+            if self.bias is not None:
+                rc = _lib.load().edgedict_beam_stream_advance_detail_bias(*dargs, self._bref(), *dtail)
+            else:
+                rc = _lib.load().edgedict_beam_stream_advance_detail(*dargs, *dtail)
         else:
             rc = _native("beam_stream_advance", self._fusion(), *args,
-                         tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()))
+                         tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()), bref=self._bref())
         _lib.check(rc, "beam_stream_advance")
+        self._frames += nf
         self.last_expansions = int(nexp.value)
         for s in np.nonzero(self._ncommit)[0]:
             self._committed[s].extend(self._commit_buf[s, :self._ncommit[s]].tolist())

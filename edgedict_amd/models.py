@@ -1034,23 +1034,24 @@ class Transducer(nn.Module):
         return greedy_decode_batch(self, xs, xlen)
 
     def beam_search(self, xs, xlen=None, W=10, prefix=False, max_expansions=None, *, lm=None, lm_weight=None,
-                    length_bonus=0.0, lm_bos=1):
+                    length_bonus=0.0, lm_bos=1, bias=None):
         """Beam search of the reference's legacy model (models.py:121-202), batched; see
         ``decode.beam_search_batch``.  ``prefix=True`` is its prefix-sum variant (:145-161).  ``lm`` (an
-        ``edgedict_amd.lm.LMModel``) with ``lm_weight`` adds LM shallow fusion (``decode`` module docstring)."""
+        ``edgedict_amd.lm.LMModel``) with ``lm_weight`` adds LM shallow fusion, ``bias`` (an
+        ``edgedict_amd.bias.ContextGraph``) contextual biasing towards a phrase list (``decode`` module docstring)."""
         from .decode import beam_search_batch
         return beam_search_batch(self, xs, xlen, W, max_expansions, prefix=prefix, lm=lm, lm_weight=lm_weight,
-                                 length_bonus=length_bonus, lm_bos=lm_bos)
+                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
     def beam_search_nbest(self, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                          lm_bos=1):
+                          lm_bos=1, bias=None):
         """``beam_search`` (``prefix=False``) returning per utterance a ``decode.NBestResult``: the whole list B of the
         last frame in B's order, every hypothesis with its tokens, the encoder frame each token was emitted on, each
         token's score increment, and its log p; entry 0 is what ``beam_search`` returns.  See
         ``decode.beam_search_nbest``."""
         from .decode import beam_search_nbest
         return beam_search_nbest(self, xs, xlen, W, max_expansions, lm=lm, lm_weight=lm_weight,
-                                 length_bonus=length_bonus, lm_bos=lm_bos)
+                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
 class _CausalConvFn(torch.autograd.Function):

@@ -306,14 +306,17 @@ class BatchedStreamBeamDecoder(StreamTransducerDecoder):
     to chunk, so after any chunk a stream's ``best()`` is what the offline beam search over its audio so far returns.
     There is no ``<unk>`` rule: the offline beam search has none.  ``prefix=True`` is not supported when streaming
     (``ValueError``).  ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion, as in
-    ``decode.StreamingBeamSearch``.  ``detail=True`` keeps every token's emission frame and score increment:
+    ``decode.StreamingBeamSearch``; ``bias``: a contextual-biasing list (``edgedict_amd.bias.ContextGraph``), as
+    there (``self.search.set_bias`` swaps it between utterances).  ``detail=True`` keeps every token's emission frame and score increment:
     ``nbest()`` and ``committed_detail()`` then work as the search's do (they raise without it)."""
 
     def __init__(self, transducer, flags, n_streams, W=10, max_expansions=None, node_capacity=None, prefix=False,
-                 dither=None, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, detail=False):
+                 dither=None, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, detail=False, bias=None):
+        from .bias import check_bias_args
         from .decode import StreamingBeamSearch, _vocab
         from .lm import check_fusion_args
         check_fusion_args(lm, lm_weight, _vocab(transducer), prefix)
+        check_bias_args(bias, _vocab(transducer), prefix)
         self.model = transducer.eval()
         self.flags = flags
         self.S = n_streams
@@ -321,7 +324,7 @@ class BatchedStreamBeamDecoder(StreamTransducerDecoder):
         self.device = dev
         self.search = StreamingBeamSearch(transducer, n_streams, W=W, max_expansions=max_expansions,
                                           node_capacity=node_capacity, prefix=prefix, lm=lm, lm_weight=lm_weight,
-                                          length_bonus=length_bonus, lm_bos=lm_bos, detail=detail)
+                                          length_bonus=length_bonus, lm_bos=lm_bos, detail=detail, bias=bias)
         self.transform = StackedLogFbank(
             n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
             hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,

@@ -924,6 +924,109 @@ int edgedict_beam_stream_read_nbest(int S, int L, int H, int W, int node_capacit
                                     long long* frames_done_host, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Contextual biasing (phrase boosting) for both beam searches: a phrase automaton (the phrases' trie with
+ * Aho-Corasick failure links, built on the host: edgedict_amd/bias.py) whose state every hypothesis
+ * carries under the same state reference as the prediction network's (h, c) - the state BEFORE the
+ * hypothesis' last token.  Popping y* with last token tok from carried state s0 gives s = goto(s0, tok),
+ * kept under the expansion's slot; the children are scored, in fp64 and in exactly this order,
+ *   non-blank child k:  (base + (double)lp_rnnt[k]) + D(s, k)              D(s, k) = held[goto(s, k)] - pend[s]
+ *   with an LM:         ((base + (double)lp_rnnt[k]) + (weight * (double)lp_lm[k] + length_bonus)) + D(s, k)
+ *   blank child:        base + (double)lp_rnnt[blank]
+ * The kernels read only these DEVICE tables:
+ *   root_next [V] int32   goto(0, k)
+ *   held, pend [S] fp64   bonus held on entering a state / still pending in it (0 once a phrase ended)
+ *   row_ptr [S + 1] int32, exc_tok / exc_next [n_exc] int32: per state the EXCEPTIONS, the tokens (sorted)
+ *                         where goto(s, k) != goto(0, k), and their targets; every other token takes root_next
+ * All targets must lie in [0, S) and exc_tok in [0, V): the tables are trusted (ContextGraph writes them).
+ * The *_bias entry points take the _lm ones' arguments with `bias` behind `lm`, both nullable: bias = null
+ * is exactly the _lm call (same kernels, same layouts).  With a bias list the searches run the separately
+ * compiled beam_pop[_detail]_bias / beam_expand[_lm]_bias kernels; prefix = 1 is refused.  The offline
+ * workspace and the streams' state / workspace append the bias state arrays behind the LM's part, so
+ * edgedict_beam_stream_read[_nbest] serve every form; a state sized with a bias list must be reset and
+ * advanced with one (the list may change at a reset: the root state is 0 in every automaton).
+ * beam_stream_reset_bias: detail_state nullable (non-null: as edgedict_beam_stream_reset_detail).
+ * beam_bias_struct_bytes: sizeof(edgedict_beam_bias_t), for bindings that mirror it.
+ */
+typedef struct edgedict_beam_bias_t {
+    int S, V, n_exc;
+    const int32_t* root_next;
+    const double* held;
+    const double* pend;
+    const int32_t* row_ptr;
+    const int32_t* exc_tok;
+    const int32_t* exc_next;
+} edgedict_beam_bias_t;
+
+size_t edgedict_beam_bias_struct_bytes(void);
+size_t edgedict_beam_workspace_bytes_bias(int dtype, int B, int T, int J, int V, int E, int L, int H,
+                                          int P2, int W, int max_expansions, int prefix,
+                                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias);
+int edgedict_beam_search_bias(int dtype, const void* E1, long long e_row_stride,
+                              long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
+                              const void* W1d, long long ldw1, const float* b1, int P2,
+                              const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
+                              int E, int L, const void* const* w_ih, const void* const* w_hh,
+                              const float* const* b_ih, const float* const* b_hh, int H,
+                              const void* Wp, const float* bp, int blank, int bos, int W,
+                              int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
+                              int32_t* ntokens_host, double* score_host, long long* expansions_host,
+                              const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                              void* workspace, void* stream);
+int edgedict_beam_search_nbest_bias(int dtype, const void* E1, long long e_row_stride,
+                                    long long e_frame_stride, int B, int T, const int32_t* lens_host,
+                                    int J, const void* W1d, long long ldw1, const float* b1, int P2,
+                                    const void* W2, const float* b2, int V, const void* emb,
+                                    int emb_dtype, int E, int L, const void* const* w_ih,
+                                    const void* const* w_hh, const float* const* b_ih,
+                                    const float* const* b_hh, int H, const void* Wp, const float* bp,
+                                    int blank, int bos, int W, int max_expansions, int prefix,
+                                    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
+                                    int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host,
+                                    double* logp_host, long long* expansions_host,
+                                    const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                    void* workspace, void* detail, void* result, void* stream);
+size_t edgedict_beam_stream_state_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
+                                             int P2, int W, int max_expansions, int node_capacity,
+                                             const edgedict_beam_lm_t* lm,
+                                             const edgedict_beam_bias_t* bias);
+size_t edgedict_beam_stream_workspace_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
+                                                 int P2, int W, int max_expansions, int node_capacity,
+                                                 const edgedict_beam_lm_t* lm,
+                                                 const edgedict_beam_bias_t* bias);
+int edgedict_beam_stream_reset_bias(int S, int L, int H, int W, int node_capacity, int bos,
+                                    const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
+                                    const edgedict_beam_bias_t* bias, void* state, void* detail_state,
+                                    void* stream);
+int edgedict_beam_stream_advance_bias(int dtype, const void* E1, long long e_row_stride,
+                                      long long e_frame_stride, int S, const int32_t* n_frames_host,
+                                      int J, const void* W1d, long long ldw1, const float* b1, int P2,
+                                      const void* W2, const float* b2, int V, const void* emb,
+                                      int emb_dtype, int E, int L, const void* const* w_ih,
+                                      const void* const* w_hh, const float* const* b_ih,
+                                      const float* const* b_hh, int H, const void* Wp,
+                                      const float* bp, int blank, int bos, int W, int max_expansions,
+                                      int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+                                      long long* expansions_host, const edgedict_beam_lm_t* lm,
+                                      const edgedict_beam_bias_t* bias, void* state, void* workspace,
+                                      void* stream);
+int edgedict_beam_stream_advance_detail_bias(int dtype, const void* E1, long long e_row_stride,
+                                             long long e_frame_stride, int S,
+                                             const int32_t* n_frames_host, int J, const void* W1d,
+                                             long long ldw1, const float* b1, int P2, const void* W2,
+                                             const float* b2, int V, const void* emb, int emb_dtype,
+                                             int E, int L, const void* const* w_ih,
+                                             const void* const* w_hh, const float* const* b_ih,
+                                             const float* const* b_hh, int H, const void* Wp,
+                                             const float* bp, int blank, int bos, int W,
+                                             int max_expansions, int node_capacity, int32_t* commit_host,
+                                             int32_t* commit_frame_host, double* commit_logp_host,
+                                             int32_t* ncommit_host, long long* expansions_host,
+                                             const edgedict_beam_lm_t* lm,
+                                             const edgedict_beam_bias_t* bias, void* state,
+                                             void* workspace, void* detail_state,
+                                             void* detail_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Row log-softmax (LMModel.forward's F.log_softmax(decoded, dim=-1), models.py:251):
  *   x fp32 or bf16 (x_dtype) [M, N] rows of leading dimension ldx;  y fp32 [M, N] contiguous.
  *   y = (x - max) - log(sum exp(x - max)) per row, fp32 arithmetic.
