@@ -132,7 +132,9 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
             const float* w = a.fb + (long long)m * nbins;
             float acc = 0.f;
             for (int k = lo; k < hi; ++k) acc += w[k] * re[k];
-            v = a.do_log ? logf(acc + 1e-20f) : acc;
+            // in double: the device logf is 2 ulp (6.4e-6) off at log(1e-20f) = -46.05, the value of every silent
+            // frame; 80 double logs per frame are nothing next to the FFT
+            v = a.do_log ? (float)log((double)acc + 1e-20) : acc;
         }
         for (int c = 0; c < a.copies; ++c)
             ElemIO<TO>::store(out + obase + c * a.o_copy + (long long)m * a.o_m, v);
