@@ -42,12 +42,16 @@ inline WsLayout ws_layout(int B, int T, int U1) {
 
 // ------------------------------------------------------------------ kernel 1
 // grid-stride over rows; 4 waves per block, one row per wave per iteration.
-template <typename T>
+// AR = true (alignment-restricted loss): label u of utterance b may be emitted on frames win_lo[b][u] .. win_hi[b][u]
+// only - the label log-probability of every other frame is written as -inf, and that plane of the workspace is all the
+// lattice walks, the back-trace and the gradient see of the windows.  AR = false is the kernel as it was.
+template <typename T, bool AR = false>
 __global__ __launch_bounds__(256) void rnnt_lse_gather(
     const T* __restrict__ acts, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int B, int Tm,
     int U1, int V, int blank, float* __restrict__ denom, float* __restrict__ lpb,
-    float* __restrict__ lpl, int vec_ok, const long long* __restrict__ pk_off) {
+    float* __restrict__ lpl, int vec_ok, const long long* __restrict__ pk_off,
+    const int32_t* __restrict__ win_lo = nullptr, const int32_t* __restrict__ win_hi = nullptr) {
     constexpr int VEC = ElemIO<T>::VEC;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -99,6 +103,7 @@ __global__ __launch_bounds__(256) void rnnt_lse_gather(
             if (u < Ub) {
                 const int y = labels[(long long)b * (U1 - 1) + u];
                 l = ElemIO<T>::load(z + y) - lse;
+                if (AR && (t < win_lo[(long long)b * (U1 - 1) + u] || t > win_hi[(long long)b * (U1 - 1) + u])) l = -INFINITY;
             }
             lpl[row] = l;
         }
@@ -108,12 +113,15 @@ __global__ __launch_bounds__(256) void rnnt_lse_gather(
 // kernel 1 with the row maxima / exp-sums already reduced per 64-column slot by the logits product's
 // epilogue (gemm_nt256.hip): half a wave per lattice row combines the `slots` pairs, one lane picks the
 // blank / label logits out of the stored row.  Reads 8 * slots + 4 bytes per row instead of 2 V.
+// AR as in rnnt_lse_gather.
+template <bool AR = false>
 __global__ __launch_bounds__(256) void rnnt_lse_from_parts(
     const bf16_t* __restrict__ acts, const float2* __restrict__ parts, int slots,
     const int32_t* __restrict__ labels, const int32_t* __restrict__ act_lens,
     const int32_t* __restrict__ label_lens, int Tm, int U1, int V, int blank,
     float* __restrict__ denom, float* __restrict__ lpb, float* __restrict__ lpl,
-    const long long* __restrict__ pk_off) {
+    const long long* __restrict__ pk_off, const int32_t* __restrict__ win_lo = nullptr,
+    const int32_t* __restrict__ win_hi = nullptr) {
     // ONE LANE per lattice row (no cross-lane reduction, the three outputs of consecutive rows leave as coalesced
     // stores), but the row's `slots` pairs (8 * slots contiguous bytes) reach the lane through LDS: a wave copies the
     // pairs of its next 64 (32) rows - one contiguous block of the packed lattice - with coalesced 16-byte loads and each
@@ -180,6 +188,7 @@ __global__ __launch_bounds__(256) void rnnt_lse_from_parts(
         lpb[row] = bf16_to_f32(z[blank]) - lse;
         float l = 0.f;
         if (u < Ub) l = bf16_to_f32(z[labels[(long long)b * (U1 - 1) + u]]) - lse;
+        if (AR && u < Ub && (t < win_lo[(long long)b * (U1 - 1) + u] || t > win_hi[(long long)b * (U1 - 1) + u])) l = -INFINITY;
         lpl[row] = l;
     }
 }
@@ -216,6 +225,10 @@ __device__ __forceinline__ double log_add64(double a, double b) {
 // VIT = true is the Viterbi walk of the forced aligner: ONE wave per utterance (blockIdx.x = b, direction 0 only), max
 // in place of the log-add, v(t,u) written where the alphas go and the best path's score into ll[2 b].  The VIT = false
 // instantiation is the kernel as it was.
+// Alignment-restricted loss: masked label log-probabilities arrive as -inf and need nothing here.  No sum below has
+// +inf as an operand, so no -inf - (-inf) is ever formed; log_add64 returns -inf for two -inf operands and m + 0 for
+// one (expf(-inf) = 0); a cell no window-respecting alignment passes through gets alpha = -inf or beta = -inf, and an
+// utterance whose windows admit no alignment ll = -inf on both sides.
 template <int C, bool VIT = false>
 __global__ __launch_bounds__(64) void rnnt_alpha_beta(const float* __restrict__ lpb, const float* __restrict__ lpl,
                                                       const int32_t* __restrict__ act_lens,
@@ -340,6 +353,9 @@ __global__ __launch_bounds__(256) void rnnt_costs(const double* __restrict__ ll,
 // v(t,u) is the maximum - one of them is v(t,u) bit for bit, no back-pointers are stored.  TIE RULE: equal candidates
 // take the blank predecessor (come from t - 1).  frames[b][u] = frame on which label u is emitted (the step
 // (t,u) -> (t,u+1)); the other lanes write the -1 padding behind U_b.  T_b + U_b - 1 dependent steps of four loads.
+// AR = true (windows): an utterance whose windows admit no alignment (score -inf) gets a frames row of all -1; on any
+// other the walk stays on cells with a finite v, where one candidate still reproduces v(t,u) bit for bit.
+template <bool AR = false>
 __global__ __launch_bounds__(64) void rnnt_viterbi_backtrace(const float* __restrict__ lpb, const float* __restrict__ lpl,
                                                              const double* __restrict__ v, const double* __restrict__ ll,
                                                              const int32_t* __restrict__ act_lens,
@@ -349,10 +365,11 @@ __global__ __launch_bounds__(64) void rnnt_viterbi_backtrace(const float* __rest
     const int lane = threadIdx.x;
     const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U1 - 1));   // as rnnt_alpha_beta
     int32_t* fr = frames + (long long)b * (U1 - 1);
-    for (int u = (Tb > 0 ? Ub : 0) + lane; u < U1 - 1; u += 64) fr[u] = -1;
+    const bool none = AR && ll[2 * b] == -(double)INFINITY;
+    for (int u = (Tb > 0 && !none ? Ub : 0) + lane; u < U1 - 1; u += 64) fr[u] = -1;
     if (lane != 0) return;
     scores[b] = (float)ll[2 * b];                    // -inf for an empty utterance
-    if (Tb == 0) return;
+    if (Tb == 0 || none) return;
     const long long base = (long long)b * Tm * U1;
     int t = Tb - 1, u = Ub;
     while (u > 0) {
@@ -386,10 +403,15 @@ __device__ __forceinline__ float fastemit_log1p(float lambda, float d) {
 // c_label grows by log1p(lambda) (fe_log1p, formed on the host) and c_all by log(1 + lambda wl / (wb + wl)), the
 // exponent lpl + beta(t,u+1) - beta(t,u) formed in fp64 - one read of the lpl plane per CELL.  FE = false is the
 // kernel as it was: the three extra arguments are not touched.
+// AR = true (alignment-restricted loss, windows masked into the lpl plane by the first stage): a cell with alpha = -inf
+// or beta = -inf (no window-respecting alignment passes through it), or of an utterance with L = -inf, gets a zero row
+// and its logits are NOT read - the test comes before any arithmetic, which would form -inf - (-inf); a live cell whose
+// label is masked (lpl = -inf) has c_label = -inf (wl = 0).  Everything else - arithmetic and operand order per cell -
+// is that of AR = false, which is the kernel as it was.
 #ifndef ED_GRAD_OCC
 #define ED_GRAD_OCC 1
 #endif
-template <typename T, bool FE>
+template <typename T, bool FE, bool AR = false>
 __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
     const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int B, int Tm,
@@ -409,7 +431,11 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
     for (int r = blockIdx.x * 4 + wave; r < ncells; r += gridDim.x * 4) {
         const int t = r / Wb, u = r - t * Wb;
         const long long row = ((long long)b * Tm + t) * U1 + u;
-        const bool inside = (t < Tb && u <= Ub);
+        bool inside = (t < Tb && u <= Ub);
+        if (AR && inside) {
+            const double NEG = -(double)INFINITY;
+            inside = !(alphas[row] == NEG || betas[row] == NEG || ll[2 * b] == NEG);
+        }
         const long long arow = pk_off ? pk_off[b] + r : row;
         const T* z = acts + arow * (long long)V;
         T* g = grads + arow * (long long)V;
@@ -443,6 +469,7 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
                     c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
                     c_label += fe_log1p;
                 }
+                if (AR && lpl[row] == -INFINITY) c_label = -INFINITY;
             }
         }
         if (vec_ok) {
@@ -495,7 +522,8 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad(
 // row - VEC accumulators per lane with static indices, four loads in flight as before.  (Tried first: one row per wave
 // with 4 x VEC register accumulators, 1.09 instead of 0.88 ms; LDS ds_add_f32 accumulators, 5.8 ms.)
 // Needs 16-byte aligned rows and V <= 4 * 64 * VEC (2048 in bf16, 1024 in f32); arithmetic per cell as in rnnt_grad.
-template <typename T, bool FE>
+// AR as in rnnt_grad: a dead cell's logits are not read, its row is zeros and adds nothing to the column sums.
+template <typename T, bool FE, bool AR = false>
 __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
     const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int B, int Tm,
@@ -518,13 +546,32 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
     for (int i = 0; i < VEC; ++i) cs[i] = 0.f;
     for (int r0 = blockIdx.x * 4; r0 < ncells; r0 += gridDim.x * 4) {
         uint4 raw[4];
+        bool live[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (col_live && r0 + q < ncells) raw[q] = *reinterpret_cast<const uint4*>(acts + (pk_off[b] + r0 + q) * (long long)V + v);
+        for (int q = 0; q < 4; ++q) {
+            live[q] = r0 + q < ncells;
+            if (AR && live[q]) {
+                const int r = r0 + q;
+                const int t = r / Wb, u = r - t * Wb;
+                const long long row = ((long long)b * Tm + t) * U1 + u;
+                const double NEG = -(double)INFINITY;
+                live[q] = !(alphas[row] == NEG || betas[row] == NEG || L == NEG);
+            }
+            if (col_live && live[q]) raw[q] = *reinterpret_cast<const uint4*>(acts + (pk_off[b] + r0 + q) * (long long)V + v);
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int r = r0 + q;
             if (r >= ncells) break;
+            if (AR && !live[q]) {
+                if (col_live) {
+                    float o[VEC];
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) o[i] = 0.f;
+                    ElemIO<T>::store_vec(grads + (pk_off[b] + r) * (long long)V + v, o);
+                }
+                continue;
+            }
             const int t = r / Wb, u = r - t * Wb;
             const long long row = ((long long)b * Tm + t) * U1 + u;
             const double a = alphas[row], bt_ = betas[row];
@@ -544,6 +591,7 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
                     c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
                     c_label += fe_log1p;
                 }
+                if (AR && lpl[row] == -INFINITY) c_label = -INFINITY;
             }
             if (col_live) {
                 float x[VEC], o[VEC];
@@ -565,6 +613,93 @@ __global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs(
 #pragma unroll
         for (int i = 0; i < VEC; ++i) out[i] = cs[i];
     }
+}
+
+// ------------------------------------------------------------------ window helpers (not on the hot path)
+// windows around the frames of an alignment (rnnt_viterbi_backtrace's output, or an outside aligner's): one thread per
+// (b, u).  Label u of utterance b: lo = max(0, f - left), hi = min(T_b - 1, f + right); behind the labels the window
+// covers every frame (lo = 0, hi = Tm - 1; the loss ignores those entries).  Tm == 0: the largest act_lens of the batch
+// (a caller that has the lengths on the device only; B reads per thread).
+__global__ __launch_bounds__(256) void rnnt_windows_from_frames(const int32_t* __restrict__ frames,
+                                                                const int32_t* __restrict__ act_lens,
+                                                                const int32_t* __restrict__ label_lens, int B, int Tm,
+                                                                int U, int left, int right, int32_t* __restrict__ lo,
+                                                                int32_t* __restrict__ hi) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * U) return;
+    const int b = (int)(i / U), u = (int)(i - (long long)b * U);
+    if (Tm == 0)
+        for (int k = 0; k < B; ++k) Tm = max(Tm, act_lens[k]);
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U));
+    int l = 0, h = Tm - 1;
+    if (u < Ub) {
+        const long long f = frames[i];
+        l = (int)max(0ll, f - left);
+        h = (int)min((long long)Tb - 1, f + right);
+    }
+    lo[i] = l;
+    hi[i] = h;
+}
+
+// The cells of the lattice a window-respecting alignment can pass through (finite alpha AND finite beta), from the
+// windows alone: with elo_u = max(lo_0 .. lo_u) and ehi_u = min(hi_u .. hi_{U_b - 1}, T_b - 1), column u is alive on the
+// frames [elo_{u-1}, ehi_u] (column 0 from frame 0, column U_b up to frame T_b - 1), and no alignment exists iff
+// elo_u > ehi_u for some u.  Both ends are non-decreasing in u, so the live columns of frame t are the interval
+// [#{u : end_u < t}, #{u : start_u <= t} - 1].  One workgroup per utterance: thread 0 forms the two running extremes
+// in LDS (U1 <= 2048 steps), a thread per frame then counts.  band[b][t] = (ulo, uhi), (0, -1) where no cell of the
+// frame is alive (frames behind T_b; every frame of an utterance without an alignment); cells[b] = live cells.
+constexpr int BAND_MAX_U1 = 2048;
+__global__ __launch_bounds__(256) void rnnt_band_table(const int32_t* __restrict__ win_lo, const int32_t* __restrict__ win_hi,
+                                                       const int32_t* __restrict__ act_lens,
+                                                       const int32_t* __restrict__ label_lens, int Tm, int U1,
+                                                       int32_t* __restrict__ band, long long* __restrict__ cells) {
+    __shared__ int col_start[BAND_MAX_U1], col_end[BAND_MAX_U1];
+    __shared__ int feasible;
+    __shared__ unsigned long long total;
+    const int b = blockIdx.x;
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U1 - 1));
+    const int32_t* lo = win_lo + (long long)b * (U1 - 1);
+    const int32_t* hi = win_hi + (long long)b * (U1 - 1);
+    if (threadIdx.x == 0) {
+        int ok = Tb > 0, m = 0;
+        col_start[0] = 0;
+        for (int u = 0; u < Ub; ++u) {
+            m = max(m, lo[u]);
+            col_start[u + 1] = m;                    // elo_u
+        }
+        m = Tb - 1;
+        col_end[Ub] = m;
+        for (int u = Ub - 1; u >= 0; --u) {
+            m = min(m, hi[u]);
+            col_end[u] = m;                          // ehi_u
+            if (col_start[u + 1] > m) ok = 0;
+        }
+        feasible = ok;
+        total = 0ull;
+    }
+    __syncthreads();
+    const bool ok = feasible != 0;
+    unsigned long long mine = 0;
+    for (int t = threadIdx.x; t < Tm; t += 256) {
+        int ulo = 0, uhi = -1;
+        if (ok && t < Tb) {
+            int below = 0, started = 0;
+            for (int u = 0; u <= Ub; ++u) {
+                below += col_end[u] < t;
+                started += col_start[u] <= t;
+            }
+            if (below <= started - 1) {
+                ulo = below;
+                uhi = started - 1;
+                mine += (unsigned long long)(uhi - ulo + 1);
+            }
+        }
+        band[((long long)b * Tm + t) * 2] = ulo;
+        band[((long long)b * Tm + t) * 2 + 1] = uhi;
+    }
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) cells[b] = (long long)total;
 }
 
 inline int check_common(int B, int T, int U1, int V, int blank, int dtype) {
@@ -602,9 +737,11 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
                         int V, int blank, float* costs, float* reduced, float reduce_scale,
                         void* workspace, const long long* pk_off, void* stream_,
                         const float* lse_parts = nullptr, int lse_slots = 0,
-                        int32_t* al_frames = nullptr, float* al_scores = nullptr) {
+                        int32_t* al_frames = nullptr, float* al_scores = nullptr,
+                        const int32_t* win_lo = nullptr, const int32_t* win_hi = nullptr) {
     // al_scores set: the forced aligner (edgedict_rnnt_align*): same first stage, then the Viterbi walk and its
-    // back-trace in place of the two lattice walks and the costs
+    // back-trace in place of the two lattice walks and the costs.  win_lo set: the alignment-restricted entry points
+    // (*_ar) - the first stage masks the label log-probabilities, the back-trace knows about impossible windows
     if (int rc = check_common(B, T, U1, V, blank, acts_dtype)) return rc;
     ED_CHECK_ARG(acts && (labels || U1 == 1) && act_lens && label_lens && (costs || al_scores) && workspace,
                  "rnnt_loss_forward: null pointer argument");
@@ -628,17 +765,31 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
         ED_CHECK_ARG(acts_dtype == ED_BF16 && pk_off && lse_slots > 0,
                      "rnnt_loss_forward: log-sum-exp partials need bf16 logits on the packed lattice");
         const dim3 gridp(ed_grid_for((long long)T * U1, 256, max(1, 256 * 16 / B)), B);
-        hipLaunchKernelGGL(rnnt_lse_from_parts, gridp, dim3(256), 0, stream, (const bf16_t*)acts,
-                           (const float2*)lse_parts, lse_slots, labels, act_lens, label_lens, T, U1, V,
-                           blank, denom, lpb, lpl, pk_off);
+        if (win_lo)
+            hipLaunchKernelGGL(rnnt_lse_from_parts<true>, gridp, dim3(256), 0, stream, (const bf16_t*)acts,
+                               (const float2*)lse_parts, lse_slots, labels, act_lens, label_lens, T, U1, V,
+                               blank, denom, lpb, lpl, pk_off, win_lo, win_hi);
+        else
+            hipLaunchKernelGGL(rnnt_lse_from_parts<false>, gridp, dim3(256), 0, stream, (const bf16_t*)acts,
+                               (const float2*)lse_parts, lse_slots, labels, act_lens, label_lens, T, U1, V,
+                               blank, denom, lpb, lpl, pk_off, nullptr, nullptr);
+    } else if (win_lo) {
+        if (acts_dtype == ED_F32)
+            hipLaunchKernelGGL((rnnt_lse_gather<float, true>), grid1, dim3(256), 0, stream,
+                               (const float*)acts, labels, act_lens, label_lens, B, T, U1, V, blank,
+                               denom, lpb, lpl, vec_ok, pk_off, win_lo, win_hi);
+        else
+            hipLaunchKernelGGL((rnnt_lse_gather<bf16_t, true>), grid1, dim3(256), 0, stream,
+                               (const bf16_t*)acts, labels, act_lens, label_lens, B, T, U1, V, blank,
+                               denom, lpb, lpl, vec_ok, pk_off, win_lo, win_hi);
     } else if (acts_dtype == ED_F32)
-        hipLaunchKernelGGL(rnnt_lse_gather<float>, grid1, dim3(256), 0, stream,
+        hipLaunchKernelGGL((rnnt_lse_gather<float, false>), grid1, dim3(256), 0, stream,
                            (const float*)acts, labels, act_lens, label_lens, B, T, U1, V, blank,
-                           denom, lpb, lpl, vec_ok, pk_off);
+                           denom, lpb, lpl, vec_ok, pk_off, nullptr, nullptr);
     else
-        hipLaunchKernelGGL(rnnt_lse_gather<bf16_t>, grid1, dim3(256), 0, stream,
+        hipLaunchKernelGGL((rnnt_lse_gather<bf16_t, false>), grid1, dim3(256), 0, stream,
                            (const bf16_t*)acts, labels, act_lens, label_lens, B, T, U1, V, blank,
-                           denom, lpb, lpl, vec_ok, pk_off);
+                           denom, lpb, lpl, vec_ok, pk_off, nullptr, nullptr);
     ED_CHECK_LAUNCH("rnnt_lse_gather");
 
     // one wave per (utterance, direction), C = ceil(U1 / 64) label columns per lane (rounded up to a power of two)
@@ -662,8 +813,12 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
 #undef ED_AB_LAUNCH
     ED_CHECK_LAUNCH("rnnt_alpha_beta");
     if (al_scores) {
-        hipLaunchKernelGGL(rnnt_viterbi_backtrace, dim3(B), dim3(64), 0, stream, lpb, lpl, alphas, ll, act_lens,
-                           label_lens, T, U1, al_frames, al_scores);
+        if (win_lo)
+            hipLaunchKernelGGL(rnnt_viterbi_backtrace<true>, dim3(B), dim3(64), 0, stream, lpb, lpl, alphas, ll, act_lens,
+                               label_lens, T, U1, al_frames, al_scores);
+        else
+            hipLaunchKernelGGL(rnnt_viterbi_backtrace<false>, dim3(B), dim3(64), 0, stream, lpb, lpl, alphas, ll, act_lens,
+                               label_lens, T, U1, al_frames, al_scores);
         ED_CHECK_LAUNCH("rnnt_viterbi_backtrace");
         return ED_OK;
     }
@@ -715,7 +870,7 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
                          int V, int blank, const void* workspace, float grad_scale_host,
                          const float* grad_scale_dev, int grad_scale_stride,
                          const long long* pk_off, void* stream_, int b0 = 0, int nb = -1,
-                         float* colsum_parts = nullptr, float fe_lambda = 0.f) {
+                         float* colsum_parts = nullptr, float fe_lambda = 0.f, bool ar = false) {
     // (first: a bad lambda is refused whatever else the call holds, before any launch)
     ED_CHECK_ARG(fe_lambda >= 0.f && fe_lambda <= FLT_MAX, "rnnt_loss_backward: fastemit_lambda must be finite and >= 0 (got %g)",
                  (double)fe_lambda);
@@ -746,31 +901,45 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
                      "rnnt_loss_backward: fused column sums need the packed lattice, 16-byte aligned rows and V <= %d (got V = %d)",
                      cs_width, V);
 #define ED_CS_LAUNCH(TT, FE)                                                                                           \
-    hipLaunchKernelGGL((rnnt_grad_cs<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
+    hipLaunchKernelGGL((rnnt_grad_cs<TT, FE, AR>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
                        label_lens, B, T, U1, V, blank, denom, alphas, betas, ll, grad_scale_host, grad_scale_dev,        \
                        grad_scale_stride, pk_off, colsum_parts, lpl, fe_lambda, fe_log1p)
-        if (acts_dtype == ED_F32) {
-            if (fe) ED_CS_LAUNCH(float, true);
-            else ED_CS_LAUNCH(float, false);
-        } else {
-            if (fe) ED_CS_LAUNCH(bf16_t, true);
-            else ED_CS_LAUNCH(bf16_t, false);
-        }
+#define ED_CS_PICK(AR_)                                  \
+    do {                                                 \
+        constexpr bool AR = AR_;                         \
+        if (acts_dtype == ED_F32) {                      \
+            if (fe) ED_CS_LAUNCH(float, true);           \
+            else ED_CS_LAUNCH(float, false);             \
+        } else {                                         \
+            if (fe) ED_CS_LAUNCH(bf16_t, true);          \
+            else ED_CS_LAUNCH(bf16_t, false);            \
+        }                                                \
+    } while (0)
+        if (ar) ED_CS_PICK(true);
+        else ED_CS_PICK(false);
+#undef ED_CS_PICK
 #undef ED_CS_LAUNCH
         ED_CHECK_LAUNCH("rnnt_grad_cs");
         return ED_OK;
     }
 #define ED_GRAD_LAUNCH(TT, FE)                                                                                         \
-    hipLaunchKernelGGL((rnnt_grad<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
+    hipLaunchKernelGGL((rnnt_grad<TT, FE, AR>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads, labels, act_lens, \
                        label_lens, B, T, U1, V, blank, denom, alphas, betas, ll, grad_scale_host, grad_scale_dev,     \
                        grad_scale_stride, vec_ok, pk_off, b0, lpl, fe_lambda, fe_log1p)
-    if (acts_dtype == ED_F32) {
-        if (fe) ED_GRAD_LAUNCH(float, true);
-        else ED_GRAD_LAUNCH(float, false);
-    } else {
-        if (fe) ED_GRAD_LAUNCH(bf16_t, true);
-        else ED_GRAD_LAUNCH(bf16_t, false);
-    }
+#define ED_GRAD_PICK(AR_)                                \
+    do {                                                 \
+        constexpr bool AR = AR_;                         \
+        if (acts_dtype == ED_F32) {                      \
+            if (fe) ED_GRAD_LAUNCH(float, true);         \
+            else ED_GRAD_LAUNCH(float, false);           \
+        } else {                                         \
+            if (fe) ED_GRAD_LAUNCH(bf16_t, true);        \
+            else ED_GRAD_LAUNCH(bf16_t, false);          \
+        }                                                \
+    } while (0)
+    if (ar) ED_GRAD_PICK(true);
+    else ED_GRAD_PICK(false);
+#undef ED_GRAD_PICK
 #undef ED_GRAD_LAUNCH
     ED_CHECK_LAUNCH("rnnt_grad");
     return ED_OK;
@@ -918,4 +1087,174 @@ extern "C" int edgedict_rnnt_align_packed_parts(const void* acts, const int32_t*
     ED_CHECK_ARG(lse_slots == (V + 63) / 64, "rnnt_align_packed_parts: lse_slots must be ceil(V / 64)");
     return loss_forward(acts, ED_BF16, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
                         workspace, row_offsets, stream_, lse_parts, lse_slots, frames, scores);
+}
+
+// ------------------------------------------------------------------------------- alignment-restricted loss (Ar-RNN-T)
+// Mahadeokar et al. 2021: label u of utterance b may be emitted (the lattice step (t,u) -> (t,u+1)) on the frames
+// win_lo[b][u] <= t <= win_hi[b][u] only; cost_b = -log of the probability summed over the alignments that respect every
+// window.  win_lo / win_hi: int32 [B][U1-1] on the device, entries behind label_lens[b] ignored, values outside
+// [0, T_b) match no frame.  The forward entry points are the plain ones with the windows behind label_lens; windows
+// that admit no alignment give cost +inf (aligner: score -inf, frames all -1), decided on the device.  Null windows
+// are refused before anything is launched.
+#define ED_CHECK_WINDOWS(name) \
+    ED_CHECK_ARG((win_lo && win_hi) || U1 == 1, name ": null windows (win_lo / win_hi); the plain entry point takes none")
+
+extern "C" int edgedict_rnnt_loss_forward_ar(const void* acts, int acts_dtype, const int32_t* labels,
+                                             const int32_t* act_lens, const int32_t* label_lens, const int32_t* win_lo,
+                                             const int32_t* win_hi, int B, int T, int U1, int V, int blank, float* costs,
+                                             float* reduced, float reduce_scale, void* workspace, void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_loss_forward_ar");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, costs, reduced,
+                        reduce_scale, workspace, nullptr, stream_, nullptr, 0, nullptr, nullptr, win_lo, win_hi);
+}
+
+extern "C" int edgedict_rnnt_loss_forward_packed_ar(const void* acts, int acts_dtype, const int32_t* labels,
+                                                    const int32_t* act_lens, const int32_t* label_lens,
+                                                    const int32_t* win_lo, const int32_t* win_hi,
+                                                    const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                                    float* costs, float* reduced, float reduce_scale, void* workspace,
+                                                    void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_loss_forward_packed_ar");
+    ED_CHECK_ARG(row_offsets, "rnnt_loss_forward_packed_ar: null row_offsets");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, costs, reduced,
+                        reduce_scale, workspace, row_offsets, stream_, nullptr, 0, nullptr, nullptr, win_lo, win_hi);
+}
+
+extern "C" int edgedict_rnnt_loss_forward_packed_parts_ar(const void* acts, const int32_t* labels,
+                                                          const int32_t* act_lens, const int32_t* label_lens,
+                                                          const int32_t* win_lo, const int32_t* win_hi,
+                                                          const long long* row_offsets, int B, int T, int U1, int V,
+                                                          int blank, float* costs, float* reduced, float reduce_scale,
+                                                          void* workspace, const float* lse_parts, int lse_slots,
+                                                          void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_loss_forward_packed_parts_ar");
+    ED_CHECK_ARG(row_offsets && lse_parts, "rnnt_loss_forward_packed_parts_ar: null pointer");
+    ED_CHECK_ARG(lse_slots == (V + 63) / 64, "rnnt_loss_forward_packed_parts_ar: lse_slots must be ceil(V / 64)");
+    return loss_forward(acts, ED_BF16, labels, act_lens, label_lens, B, T, U1, V, blank, costs, reduced,
+                        reduce_scale, workspace, row_offsets, stream_, lse_parts, lse_slots, nullptr, nullptr, win_lo,
+                        win_hi);
+}
+
+// Backward of a workspace an *_ar forward entry point filled: the *_fe entry points' arguments (fastemit_lambda >= 0,
+// 0 = none), the gradient kernels built with the dead-cell test.  The windows themselves are not needed: they are in
+// the workspace (lp_label = -inf).  On a workspace of a plain forward call the result is the plain gradient.
+extern "C" int edgedict_rnnt_loss_backward_ar(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                              const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U1,
+                                              int V, int blank, const void* workspace, float grad_scale_host,
+                                              const float* grad_scale_dev, int grad_scale_stride,
+                                              float fastemit_lambda, void* stream_) {
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, nullptr, stream_, 0, -1, nullptr,
+                         fastemit_lambda, true);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_ar(const void* acts, int acts_dtype, void* grads,
+                                                     const int32_t* labels, const int32_t* act_lens,
+                                                     const int32_t* label_lens, const long long* row_offsets, int B,
+                                                     int T, int U1, int V, int blank, const void* workspace,
+                                                     float grad_scale_host, const float* grad_scale_dev,
+                                                     int grad_scale_stride, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_ar: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets, "rnnt_loss_backward_packed_ar: null row_offsets");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, 0, -1, nullptr,
+                         fastemit_lambda, true);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_colsum_ar(const void* acts, int acts_dtype, void* grads,
+                                                            const int32_t* labels, const int32_t* act_lens,
+                                                            const int32_t* label_lens, const long long* row_offsets,
+                                                            int B, int T, int U1, int V, int blank,
+                                                            const void* workspace, float grad_scale_host,
+                                                            const float* grad_scale_dev, int grad_scale_stride,
+                                                            float* colsum_parts, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_colsum_ar: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets && colsum_parts, "rnnt_loss_backward_packed_colsum_ar: null pointer");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, 0, -1, colsum_parts,
+                         fastemit_lambda, true);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_packed_range_ar(const void* acts, int acts_dtype, void* grads,
+                                                           const int32_t* labels, const int32_t* act_lens,
+                                                           const int32_t* label_lens, const long long* row_offsets,
+                                                           int B, int T, int U1, int V, int blank,
+                                                           const void* workspace, float grad_scale_host,
+                                                           const float* grad_scale_dev, int grad_scale_stride, int b0,
+                                                           int nb, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_packed_range_ar: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_ARG(row_offsets, "rnnt_loss_backward_packed_range_ar: null row_offsets");
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, row_offsets, stream_, b0, nb, nullptr,
+                         fastemit_lambda, true);
+}
+
+extern "C" int edgedict_rnnt_align_ar(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                                      const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi, int B,
+                                      int T, int U1, int V, int blank, int32_t* frames, float* scores, void* workspace,
+                                      void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_align_ar");
+    ED_CHECK_ARG(scores, "rnnt_align_ar: null scores");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, nullptr, stream_, nullptr, 0, frames, scores, win_lo, win_hi);
+}
+
+extern "C" int edgedict_rnnt_align_packed_ar(const void* acts, int acts_dtype, const int32_t* labels,
+                                             const int32_t* act_lens, const int32_t* label_lens, const int32_t* win_lo,
+                                             const int32_t* win_hi, const long long* row_offsets, int B, int T, int U1,
+                                             int V, int blank, int32_t* frames, float* scores, void* workspace,
+                                             void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_align_packed_ar");
+    ED_CHECK_ARG(row_offsets && scores, "rnnt_align_packed_ar: null pointer");
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, row_offsets, stream_, nullptr, 0, frames, scores, win_lo, win_hi);
+}
+
+extern "C" int edgedict_rnnt_align_packed_parts_ar(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                                   const int32_t* label_lens, const int32_t* win_lo,
+                                                   const int32_t* win_hi, const long long* row_offsets, int B, int T,
+                                                   int U1, int V, int blank, int32_t* frames, float* scores,
+                                                   void* workspace, const float* lse_parts, int lse_slots,
+                                                   void* stream_) {
+    ED_CHECK_WINDOWS("rnnt_align_packed_parts_ar");
+    ED_CHECK_ARG(row_offsets && lse_parts && scores, "rnnt_align_packed_parts_ar: null pointer");
+    ED_CHECK_ARG(lse_slots == (V + 63) / 64, "rnnt_align_packed_parts_ar: lse_slots must be ceil(V / 64)");
+    return loss_forward(acts, ED_BF16, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, nullptr, 0.f,
+                        workspace, row_offsets, stream_, lse_parts, lse_slots, frames, scores, win_lo, win_hi);
+}
+#undef ED_CHECK_WINDOWS
+
+// windows of `left` frames before and `right` frames after the frames of an alignment (frames [B][U] as the aligner
+// writes them): lo = max(0, f - left), hi = min(T_b - 1, f + right); behind label_lens[b]: lo = 0, hi = T - 1.
+// T = 0: the largest act_lens of the batch, found on the device.
+extern "C" int edgedict_rnnt_alignment_windows(const int32_t* frames, const int32_t* act_lens, const int32_t* label_lens,
+                                               int B, int T, int U, int left, int right, int32_t* win_lo,
+                                               int32_t* win_hi, void* stream_) {
+    ED_CHECK_ARG(B > 0 && T >= 0 && U >= 0, "rnnt_alignment_windows: B must be positive, T and U >= 0 (got %d,%d,%d)", B, T, U);
+    ED_CHECK_ARG(left >= 0 && right >= 0, "rnnt_alignment_windows: left and right must be >= 0 (got %d, %d)", left, right);
+    if (U == 0) return ED_OK;
+    ED_CHECK_ARG(frames && act_lens && label_lens && win_lo && win_hi, "rnnt_alignment_windows: null pointer argument");
+    const long long n = (long long)B * U;
+    hipLaunchKernelGGL(rnnt_windows_from_frames, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
+                       frames, act_lens, label_lens, B, T, U, left, right, win_lo, win_hi);
+    ED_CHECK_LAUNCH("rnnt_windows_from_frames");
+    return ED_OK;
+}
+
+// the live cells of the restricted lattice from the windows alone: band [B][T][2] int32 = (first, last) live label
+// column of every frame, (0, -1) where the frame has none; cells [B] int64 = live cells of the utterance (0 where the
+// windows admit no alignment).  Equals isfinite(alpha) & isfinite(beta) of the *_ar forward call's workspace.
+extern "C" int edgedict_rnnt_band(const int32_t* win_lo, const int32_t* win_hi, const int32_t* act_lens,
+                                  const int32_t* label_lens, int B, int T, int U1, int32_t* band, long long* cells,
+                                  void* stream_) {
+    ED_CHECK_ARG(B > 0 && T > 0 && U1 > 0, "rnnt_band: B, T, U1 must be positive (got %d,%d,%d)", B, T, U1);
+    ED_CHECK_ARG(U1 <= BAND_MAX_U1, "rnnt_band: U+1 = %d exceeds the supported maximum of %d", U1, BAND_MAX_U1);
+    ED_CHECK_ARG(((win_lo && win_hi) || U1 == 1) && act_lens && label_lens && band && cells, "rnnt_band: null pointer argument");
+    hipLaunchKernelGGL(rnnt_band_table, dim3(B), dim3(256), 0, (hipStream_t)stream_, win_lo, win_hi, act_lens, label_lens,
+                       T, U1, band, cells);
+    ED_CHECK_LAUNCH("rnnt_band_table");
+    return ED_OK;
 }

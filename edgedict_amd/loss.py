@@ -20,6 +20,14 @@ Difference from upstream that is deliberate: upstream computes the full gradient
 forks) scales the gradient that flows through the label emissions by ``1 + lambda``.  The returned
 costs stay the plain negative log-likelihood: only the gradient changes.  ``rnnt_align`` is the forced
 aligner over the same lattice (the frames on which a known transcript is emitted).
+
+``windows=(lo, hi)`` (alignment-restricted RNN-T, Mahadeokar et al. 2021): int32 ``[B, U]`` device tensors; label ``u``
+of utterance ``b`` may be emitted only on the frames ``lo[b, u] <= t <= hi[b, u]`` and the loss sums over the alignments
+that respect every window (entries behind ``label_lens[b]`` are ignored, blanks are never restricted, values outside
+``[0, T_b)`` match no frame).  Windows that admit no alignment give that utterance the cost ``+inf`` and a zero
+gradient - a ``'mean'`` or ``'sum'`` reduction is then ``+inf`` as well - decided on the device, without a host sync.
+``alignment_windows`` builds windows from an alignment (``rnnt_align``'s frames, or an outside aligner's),
+``rnnt_band`` the table of lattice cells that stay alive under them.
 """
 import math
 
@@ -61,6 +69,26 @@ def _certify_inputs(acts, labels, act_lens, label_lens, check_lengths):
             raise ValueError("Output length mismatch")
 
 
+def check_windows(windows, B, U, device, name="windows"):
+    """``windows`` as the loss takes them: a pair ``(lo, hi)`` of contiguous int32 ``[B, U]`` tensors on ``device``.
+    Returns the pair; TypeError / ValueError otherwise (the classes ``_certify_inputs`` uses for the labels)."""
+    if not isinstance(windows, (tuple, list)) or len(windows) != 2:
+        raise TypeError("%s must be a pair (lo, hi) of int32 [B, U] tensors" % name)
+    lo, hi = windows
+    for part, t in (("lo", lo), ("hi", hi)):
+        if not torch.is_tensor(t):
+            raise TypeError("%s %s must be a tensor, got %s" % (name, part, type(t).__name__))
+        if t.dtype != torch.int32:
+            raise TypeError("%s %s must be int32, got %s" % (name, part, t.dtype))
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != U:
+            raise ValueError("%s %s must have shape [B,U] = [%d,%d], got %s" % (name, part, B, U, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s %s must be contiguous" % (name, part))
+        if t.device != device:
+            raise ValueError("%s %s must be on %s, got %s" % (name, part, device, t.device))
+    return lo, hi
+
+
 def check_fastemit_lambda(value):
     """``float(value)``; ValueError unless it is finite and >= 0."""
     lam = float(value)
@@ -71,8 +99,9 @@ def check_fastemit_lambda(value):
 
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda=0.0):
-        _lib.require_cuda(acts, labels, act_lens, label_lens)
+    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda=0.0, win_lo=None,
+                win_hi=None):
+        _lib.require_cuda(acts, labels, act_lens, label_lens, win_lo, win_hi)
         B, T, U1, V = acts.shape
         lib = _lib.load()
         ws = torch.empty(lib.edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8,
@@ -80,9 +109,14 @@ class _RNNTLossFn(torch.autograd.Function):
         costs = torch.empty(B, dtype=torch.float32, device=acts.device)
         reduced = torch.empty(1, dtype=torch.float32, device=acts.device)
         scale = 1.0 / B if reduction == "mean" else 1.0
-        _lib.call("rnnt_loss_forward", acts, _lib.dtype_code(acts.dtype), labels, act_lens,
-                  label_lens, B, T, U1, V, int(blank), costs, reduced, float(scale), ws)
+        if win_lo is None:
+            _lib.call("rnnt_loss_forward", acts, _lib.dtype_code(acts.dtype), labels, act_lens,
+                      label_lens, B, T, U1, V, int(blank), costs, reduced, float(scale), ws)
+        else:
+            _lib.call("rnnt_loss_forward_ar", acts, _lib.dtype_code(acts.dtype), labels, act_lens, label_lens,
+                      win_lo, win_hi, B, T, U1, V, int(blank), costs, reduced, float(scale), ws)
         ctx.save_for_backward(acts, labels, act_lens, label_lens, ws)
+        ctx.restricted = win_lo is not None
         ctx.blank = int(blank)
         ctx.reduction = reduction
         ctx.fastemit_lambda = float(fastemit_lambda)
@@ -97,14 +131,19 @@ class _RNNTLossFn(torch.autograd.Function):
         go = grad_output.contiguous().float()
         host_scale = 1.0 / B if ctx.reduction == "mean" else 1.0
         stride = 1 if ctx.reduction == "none" else 0
-        if ctx.fastemit_lambda == 0.0:
+        if ctx.restricted:
+            # (the windows are in the workspace: masked label log-probabilities are -inf there)
+            _lib.call("rnnt_loss_backward_ar", acts, _lib.dtype_code(acts.dtype), grads, labels,
+                      act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride,
+                      ctx.fastemit_lambda)
+        elif ctx.fastemit_lambda == 0.0:
             _lib.call("rnnt_loss_backward", acts, _lib.dtype_code(acts.dtype), grads, labels,
                       act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride)
         else:
             _lib.call("rnnt_loss_backward_fe", acts, _lib.dtype_code(acts.dtype), grads, labels,
                       act_lens, label_lens, B, T, U1, V, ctx.blank, ws, float(host_scale), go, stride,
                       ctx.fastemit_lambda)
-        return grads, None, None, None, None, None, None
+        return grads, None, None, None, None, None, None, None, None
 
 
 class RNNTLoss(torch.nn.Module):
@@ -116,6 +155,12 @@ class RNNTLoss(torch.nn.Module):
     ``fastemit_lambda`` >= 0 (default 0: the plain loss, bit for bit): FastEmit regularisation.  The
     gradient through the label emissions is scaled by ``1 + lambda``; the returned value stays the plain
     negative log-likelihood, so losses are comparable across lambdas.
+
+    ``forward(..., windows=(lo, hi))`` (keyword only; default ``None``: the plain loss, the same kernels as before) is
+    the alignment-restricted loss of the module docstring.  An utterance whose windows admit no alignment has cost
+    ``+inf`` and a zero gradient, and makes a ``'mean'`` / ``'sum'`` result ``+inf`` while the gradient of the batch
+    stays finite (the other utterances' usual share): check the returned loss to drop such a step, or build windows
+    that are feasible (``alignment_windows`` of a valid alignment always are).
     """
 
     def __init__(self, blank=0, reduction="mean", check_lengths=True, fastemit_lambda=0.0):
@@ -127,20 +172,26 @@ class RNNTLoss(torch.nn.Module):
         self.reduction = reduction
         self.check_lengths = check_lengths
 
-    def forward(self, acts, labels, act_lens, label_lens):
+    def forward(self, acts, labels, act_lens, label_lens, *, windows=None):
         _certify_inputs(acts, labels, act_lens, label_lens, self.check_lengths)
+        if windows is None:
+            return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, self.blank, self.reduction,
+                                     self.fastemit_lambda)
+        lo, hi = check_windows(windows, labels.shape[0], labels.shape[1], acts.device)
         return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, self.blank, self.reduction,
-                                 self.fastemit_lambda)
+                                 self.fastemit_lambda, lo, hi)
 
 
 @torch.no_grad()
-def rnnt_align(acts, labels, act_lens, label_lens, blank=0):
+def rnnt_align(acts, labels, act_lens, label_lens, blank=0, *, windows=None):
     """Forced alignment: the single most probable alignment of the transcripts ``labels`` (Viterbi over
     the lattice of the loss).  Arguments as ``RNNTLoss.forward`` (validated the same way).  Returns
     ``(frames, scores)``: ``frames`` int32 ``[B, U]``, ``frames[b, u]`` the frame on which label ``u`` of
     utterance ``b`` is emitted (non-decreasing in ``u``; -1 for ``u >= label_lens[b]``), and ``scores``
     float32 ``[B]``, the log-probability of that alignment (``<= -cost``).  Where two alignments score
-    equal, the one that waits (takes the blank predecessor) wins."""
+    equal, the one that waits (takes the blank predecessor) wins.  ``windows=(lo, hi)`` (as ``RNNTLoss.forward``): the
+    best alignment among those that respect the windows; a row whose windows admit none has score ``-inf`` and frames
+    of all -1."""
     _certify_inputs(acts, labels, act_lens, label_lens, True)
     _lib.require_cuda(acts, labels, act_lens, label_lens)
     B, T, U1, V = acts.shape
@@ -148,12 +199,65 @@ def rnnt_align(acts, labels, act_lens, label_lens, blank=0):
     ws = torch.empty(lib.edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=acts.device)
     frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=acts.device)
     scores = torch.empty(B, dtype=torch.float32, device=acts.device)
-    _lib.call("rnnt_align", acts.detach(), _lib.dtype_code(acts.dtype), labels, act_lens, label_lens, B, T, U1, V,
-              int(blank), frames, scores, ws)
+    if windows is None:
+        _lib.call("rnnt_align", acts.detach(), _lib.dtype_code(acts.dtype), labels, act_lens, label_lens, B, T, U1, V,
+                  int(blank), frames, scores, ws)
+    else:
+        lo, hi = check_windows(windows, B, U1 - 1, acts.device)
+        _lib.call("rnnt_align_ar", acts.detach(), _lib.dtype_code(acts.dtype), labels, act_lens, label_lens, lo, hi,
+                  B, T, U1, V, int(blank), frames, scores, ws)
     return frames, scores
 
 
-def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0):
+def _check_lens(act_lens, label_lens, B, device):
+    for name, t in (("act_lens", act_lens), ("label_lens", label_lens)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != B:
+            raise ValueError("%s must be an int32 tensor of shape [%d]" % (name, B))
+        if not t.is_contiguous() or t.device != device:
+            raise ValueError("%s must be contiguous and on %s" % (name, device))
+
+
+@torch.no_grad()
+def alignment_windows(frames, act_lens, label_lens, left, right):
+    """Windows for ``RNNTLoss.forward(..., windows=)`` around an alignment: ``frames`` int32 ``[B, U]`` as ``rnnt_align``
+    returns them (device), ``left``, ``right`` >= 0 frames of slack.  Returns ``(lo, hi)`` with
+    ``lo = max(0, f - left)``, ``hi = min(T_b - 1, f + right)``; behind ``label_lens[b]``: ``lo = 0, hi = T - 1`` with
+    ``T = max(act_lens)``, found on the device.  One small kernel, no host sync."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.int32 or frames.dim() != 2 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous int32 tensor [B, U]")
+    left, right = int(left), int(right)
+    if left < 0 or right < 0:
+        raise ValueError("left and right must be >= 0, got %d, %d" % (left, right))
+    _lib.require_cuda(frames, act_lens, label_lens)
+    B, U = frames.shape
+    _check_lens(act_lens, label_lens, B, frames.device)
+    lo = torch.empty_like(frames)
+    hi = torch.empty_like(frames)
+    _lib.call("rnnt_alignment_windows", frames, act_lens, label_lens, B, 0, U, left, right, lo, hi)
+    return lo, hi
+
+
+@torch.no_grad()
+def rnnt_band(lo, hi, act_lens, label_lens, T):
+    """The lattice cells that stay alive under the windows ``(lo, hi)`` - those a window-respecting alignment can pass
+    through, i.e. with finite alpha and finite beta - from the windows alone.  Returns ``(band, cells)``: ``band``
+    int32 ``[B, T, 2]``, ``band[b, t] = (first, last)`` live label column of frame ``t`` (``(0, -1)`` where the frame
+    has none: behind ``act_lens[b]``, or everywhere when the windows admit no alignment), and ``cells`` int64 ``[B]``,
+    the number of live cells.  One small kernel, no host sync."""
+    if not torch.is_tensor(lo):
+        raise TypeError("lo must be a tensor")
+    B, U = lo.shape[0], lo.shape[1] if lo.dim() == 2 else -1
+    lo, hi = check_windows((lo, hi), B, U, lo.device)
+    _lib.require_cuda(lo, hi, act_lens, label_lens)
+    _check_lens(act_lens, label_lens, B, lo.device)
+    T = int(T)
+    band = torch.empty(B, T, 2, dtype=torch.int32, device=lo.device)
+    cells = torch.empty(B, dtype=torch.int64, device=lo.device)
+    _lib.call("rnnt_band", lo, hi, act_lens, label_lens, B, T, U + 1, band, cells)
+    return band, cells
+
+
+def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0, *, windows=None):
     """Test hook: run forward and return (costs, denominators, alphas, betas, loglikes[B,2])."""
     _lib.require_cuda(acts)
     B, T, U1, V = acts.shape
@@ -161,8 +265,13 @@ def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0):
     nbytes = lib.edgedict_rnnt_workspace_bytes(B, T, U1)
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=acts.device)
     costs = torch.empty(B, dtype=torch.float32, device=acts.device)
-    _lib.call("rnnt_loss_forward", acts, _lib.dtype_code(acts.dtype), labels, act_lens,
-              label_lens, B, T, U1, V, int(blank), costs, None, 1.0, ws)
+    if windows is None:
+        _lib.call("rnnt_loss_forward", acts, _lib.dtype_code(acts.dtype), labels, act_lens,
+                  label_lens, B, T, U1, V, int(blank), costs, None, 1.0, ws)
+    else:
+        lo, hi = check_windows(windows, B, U1 - 1, acts.device)
+        _lib.call("rnnt_loss_forward_ar", acts, _lib.dtype_code(acts.dtype), labels, act_lens, label_lens, lo, hi,
+                  B, T, U1, V, int(blank), costs, None, 1.0, ws)
     base = ws.data_ptr()
 
     def view(which, shape, dtype):

@@ -421,10 +421,14 @@ class _JointLossFn(torch.autograd.Function):
     numerically; the two big products and the loss kernels just do not touch padding
     (35 % of the rows on the bench batch).  Needs the lengths on the HOST (they size M_valid).
     ``fastemit_lambda`` > 0 scales the gradient through the label emissions by 1 + lambda (loss.py);
-    the returned loss stays the plain negative log-likelihood."""
+    the returned loss stays the plain negative log-likelihood.
+    ``win_lo`` / ``win_hi`` (int32 [B, U] on the device, or None): the alignment-restricted loss (loss.py).  The joint
+    still runs on every cell of the boxes; only the loss gradient skips the cells the windows kill, and
+    ``ops.LAST["joint_band_rows"]`` holds how many of the ``joint_rows`` stay alive (device tensor, no sync)."""
 
     @staticmethod
-    def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd, fastemit_lambda=0.0):
+    def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd, fastemit_lambda=0.0,
+                win_lo=None, win_hi=None):
         from ._staging import to_device
         B, T, P = enc.shape
         U1, P2 = dec.shape[1], dec.shape[2]
@@ -452,6 +456,14 @@ class _JointLossFn(torch.autograd.Function):
             _lib.call("joint_hidden_fwd_packed", _lib.dtype_code(cd), E1, D1, hid, al_d, ll_d, off_d,
                       B, T, U1, J)
         ops.LAST["joint_rows"] = M
+        restricted = win_lo is not None
+        if restricted:
+            band = torch.empty(B, T, 2, dtype=torch.int32, device=dev)
+            cells = torch.empty(B, dtype=torch.int64, device=dev)
+            _lib.call("rnnt_band", win_lo, win_hi, al_d, ll_d, B, T, U1, band, cells)
+            ops.LAST["joint_band_rows"] = cells.sum()
+        else:
+            ops.LAST.pop("joint_band_rows", None)
         lib = _lib.load()
         ws = torch.empty(lib.edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=dev)
         costs = torch.empty(B, dtype=F32, device=dev)
@@ -469,18 +481,27 @@ class _JointLossFn(torch.autograd.Function):
                 _lib.call("gemm_nt_lse", hid, ops._ll(J), w2c, ops._ll(J), logits, ops._ll(V), M, V, J,
                           b2.detach(), parts)
             with ops.timed("rnnt_loss_fwd"):
-                _lib.call("rnnt_loss_forward_packed_parts", logits, labels, al_d, ll_d, off_d, B, T, U1, V,
-                          int(blank), costs, reduced, 1.0 / B, ws, parts, slots)
+                if restricted:
+                    _lib.call("rnnt_loss_forward_packed_parts_ar", logits, labels, al_d, ll_d, win_lo, win_hi, off_d,
+                              B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws, parts, slots)
+                else:
+                    _lib.call("rnnt_loss_forward_packed_parts", logits, labels, al_d, ll_d, off_d, B, T, U1, V,
+                              int(blank), costs, reduced, 1.0 / B, ws, parts, slots)
         else:
             with ops.timed("joint_logits_gemm"):
                 logits = ops.gemm(hid, w2c, bias=b2.detach())
-            _lib.call("rnnt_loss_forward_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d,
-                      B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws)
+            if restricted:
+                _lib.call("rnnt_loss_forward_packed_ar", logits, _lib.dtype_code(cd), labels, al_d, ll_d, win_lo,
+                          win_hi, off_d, B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws)
+            else:
+                _lib.call("rnnt_loss_forward_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d,
+                          B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws)
         ops.LAST["joint_costs"] = costs       # per-utterance costs of the last packed joint + loss ([B], device)
         ctx.save_for_backward(enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, off_d, ws)
         ctx.b1, ctx.b2 = b1, b2
         ctx.cfg = (cd, B, T, U1, P, P2, J, V, M, int(blank))
         ctx.fastemit_lambda = float(fastemit_lambda)
+        ctx.restricted = restricted
         return reduced
 
     @staticmethod
@@ -502,7 +523,15 @@ class _JointLossFn(torch.autograd.Function):
         db2_parts = torch.empty(cs_rows, V, dtype=F32, device=dl.device) if cs_rows > 0 else None
         lam = ctx.fastemit_lambda
         with ops.timed("rnnt_grad"):
-            if lam != 0.0:
+            if ctx.restricted:
+                # gradient kernels with the dead-cell test (the windows are in the workspace)
+                if db2_parts is not None:
+                    _lib.call("rnnt_loss_backward_packed_colsum_ar", logits, _lib.dtype_code(cd), dl, labels, al_d,
+                              ll_d, off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, lam)
+                else:
+                    _lib.call("rnnt_loss_backward_packed_ar", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
+                              off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, lam)
+            elif lam != 0.0:
                 if db2_parts is not None:
                     _lib.call("rnnt_loss_backward_packed_colsum_fe", logits, _lib.dtype_code(cd), dl, labels, al_d,
                               ll_d, off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, lam)
@@ -533,7 +562,7 @@ class _JointLossFn(torch.autograd.Function):
             wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
             wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return (denc, ddec, *wg.grads, None, None, None, None, None, None)
+        return (denc, ddec, *wg.grads, None, None, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -901,9 +930,25 @@ class Transducer(nn.Module):
         xlen = (xlen / scale).ceil().int()
         return xlen
 
-    def forward(self, xs, ys, xlen, ylen):
+    def _windows(self, windows, B, U, device):
+        """``windows=(lo, hi)`` of forward() / align(): int32 [B, >= U] device tensors, cut to the label columns in use
+        (as ``ys`` is) and validated as the loss validates them."""
+        from .loss import check_windows
+        if not isinstance(windows, (tuple, list)) or len(windows) != 2:
+            raise TypeError("windows must be a pair (lo, hi) of int32 [B, U] tensors")
+        lo, hi = windows
+        if torch.is_tensor(lo) and torch.is_tensor(hi) and lo.dim() == 2 and hi.dim() == 2:
+            lo, hi = lo[:, :U].contiguous(), hi[:, :U].contiguous()
+        return check_windows((lo, hi), B, U, device)
+
+    def forward(self, xs, ys, xlen, ylen, *, windows=None):
+        """The reference's forward (rnnt/models.py:209-241).  ``windows=(lo, hi)`` (keyword only): the
+        alignment-restricted loss of ``loss.RNNTLoss`` on either loss path, in ENCODER frames as ``align`` counts them;
+        a batch with an utterance whose windows admit no alignment returns ``+inf`` (zero gradient for that utterance)."""
         xs = xs[:, :xlen.max()].contiguous()
         ys = ys[:, :ylen.max()].contiguous()
+        if windows is not None and not self.output_loss:
+            raise ValueError("windows need output_loss=True")
         if xs.is_cuda and not ys.is_cuda:
             # a host-side label batch (seq_collate output with only xs uploaded): one upload here,
             # the prediction network and the loss kernels both read the device copy
@@ -942,8 +987,13 @@ class Transducer(nn.Module):
             # the loss kernels take a raw device pointer: a host-side label batch (seq_collate
             # output with only xs uploaded) is moved, as Decoder.forward does for its own copy
             labels = ys.to(device=h_enc.device, dtype=torch.int32).contiguous()
-            loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias,
-                                      l2.weight, l2.bias, labels, act, ylen, self.blank, cd, self.fastemit_lambda)
+            if windows is None:
+                loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias,
+                                          l2.weight, l2.bias, labels, act, ylen, self.blank, cd, self.fastemit_lambda)
+            else:
+                lo, hi = self._windows(windows, labels.shape[0], labels.shape[1], h_enc.device)
+                loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias, l2.weight, l2.bias,
+                                          labels, act, ylen, self.blank, cd, self.fastemit_lambda, lo, hi)
             ops.mark("joint:exit")
             return loss
         logits = self.joint(h_enc, h_dec)
@@ -952,22 +1002,25 @@ class Transducer(nn.Module):
             xlen = self.scale_length(logits, xlen)
             dev = logits.device   # lengths may live on the host (no sync for the slicing above)
             labels = ys.to(device=dev, dtype=torch.int32).contiguous()
+            tail = () if windows is None else self._windows(windows, labels.shape[0], labels.shape[1], dev)
             loss = _RNNTLossFn.apply(
                 logits, labels,
                 xlen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
                 ylen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
-                self.blank, "mean", self.fastemit_lambda)
+                self.blank, "mean", self.fastemit_lambda, *tail)
             return loss
         return logits
 
     @torch.no_grad()
-    def align(self, xs, ys, xlen, ylen):
+    def align(self, xs, ys, xlen, ylen, *, windows=None):
         """Forced alignment of the transcripts ``ys`` (``loss.rnnt_align`` on this model's joint logits): returns
         ``(frames, scores)``, ``frames`` int32 ``[B, U]`` with the ENCODER frame (after the time reductions, as
         ``scale_length`` counts them) on which each label is emitted, -1 behind ``ylen[b]``; ``scores`` float32 ``[B]``, the
         log-probability of the best alignment.  ``decode.emission_times`` turns the frames into seconds.  Arguments as
         ``forward``; with host-side lengths the joint runs on the packed lattice as the training path does (the dense
-        logits are never formed).  Leaves no state behind: run it in ``eval()`` mode, or dropout takes part."""
+        logits are never formed).  Leaves no state behind: run it in ``eval()`` mode, or dropout takes part.
+        ``windows=(lo, hi)`` (keyword only, as ``forward``): the best alignment among those that respect the windows; a
+        row whose windows admit none has score -inf and frames of all -1."""
         from ._staging import to_device
         xs = xs[:, :xlen.max()].contiguous()
         ys = ys[:, :ylen.max()].contiguous()
@@ -978,11 +1031,13 @@ class Transducer(nn.Module):
         act = self.scale_length(h_enc, xlen)
         dev = h_enc.device
         labels = ys.to(device=dev, dtype=torch.int32).contiguous()
+        if windows is not None:
+            windows = self._windows(windows, labels.shape[0], labels.shape[1], dev)
         if not (config.PACKED_LATTICE and not xlen.is_cuda and not ylen.is_cuda and h_enc.is_cuda):
             from .loss import rnnt_align
             return rnnt_align(self.joint(h_enc, h_dec).contiguous(), labels,
                               act.to(device=dev, dtype=torch.int32).contiguous(),
-                              ylen.to(device=dev, dtype=torch.int32).contiguous(), self.blank)
+                              ylen.to(device=dev, dtype=torch.int32).contiguous(), self.blank, windows=windows)
         cd = self.compute_dtype
         l1, l2 = self.joint.joint[0], self.joint.joint[2]
         enc, dec = _to_cd(h_enc, cd), _to_cd(h_dec, cd)
@@ -1016,13 +1071,21 @@ class Transducer(nn.Module):
             _lib.call("gemm_nt_lse", hid, ops._ll(J), w2c, ops._ll(J), logits, ops._ll(V), M, V, J,
                       l2.bias.detach(), parts)
             with ops.timed("rnnt_align"):
-                _lib.call("rnnt_align_packed_parts", logits, labels, al_d, ll_d, off_d, B, T, U1, V, int(self.blank),
-                          frames, scores, ws, parts, slots)
+                if windows is not None:
+                    _lib.call("rnnt_align_packed_parts_ar", logits, labels, al_d, ll_d, windows[0], windows[1], off_d,
+                              B, T, U1, V, int(self.blank), frames, scores, ws, parts, slots)
+                else:
+                    _lib.call("rnnt_align_packed_parts", logits, labels, al_d, ll_d, off_d, B, T, U1, V,
+                              int(self.blank), frames, scores, ws, parts, slots)
         else:
             logits = ops.gemm(hid, w2c, bias=l2.bias.detach())
             with ops.timed("rnnt_align"):
-                _lib.call("rnnt_align_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d, B, T, U1, V,
-                          int(self.blank), frames, scores, ws)
+                if windows is not None:
+                    _lib.call("rnnt_align_packed_ar", logits, _lib.dtype_code(cd), labels, al_d, ll_d, windows[0],
+                              windows[1], off_d, B, T, U1, V, int(self.blank), frames, scores, ws)
+                else:
+                    _lib.call("rnnt_align_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d, B, T, U1, V,
+                              int(self.blank), frames, scores, ws)
         return frames, scores
 
     @torch.no_grad()

@@ -185,10 +185,15 @@ class TrainEngine:
         if self.sched is not None:
             self.sched.step(val_loss)
 
-    def train_step(self, wave, wave_len, ys, ylen, next_batch=None):
+    def train_step(self, wave, wave_len, ys, ylen, next_batch=None, *, windows=None):
         """wave f32[B,N] (device), wave_len i32[B] samples (or None), ys i32[B,U], ylen i32[B].
         next_batch: optional (wave, wave_len) of the batch the NEXT call will be given - its front-end then runs on the
         auxiliary stream during this step (one slice per step only; a different batch at the next call just discards it).
+        windows: optional (lo, hi), int32 [B, U] on the device - the alignment-restricted loss (loss.py), in encoder
+        frames as Transducer.align counts them; cut per sub-batch as ys is.  A batch with an utterance whose windows admit
+        no alignment returns the loss +inf; its gradients stay finite (that utterance contributes zeros, the others their
+        usual share) and the update is applied - this engine has no non-finite guard, a caller that wants to drop such a
+        step checks the returned loss.
         Returns the mean loss of the local batch as a device tensor (no host sync)."""
         from . import ops
         ops.mark("step:enter")
@@ -213,7 +218,10 @@ class TrainEngine:
                 # recurrence it cost the recurrence what it saved at the head of the step (profiles/r6_prefetch.txt)
                 ops.set_hook("before_logits_gemm", lambda nb=next_batch: self._prefetch(nb[0], nb[1]))
             try:
-                loss = self.model(xs, ys[s:e], xlen, ylen[s:e])
+                if windows is None:
+                    loss = self.model(xs, ys[s:e], xlen, ylen[s:e])
+                else:
+                    loss = self.model(xs, ys[s:e], xlen, ylen[s:e], windows=(windows[0][s:e], windows[1][s:e]))
             finally:
                 late = ops.pop_hook("before_logits_gemm")
             if late is not None:

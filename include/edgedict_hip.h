@@ -174,6 +174,84 @@ int edgedict_rnnt_align_packed_parts(const void* acts, const int32_t* labels, co
                                      const int32_t* label_lens, const long long* row_offsets, int B, int T, int U1,
                                      int V, int blank, int32_t* frames, float* scores, void* workspace,
                                      const float* lse_parts, int lse_slots, void* stream);
+/* Alignment-restricted RNN-T loss (Ar-RNN-T, Mahadeokar et al. 2021): per-label emission windows.
+ *   win_lo, win_hi  [B, U1-1] int32 (device): label u of utterance b may be emitted - the lattice step (t,u) -> (t,u+1) -
+ *                   on the frames win_lo[b][u] <= t <= win_hi[b][u] only.  Entries with u >= label_lens[b] are ignored,
+ *                   blank transitions are never restricted, values outside [0, T_b) match no frame.
+ * cost_b = -log of the probability summed over the alignments that respect every window (windows that cover every frame:
+ * the plain loss, bit for bit).  The *_ar forward entry points are the plain ones with the windows behind label_lens:
+ * the first stage writes lp_label = -inf for the masked cells into the workspace, which is all the later stages see of
+ * the windows.  With elo_u = max(lo_0..lo_u) and ehi_u = min(hi_u..hi_{U_b-1}, T_b-1), no alignment exists iff
+ * elo_u > ehi_u for some u: then cost_b = +inf (and `reduced` = +inf), the gradient of utterance b is zero, nothing is
+ * NaN and the other utterances are unaffected - decided on the device.  Null windows are ED_ERR_INVALID before anything
+ * is launched (U1 == 1, no labels, excepted). */
+int edgedict_rnnt_loss_forward_ar(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                                  const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi, int B, int T,
+                                  int U1, int V, int blank, float* costs, float* reduced, float reduce_scale,
+                                  void* workspace, void* stream);
+int edgedict_rnnt_loss_forward_packed_ar(const void* acts, int acts_dtype, const int32_t* labels,
+                                         const int32_t* act_lens, const int32_t* label_lens, const int32_t* win_lo,
+                                         const int32_t* win_hi, const long long* row_offsets, int B, int T, int U1, int V,
+                                         int blank, float* costs, float* reduced, float reduce_scale, void* workspace,
+                                         void* stream);
+int edgedict_rnnt_loss_forward_packed_parts_ar(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                               const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi,
+                                               const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                               float* costs, float* reduced, float reduce_scale, void* workspace,
+                                               const float* lse_parts, int lse_slots, void* stream);
+/* Backward of a workspace an *_ar forward call filled; arguments as the *_fe entry points' (fastemit_lambda >= 0, 0 for
+ * none).  With the restricted alpha, beta and L:
+ *   grad(t,u,k) = softmax_k (wb + (1 + lambda) wl) - [k == blank] wb - [k == labels[u]] (1 + lambda) wl,
+ * wl = 0 where the label is masked; a cell with alpha = -inf or beta = -inf (no window-respecting alignment passes
+ * through it) gets an all-zero row and its logits are not read.  Takes no windows: they are in the workspace. */
+int edgedict_rnnt_loss_backward_ar(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                   const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U1, int V,
+                                   int blank, const void* workspace, float grad_scale_host,
+                                   const float* grad_scale_dev, int grad_scale_stride, float fastemit_lambda,
+                                   void* stream);
+int edgedict_rnnt_loss_backward_packed_ar(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                          const int32_t* act_lens, const int32_t* label_lens,
+                                          const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                          const void* workspace, float grad_scale_host, const float* grad_scale_dev,
+                                          int grad_scale_stride, float fastemit_lambda, void* stream);
+int edgedict_rnnt_loss_backward_packed_colsum_ar(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                                 const int32_t* act_lens, const int32_t* label_lens,
+                                                 const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                                 const void* workspace, float grad_scale_host,
+                                                 const float* grad_scale_dev, int grad_scale_stride,
+                                                 float* colsum_parts, float fastemit_lambda, void* stream);
+int edgedict_rnnt_loss_backward_packed_range_ar(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                                const int32_t* act_lens, const int32_t* label_lens,
+                                                const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                                const void* workspace, float grad_scale_host,
+                                                const float* grad_scale_dev, int grad_scale_stride, int b0, int nb,
+                                                float fastemit_lambda, void* stream);
+/* The forced aligner under windows: the best alignment among those that respect them.  Windows that admit none give
+ * score -inf and a frames row of all -1. */
+int edgedict_rnnt_align_ar(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                           const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi, int B, int T, int U1,
+                           int V, int blank, int32_t* frames, float* scores, void* workspace, void* stream);
+int edgedict_rnnt_align_packed_ar(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                                  const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi,
+                                  const long long* row_offsets, int B, int T, int U1, int V, int blank, int32_t* frames,
+                                  float* scores, void* workspace, void* stream);
+int edgedict_rnnt_align_packed_parts_ar(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                        const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi,
+                                        const long long* row_offsets, int B, int T, int U1, int V, int blank,
+                                        int32_t* frames, float* scores, void* workspace, const float* lse_parts,
+                                        int lse_slots, void* stream);
+/* Windows around the frames of an alignment (frames [B, U] int32 as the aligner writes them), left, right >= 0:
+ * win_lo = max(0, f - left), win_hi = min(T_b - 1, f + right); for u >= label_lens[b]: win_lo = 0, win_hi = T - 1.
+ * T = 0 stands for the largest act_lens of the batch (found on the device). */
+int edgedict_rnnt_alignment_windows(const int32_t* frames, const int32_t* act_lens, const int32_t* label_lens, int B,
+                                    int T, int U, int left, int right, int32_t* win_lo, int32_t* win_hi, void* stream);
+/* The live cells of the restricted lattice (finite alpha and finite beta) from the windows alone: column u is alive on
+ * the frames [elo_{u-1}, ehi_u] (column 0 from frame 0, column U_b up to frame T_b - 1).
+ *   band   [B, T, 2] int32  out: (first, last) live label column of each frame; (0, -1) where the frame has none
+ *   cells  [B] int64        out: live cells of the utterance (0 where the windows admit no alignment)
+ * U1 <= 2048. */
+int edgedict_rnnt_band(const int32_t* win_lo, const int32_t* win_hi, const int32_t* act_lens, const int32_t* label_lens,
+                       int B, int T, int U1, int32_t* band, long long* cells, void* stream);
 /* debug / test accessors into a filled workspace (device pointers):
  * which: 0 = log-softmax denominators f32[B,T,U1], 1 = alphas f64[B,T,U1], 2 = betas f64,
  * 3 = log-likelihoods f64[B,2] (alpha-side, beta-side), 4 = lp_blank f32[B,T,U1], 5 = lp_label */
