@@ -56,6 +56,11 @@ PACKED_LATTICE = os.environ.get("EDGEDICT_PACKED_LATTICE", "1") != "0"
 # (csrc/gemm_nt256.hip) instead of a separate pass over the logits (rnnt_lse_gather)
 FUSED_LSE = os.environ.get("EDGEDICT_FUSED_LSE", "1") != "0"
 
+# under emission windows (Transducer.forward(..., windows=) on the packed path): joint + loss on the rows of the live
+# cells only (the band of loss.rnnt_band_plan) instead of every row of the boxes.  Off by default: the step-level
+# measurement is tools/band_joint_time.py's, and the box path is what tests/test_arloss_gpu.py pins by name.
+BAND_LATTICE = os.environ.get("EDGEDICT_BAND_LATTICE", "0") != "0"
+
 # bf16 inference on a chunk shorter than STACK_MIN_FRAMES (the streaming decoder): one native call with a fused launch
 # per layer-frame instead of the per-layer kernels (EDGEDICT_STREAM_ENCODER_STEP=0 restores them)
 STREAM_ENCODER_STEP = os.environ.get("EDGEDICT_STREAM_ENCODER_STEP", "1") != "0"

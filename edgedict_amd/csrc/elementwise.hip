@@ -191,6 +191,38 @@ __global__ __launch_bounds__(256) void joint_hidden_fwd(const T* __restrict__ E1
     }
 }
 
+// joint_hidden_fwd on the band-packed lattice (csrc/rnnt_loss.hip: rnnt_band_table / rnnt_band_scan): frame (b, t) owns
+// the rows row_off[b][t] + (u - ulo) of its live label columns ulo <= u <= uhi only; a frame without one is skipped.
+template <typename T>
+__global__ __launch_bounds__(256) void joint_hidden_fwd_band(const T* __restrict__ E1, const T* __restrict__ D1,
+                                                             T* __restrict__ hid, int B, int Tn, int U1, int J,
+                                                             const int32_t* __restrict__ band,
+                                                             const long long* __restrict__ row_off, long long rows) {
+    constexpr int VEC = ElemIO<T>::VEC;
+    const int chunks = J / VEC;
+    const int ulanes = max(1, 256 / chunks);
+    const int c = threadIdx.x % chunks, ul = threadIdx.x / chunks;
+    if (ul >= ulanes) return;
+    for (int bt = blockIdx.x; bt < B * Tn; bt += gridDim.x) {
+        const int ulo = max(0, band[2 * (long long)bt]), uhi = min(U1 - 1, band[2 * (long long)bt + 1]);
+        if (uhi < ulo) continue;
+        const long long row0 = row_off[bt];
+        if (row0 < 0 || row0 + (uhi - ulo) >= rows) continue;      // (offsets that do not belong to this table)
+        const int b = bt / Tn;
+        float e[VEC];
+        ElemIO<T>::load_vec(E1 + (long long)bt * J + c * VEC, e);
+        const T* drow = D1 + (long long)b * U1 * J + c * VEC;
+        T* orow = hid + row0 * J + c * VEC;
+        for (int u = ulo + ul; u <= uhi; u += ulanes) {
+            float d[VEC], o[VEC];
+            ElemIO<T>::load_vec(drow + (long long)u * J, d);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o[k] = joint_tanh<T>(e[k] + d[k]);
+            ElemIO<T>::store_vec(orow + (long long)(u - ulo) * J, o);
+        }
+    }
+}
+
 // backward of the broadcast-add + tanh:  dpre = dhid * (1 - hid^2)
 //   dE1[b,t,j] = sum_u dpre[b,t,u,j]        dD1[b,u,j] = sum_t dpre[b,t,u,j]
 // HBM-bound (reads 2 x B*T*U1*J elements once).  One workgroup per (64-wide j block, b, t slab);
@@ -309,6 +341,124 @@ __global__ __launch_bounds__(256) void joint_hidden_bwd(const T* __restrict__ dh
             for (int i = 0; i < JB_NU; ++i) {
                 const int u = uc + ug + 8 * i;
                 if (u >= U1) continue;
+                const float4 p = red[0][i][0][lane], q = red[0][i][1][lane];
+                float* dd = dD1 + ((long long)b * U1 + u) * J + j0;
+                atomicAdd(dd + 0, usum[i][0] + p.x); atomicAdd(dd + 1, usum[i][1] + p.y);
+                atomicAdd(dd + 2, usum[i][2] + p.z); atomicAdd(dd + 3, usum[i][3] + p.w);
+                atomicAdd(dd + 4, usum[i][4] + q.x); atomicAdd(dd + 5, usum[i][5] + q.y);
+                atomicAdd(dd + 6, usum[i][6] + q.z); atomicAdd(dd + 7, usum[i][7] + q.w);
+            }
+        }
+    }
+}
+
+// joint_hidden_bwd on the band-packed lattice: dE1[b,t] = sum over the live columns of frame t, dD1[b,u] = sum over the
+// frames on which column u is alive.  Tile, passes, wave split, LDS hand-off and atomics as above; what changes is the
+// label axis.  Both ends of a frame's interval are non-decreasing in t and consecutive live frames overlap, so the
+// columns a slab of frames touches are ONE interval [ubase, uend]: a lane's label positions are counted from the slab's
+// ubase (so that a register accumulator stays one column of dD1 over the frames of the slab), the row of a cell is
+// row_off[b][t] + (u - ulo[b][t]).  A frame without a live cell (behind T_b, or an utterance without an alignment) gets
+// a zero row of dE1; a column that is never alive keeps the zeros of the memset in front of the launch.
+template <typename T>
+__global__ __launch_bounds__(256) void joint_hidden_bwd_band(const T* __restrict__ dhid, const T* __restrict__ hid,
+                                                             float* __restrict__ dE1, float* __restrict__ dD1, int B,
+                                                             int Tn, int U1, int J, int t_per_block,
+                                                             const int32_t* __restrict__ band,
+                                                             const long long* __restrict__ row_off, long long rows) {
+    __shared__ float4 red[2][JB_NU][2][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int jv = lane & 7, ug = lane >> 3;
+    const int j0 = blockIdx.x * 64 + jv * 8;
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.z * t_per_block, t1 = min(Tn, t0 + t_per_block);
+    const bool jlive = j0 < J;
+    const int32_t* bd = band + (long long)b * Tn * 2;
+    const long long* ro = row_off + (long long)b * Tn;
+    int ubase = U1, uend = -1;                      // the slab's columns (uniform over the workgroup)
+    for (int t = t0; t < t1; ++t) {
+        const int lo = max(0, bd[2 * t]), hi = min(U1 - 1, bd[2 * t + 1]);
+        if (hi >= lo) {
+            ubase = min(ubase, lo);
+            uend = max(uend, hi);
+        }
+    }
+    const int span = uend - ubase + 1;              // <= 0: no live cell in the slab, one pass that writes the zeros of dE1
+    for (int uc = 0; uc == 0 || uc < span; uc += JB_UCHUNK) {
+        float usum[JB_NU][8];
+#pragma unroll
+        for (int i = 0; i < JB_NU; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) usum[i][e] = 0.f;
+        for (int t = t0 + wave; t < t1; t += 4) {
+            const int lo = max(0, bd[2 * t]), hi = min(U1 - 1, bd[2 * t + 1]);
+            const long long r0 = ro[t];
+            const bool ok = hi >= lo && r0 >= 0 && r0 + (hi - lo) < rows;     // (offsets that belong to this table)
+            const long long base = (r0 - lo) * J + j0;
+            float tsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < JB_NU; ++i) {
+                const int u = ubase + uc + ug + 8 * i;
+                if (ok && u >= lo && u <= hi && jlive) {
+                    float h[8], g[8];
+                    Load8<T>::ld(hid + base + (long long)u * J, h);
+                    Load8<T>::ld(dhid + base + (long long)u * J, g);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float dp = g[e] * (1.f - h[e] * h[e]);
+                        tsum[e] += dp;
+                        usum[i][e] += dp;
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                tsum[e] += __shfl_xor(tsum[e], 8, 64);
+                tsum[e] += __shfl_xor(tsum[e], 16, 64);
+                tsum[e] += __shfl_xor(tsum[e], 32, 64);
+            }
+            if (ug == 0 && jlive) {
+                float* de = dE1 + ((long long)b * Tn + t) * J + j0;
+                if (uc == 0) {
+                    *reinterpret_cast<float4*>(de) = make_float4(tsum[0], tsum[1], tsum[2], tsum[3]);
+                    *reinterpret_cast<float4*>(de + 4) = make_float4(tsum[4], tsum[5], tsum[6], tsum[7]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) de[e] += tsum[e];
+                }
+            }
+        }
+        if (span <= 0) break;                       // (uniform) nothing for dD1
+        if (uc > 0) __syncthreads();
+        if (wave >= 2) {
+#pragma unroll
+            for (int i = 0; i < JB_NU; ++i) {
+                red[wave - 2][i][0][lane] = make_float4(usum[i][0], usum[i][1], usum[i][2], usum[i][3]);
+                red[wave - 2][i][1][lane] = make_float4(usum[i][4], usum[i][5], usum[i][6], usum[i][7]);
+            }
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int i = 0; i < JB_NU; ++i) {
+                const float4 p = red[wave][i][0][lane], q = red[wave][i][1][lane];
+                usum[i][0] += p.x; usum[i][1] += p.y; usum[i][2] += p.z; usum[i][3] += p.w;
+                usum[i][4] += q.x; usum[i][5] += q.y; usum[i][6] += q.z; usum[i][7] += q.w;
+            }
+        }
+        __syncthreads();
+        if (wave == 1) {
+#pragma unroll
+            for (int i = 0; i < JB_NU; ++i) {
+                red[0][i][0][lane] = make_float4(usum[i][0], usum[i][1], usum[i][2], usum[i][3]);
+                red[0][i][1][lane] = make_float4(usum[i][4], usum[i][5], usum[i][6], usum[i][7]);
+            }
+        }
+        __syncthreads();
+        if (wave == 0 && jlive) {
+#pragma unroll
+            for (int i = 0; i < JB_NU; ++i) {
+                const int u = ubase + uc + ug + 8 * i;
+                if (u > uend) continue;
                 const float4 p = red[0][i][0][lane], q = red[0][i][1][lane];
                 float* dd = dD1 + ((long long)b * U1 + u) * J + j0;
                 atomicAdd(dd + 0, usum[i][0] + p.x); atomicAdd(dd + 1, usum[i][1] + p.y);
@@ -642,6 +792,56 @@ extern "C" int edgedict_joint_hidden_bwd_packed(int dtype, const void* dhid, con
                                                 int J, void* stream_) {
     ED_CHECK_ARG(act_lens && label_lens && row_offsets, "joint_hidden_bwd_packed: null lengths/offsets");
     return joint_hidden_bwd_impl(dtype, dhid, hid, dE1, dD1, B, T, U1, J, act_lens, label_lens, row_offsets, stream_);
+}
+
+// band-packed forms (see edgedict_rnnt_band / edgedict_rnnt_band_offsets): hid / dhid hold the `rows` live cells only
+extern "C" int edgedict_joint_hidden_fwd_band(int dtype, const void* E1, const void* D1, void* hid, const int32_t* band,
+                                              const long long* row_off, long long rows, int B, int T, int U1, int J,
+                                              void* stream_) {
+    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "joint_hidden_fwd_band: bad dtype");
+    ED_CHECK_ARG(B > 0 && T > 0 && U1 > 0 && J > 0 && rows >= 0, "joint_hidden_fwd_band: bad shape");
+    const int vec = dtype == ED_F32 ? 4 : 8;
+    ED_CHECK_ARG(J % vec == 0, "joint_hidden_fwd_band: joint size %d must be a multiple of %d", J, vec);
+    ED_CHECK_ARG(J / vec <= 256, "joint_hidden_fwd_band: joint size %d too large", J);
+    if (rows == 0) return ED_OK;
+    ED_CHECK_ARG(E1 && D1 && hid && band && row_off, "joint_hidden_fwd_band: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    const int grid = ed_grid_for((long long)B * T, 1, 256 * 64);
+    if (dtype == ED_F32)
+        hipLaunchKernelGGL(joint_hidden_fwd_band<float>, dim3(grid), dim3(256), 0, s, (const float*)E1, (const float*)D1, (float*)hid, B, T, U1, J, band, row_off, rows);
+    else
+        hipLaunchKernelGGL(joint_hidden_fwd_band<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)E1, (const bf16_t*)D1, (bf16_t*)hid, B, T, U1, J, band, row_off, rows);
+    ED_CHECK_LAUNCH("joint_hidden_fwd_band");
+    return ED_OK;
+}
+
+extern "C" int edgedict_joint_hidden_bwd_band(int dtype, const void* dhid, const void* hid, float* dE1, float* dD1,
+                                              const int32_t* band, const long long* row_off, long long rows, int B, int T,
+                                              int U1, int J, void* stream_) {
+    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "joint_hidden_bwd_band: bad dtype");
+    ED_CHECK_ARG(B > 0 && T > 0 && U1 > 0 && J > 0 && rows >= 0, "joint_hidden_bwd_band: bad shape");
+    ED_CHECK_ARG((rows == 0 || (dhid && hid)) && dE1 && dD1 && band && row_off, "joint_hidden_bwd_band: null pointer");
+    ED_CHECK_ARG(J % 8 == 0, "joint_hidden_bwd_band: joint size %d must be a multiple of 8", J);
+    hipStream_t s = (hipStream_t)stream_;
+    // dD1 is accumulated with atomics across t slabs, and a column that is never alive is not touched: zero it first
+    hipError_t e = hipMemsetAsync(dD1, 0, (size_t)B * U1 * J * sizeof(float), s);
+    if (e != hipSuccess) {
+        ed_set_error("joint_hidden_bwd_band: memset failed: %s", hipGetErrorString(e));
+        return ED_ERR_LAUNCH;
+    }
+    const int jblocks = (J + 63) / 64;
+    int tslabs = (1280 + B * jblocks - 1) / (B * jblocks);      // as joint_hidden_bwd
+    if (tslabs > (T + 7) / 8) tslabs = (T + 7) / 8;
+    if (tslabs < 1) tslabs = 1;
+    const int tpb = (T + tslabs - 1) / tslabs;
+    tslabs = (T + tpb - 1) / tpb;
+    dim3 grid(jblocks, B, tslabs);
+    if (dtype == ED_F32)
+        hipLaunchKernelGGL(joint_hidden_bwd_band<float>, grid, dim3(256), 0, s, (const float*)dhid, (const float*)hid, dE1, dD1, B, T, U1, J, tpb, band, row_off, rows);
+    else
+        hipLaunchKernelGGL(joint_hidden_bwd_band<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dhid, (const bf16_t*)hid, dE1, dD1, B, T, U1, J, tpb, band, row_off, rows);
+    ED_CHECK_LAUNCH("joint_hidden_bwd_band");
+    return ED_OK;
 }
 
 extern "C" int edgedict_adam_step_guarded(float* p, const float* g, float* m, float* v, long long n,

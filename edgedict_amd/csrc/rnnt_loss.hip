@@ -702,6 +702,385 @@ __global__ __launch_bounds__(256) void rnnt_band_table(const int32_t* __restrict
     if (threadIdx.x == 0) cells[b] = (long long)total;
 }
 
+// ------------------------------------------------------------------ band-packed lattice (joint + loss on the live cells)
+// Only the cells of the band table exist as rows: row(b,t,u) = row_off[b][t] + (u - ulo[b][t]), ulo <= u <= uhi.  Rows
+// of a frame are contiguous, frames of an utterance are contiguous, utterances in batch order: utterance b owns the
+// cells[b] rows from row_off[b][0] on; one whose windows admit no alignment owns none.
+struct BandArgs {
+    const int32_t* band;        // [B][T][2]
+    const long long* row_off;   // [B][T]
+    const int32_t* row_tu;      // [M_band]: t << 16 | u
+    const long long* cells;     // [B]
+};
+
+// row_off = exclusive prefix sum of the frame widths in (b, t) order; total[0] = M_band.  One workgroup per utterance:
+// its base is the sum of the cells of the utterances in front of it (B reads), the frames are scanned 256 at a time.
+__global__ __launch_bounds__(256) void rnnt_band_scan(const int32_t* __restrict__ band, const long long* __restrict__ cells,
+                                                      int B, int Tm, long long* __restrict__ row_off,
+                                                      long long* __restrict__ total) {
+    __shared__ int part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    long long base = 0;
+    for (int k = 0; k < b; ++k) base += cells[k];
+    if (b == 0 && tid == 0) {
+        long long all = 0;
+        for (int k = 0; k < B; ++k) all += cells[k];
+        total[0] = all;
+    }
+    for (int c0 = 0; c0 < Tm; c0 += 256) {
+        const int t = c0 + tid;
+        int w = 0;
+        if (t < Tm) w = max(0, band[((long long)b * Tm + t) * 2 + 1] - band[((long long)b * Tm + t) * 2] + 1);
+        part[tid] = w;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {              // inclusive scan of the chunk
+            const int add = tid >= d ? part[tid - d] : 0;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        if (t < Tm) row_off[(long long)b * Tm + t] = base + (part[tid] - w);
+        base += part[255];
+        __syncthreads();
+    }
+}
+
+// row_tu[row] = t << 16 | u of every band row: one thread per frame walks the frame's interval
+__global__ __launch_bounds__(256) void rnnt_band_fill(const int32_t* __restrict__ band, const long long* __restrict__ row_off,
+                                                      int B, int Tm, long long rows, int32_t* __restrict__ row_tu) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * Tm) return;
+    const int t = (int)(i % Tm);
+    const int ulo = band[i * 2], uhi = band[i * 2 + 1];
+    const long long r0 = row_off[i];
+    for (int u = ulo; u <= uhi; ++u) {
+        const long long r = r0 + (u - ulo);
+        if (r >= 0 && r < rows) row_tu[r] = (int32_t)(((unsigned)t << 16) | (unsigned)u);
+    }
+}
+
+// first loss stage on band rows, part 1: the cells of the boxes that are NOT in the band get lp_blank = lp_label = -inf
+// and a denominator of 0 - what the lattice walks see of a dead cell on the box path is an alpha or a beta of -inf, and
+// log_add64 treats every -inf operand alike, so alpha and beta of the live cells, L and the costs are the box path's.
+__global__ __launch_bounds__(256) void rnnt_band_dead_cells(const int32_t* __restrict__ band,
+                                                            const int32_t* __restrict__ act_lens,
+                                                            const int32_t* __restrict__ label_lens, int Tm, int U1,
+                                                            float* __restrict__ denom, float* __restrict__ lpb,
+                                                            float* __restrict__ lpl) {
+    const int b = blockIdx.y;
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U1 - 1));
+    const int Wb = Ub + 1, nvalid = Tb * Wb;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < nvalid; r += gridDim.x * 256) {
+        const int t = r / Wb, u = r - t * Wb;
+        const long long f = (long long)b * Tm + t;
+        if (u >= band[f * 2] && u <= band[f * 2 + 1]) continue;
+        const long long row = f * U1 + u;
+        denom[row] = 0.f;
+        lpb[row] = -INFINITY;
+        lpl[row] = -INFINITY;
+    }
+}
+
+// ... part 2: rnnt_lse_gather<T, true> over the band rows of utterance b - the cell comes from row_tu, the logits row is
+// the band row; arithmetic, window mask and operand order are that kernel's.
+template <typename T>
+__global__ __launch_bounds__(256) void rnnt_lse_gather_band(
+    const T* __restrict__ acts, const int32_t* __restrict__ labels, const int32_t* __restrict__ act_lens,
+    const int32_t* __restrict__ label_lens, int Tm, int U1, int V, int blank, float* __restrict__ denom,
+    float* __restrict__ lpb, float* __restrict__ lpl, int vec_ok, const int32_t* __restrict__ win_lo,
+    const int32_t* __restrict__ win_hi, BandArgs bd) {
+    constexpr int VEC = ElemIO<T>::VEC;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int Tb = min(act_lens[b], Tm), Ub = min(label_lens[b], U1 - 1);
+    const int nrows = (int)bd.cells[b];
+    const long long base = bd.row_off[(long long)b * Tm];
+    for (int r = blockIdx.x * 4 + wave; r < nrows; r += gridDim.x * 4) {
+        const long long arow = base + r;
+        const unsigned tu = (unsigned)bd.row_tu[arow];
+        const int t = (int)(tu >> 16), u = (int)(tu & 0xffffu);
+        if (t >= Tb || u > Ub) continue;                 // (a table that does not belong to these lengths)
+        const long long row = ((long long)b * Tm + t) * U1 + u;
+        const T* z = acts + arow * (long long)V;
+        float m = -INFINITY, s = 0.f;
+        if (vec_ok) {
+            for (int v = lane * VEC; v < V; v += 64 * VEC) {
+                float x[VEC];
+                ElemIO<T>::load_vec(z + v, x);
+                float mx = x[0];
+#pragma unroll
+                for (int i = 1; i < VEC; ++i) mx = fmaxf(mx, x[i]);
+                const float mn = fmaxf(m, mx);
+                float acc = 0.f;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc += __expf(x[i] - mn);
+                s = s * __expf(m - mn) + acc;
+                m = mn;
+            }
+        } else {
+            for (int v = lane; v < V; v += 64) {
+                const float x = ElemIO<T>::load(z + v);
+                const float mn = fmaxf(m, x);
+                s = s * __expf(m - mn) + __expf(x - mn);
+                m = mn;
+            }
+        }
+        const float M = wave_max(m);
+        const float part = (m == -INFINITY) ? 0.f : s * __expf(m - M);
+        const float S = wave_sum(part);
+        const float lse = M + logf(S);
+        if (lane == 0) {
+            denom[row] = lse;
+            lpb[row] = ElemIO<T>::load(z + blank) - lse;
+            float l = 0.f;
+            if (u < Ub) {
+                const int y = labels[(long long)b * (U1 - 1) + u];
+                l = ElemIO<T>::load(z + y) - lse;
+                if (t < win_lo[(long long)b * (U1 - 1) + u] || t > win_hi[(long long)b * (U1 - 1) + u]) l = -INFINITY;
+            }
+            lpl[row] = l;
+        }
+    }
+}
+
+// ... and rnnt_lse_from_parts<true> over the band rows: one lane per row, the rows' pairs staged through LDS a wave's
+// block of consecutive band rows at a time; the pairs are merged in that kernel's order.
+__global__ __launch_bounds__(256) void rnnt_lse_from_parts_band(
+    const bf16_t* __restrict__ acts, const float2* __restrict__ parts, int slots, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int Tm, int U1, int V, int blank,
+    float* __restrict__ denom, float* __restrict__ lpb, float* __restrict__ lpl, const int32_t* __restrict__ win_lo,
+    const int32_t* __restrict__ win_hi, BandArgs bd) {
+    constexpr int WAVE_F4 = 64 * 17;
+    __shared__ float4 stage[4][WAVE_F4];
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U1 - 1));
+    const int nvalid = (int)bd.cells[b];
+    const long long base = bd.row_off[(long long)b * Tm];
+    const int q4 = slots >> 1;
+    const int RP = (slots & 1) ? 0 : (q4 <= 16 ? 64 : (q4 <= 33 ? 32 : 0));
+    const int stride = q4 + 1;
+    float4* sp = stage[wave];
+    const int step = RP ? RP : 64;
+    for (int r0 = (blockIdx.x * 4 + wave) * step; r0 < nvalid; r0 += gridDim.x * 4 * step) {
+        const int nrows = min(step, nvalid - r0);
+        const long long arow0 = base + r0;
+        if (RP) {
+            const float4* p4 = reinterpret_cast<const float4*>(parts + arow0 * slots);
+            __builtin_amdgcn_wave_barrier();
+            for (int i = lane; i < nrows * q4; i += 64) {
+                const int rr = i / q4;
+                sp[rr * stride + (i - rr * q4)] = p4[i];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (lane >= nrows) continue;
+        const long long arow = arow0 + lane;
+        const unsigned tu = (unsigned)bd.row_tu[arow];
+        const int t = (int)(tu >> 16), u = (int)(tu & 0xffffu);
+        if (t >= Tb || u > Ub) continue;                 // (a table that does not belong to these lengths)
+        const long long row = ((long long)b * Tm + t) * U1 + u;
+        float m = -INFINITY, sm = 0.f;
+        int k = 0;
+        if (RP) {
+            for (; k + 1 < slots; k += 2) {
+                const float4 p = sp[lane * stride + (k >> 1)];
+                const float nm = fmaxf(m, fmaxf(p.x, p.z));
+                if (nm != -INFINITY) sm = sm * __expf(m - nm) + p.y * __expf(p.x - nm) + p.w * __expf(p.z - nm);
+                m = nm;
+            }
+        } else {
+            const float4* p4 = reinterpret_cast<const float4*>(parts + arow * slots);
+            for (; (slots & 1) == 0 && k + 1 < slots; k += 2) {
+                const float4 p = p4[k >> 1];
+                const float nm = fmaxf(m, fmaxf(p.x, p.z));
+                if (nm != -INFINITY) sm = sm * __expf(m - nm) + p.y * __expf(p.x - nm) + p.w * __expf(p.z - nm);
+                m = nm;
+            }
+            for (; k < slots; ++k) {
+                const float2 p = parts[arow * slots + k];
+                const float nm = fmaxf(m, p.x);
+                if (nm != -INFINITY) sm = sm * __expf(m - nm) + p.y * __expf(p.x - nm);
+                m = nm;
+            }
+        }
+        const float lse = m + logf(sm);
+        const bf16_t* z = acts + arow * (long long)V;
+        denom[row] = lse;
+        lpb[row] = bf16_to_f32(z[blank]) - lse;
+        float l = 0.f;
+        if (u < Ub) l = bf16_to_f32(z[labels[(long long)b * (U1 - 1) + u]]) - lse;
+        if (u < Ub && (t < win_lo[(long long)b * (U1 - 1) + u] || t > win_hi[(long long)b * (U1 - 1) + u])) l = -INFINITY;
+        lpl[row] = l;
+    }
+}
+
+// rnnt_grad<T, FE, true> over the band rows of utterance b: every row is a live cell, so there is no dead-cell test and
+// no zero row; per cell the arithmetic and its operand order are the live-cell code of that kernel.
+template <typename T, bool FE>
+__global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_band(
+    const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int Tm, int U1, int V, int blank,
+    const float* __restrict__ denom, const double* __restrict__ alphas, const double* __restrict__ betas,
+    const double* __restrict__ ll, float scale_host, const float* __restrict__ scale_dev, int scale_stride, int vec_ok,
+    const float* __restrict__ lpl, float fe_lambda, float fe_log1p, BandArgs bd) {
+    constexpr int VEC = ElemIO<T>::VEC;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int Tb = min(act_lens[b], Tm), Ub = min(label_lens[b], U1 - 1);
+    const float scale = scale_host * (scale_dev ? scale_dev[(long long)b * scale_stride] : 1.f);
+    const int nrows = (int)bd.cells[b];
+    const long long base = bd.row_off[(long long)b * Tm];
+    for (int r = blockIdx.x * 4 + wave; r < nrows; r += gridDim.x * 4) {
+        const long long arow = base + r;
+        const unsigned tu = (unsigned)bd.row_tu[arow];
+        const int t = (int)(tu >> 16), u = (int)(tu & 0xffffu);
+        if (t >= Tb || u > Ub) continue;                 // (a table that does not belong to these lengths)
+        const long long row = ((long long)b * Tm + t) * U1 + u;
+        const T* z = acts + arow * (long long)V;
+        T* g = grads + arow * (long long)V;
+        constexpr int NB = 4;
+        uint4 raw[NB];
+        if (vec_ok) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const int v = (lane + 64 * j) * VEC;
+                if (v < V) raw[j] = *reinterpret_cast<const uint4*>(z + v);
+            }
+        }
+        float c_all, c_blank = -INFINITY, c_label = -INFINITY;
+        int y = -1;
+        {
+            const double a = alphas[row], bt_ = betas[row];
+            const double L = ll[2 * b];
+            const float lse = denom[row];
+            c_all = (float)(a + bt_ - L) - lse;
+            if (t < Tb - 1)
+                c_blank = (float)(a + betas[row + U1] - L) - lse;
+            else if (u == Ub)
+                c_blank = (float)(a - L) - lse;
+            if (u < Ub) {
+                y = labels[(long long)b * (U1 - 1) + u];
+                const double bl = betas[row + 1];
+                c_label = (float)(a + bl - L) - lse;
+                if (FE) {
+                    c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
+                    c_label += fe_log1p;
+                }
+                if (lpl[row] == -INFINITY) c_label = -INFINITY;
+            }
+        }
+        if (vec_ok) {
+            for (int v = lane * VEC, j = 0; v < V; v += 64 * VEC, ++j) {
+                float o[VEC], x[VEC];
+                if (j < NB) {
+                    const uint4 rv = j == 0 ? raw[0] : (j == 1 ? raw[1] : (j == 2 ? raw[2] : raw[3]));
+                    ElemIO<T>::cvt_vec(rv, x);
+                } else {
+                    ElemIO<T>::load_vec(z + v, x);
+                }
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    float gv = __expf(x[i] + c_all);
+                    if (v + i == blank) gv -= __expf(x[i] + c_blank);
+                    if (v + i == y) gv -= __expf(x[i] + c_label);
+                    o[i] = gv * scale;
+                }
+                ElemIO<T>::store_vec(g + v, o);
+            }
+        } else {
+            for (int v = lane; v < V; v += 64) {
+                const float x = ElemIO<T>::load(z + v);
+                float gv = __expf(x + c_all);
+                if (v == blank) gv -= __expf(x + c_blank);
+                if (v == y) gv -= __expf(x + c_label);
+                gv *= scale;
+                ElemIO<T>::store(g + v, gv);
+            }
+        }
+    }
+}
+
+// rnnt_grad_cs<T, FE, true> over the band rows: work split, limits and arithmetic as there.  Every workgroup writes its
+// partial row of column sums, zeros where it had no rows.
+template <typename T, bool FE>
+__global__ __launch_bounds__(256, ED_GRAD_OCC) void rnnt_grad_cs_band(
+    const T* __restrict__ acts, T* __restrict__ grads, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ act_lens, const int32_t* __restrict__ label_lens, int Tm, int U1, int V, int blank,
+    const float* __restrict__ denom, const double* __restrict__ alphas, const double* __restrict__ betas,
+    const double* __restrict__ ll, float scale_host, const float* __restrict__ scale_dev, int scale_stride,
+    float* __restrict__ colsum_parts, const float* __restrict__ lpl, float fe_lambda, float fe_log1p, BandArgs bd) {
+    constexpr int VEC = ElemIO<T>::VEC;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int Tb = min(act_lens[b], Tm), Ub = min(label_lens[b], U1 - 1);
+    const float scale = scale_host * (scale_dev ? scale_dev[(long long)b * scale_stride] : 1.f);
+    const int ncells = (int)bd.cells[b];
+    const long long base = bd.row_off[(long long)b * Tm];
+    const int v = (wave * 64 + lane) * VEC;
+    const bool col_live = v < V;
+    const double L = ll[2 * b];
+    float cs[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) cs[i] = 0.f;
+    for (int r0 = blockIdx.x * 4; r0 < ncells; r0 += gridDim.x * 4) {
+        uint4 raw[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (col_live && r0 + q < ncells) raw[q] = *reinterpret_cast<const uint4*>(acts + (base + r0 + q) * (long long)V + v);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = r0 + q;
+            if (r >= ncells) break;
+            const unsigned tu = (unsigned)bd.row_tu[base + r];
+            const int t = (int)(tu >> 16), u = (int)(tu & 0xffffu);
+            if (t >= Tb || u > Ub) continue;             // (a table that does not belong to these lengths)
+            const long long row = ((long long)b * Tm + t) * U1 + u;
+            const double a = alphas[row], bt_ = betas[row];
+            const float lse = denom[row];
+            float c_all = (float)(a + bt_ - L) - lse;
+            float c_blank = -INFINITY, c_label = -INFINITY;
+            int y = -1;
+            if (t < Tb - 1)
+                c_blank = (float)(a + betas[row + U1] - L) - lse;
+            else if (u == Ub)
+                c_blank = (float)(a - L) - lse;
+            if (u < Ub) {
+                y = labels[(long long)b * (U1 - 1) + u];
+                const double bl = betas[row + 1];
+                c_label = (float)(a + bl - L) - lse;
+                if (FE) {
+                    c_all = (float)((a + bt_ - L) + (double)fastemit_log1p(fe_lambda, (float)((double)lpl[row] + bl - bt_))) - lse;
+                    c_label += fe_log1p;
+                }
+                if (lpl[row] == -INFINITY) c_label = -INFINITY;
+            }
+            if (col_live) {
+                float x[VEC], o[VEC];
+                ElemIO<T>::cvt_vec(raw[q], x);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    float gv = __expf(x[i] + c_all);
+                    if (v + i == blank) gv -= __expf(x[i] + c_blank);
+                    if (v + i == y) gv -= __expf(x[i] + c_label);
+                    o[i] = gv * scale;
+                    cs[i] += o[i];
+                }
+                ElemIO<T>::store_vec(grads + (base + r) * (long long)V + v, o);
+            }
+        }
+    }
+    if (col_live) {
+        float* out = colsum_parts + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * V + v;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) out[i] = cs[i];
+    }
+}
+
 inline int check_common(int B, int T, int U1, int V, int blank, int dtype) {
     ED_CHECK_ARG(B > 0 && T > 0 && U1 > 0 && V > 0, "rnnt_loss: B,T,U1,V must be positive (got %d,%d,%d,%d)", B, T, U1, V);
     ED_CHECK_ARG(U1 <= 1024, "rnnt_loss: U+1 = %d exceeds the supported maximum of 1024", U1);
@@ -738,7 +1117,8 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
                         void* workspace, const long long* pk_off, void* stream_,
                         const float* lse_parts = nullptr, int lse_slots = 0,
                         int32_t* al_frames = nullptr, float* al_scores = nullptr,
-                        const int32_t* win_lo = nullptr, const int32_t* win_hi = nullptr) {
+                        const int32_t* win_lo = nullptr, const int32_t* win_hi = nullptr,
+                        const BandArgs* band = nullptr) {
     // al_scores set: the forced aligner (edgedict_rnnt_align*): same first stage, then the Viterbi walk and its
     // back-trace in place of the two lattice walks and the costs.  win_lo set: the alignment-restricted entry points
     // (*_ar) - the first stage masks the label log-probabilities, the back-trace knows about impossible windows
@@ -760,7 +1140,24 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
     const size_t esz = acts_dtype == ED_F32 ? 4 : 2;
     const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)acts & 15) == 0);
     const dim3 grid1(ed_grid_for((long long)T * U1, 4, max(1, 256 * 16 / B)), B);
-    if (lse_parts) {
+    if (band) {
+        // band rows (band != null: *_band entry points): the dead cells of the boxes, then the live rows
+        const dim3 gridp(ed_grid_for((long long)T * U1, 256, max(1, 256 * 16 / B)), B);
+        hipLaunchKernelGGL(rnnt_band_dead_cells, gridp, dim3(256), 0, stream, band->band, act_lens, label_lens, T, U1,
+                           denom, lpb, lpl);
+        ED_CHECK_LAUNCH("rnnt_band_dead_cells");
+        if (lse_parts) {
+            ED_CHECK_ARG(((uintptr_t)lse_parts & 15) == 0, "rnnt_loss_forward_band_parts: lse_parts must be 16-byte aligned");
+            hipLaunchKernelGGL(rnnt_lse_from_parts_band, gridp, dim3(256), 0, stream, (const bf16_t*)acts,
+                               (const float2*)lse_parts, lse_slots, labels, act_lens, label_lens, T, U1, V, blank, denom,
+                               lpb, lpl, win_lo, win_hi, *band);
+        } else if (acts_dtype == ED_F32)
+            hipLaunchKernelGGL(rnnt_lse_gather_band<float>, grid1, dim3(256), 0, stream, (const float*)acts, labels,
+                               act_lens, label_lens, T, U1, V, blank, denom, lpb, lpl, vec_ok, win_lo, win_hi, *band);
+        else
+            hipLaunchKernelGGL(rnnt_lse_gather_band<bf16_t>, grid1, dim3(256), 0, stream, (const bf16_t*)acts, labels,
+                               act_lens, label_lens, T, U1, V, blank, denom, lpb, lpl, vec_ok, win_lo, win_hi, *band);
+    } else if (lse_parts) {
         ED_CHECK_ARG(((uintptr_t)lse_parts & 15) == 0, "rnnt_loss_forward: lse_parts must be 16-byte aligned");
         ED_CHECK_ARG(acts_dtype == ED_BF16 && pk_off && lse_slots > 0,
                      "rnnt_loss_forward: log-sum-exp partials need bf16 logits on the packed lattice");
@@ -870,7 +1267,8 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
                          int V, int blank, const void* workspace, float grad_scale_host,
                          const float* grad_scale_dev, int grad_scale_stride,
                          const long long* pk_off, void* stream_, int b0 = 0, int nb = -1,
-                         float* colsum_parts = nullptr, float fe_lambda = 0.f, bool ar = false) {
+                         float* colsum_parts = nullptr, float fe_lambda = 0.f, bool ar = false,
+                         const BandArgs* band = nullptr) {
     // (first: a bad lambda is refused whatever else the call holds, before any launch)
     ED_CHECK_ARG(fe_lambda >= 0.f && fe_lambda <= FLT_MAX, "rnnt_loss_backward: fastemit_lambda must be finite and >= 0 (got %g)",
                  (double)fe_lambda);
@@ -895,6 +1293,37 @@ static int loss_backward(const void* acts, int acts_dtype, void* grads, const in
     const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)acts & 15) == 0) &&
                        (((uintptr_t)grads & 15) == 0);
     const dim3 grid(grad_grid_x(B, T, U1), nb);
+    if (band) {
+        // band rows (*_band entry points): the whole batch in one pass, no dead rows to zero
+        const int cs_width = 4 * 64 * (acts_dtype == ED_F32 ? 4 : 8);
+        ED_CHECK_ARG(b0 == 0 && nb == B, "rnnt_loss_backward_band: no utterance ranges");
+        ED_CHECK_ARG(!colsum_parts || (vec_ok && V <= cs_width),
+                     "rnnt_loss_backward_band_colsum: fused column sums need 16-byte aligned rows and V <= %d (got V = %d)",
+                     cs_width, V);
+#define ED_BAND_LAUNCH(TT, FE)                                                                                         \
+    do {                                                                                                               \
+        if (colsum_parts)                                                                                              \
+            hipLaunchKernelGGL((rnnt_grad_cs_band<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads,   \
+                               labels, act_lens, label_lens, T, U1, V, blank, denom, alphas, betas, ll,                \
+                               grad_scale_host, grad_scale_dev, grad_scale_stride, colsum_parts, lpl, fe_lambda,       \
+                               fe_log1p, *band);                                                                       \
+        else                                                                                                           \
+            hipLaunchKernelGGL((rnnt_grad_band<TT, FE>), grid, dim3(256), 0, stream, (const TT*)acts, (TT*)grads,      \
+                               labels, act_lens, label_lens, T, U1, V, blank, denom, alphas, betas, ll,                \
+                               grad_scale_host, grad_scale_dev, grad_scale_stride, vec_ok, lpl, fe_lambda, fe_log1p,   \
+                               *band);                                                                                 \
+    } while (0)
+        if (acts_dtype == ED_F32) {
+            if (fe) ED_BAND_LAUNCH(float, true);
+            else ED_BAND_LAUNCH(float, false);
+        } else {
+            if (fe) ED_BAND_LAUNCH(bf16_t, true);
+            else ED_BAND_LAUNCH(bf16_t, false);
+        }
+#undef ED_BAND_LAUNCH
+        ED_CHECK_LAUNCH("rnnt_grad_band");
+        return ED_OK;
+    }
     if (colsum_parts) {
         const int cs_width = 4 * 64 * (acts_dtype == ED_F32 ? 4 : 8);      // four column slices of 64 lanes x 16 bytes
         ED_CHECK_ARG(vec_ok && V <= cs_width && pk_off && b0 == 0 && nb == B,
@@ -1258,3 +1687,103 @@ extern "C" int edgedict_rnnt_band(const int32_t* win_lo, const int32_t* win_hi, 
     ED_CHECK_LAUNCH("rnnt_band_table");
     return ED_OK;
 }
+
+// ------------------------------------------------------------------------------------------- band-packed joint + loss
+// The plan's device work: row_off [B][T] int64 = exclusive prefix sum of the widths max(0, uhi - ulo + 1) of the band
+// table in (b, t) order, total [1] int64 = M_band (= the sum of cells) ...
+extern "C" int edgedict_rnnt_band_offsets(const int32_t* band, const long long* cells, int B, int T, long long* row_off,
+                                          long long* total, void* stream_) {
+    ED_CHECK_ARG(B > 0 && T > 0, "rnnt_band_offsets: B, T must be positive (got %d,%d)", B, T);
+    ED_CHECK_ARG(band && cells && row_off && total, "rnnt_band_offsets: null pointer argument");
+    hipLaunchKernelGGL(rnnt_band_scan, dim3(B), dim3(256), 0, (hipStream_t)stream_, band, cells, B, T, row_off, total);
+    ED_CHECK_LAUNCH("rnnt_band_scan");
+    return ED_OK;
+}
+
+// ... and, once the host knows M_band: row_tu [rows] int32 = t << 16 | u of every band row (T, U1 < 65536).
+extern "C" int edgedict_rnnt_band_rows(const int32_t* band, const long long* row_off, int B, int T, int U1, long long rows,
+                                       int32_t* row_tu, void* stream_) {
+    ED_CHECK_ARG(B > 0 && T > 0 && U1 > 0 && rows >= 0, "rnnt_band_rows: bad shape (got %d,%d,%d, %lld rows)", B, T, U1, rows);
+    ED_CHECK_ARG(T < 65536 && U1 < 65536, "rnnt_band_rows: T and U+1 must be below 65536 (got %d, %d)", T, U1);
+    if (rows == 0) return ED_OK;
+    ED_CHECK_ARG(band && row_off && row_tu, "rnnt_band_rows: null pointer argument");
+    const long long n = (long long)B * T;
+    hipLaunchKernelGGL(rnnt_band_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, band, row_off,
+                       B, T, rows, row_tu);
+    ED_CHECK_LAUNCH("rnnt_band_fill");
+    return ED_OK;
+}
+
+#define ED_CHECK_BAND(name)                                                                                   \
+    ED_CHECK_ARG(row_off && row_tu && cells, name ": null band rows (row_off / row_tu / cells)");              \
+    ED_CHECK_ARG(T < 65536 && U1 < 65536, name ": T and U+1 must be below 65536 (got %d, %d)", T, U1)
+
+// The *_packed_ar forward entry points with the logits (and the log-sum-exp partials) on BAND rows: every cell of the
+// boxes gets its workspace planes - a live cell from its band row exactly as the *_ar kernels form them, a dead cell
+// lp_blank = lp_label = -inf and denominator 0 - and the lattice walks and the costs run unchanged behind that.
+extern "C" int edgedict_rnnt_loss_forward_band(const void* acts, int acts_dtype, const int32_t* labels,
+                                               const int32_t* act_lens, const int32_t* label_lens, const int32_t* win_lo,
+                                               const int32_t* win_hi, const int32_t* band, const long long* row_off,
+                                               const int32_t* row_tu, const long long* cells, int B, int T, int U1, int V,
+                                               int blank, float* costs, float* reduced, float reduce_scale,
+                                               void* workspace, void* stream_) {
+    ED_CHECK_ARG((win_lo && win_hi) || U1 == 1, "rnnt_loss_forward_band: null windows (win_lo / win_hi)");
+    ED_CHECK_ARG(band, "rnnt_loss_forward_band: null band table");
+    ED_CHECK_BAND("rnnt_loss_forward_band");
+    const BandArgs bd{band, row_off, row_tu, cells};
+    return loss_forward(acts, acts_dtype, labels, act_lens, label_lens, B, T, U1, V, blank, costs, reduced,
+                        reduce_scale, workspace, nullptr, stream_, nullptr, 0, nullptr, nullptr, win_lo, win_hi, &bd);
+}
+
+extern "C" int edgedict_rnnt_loss_forward_band_parts(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                                     const int32_t* label_lens, const int32_t* win_lo,
+                                                     const int32_t* win_hi, const int32_t* band, const long long* row_off,
+                                                     const int32_t* row_tu, const long long* cells, int B, int T, int U1,
+                                                     int V, int blank, float* costs, float* reduced, float reduce_scale,
+                                                     void* workspace, const float* lse_parts, int lse_slots,
+                                                     void* stream_) {
+    ED_CHECK_ARG((win_lo && win_hi) || U1 == 1, "rnnt_loss_forward_band_parts: null windows (win_lo / win_hi)");
+    ED_CHECK_BAND("rnnt_loss_forward_band_parts");
+    ED_CHECK_ARG(band && lse_parts, "rnnt_loss_forward_band_parts: null pointer");
+    ED_CHECK_ARG(lse_slots == (V + 63) / 64, "rnnt_loss_forward_band_parts: lse_slots must be ceil(V / 64)");
+    const BandArgs bd{band, row_off, row_tu, cells};
+    return loss_forward(acts, ED_BF16, labels, act_lens, label_lens, B, T, U1, V, blank, costs, reduced, reduce_scale,
+                        workspace, nullptr, stream_, lse_parts, lse_slots, nullptr, nullptr, win_lo, win_hi, &bd);
+}
+
+// Backward of a workspace a *_band forward call filled: logits and gradient on band rows, every row a live cell (no
+// zero rows are written: there are none).  fastemit_lambda as the *_ar entry points'.  The colsum form writes
+// edgedict_rnnt_grad_colsum_rows(...) partial rows, all of them (zeros where a workgroup had no rows).
+extern "C" int edgedict_rnnt_loss_backward_band(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                                const int32_t* act_lens, const int32_t* label_lens,
+                                                const long long* row_off, const int32_t* row_tu, const long long* cells,
+                                                int B, int T, int U1, int V, int blank, const void* workspace,
+                                                float grad_scale_host, const float* grad_scale_dev,
+                                                int grad_scale_stride, float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_band: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_BAND("rnnt_loss_backward_band");
+    const BandArgs bd{nullptr, row_off, row_tu, cells};
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, nullptr, stream_, 0, -1, nullptr,
+                         fastemit_lambda, true, &bd);
+}
+
+extern "C" int edgedict_rnnt_loss_backward_band_colsum(const void* acts, int acts_dtype, void* grads,
+                                                       const int32_t* labels, const int32_t* act_lens,
+                                                       const int32_t* label_lens, const long long* row_off,
+                                                       const int32_t* row_tu, const long long* cells, int B, int T,
+                                                       int U1, int V, int blank, const void* workspace,
+                                                       float grad_scale_host, const float* grad_scale_dev,
+                                                       int grad_scale_stride, float* colsum_parts,
+                                                       float fastemit_lambda, void* stream_) {
+    ED_CHECK_ARG(fastemit_lambda >= 0.f && fastemit_lambda <= FLT_MAX,
+                 "rnnt_loss_backward_band_colsum: fastemit_lambda must be finite and >= 0 (got %g)", (double)fastemit_lambda);
+    ED_CHECK_BAND("rnnt_loss_backward_band_colsum");
+    ED_CHECK_ARG(colsum_parts, "rnnt_loss_backward_band_colsum: null pointer");
+    const BandArgs bd{nullptr, row_off, row_tu, cells};
+    return loss_backward(acts, acts_dtype, grads, labels, act_lens, label_lens, B, T, U1, V, blank, workspace,
+                         grad_scale_host, grad_scale_dev, grad_scale_stride, nullptr, stream_, 0, -1, colsum_parts,
+                         fastemit_lambda, true, &bd);
+}
+#undef ED_CHECK_BAND

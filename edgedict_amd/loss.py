@@ -27,8 +27,10 @@ that respect every window (entries behind ``label_lens[b]`` are ignored, blanks 
 ``[0, T_b)`` match no frame).  Windows that admit no alignment give that utterance the cost ``+inf`` and a zero
 gradient - a ``'mean'`` or ``'sum'`` reduction is then ``+inf`` as well - decided on the device, without a host sync.
 ``alignment_windows`` builds windows from an alignment (``rnnt_align``'s frames, or an outside aligner's),
-``rnnt_band`` the table of lattice cells that stay alive under them.
+``rnnt_band`` the table of lattice cells that stay alive under them, ``rnnt_band_plan`` the row layout that packs the
+joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`` under ``config.BAND_LATTICE``).
 """
+import ctypes
 import math
 
 import torch
@@ -255,6 +257,61 @@ def rnnt_band(lo, hi, act_lens, label_lens, T):
     cells = torch.empty(B, dtype=torch.int64, device=lo.device)
     _lib.call("rnnt_band", lo, hi, act_lens, label_lens, B, T, U + 1, band, cells)
     return band, cells
+
+
+class BandPlan:
+    """Row layout of the band-packed lattice: only the live cells of the band table exist as rows of the joint's
+    ``[M_band, .]`` matrices, ``row(b, t, u) = row_off[b, t] + (u - ulo[b, t])`` for ``ulo <= u <= uhi``.
+
+    ``band`` int32 ``[B, T, 2]`` and ``cells`` int64 ``[B]`` as ``rnnt_band`` returns them, ``row_off`` int64 ``[B, T]``
+    (exclusive prefix sum of the frame widths in ``(b, t)`` order), ``row_tu`` int32 ``[M_band]`` (``t << 16 | u`` of
+    every row) and ``rows``, the host int ``M_band = cells.sum()``.  ``rows`` and ``row_tu`` exist after ``finish()``:
+    the band table and the scan are device work, the total reaches the host through one asynchronous copy into pinned
+    memory, and ``finish()`` waits for the event recorded behind that copy only - work enqueued after the plan was
+    started (the encoder) is not waited for."""
+
+    def __init__(self, band, cells, row_off, total_host, event, U1):
+        self.band, self.cells, self.row_off = band, cells, row_off
+        self.row_tu = None
+        self.rows = None
+        self.U1 = U1
+        self._total_host, self._event = total_host, event
+
+    def wait(self):
+        """The one host read: wait for the event behind the copy of the total.  Returns ``M_band``."""
+        self._event.synchronize()
+        return int(self._total_host.item())
+
+    def finish(self):
+        """``wait()``, then fill ``row_tu`` on the current stream.  Returns ``self``."""
+        if self.rows is None:
+            self.rows = self.wait()
+            B, T = self.band.shape[0], self.band.shape[1]
+            self.row_tu = torch.empty(self.rows, dtype=torch.int32, device=self.band.device)
+            if self.rows:
+                _lib.call("rnnt_band_rows", self.band, self.row_off, B, T, self.U1, ctypes.c_longlong(self.rows),
+                          self.row_tu)
+        return self
+
+
+@torch.no_grad()
+def rnnt_band_plan(lo, hi, act_lens, label_lens, T, *, finish=True):
+    """``BandPlan`` of the windows ``(lo, hi)`` (arguments as ``rnnt_band``; the lengths on the device).  Device work
+    plus exactly one host read, which depends on the windows and the lengths only.  ``finish=False`` returns right
+    behind the asynchronous copy of the total - enqueue other work, then call ``plan.finish()``."""
+    band, cells = rnnt_band(lo, hi, act_lens, label_lens, T)
+    B, T, U1 = band.shape[0], band.shape[1], lo.shape[1] + 1
+    if T >= 65536 or U1 >= 65536:
+        raise ValueError("rnnt_band_plan: T and U + 1 must be below 65536 (got %d, %d)" % (T, U1))
+    row_off = torch.empty(B, T, dtype=torch.int64, device=band.device)
+    total = torch.empty(1, dtype=torch.int64, device=band.device)
+    _lib.call("rnnt_band_offsets", band, cells, B, T, row_off, total)
+    total_host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+    total_host.copy_(total, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    plan = BandPlan(band, cells, row_off, total_host, event, U1)
+    return plan.finish() if finish else plan
 
 
 def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0, *, windows=None):

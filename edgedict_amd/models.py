@@ -424,11 +424,17 @@ class _JointLossFn(torch.autograd.Function):
     the returned loss stays the plain negative log-likelihood.
     ``win_lo`` / ``win_hi`` (int32 [B, U] on the device, or None): the alignment-restricted loss (loss.py).  The joint
     still runs on every cell of the boxes; only the loss gradient skips the cells the windows kill, and
-    ``ops.LAST["joint_band_rows"]`` holds how many of the ``joint_rows`` stay alive (device tensor, no sync)."""
+    ``ops.LAST["joint_band_rows"]`` holds how many of the ``joint_rows`` stay alive (device tensor, no sync).
+    ``plan`` (a finished ``loss.BandPlan`` of the same windows and lengths, or None): joint and loss on the BAND rows -
+    hid, logits and their gradients are [M_band, .] matrices of the live cells only, the same products with a smaller
+    M; the dense workspace planes of the loss get -inf log-probabilities on the dead cells of the boxes, which is what
+    the lattice walks saw of them before (an alpha or a beta of -inf), so the loss is the box path's.  With
+    ``plan.rows == 0`` (no utterance has an alignment) nothing is launched: the loss is +inf, every gradient zero.
+    ``ops.LAST["joint_packed_rows"]`` is the number of rows materialised (``joint_rows`` without a plan)."""
 
     @staticmethod
     def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd, fastemit_lambda=0.0,
-                win_lo=None, win_hi=None):
+                win_lo=None, win_hi=None, plan=None):
         from ._staging import to_device
         B, T, P = enc.shape
         U1, P2 = dec.shape[1], dec.shape[2]
@@ -445,6 +451,14 @@ class _JointLossFn(torch.autograd.Function):
         off_d = to_device(off, dev)
         al_d = to_device(al.to(torch.int32), dev)
         ll_d = to_device(ll.to(torch.int32), dev)
+        ops.LAST["joint_rows"] = M
+        if plan is not None:
+            if win_lo is None or plan.rows is None or tuple(plan.band.shape) != (B, T, 2) or plan.U1 != U1:
+                raise ValueError("the band plan needs windows, finish() and the lattice's shape [%d, %d, %d]" % (B, T, U1))
+            return _JointLossFn._forward_band(ctx, enc, dec, w1, b1, w2, b2, labels, al_d, ll_d, blank, cd,
+                                              fastemit_lambda, win_lo, win_hi, plan, M)
+        ops.LAST["joint_packed_rows"] = M
+        ctx.plan = None
         w1c = WEIGHTS.get(w1, cd)
         w2c = WEIGHTS.get(w2, cd)
         enc2 = enc.reshape(B * T, P)
@@ -455,7 +469,6 @@ class _JointLossFn(torch.autograd.Function):
         with ops.timed("joint_hidden_fwd"):
             _lib.call("joint_hidden_fwd_packed", _lib.dtype_code(cd), E1, D1, hid, al_d, ll_d, off_d,
                       B, T, U1, J)
-        ops.LAST["joint_rows"] = M
         restricted = win_lo is not None
         if restricted:
             band = torch.empty(B, T, 2, dtype=torch.int32, device=dev)
@@ -505,8 +518,116 @@ class _JointLossFn(torch.autograd.Function):
         return reduced
 
     @staticmethod
+    def _forward_band(ctx, enc, dec, w1, b1, w2, b2, labels, al_d, ll_d, blank, cd, fastemit_lambda, win_lo, win_hi,
+                      plan, M_box):
+        """forward() on the band rows of ``plan``: the same chain with M = plan.rows and the *_band entry points."""
+        B, T, P = enc.shape
+        U1, P2 = dec.shape[1], dec.shape[2]
+        J, V = w1.shape[0], w2.shape[0]
+        dev = enc.device
+        M = plan.rows
+        ops.LAST["joint_packed_rows"] = M
+        ops.LAST["joint_band_rows"] = plan.cells.sum()
+        ctx.plan = plan
+        ctx.b1, ctx.b2 = b1, b2
+        ctx.cfg = (cd, B, T, U1, P, P2, J, V, M, int(blank))
+        ctx.fastemit_lambda = float(fastemit_lambda)
+        ctx.restricted = True
+        enc2 = enc.reshape(B * T, P)
+        dec2 = dec.reshape(B * U1, P2)
+        if M == 0:
+            # no utterance has a window-respecting alignment: no product, no band kernel; +inf and zero gradients
+            ops.LAST["joint_costs"] = torch.full((B,), float("inf"), dtype=F32, device=dev)
+            ctx.save_for_backward(enc2, dec2, w1, w2)
+            return torch.full((1,), float("inf"), dtype=F32, device=dev)
+        w1c = WEIGHTS.get(w1, cd)
+        w2c = WEIGHTS.get(w2, cd)
+        E1 = ops.gemm(enc2, w1c[:, :P])
+        D1 = ops.gemm(dec2, w1c[:, P:], bias=b1.detach())
+        hid = torch.empty(M, J, dtype=cd, device=dev)
+        with ops.timed("joint_hidden_fwd"):
+            _lib.call("joint_hidden_fwd_band", _lib.dtype_code(cd), E1, D1, hid, plan.band, plan.row_off, ops._ll(M),
+                      B, T, U1, J)
+        lib = _lib.load()
+        ws = torch.empty(lib.edgedict_rnnt_workspace_bytes(B, T, U1), dtype=torch.uint8, device=dev)
+        costs = torch.empty(B, dtype=F32, device=dev)
+        reduced = torch.empty(1, dtype=F32, device=dev)
+        tables = (plan.band, plan.row_off, plan.row_tu, plan.cells)
+        if config.FUSED_LSE and cd == torch.bfloat16 and J >= 128 and J % 64 == 0 and V % 8 == 0 and M >= 256:
+            slots = (V + 63) // 64
+            parts = torch.empty(M, slots, 2, dtype=F32, device=dev)
+            logits = torch.empty(M, V, dtype=cd, device=dev)
+            ops.fire("before_logits_gemm")
+            with ops.timed("joint_logits_gemm"):
+                _lib.call("gemm_nt_lse", hid, ops._ll(J), w2c, ops._ll(J), logits, ops._ll(V), M, V, J,
+                          b2.detach(), parts)
+            with ops.timed("rnnt_loss_fwd"):
+                _lib.call("rnnt_loss_forward_band_parts", logits, labels, al_d, ll_d, win_lo, win_hi, *tables,
+                          B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws, parts, slots)
+        else:
+            with ops.timed("joint_logits_gemm"):
+                logits = ops.gemm(hid, w2c, bias=b2.detach())
+            _lib.call("rnnt_loss_forward_band", logits, _lib.dtype_code(cd), labels, al_d, ll_d, win_lo, win_hi, *tables,
+                      B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws)
+        ops.LAST["joint_costs"] = costs
+        ctx.save_for_backward(enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, ws)
+        return reduced
+
+    @staticmethod
+    def _backward_band(ctx, gout):
+        plan = ctx.plan
+        cd, B, T, U1, P, P2, J, V, M, blank = ctx.cfg
+        tail = (None,) * 9
+        if M == 0:
+            enc2, dec2, w1, w2 = ctx.saved_tensors
+            with side.WeightGrads(ctx, 2, (w1, ctx.b1, w2, ctx.b2)) as wg:
+                for i in range(4):
+                    wg.zero(i)
+            ops.mark("joint_bwd:exit")
+            return (torch.zeros(B, T, P, dtype=enc2.dtype, device=enc2.device),
+                    torch.zeros(B, U1, P2, dtype=dec2.dtype, device=dec2.device), *wg.grads, *tail)
+        enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, ws = ctx.saved_tensors
+        dl = torch.empty_like(logits)
+        gscale = gout.contiguous().float()
+        w1c = WEIGHTS.get(w1, cd)
+        w2t = WEIGHTS.get(w2, cd, transposed=True)
+        dE1 = torch.empty(B, T, J, dtype=F32, device=dl.device)
+        dD1 = torch.empty(B, U1, J, dtype=F32, device=dl.device)
+        cs_rows = _lib.load().edgedict_rnnt_grad_colsum_rows(_lib.dtype_code(cd), B, T, U1, V) if config.FUSED_DB2 else 0
+        db2_parts = torch.empty(cs_rows, V, dtype=F32, device=dl.device) if cs_rows > 0 else None
+        rows = (plan.row_off, plan.row_tu, plan.cells)
+        with ops.timed("rnnt_grad"):
+            if db2_parts is not None:
+                _lib.call("rnnt_loss_backward_band_colsum", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d, *rows,
+                          B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, ctx.fastemit_lambda)
+            else:
+                _lib.call("rnnt_loss_backward_band", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d, *rows,
+                          B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, ctx.fastemit_lambda)
+        del logits
+        with ops.timed("joint_dhid_gemm"):
+            dhid = ops.gemm(dl, w2t)
+        with ops.timed("joint_hidden_bwd"):
+            _lib.call("joint_hidden_bwd_band", _lib.dtype_code(cd), dhid, hid, dE1, dD1, plan.band, plan.row_off,
+                      ops._ll(M), B, T, U1, J)
+        del dhid
+        dE1c = ops.cast(dE1, cd).view(B * T, J)
+        dD1c = ops.cast(dD1, cd).view(B * U1, J)
+        denc = ops.gemm(dE1c, w1c[:, :P].t()).view(B, T, P)
+        ddec = ops.gemm(dD1c, w1c[:, P:].t()).view(B, U1, P2)
+        with side.WeightGrads(ctx, 2, (w1, ctx.b1, w2, ctx.b2), dl, hid, dE1c, dD1c, dD1, enc2, dec2, db2_parts) as wg:
+            wg.gemm(2, dl.t(), hid.t(), split_k=ops.pick_split_k(V, J, M), aux=dict(split_k=8, max_wg_per_cu=2))
+            wg.colsum(3, dl if db2_parts is None else db2_parts)
+            wg.gemm(0, dE1c.t(), enc2.t(), cols=slice(None, P), split_k=ops.pick_split_k(J, P, B * T))
+            wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
+            wg.colsum(1, dD1.view(B * U1, J))
+        ops.mark("joint_bwd:exit")
+        return (denc, ddec, *wg.grads, *tail)
+
+    @staticmethod
     def backward(ctx, gout):
         ops.mark("joint_bwd:enter")
+        if ctx.plan is not None:
+            return _JointLossFn._backward_band(ctx, gout)
         enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, off_d, ws = ctx.saved_tensors
         cd, B, T, U1, P, P2, J, V, M, blank = ctx.cfg
         dl = torch.empty_like(logits)
@@ -562,7 +683,7 @@ class _JointLossFn(torch.autograd.Function):
             wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
             wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return (denc, ddec, *wg.grads, None, None, None, None, None, None, None, None)
+        return (denc, ddec, *wg.grads, None, None, None, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -738,6 +859,12 @@ class Encoder(nn.Module):
         if has_proj:
             self.proj = _LinearParams(hidden_size, proj_size)
 
+    def output_frames(self, T):
+        """Frames the encoder returns for ``T`` input frames (every time reduction rounds up)."""
+        for r in self.lstm.reductions:
+            T = (T + r - 1) // r
+        return T
+
     def forward(self, xs, hiddens=None):
         require_cuda(xs)
         cd = getattr(self, "compute_dtype", None) or config.get_compute_dtype()
@@ -804,9 +931,7 @@ def _stream_encoder_step(enc, xs, hiddens):
     b_hh = [m.layer(0)[3].detach() for m in lstm.lstms]
     g = [p[0].weight.detach() for p in lstm.projs]
     bt = [p[0].bias.detach() for p in lstm.projs]
-    T_out = T
-    for r in lstm.reductions:
-        T_out = (T_out + r - 1) // r
+    T_out = enc.output_frames(T)
     out = torch.empty(B, T_out, H, dtype=cd, device=dev)
     lib = _lib.load()
     ws = torch.empty(lib.edgedict_stream_encoder_workspace_bytes(B, T, I0, H, L), dtype=torch.uint8, device=dev)
@@ -926,9 +1051,26 @@ class Transducer(nn.Module):
 
     def scale_length(self, logits, xlen):
         # rnnt/models.py:223-226 (host-side integer logic on a [B] tensor)
-        scale = (xlen.max().float() / logits.shape[1]).ceil()
+        return self._scale_to(logits.shape[1], xlen)
+
+    @staticmethod
+    def _scale_to(T, xlen):
+        """scale_length's arithmetic for an encoder output of ``T`` frames."""
+        scale = (xlen.max().float() / T).ceil()
         xlen = (xlen / scale).ceil().int()
         return xlen
+
+    def _band_plan(self, xs, xlen, ylen, lo, hi):
+        """Start the band plan of forward() (config.BAND_LATTICE): it depends on the windows and the lengths only, so
+        its device work and the copy of its row total are enqueued BEFORE the encoder - forward() picks the total up
+        (``plan.finish()``: one event, recorded in front of the encoder) once the encoder and the prediction network
+        are enqueued."""
+        from ._staging import to_device
+        from .loss import rnnt_band_plan
+        T = self.encoder.output_frames(xs.shape[1])
+        al_d = to_device(self._scale_to(T, xlen).to(torch.int32), xs.device)
+        ll_d = to_device(ylen.to(torch.int32), xs.device)
+        return rnnt_band_plan(lo, hi, al_d, ll_d, T, finish=False)
 
     def _windows(self, windows, B, U, device):
         """``windows=(lo, hi)`` of forward() / align(): int32 [B, >= U] device tensors, cut to the label columns in use
@@ -953,6 +1095,11 @@ class Transducer(nn.Module):
             # a host-side label batch (seq_collate output with only xs uploaded): one upload here,
             # the prediction network and the loss kernels both read the device copy
             ys = ys.to(xs.device, non_blocking=True)
+        plan = checked = None
+        if (windows is not None and config.BAND_LATTICE and config.PACKED_LATTICE and not xlen.is_cuda
+                and not ylen.is_cuda and xs.dim() == 3 and xs.is_cuda):
+            checked = self._windows(windows, ys.shape[0], ys.shape[1], xs.device)
+            plan = self._band_plan(xs, xlen, ylen, *checked)
         if config.DECODER_ON_AUX_STREAM and xs.is_cuda:
             # the prediction network does not depend on the encoder: it runs on the auxiliary
             # stream under the encoder's recurrences.  Autograd replays each node on its forward
@@ -991,9 +1138,14 @@ class Transducer(nn.Module):
                 loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias,
                                           l2.weight, l2.bias, labels, act, ylen, self.blank, cd, self.fastemit_lambda)
             else:
-                lo, hi = self._windows(windows, labels.shape[0], labels.shape[1], h_enc.device)
+                lo, hi = checked or self._windows(windows, labels.shape[0], labels.shape[1], h_enc.device)
+                if plan is not None:
+                    if plan.band.shape[1] != h_enc.shape[1]:
+                        raise RuntimeError("band plan built for %d encoder frames, the encoder returned %d"
+                                           % (plan.band.shape[1], h_enc.shape[1]))
+                    plan.finish()                # the one host read: an event in front of the encoder's work
                 loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias, l2.weight, l2.bias,
-                                          labels, act, ylen, self.blank, cd, self.fastemit_lambda, lo, hi)
+                                          labels, act, ylen, self.blank, cd, self.fastemit_lambda, lo, hi, plan)
             ops.mark("joint:exit")
             return loss
         logits = self.joint(h_enc, h_dec)

@@ -124,6 +124,11 @@ class WeightGrads:
             kw = aux if self.defer and aux is not None else {"split_k": split_k}
             ops.gemm(a, b, out=out if cols is None else out[:, cols], accumulate=self.defer, **kw)
 
+    def zero(self, i):
+        """grad_i (+)= 0: a fresh zero tensor, or the .grad buffer as it is."""
+        if self.need[i]:
+            self._out(i, torch.zeros)
+
     def colsum(self, i, x):
         """grad_i (+)= the column sums of ``x``."""
         if self.need[i]:

@@ -252,6 +252,44 @@ int edgedict_rnnt_alignment_windows(const int32_t* frames, const int32_t* act_le
  * U1 <= 2048. */
 int edgedict_rnnt_band(const int32_t* win_lo, const int32_t* win_hi, const int32_t* act_lens, const int32_t* label_lens,
                        int B, int T, int U1, int32_t* band, long long* cells, void* stream);
+/* ---- band-packed lattice: joint + loss on the live cells of the band table only (edgedict_rnnt_band).
+ * Band row of a live cell: row(b,t,u) = row_off[b][t] + (u - ulo[b][t]), ulo <= u <= uhi; rows of a frame, frames of an
+ * utterance and utterances follow each other; an utterance without an alignment owns no rows.
+ *   edgedict_rnnt_band_offsets: row_off [B, T] int64 out = exclusive prefix sum of the widths max(0, uhi - ulo + 1) in
+ *                               (b, t) order; total [1] int64 out = M_band (= sum of cells)
+ *   edgedict_rnnt_band_rows:    row_tu [rows] int32 out = t << 16 | u of every band row (T, U1 < 65536) */
+int edgedict_rnnt_band_offsets(const int32_t* band, const long long* cells, int B, int T, long long* row_off,
+                               long long* total, void* stream);
+int edgedict_rnnt_band_rows(const int32_t* band, const long long* row_off, int B, int T, int U1, long long rows,
+                            int32_t* row_tu, void* stream);
+/* The *_packed_ar forward entry points with acts (and lse_parts) on band rows [M_band, .].  Every cell of the boxes
+ * gets its workspace planes: a live cell exactly as the *_ar kernels form them, a dead cell lp_blank = lp_label = -inf
+ * and denominator 0; alpha and beta on live cells, the likelihoods and the costs are the *_packed_ar path's. */
+int edgedict_rnnt_loss_forward_band(const void* acts, int acts_dtype, const int32_t* labels, const int32_t* act_lens,
+                                    const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi,
+                                    const int32_t* band, const long long* row_off, const int32_t* row_tu,
+                                    const long long* cells, int B, int T, int U1, int V, int blank, float* costs,
+                                    float* reduced, float reduce_scale, void* workspace, void* stream);
+int edgedict_rnnt_loss_forward_band_parts(const void* acts, const int32_t* labels, const int32_t* act_lens,
+                                          const int32_t* label_lens, const int32_t* win_lo, const int32_t* win_hi,
+                                          const int32_t* band, const long long* row_off, const int32_t* row_tu,
+                                          const long long* cells, int B, int T, int U1, int V, int blank, float* costs,
+                                          float* reduced, float reduce_scale, void* workspace, const float* lse_parts,
+                                          int lse_slots, void* stream);
+/* Backward of a workspace a *_band forward call filled: acts and grads on band rows, every row a live cell (the live-cell
+ * arithmetic of the *_ar kernels; no zero rows exist).  The colsum form writes all
+ * edgedict_rnnt_grad_colsum_rows(...) partial rows, zeros where a workgroup had no rows. */
+int edgedict_rnnt_loss_backward_band(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                     const int32_t* act_lens, const int32_t* label_lens, const long long* row_off,
+                                     const int32_t* row_tu, const long long* cells, int B, int T, int U1, int V, int blank,
+                                     const void* workspace, float grad_scale_host, const float* grad_scale_dev,
+                                     int grad_scale_stride, float fastemit_lambda, void* stream);
+int edgedict_rnnt_loss_backward_band_colsum(const void* acts, int acts_dtype, void* grads, const int32_t* labels,
+                                            const int32_t* act_lens, const int32_t* label_lens, const long long* row_off,
+                                            const int32_t* row_tu, const long long* cells, int B, int T, int U1, int V,
+                                            int blank, const void* workspace, float grad_scale_host,
+                                            const float* grad_scale_dev, int grad_scale_stride, float* colsum_parts,
+                                            float fastemit_lambda, void* stream);
 /* debug / test accessors into a filled workspace (device pointers):
  * which: 0 = log-softmax denominators f32[B,T,U1], 1 = alphas f64[B,T,U1], 2 = betas f64,
  * 3 = log-likelihoods f64[B,2] (alpha-side, beta-side), 4 = lp_blank f32[B,T,U1], 5 = lp_label */
@@ -594,6 +632,13 @@ int edgedict_joint_hidden_bwd_packed(int dtype, const void* dhid, const void* hi
                                      float* dD1, const int32_t* act_lens, const int32_t* label_lens,
                                      const long long* row_offsets, int B, int T, int U1, int J,
                                      void* stream);
+/* band-packed forms (see edgedict_rnnt_band_offsets): hid / dhid hold the `rows` live cells only; dE1 rows of frames
+ * without a live cell and dD1 rows of columns that are never alive come out as zeros. */
+int edgedict_joint_hidden_fwd_band(int dtype, const void* E1, const void* D1, void* hid, const int32_t* band,
+                                   const long long* row_off, long long rows, int B, int T, int U1, int J, void* stream);
+int edgedict_joint_hidden_bwd_band(int dtype, const void* dhid, const void* hid, float* dE1, float* dD1,
+                                   const int32_t* band, const long long* row_off, long long rows, int B, int T, int U1,
+                                   int J, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Optimiser step on flat fp32 buffers (torch.optim.Adam semantics, cli/train.py:135-146,268)
