@@ -56,6 +56,8 @@ def load():
         lib.edgedict_last_error.restype = ctypes.c_char_p
         lib.edgedict_rnnt_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_rnnt_workspace_view.restype = ctypes.c_void_p
+        lib.edgedict_ctc_workspace_bytes.restype = ctypes.c_size_t
+        lib.edgedict_ctc_workspace_view.restype = ctypes.c_void_p
         lib.edgedict_greedy_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_stream_state_bytes.restype = ctypes.c_size_t

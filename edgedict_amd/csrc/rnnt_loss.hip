@@ -193,23 +193,7 @@ __global__ __launch_bounds__(256) void rnnt_lse_from_parts(
     }
 }
 
-// log(exp(a)+exp(b)) with float64 carry: only the add/sub/max are fp64, the correction term
-// log(1 + exp(-|a-b|)) in [0, ln 2] is evaluated in fp32 on the hardware transcendental units (v_exp_f32 /
-// v_log_f32, ~1 ulp each: abs error ~1e-7, the same order as libm's log1pf(expf(.)) - whose ~100 dependent
-// instructions were 90 % of a lattice step: the recurrence is a chain of T + U of these)
-__device__ __forceinline__ double log_add64(double a, double b) {
-    const double m = fmax(a, b);
-    if (m == -(double)INFINITY) return m;
-    const float d = (float)(fmin(a, b) - m);  // <= 0, may be -inf
-    // 1 + x rounds to 1 below x ~ 6e-8 and carries 6e-8 of absolute rounding error wherever it is formed: a relative
-    // error of 6e-4 in the correction term at x = 1e-4, 6e-6 at 1e-2.  Below 1e-2 the series x - x^2 / 2 + x^3 / 3
-    // (truncation < x^4 / 4 = 2.5e-9 at the switch, where 1.f + x is already off by 6e-8) keeps what
-    // `__logf(1.f + x)` drops - over a chain of T + U log-adds the dropped terms were a one-sided bias (ADVICE r4 / r5;
-    // bounded by tests/test_rnnt_loss_gpu.py on a 1000 x 201 lattice)
-    const float x = __expf(d);
-    const float c = x < 1e-2f ? x * (1.f - x * (0.5f - x * (1.f / 3.f))) : __logf(1.f + x);
-    return m + (double)c;
-}
+// (log_add64 - the log-add with float64 carry every lattice walk below uses - lives in common.hpp: ctc_loss.hip shares it)
 
 // ------------------------------------------------------------------ kernel 2
 // ONE WAVE per (utterance, direction): blockIdx.x = 2*b + dir (dir 0: alpha, dir 1: beta), 64 threads.  Lane l owns

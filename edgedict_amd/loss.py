@@ -29,6 +29,9 @@ gradient - a ``'mean'`` or ``'sum'`` reduction is then ``+inf`` as well - decide
 ``alignment_windows`` builds windows from an alignment (``rnnt_align``'s frames, or an outside aligner's),
 ``rnnt_band`` the table of lattice cells that stay alive under them, ``rnnt_band_plan`` the row layout that packs the
 joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`` under ``config.BAND_LATTICE``).
+
+``CTCLoss`` / ``ctc_greedy`` (csrc/ctc_loss.hip) are the loss and the greedy decoder of the encoder's CTC auxiliary head
+(``Transducer(ctc_weight=...)``): raw head logits ``[B, T, V]``, not in the reference.
 """
 import ctypes
 import math
@@ -342,3 +345,160 @@ def rnnt_loss_debug(acts, labels, act_lens, label_lens, blank=0, *, windows=None
 
     return (costs, view(0, (B, T, U1), torch.float32), view(1, (B, T, U1), torch.float64),
             view(2, (B, T, U1), torch.float64), view(3, (B, 2), torch.float64))
+
+
+# ------------------------------------------------------------------------------------------------ CTC
+# The auxiliary head's loss (csrc/ctc_loss.hip): raw head logits [B, T, V], the extended sequence of 2 U + 1 states.
+
+
+def _certify_ctc_inputs(logits, labels, act_lens, label_lens, check_lengths):
+    # error classes / wording of _certify_inputs
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+    for name, t in (("labels", labels), ("act_lens", act_lens), ("label_lens", label_lens)):
+        if t.dtype != torch.int32:
+            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
+    for name, t in (("logits", logits), ("labels", labels), ("act_lens", act_lens), ("label_lens", label_lens)):
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if logits.dim() != 3:
+        raise ValueError("logits must have 3 dimensions [B,T,V], got %d" % logits.dim())
+    if labels.dim() != 2:
+        raise ValueError("labels must have 2 dimensions [B,U], got %d" % labels.dim())
+    if act_lens.dim() != 1 or label_lens.dim() != 1:
+        raise ValueError("act_lens and label_lens must have 1 dimension")
+    B, T, _ = logits.shape
+    if act_lens.shape[0] != B:
+        raise ValueError("must have a length per example (act_lens has %d, batch is %d)" % (act_lens.shape[0], B))
+    if label_lens.shape[0] != B or labels.shape[0] != B:
+        raise ValueError("must have a label length per example")
+    if check_lengths:  # one host sync, as _certify_inputs
+        if int(act_lens.max()) != T:
+            raise ValueError("Input length mismatch")
+        if int(label_lens.max()) != labels.shape[1]:
+            raise ValueError("Output length mismatch")
+
+
+class _CTCLossFn(torch.autograd.Function):
+    """The shape of ``_RNNTLossFn``: forward fills the workspace, backward writes the scaled gradient once."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, act_lens, label_lens, blank, reduction, zero_infinity):
+        _lib.require_cuda(logits, labels, act_lens, label_lens)
+        B, T, V = logits.shape
+        U = labels.shape[1]
+        lib = _lib.load()
+        ws = torch.empty(lib.edgedict_ctc_workspace_bytes(B, T, U), dtype=torch.uint8, device=logits.device)
+        costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+        reduced = torch.empty(1, dtype=torch.float32, device=logits.device)
+        scale = 1.0 / B if reduction == "mean" else 1.0
+        _lib.call("ctc_loss_forward", logits, _lib.dtype_code(logits.dtype), labels if U else None, act_lens,
+                  label_lens, B, T, U, V, int(blank), bool(zero_infinity), costs, reduced, float(scale), ws)
+        ctx.save_for_backward(logits, labels, act_lens, label_lens, ws)
+        ctx.blank = int(blank)
+        ctx.reduction = reduction
+        ctx.costs = costs
+        return costs if reduction == "none" else reduced
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        logits, labels, act_lens, label_lens, ws = ctx.saved_tensors
+        B, T, V = logits.shape
+        U = labels.shape[1]
+        grads = torch.empty_like(logits)
+        go = grad_output.contiguous().float()
+        host_scale = 1.0 / B if ctx.reduction == "mean" else 1.0
+        stride = 1 if ctx.reduction == "none" else 0
+        _lib.call("ctc_loss_backward", logits, _lib.dtype_code(logits.dtype), grads, labels if U else None, act_lens,
+                  label_lens, B, T, U, V, ctx.blank, ws, float(host_scale), go, stride)
+        return grads, None, None, None, None, None, None
+
+
+class CTCLoss(torch.nn.Module):
+    """CTC loss on raw logits (the auxiliary head of ``Transducer(ctc_weight=...)``).
+
+    ``forward(logits, labels, act_lens, label_lens)``: ``logits`` float32 / bfloat16 ``[B, T, V]`` raw (NOT
+    log-softmaxed) and contiguous, ``labels`` int32 ``[B, U]`` (symbols other than ``blank``), ``act_lens`` /
+    ``label_lens`` int32 ``[B]``; differentiable with respect to ``logits``.  Device tensors only: there is no CPU
+    fallback.
+
+    ``reduction``: ``'mean'`` (default) is ``sum_b cost_b / B`` with shape ``(1,)`` - what ``RNNTLoss`` calls the mean,
+    NOT ``torch.nn.functional.ctc_loss``'s mean, which first divides every cost by its target length; ``'sum'`` (shape
+    ``(1,)``) or ``'none'`` (shape ``(B,)``).
+
+    An utterance with no path (fewer frames than labels plus adjacent repeats) has cost ``+inf`` and a zero gradient;
+    ``zero_infinity=True`` makes that cost 0 (the gradient stays zero), decided on the device without a host sync.
+    ``check_lengths=True`` asks ``max(act_lens) == T`` and ``max(label_lens) == U`` (one host sync), as ``RNNTLoss``.
+    """
+
+    def __init__(self, blank=0, reduction="mean", check_lengths=True, zero_infinity=False):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+        self.blank = blank
+        self.reduction = reduction
+        self.check_lengths = check_lengths
+        self.zero_infinity = bool(zero_infinity)
+
+    def forward(self, logits, labels, act_lens, label_lens):
+        _certify_ctc_inputs(logits, labels, act_lens, label_lens, self.check_lengths)
+        return _CTCLossFn.apply(logits, labels, act_lens, label_lens, self.blank, self.reduction, self.zero_infinity)
+
+
+@torch.no_grad()
+def ctc_greedy(logits, act_lens, blank=0):
+    """CTC greedy decoding of head logits ``[B, T, V]`` (float32 / bfloat16, contiguous, device): per frame
+    ``t < act_lens[b]`` the arg max (lowest index on ties); a frame is kept iff its symbol is not ``blank`` and differs
+    from the frame before.  Returns device tensors ``(tokens, counts, frames, neglogp)``: ``tokens`` / ``frames`` int32
+    ``[B, T]`` (kept symbols and their frame indices, -1 behind ``counts[b]``), ``counts`` int32 ``[B]``, ``neglogp``
+    float32 ``[B]`` (minus the summed log-probabilities of the kept frames' symbols).  No host sync."""
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+    if act_lens.dtype != torch.int32:
+        raise TypeError("act_lens must be int32, got %s" % act_lens.dtype)
+    if logits.dim() != 3:
+        raise ValueError("logits must have 3 dimensions [B,T,V], got %d" % logits.dim())
+    if not logits.is_contiguous() or not act_lens.is_contiguous():
+        raise ValueError("logits and act_lens must be contiguous")
+    if act_lens.dim() != 1 or act_lens.shape[0] != logits.shape[0]:
+        raise ValueError("must have a length per example (act_lens has %s, batch is %d)"
+                         % (tuple(act_lens.shape), logits.shape[0]))
+    _lib.require_cuda(logits, act_lens)
+    B, T, V = logits.shape
+    dev = logits.device
+    tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
+    frames = torch.empty(B, T, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    neglogp = torch.empty(B, dtype=torch.float32, device=dev)
+    scratch = torch.empty(2 * B * T, dtype=torch.int32, device=dev)
+    _lib.call("ctc_greedy", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, int(blank), tokens,
+              counts, frames, neglogp, scratch)
+    return tokens, counts, frames, neglogp
+
+
+def ctc_loss_debug(logits, labels, act_lens, label_lens, blank=0):
+    """Test hook: run the CTC forward and return (costs, log-sum-exps [B,T], alphas, betas [B,T,2U+1], loglikes [B,2]).
+    beta(t,s) does not contain frame t's own log-probability (csrc/ctc_loss.hip); entries outside an utterance's
+    ``[T_b, 2 U_b + 1]`` box are zeros."""
+    _lib.require_cuda(logits)
+    B, T, V = logits.shape
+    U = labels.shape[1]
+    lib = _lib.load()
+    ws = torch.zeros(lib.edgedict_ctc_workspace_bytes(B, T, U), dtype=torch.uint8, device=logits.device)
+    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+    _lib.call("ctc_loss_forward", logits, _lib.dtype_code(logits.dtype), labels if U else None, act_lens, label_lens,
+              B, T, U, V, int(blank), False, costs, None, 1.0, ws)
+    base = ws.data_ptr()
+
+    def view(which, shape, dtype):
+        p = lib.edgedict_ctc_workspace_view(_lib.ptr(ws), B, T, U, which)
+        esz = 8 if dtype == torch.float64 else 4
+        off = (p - base) // esz
+        n = 1
+        for s in shape:
+            n *= s
+        return ws.view(dtype)[off:off + n].view(*shape).clone()
+
+    S = 2 * U + 1
+    return (costs, view(0, (B, T), torch.float32), view(1, (B, T, S), torch.float64),
+            view(2, (B, T, S), torch.float64), view(3, (B, 2), torch.float64))

@@ -1018,9 +1018,14 @@ class Transducer(nn.Module):
                  enc_hidden_size, enc_layers, enc_dropout, enc_proj_size,
                  dec_hidden_size, dec_layers, dec_dropout, dec_proj_size,
                  joint_size, enc_time_reductions=[1],
-                 blank=NUL, module_type='LSTM', output_loss=True, *, fastemit_lambda=0.0):
+                 blank=NUL, module_type='LSTM', output_loss=True, *, fastemit_lambda=0.0, ctc_weight=0.0):
         super().__init__()
         self.blank = blank
+        # CTC auxiliary head (loss.CTCLoss): forward() returns rnnt + ctc_weight * ctc.  A plain attribute that may be
+        # changed later; the head's parameters exist iff it is > 0 HERE (registered last, below), and at 0 forward()
+        # skips the branch entirely - the launches, parameters and state-dict keys of a model without it.
+        self.ctc_weight = self._check_ctc_weight(ctc_weight)
+        self.loss_parts = None
         # FastEmit (loss.py): a plain attribute - no parameter, no buffer, the state dict's keys do not change.  Scales
         # the gradient through the label emissions by 1 + lambda; the loss forward() returns stays the plain one.
         from .loss import check_fastemit_lambda
@@ -1037,6 +1042,15 @@ class Transducer(nn.Module):
         self.joint = Joint(input_size=enc_proj_size + dec_proj_size, hidden_size=joint_size,
                            vocab_size=vocab_size)
         self.output_loss = output_loss
+        if self.ctc_weight > 0:
+            self.ctc_head = _LinearParams(enc_proj_size, vocab_size)
+
+    @staticmethod
+    def _check_ctc_weight(value):
+        w = float(value)
+        if not (w >= 0.0 and math.isfinite(w)):
+            raise ValueError("ctc_weight must be finite and >= 0, got %r" % (value,))
+        return w
 
     # compute dtype shared with the sub-modules -----------------------------------------
     @property
@@ -1083,6 +1097,51 @@ class Transducer(nn.Module):
             lo, hi = lo[:, :U].contiguous(), hi[:, :U].contiguous()
         return check_windows((lo, hi), B, U, device)
 
+    def _ctc_logits(self, h_enc):
+        """Head logits [B, T', V] of the encoder output (the GEMM front door, in the compute dtype)."""
+        head = getattr(self, "ctc_head", None)
+        if head is None:
+            raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+        cd = self.compute_dtype
+        return _LinearFn.apply(_to_cd(h_enc, cd), head.weight, head.bias, cd)
+
+    def _ctc_loss(self, h_enc, ys, act, ylen):
+        """The auxiliary term of forward(): CTC 'mean' loss of the head on ``h_enc`` with the frame counts ``act`` of
+        ``scale_length``.  zero_infinity: time reduction can leave a short utterance fewer frames than its labels plus
+        repeats, and an auxiliary term must not turn the logged loss into +inf.  No host sync."""
+        from ._staging import to_device
+        from .loss import _CTCLossFn
+        dev = h_enc.device
+        logits = self._ctc_logits(h_enc).contiguous()
+
+        def lens(t):
+            if t.is_cuda:
+                return t.to(device=dev, dtype=torch.int32).contiguous()
+            return to_device(t.to(torch.int32), dev)
+
+        labels = ys.to(device=dev, dtype=torch.int32).contiguous()
+        return _CTCLossFn.apply(logits, labels, lens(act), lens(ylen), self.blank, "mean", True)
+
+    def _with_ctc(self, rnnt, ctc):
+        self.loss_parts = (rnnt.detach(), ctc.detach())
+        return rnnt + self.ctc_weight * ctc
+
+    @torch.no_grad()
+    def ctc_greedy_decode(self, xs, xlen):
+        """First-pass decode from the encoder alone: encoder, CTC head, ``loss.ctc_greedy`` - neither the prediction
+        network nor the joint runs.  Returns (list of int64 numpy token arrays WITHOUT blanks, repeats collapsed;
+        -sum log p of the kept frames as a [B] tensor): the return shape of ``greedy_decode``.  Raises RuntimeError on
+        a model built without ``ctc_weight > 0``."""
+        from .loss import ctc_greedy
+        if getattr(self, "ctc_head", None) is None:
+            raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+        xs = xs[:, :xlen.max()].contiguous()
+        h_enc, _ = self.encoder(xs)
+        act = self.scale_length(h_enc, xlen).to(device=h_enc.device, dtype=torch.int32).contiguous()
+        tokens, counts, _, neglogp = ctc_greedy(self._ctc_logits(h_enc).contiguous(), act, self.blank)
+        tokens, counts = tokens.cpu().numpy(), counts.cpu().numpy()
+        return [tokens[b, :counts[b]].astype("int64") for b in range(tokens.shape[0])], neglogp
+
     def forward(self, xs, ys, xlen, ylen, *, windows=None):
         """The reference's forward (rnnt/models.py:209-241).  ``windows=(lo, hi)`` (keyword only): the
         alignment-restricted loss of ``loss.RNNTLoss`` on either loss path, in ENCODER frames as ``align`` counts them;
@@ -1124,6 +1183,9 @@ class Transducer(nn.Module):
         else:
             h_enc, _ = self.encoder(xs)
             h_dec, _ = self.decoder(ys)
+        # CTC auxiliary term: on the main stream, between the encoder and the joint; at weight 0 nothing is launched
+        use_ctc = self.output_loss and self.ctc_weight > 0
+        ctc = self._ctc_loss(h_enc, ys, self.scale_length(h_enc, xlen), ylen) if use_ctc else None
         ops.mark("joint:enter")
         if (self.output_loss and config.PACKED_LATTICE and not xlen.is_cuda and not ylen.is_cuda
                 and h_enc.dim() == 3 and h_enc.is_cuda):
@@ -1147,7 +1209,7 @@ class Transducer(nn.Module):
                 loss = _JointLossFn.apply(_to_cd(h_enc, cd), _to_cd(h_dec, cd), l1.weight, l1.bias, l2.weight, l2.bias,
                                           labels, act, ylen, self.blank, cd, self.fastemit_lambda, lo, hi, plan)
             ops.mark("joint:exit")
-            return loss
+            return self._with_ctc(loss, ctc) if use_ctc else loss
         logits = self.joint(h_enc, h_dec)
         ops.mark("joint:exit")
         if self.output_loss:
@@ -1160,7 +1222,7 @@ class Transducer(nn.Module):
                 xlen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
                 ylen.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous(),
                 self.blank, "mean", self.fastemit_lambda, *tail)
-            return loss
+            return self._with_ctc(loss, ctc) if use_ctc else loss
         return logits
 
     @torch.no_grad()

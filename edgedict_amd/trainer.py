@@ -49,7 +49,10 @@ class TrainEngine:
             from .transforms import SpecAugment
             self.spec_augment = SpecAugment(getattr(flags, "T_mask", 0), getattr(flags, "T_num_mask", 0),
                                             getattr(flags, "F_mask", 0), getattr(flags, "F_num_mask", 0))
-        self.model = Transducer(**model_kwargs(flags, vocab_size=vocab_size))
+        # CTC auxiliary head (models.Transducer): like FastEmit a flag of the training run - but its weight decides at
+        # construction whether the head's two tensors exist, so it has to be there before FlatParams lays them out
+        self.model = Transducer(**model_kwargs(flags, vocab_size=vocab_size),
+                                ctc_weight=getattr(flags, "ctc_weight", 0.0))
         # FastEmit (loss.py): a flag of the training run, not of the model's shape - model_kwargs does not carry it
         from .loss import check_fastemit_lambda
         self.model.fastemit_lambda = check_fastemit_lambda(getattr(flags, "fastemit_lambda", 0.0))

@@ -1157,6 +1157,49 @@ int edgedict_beam_stream_advance_detail_bias(int dtype, const void* E1, long lon
 int edgedict_log_softmax_rows(int x_dtype, const void* x, long long ldx, float* y, int M, int N,
                               void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * CTC loss (Graves et al. 2006) on the encoder's auxiliary head, and the CTC greedy decoder.  Not in the
+ * reference: the auxiliary term of  loss = rnnt + ctc_weight * ctc  (Transducer(ctc_weight=...)).
+ *
+ *   logits      [B, T, V]   raw head logits (NOT log-softmaxed), contiguous, dtype code
+ *   labels      [B, U]      int32, values in [0, V) other than blank, padded arbitrarily beyond label_lens[b]
+ *                           (nullable when U == 0)
+ *   act_lens    [B] int32   valid frames per utterance; rows t >= act_lens[b] are never read
+ *   label_lens  [B] int32   valid labels per utterance (0 <= label_lens[b] <= U); both are clamped to [0, T] / [0, U]
+ *   costs       [B] fp32    out: -log P(y|x) per utterance; +inf where no path exists (act_lens[b] <= 0, or fewer
+ *                           frames than labels + adjacent repeats) - with zero_infinity != 0 such a cost is 0
+ *   reduced     [1] fp32    out (nullable): reduce_scale * sum_b costs[b]  ('mean' => 1/B)
+ *   workspace   edgedict_ctc_workspace_bytes(B,T,U) bytes, 16-byte aligned; forward fills it (log-sum-exps, the
+ *               blank's and the labels' log-probabilities, fp64 alpha / beta over the 2U+1 states, log-likelihoods,
+ *               dead-utterance flags, same-label links) and backward reads it: keep it alive between the two.
+ *               beta(t,s) does NOT contain frame t's own log-probability: occupancy = exp(alpha + beta - ll).
+ *
+ * backward writes d(sum_b scale_b * cost_b)/d(logits) into grads (same shape / dtype as logits), scale_b as
+ * edgedict_rnnt_loss_backward defines it.  Rows t >= act_lens[b] and utterances without a path (or whose cost
+ * zero_infinity replaced) get exact zeros.  The gradient is bit-identical from run to run.
+ * Limits: U <= 1023, V >= 2; V*sizeof(dtype) a multiple of 16 for the vector path (other V take a scalar path).
+ * edgedict_ctc_workspace_view (debug reader): which = 0 log-sum-exp [B,T] f32, 1 alpha / 2 beta [B,T,2U+1] f64,
+ * 3 log-likelihoods [B,2] f64 (alpha side, beta side), 4 lp_blank [B,T] f32, 5 lp_label [B,T,U] f32,
+ * 6 dead flags [B] int32, 7 same-label links [B,2,U] int32.
+ *
+ * edgedict_ctc_greedy: k_t = arg max_v logits[b,t,:] (lowest index on ties) for t < act_lens[b]; frame t is kept iff
+ * k_t != blank and (t == 0 or k_t != k_{t-1}).  tokens / frames [B, T] int32: the kept symbols and their frame
+ * indices, -1 behind counts[b]; neglogp [B] fp32 = -sum over kept frames of log_softmax(logits[b,t])[k_t];
+ * scratch: 8 * B * T bytes.
+ */
+size_t edgedict_ctc_workspace_bytes(int B, int T, int U);
+const void* edgedict_ctc_workspace_view(const void* workspace, int B, int T, int U, int which);
+int edgedict_ctc_loss_forward(const void* logits, int dtype, const int32_t* labels, const int32_t* act_lens,
+                              const int32_t* label_lens, int B, int T, int U, int V, int blank, int zero_infinity,
+                              float* costs, float* reduced, float reduce_scale, void* workspace, void* stream);
+int edgedict_ctc_loss_backward(const void* logits, int dtype, void* grads, const int32_t* labels,
+                               const int32_t* act_lens, const int32_t* label_lens, int B, int T, int U, int V,
+                               int blank, const void* workspace, float grad_scale_host, const float* grad_scale_dev,
+                               int grad_scale_stride, void* stream);
+int edgedict_ctc_greedy(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V, int blank,
+                        int32_t* tokens, int32_t* counts, int32_t* frames, float* neglogp, void* scratch,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
