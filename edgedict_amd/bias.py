@@ -29,6 +29,10 @@ scores ``(base + lp_rnnt[k]) + D(s, k)``, with an LM ``((base + lp_rnnt[k]) + F)
 ``F = lm_weight * lp_lm[k] + length_bonus`` (fp64, in this order).  ``NBestResult.token_logp`` and ``logp`` include the
 bias increments (the detail is the difference of pool scores, so nothing else changes).
 
+The CTC prefix beam search (``decode.ctc_beam_search`` / ``loss.ctc_prefix_beam``, csrc/ctc_decode.hip) reads the same
+tables: a prefix carries the state AFTER its last token and the total ``score(tokens)``, which enters its ranking and
+its reported ``logp``; a frame's candidate list is cut before the bias is seen.
+
 Not in scope
 ------------
 * No output links: a phrase that occurs only INSIDE a longer partial match that then breaks is not credited.

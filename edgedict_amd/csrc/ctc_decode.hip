@@ -1,0 +1,519 @@
+// CTC prefix beam search on the encoder's CTC head for gfx950, with N-best read-out and contextual biasing.
+//
+// THE SEARCH (per utterance, scores are fp64 log-probabilities, -inf is zero).  A hypothesis is a node of a token tree
+// (parent, token, frame it was created on), node 0 the empty prefix.  It carries pb / pnb, the log-probability of its
+// paths that end in blank / in its last token; tot = logadd(pb, pnb).  The beam starts as [root: pb 0, pnb -inf].
+// For every frame t < T_b, with lp = log_softmax(z[b, t]):
+//   1. candidates  C_t = the K = min(cand, V - 1) non-blank tokens of largest lp, in that order (ties: lower id)
+//   2. stay        entry i (node n_i, last token e_i):  pb' = tot_i + lp[blank];  pnb' = pnb_i + lp[e_i] (not the root)
+//   3. extend      entry i, candidate c:  p = (c == e_i ? pb_i : tot_i) + lp[c];  if the prefix (n_i, c) is beam entry j
+//                  (node j has parent n_i and token c) then pnb'_j = logadd(pnb'_j, p), else it is a NEW candidate with
+//                  pb = -inf, pnb = p.  Nothing else is credited to a new prefix (no resurrection term).  A candidate
+//                  with p = -inf is no candidate.
+//   4. select      the W best by logadd(pb', pnb') (+ the node's bias total Bn); ties go to the lower canonical index:
+//                  the stays in beam order, then the new candidates in (i, c) order.  The new beam is in ranked order;
+//                  only selected new candidates become nodes, so a tree has at most 1 + T_b W nodes.
+// After the last frame the beam is the N-best list.  BIAS: a node carries the phrase automaton's state after its token,
+// s = goto(s(parent), token), and Bn = Bn(parent) + D(s(parent), token), D(s, k) = held[goto(s, k)] - pend[s]; Bn enters
+// the ranking and the reported logp only, pb / pnb stay pure CTC.  Pruning to C_t happens BEFORE the bias is seen.
+//
+// Kernels (no atomics, results bit-identical from run to run):
+//   ctc_beam_rows    : one wave64 per row (b, t < T_b), as ctc_lse_gather: the row's log-sum-exp (16-byte loads when
+//                      V * sizeof % 16 == 0), lp[blank], and the sorted top-K list (token, lp) by K passes of "the
+//                      largest element after the previous winner" over the row, which the first pass left in the
+//                      caches.  All O(V) work of the search is here, off the serial path.
+//   ctc_beam_walk    : ONE WAVE per utterance, all T_b frames inside the launch.  The per-frame working set (<= W (K + 1)
+//                      scores) and the double-buffered beam live in LDS; a one-wave workgroup's barrier orders its LDS
+//                      traffic and costs nothing to wait on.  A frame's candidate list, lse and lp[blank] do not depend
+//                      on the search and are requested D frames ahead; lp[e_i] of step 2 depends on the previous frame's
+//                      selection: it is requested the moment that selection is made and first used after the next
+//                      frame's extension step, so ONE dependent memory round trip per frame remains on the serial path,
+//                      partly covered.
+//   ctc_beam_readout : one wave per (utterance, hypothesis): walks the node to the root (its depth is known) and writes
+//                      the dense result arrays; everything behind a count is -1 / 0.
+#include "bias_tables.hpp"
+#include "common.hpp"
+#include "ctc_rows.hpp"
+
+namespace {
+
+constexpr int CB_MAXW = 32;    // beam width
+constexpr int CB_MAXC = 64;    // candidates per frame: one per lane of the row pass and of the walk
+constexpr int CB_NONE = 0x7fffffff;
+
+struct CbWs {
+    size_t off_lse, off_lpb, off_ctok, off_clp, off_nodes, off_fnode, off_fdepth, total;
+};
+
+inline size_t cb_up256(size_t n) { return ((n + 255) / 256) * 256; }
+
+// tree nodes of an utterance: the root and at most W per frame
+inline size_t cb_node_capacity(int T, int W) { return 1 + (size_t)T * W; }
+
+inline CbWs cb_ws(int B, int T, int W, int cand) {
+    CbWs w;
+    const size_t rows = (size_t)B * T;
+    size_t o = 0;
+    w.off_lse = o;    o += cb_up256(rows * sizeof(float));
+    w.off_lpb = o;    o += cb_up256(rows * sizeof(float));
+    w.off_ctok = o;   o += cb_up256(rows * cand * sizeof(int32_t));
+    w.off_clp = o;    o += cb_up256(rows * cand * sizeof(float));
+    // a node is (parent, token, frame, lp bits)
+    w.off_nodes = o;  o += cb_up256((size_t)B * cb_node_capacity(T, W) * sizeof(int4));
+    w.off_fnode = o;  o += cb_up256((size_t)B * W * sizeof(int32_t));
+    w.off_fdepth = o; o += cb_up256((size_t)B * W * sizeof(int32_t));
+    w.total = o;
+    return w;
+}
+
+// the automaton's tables under the names bias_tables.hpp reads them by
+struct CbBias {
+    const int32_t* bias_root_next;
+    const double* bias_held;
+    const double* bias_pend;
+    const int32_t* bias_row_ptr;
+    const int32_t* bias_exc_tok;
+    const int32_t* bias_exc_next;
+    int bias_S;
+};
+
+// max of a double over the wave, wave-uniform: the prefix-max inside each row of 16 lanes (row_shr:1, 2, 4, 8), then
+// lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast:15) and lane 31 into rows 2, 3 (row_bcast:31) - lane 63 holds the
+// maximum.  A lane without a source keeps its own value (`old` = the value, bound_ctrl off).  Six steps of two DPP moves
+// and one v_max_f64, against six steps of two ds_bpermute round trips for a butterfly.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double dpp_max64(double v) {
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROWS, 0xf, false);
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, ROWS, 0xf, false);
+    return fmax(v, __hiloint2double(hi, lo));
+}
+__device__ __forceinline__ double wave_max64(double v) {
+    v = dpp_max64<0x111, 0xf>(v);
+    v = dpp_max64<0x112, 0xf>(v);
+    v = dpp_max64<0x114, 0xf>(v);
+    v = dpp_max64<0x118, 0xf>(v);
+    v = dpp_max64<0x142, 0xa>(v);
+    v = dpp_max64<0x143, 0xc>(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
+                            __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
+template <int CTRL, int ROWS>
+__device__ __forceinline__ float dpp_max32(float v) {
+    const int o = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROWS, 0xf, false);
+    return fmaxf(v, __int_as_float(o));
+}
+__device__ __forceinline__ float wave_top(float v) {
+    v = dpp_max32<0x111, 0xf>(v);
+    v = dpp_max32<0x112, 0xf>(v);
+    v = dpp_max32<0x114, 0xf>(v);
+    v = dpp_max32<0x118, 0xf>(v);
+    v = dpp_max32<0x142, 0xa>(v);
+    v = dpp_max32<0x143, 0xc>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+__device__ __forceinline__ double wave_top(double v) { return wave_max64(v); }
+
+// The best (value, then lowest index) over the wave, wave-uniform: every lane brings its own best value bv and that
+// value's index bm (CB_NONE: the lane has nothing, whatever bv holds).  The lanes that hold the wave's maximum are
+// balloted and the lowest index among them is read out lane by lane - one lane unless values tie.  Returns the index
+// (CB_NONE: no lane has anything) and leaves the maximum in wv.  bv must not be a NaN.
+template <typename V>
+__device__ __forceinline__ int wave_pick(V bv, int bm, V& wv) {
+    wv = wave_top(bv);
+    unsigned long long tied = __ballot(bm != CB_NONE && bv == wv);
+    int wi = CB_NONE;
+    while (tied) {
+        const int l = __ffsll((long long)tied) - 1;
+        tied &= tied - 1;
+        wi = min(wi, __builtin_amdgcn_readlane(bm, l));
+    }
+    return wi;
+}
+
+// ------------------------------------------------------------------ the row pass
+// grid (x, B) as ctc_lse_gather: 4 waves per block, one row per wave per iteration, rows t >= T_b are never read.
+// Pass k of the top-K list finds the largest non-blank element AFTER the previous winner (pv, pi) in the order "value
+// descending, index ascending": x < pv, or x == pv with a higher index.  A lane sees its columns in ascending order and
+// replaces its best on a strictly larger value only; wave_pick prefers the value, then the lower index.  A NaN
+// compares false everywhere and is never a candidate; a list that runs out of elements is closed with token -1 / -inf.
+// Candidate k is kept by lane k, the list is written with one store per lane: ctok / clp [rows][cand], K used.
+template <typename T>
+__global__ __launch_bounds__(256) void ctc_beam_rows(const T* __restrict__ logits, const int32_t* __restrict__ act_lens,
+                                                     int Tm, int V, int blank, int K, int cand,
+                                                     float* __restrict__ lse, float* __restrict__ lpb,
+                                                     int32_t* __restrict__ ctok, float* __restrict__ clp, int vec_ok) {
+    constexpr int VEC = ElemIO<T>::VEC;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int Tb = max(0, min(act_lens[b], Tm));
+    for (int t = blockIdx.x * 4 + wave; t < Tb; t += gridDim.x * 4) {
+        const long long row = (long long)b * Tm + t;
+        const T* z = logits + row * (long long)V;
+        const float l = row_lse<T, false>(z, V, vec_ok, lane, nullptr, nullptr);
+        if (lane == 0) {
+            lse[row] = l;
+            lpb[row] = ElemIO<T>::load(z + blank) - l;
+        }
+        float pv = INFINITY;
+        int pi = -1;
+        int my_tok = -1;
+        float my_lp = -INFINITY;
+        for (int k = 0; k < K; ++k) {
+            float bv = -INFINITY;
+            int bi = CB_NONE;
+            auto see = [&](float x, int idx) {
+                const bool after = idx != blank && (x < pv || (x == pv && idx > pi));
+                if (after && (x > bv || bi == CB_NONE)) { bv = x; bi = idx; }
+            };
+            if (vec_ok) {
+                for (int v = lane * VEC; v < V; v += 64 * VEC) {
+                    float x[VEC];
+                    ElemIO<T>::load_vec(z + v, x);
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) see(x[i], v + i);
+                }
+            } else {
+                for (int v = lane; v < V; v += 64) see(ElemIO<T>::load(z + v), v);
+            }
+            float wv;
+            const int wi = wave_pick(bv, bi, wv);
+            if (lane == k) {
+                my_tok = wi == CB_NONE ? -1 : wi;
+                my_lp = wi == CB_NONE ? -INFINITY : wv - l;
+            }
+            pv = wi == CB_NONE ? -INFINITY : wv;      // (nothing found: after -inf / CB_NONE nothing is "after")
+            pi = wi;
+        }
+        if (lane < K) {
+            ctok[row * cand + lane] = my_tok;
+            clp[row * cand + lane] = my_lp;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the search
+// blockIdx.x = utterance, 64 threads.  LDS: the scores of the frame's items (stays 0 .. nb - 1 in beam order, then the
+// new candidates nb + i K + c: the canonical index of the tie rule), the beam twice (read `cur`, build `cur ^ 1`), the
+// stays' new pb / pnb, the frame's candidate list.  Per frame:
+//   C  every item (i, c): p and its ranking score into s_sc; lane (g, c) takes candidate c of the entries g, g + G, ...
+//      (K rounded up to a power of two Kp, G = 64 / Kp groups: no division per item)
+//   B  lane j < nb, stay j: pb', pnb' with lp[e_j] (the gather requested at the end of the previous frame, the same fp32
+//      expression z - lse the row pass formed, so a token of the list has the same bits either way and is taken from the
+//      list).  Where e_j stands in the candidate list: one ballot per entry, lane c holding candidate c; where j's
+//      parent stands in the beam: the entries' nodes read out of lane registers.  Entry j's parent can be in the beam
+//      once at most, so pnb'_j receives at most ONE extension - no order to fix - and that extension's item is struck
+//      from s_sc
+//   D  up to W rounds of (best, lowest index) over the wave (wave_pick).  Lane l owns the items l, l + 64, ...: up to
+//      R = 8 of them in registers, struck there when they win; a frame with more than 64 R items leaves them in LDS, a
+//      lane keeps the best of its own and only the round's winner looks at its items again
+//   E  lane r builds entry r of the new beam; new nodes take consecutive ids in ranked order (ballot + prefix count) and
+//      are written with one 16-byte store; the gather for the next frame is requested.
+// The ring q* holds lse, lp[blank] and lane l's candidate l of the D frames ahead (static slots, as ctc_alpha_beta).
+template <typename T, bool BIAS>
+__global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits, const int32_t* __restrict__ act_lens,
+                                                    int Tm, int V, int W, int K, int cand,
+                                                    const float* __restrict__ lse, const float* __restrict__ lpb,
+                                                    const int32_t* __restrict__ ctok, const float* __restrict__ clp,
+                                                    int4* __restrict__ nodes, int NC, int32_t* __restrict__ fnode,
+                                                    int32_t* __restrict__ fdepth, int32_t* __restrict__ n_hyp,
+                                                    double* __restrict__ logp, CbBias bt) {
+    constexpr int D = 4, R = 8;
+    __shared__ double s_sc[CB_MAXW * (CB_MAXC + 1)];
+    __shared__ double s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW], s_tot[2][CB_MAXW], s_bn[2][CB_MAXW];
+    __shared__ double s_pbn[CB_MAXW], s_pnbn[CB_MAXW];
+    __shared__ int s_node[2][CB_MAXW], s_tok[2][CB_MAXW], s_par[2][CB_MAXW], s_dep[2][CB_MAXW], s_st[2][CB_MAXW];
+    __shared__ int s_ctok[CB_MAXC];
+    __shared__ float s_clp[CB_MAXC];
+
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int Tb = max(0, min(act_lens[b], Tm));
+    const double NEG = -(double)INFINITY;
+    const long long row0 = (long long)b * Tm;
+    int4* nd = nodes + (long long)b * NC;
+
+    // the extension step's lane -> (entry group, candidate) map: Kp = K rounded up to a power of two, G = 64 / Kp groups
+    const int sh = 32 - __clz(K - 1), Kp = 1 << sh, G = 64 >> sh;
+    int cur = 0, nb = 1, nnodes = 1;
+    if (lane == 0) {
+        s_pb[0][0] = 0.0; s_pnb[0][0] = NEG; s_tot[0][0] = 0.0; s_bn[0][0] = 0.0;
+        s_node[0][0] = 0; s_tok[0][0] = -1; s_par[0][0] = -1; s_dep[0][0] = 0; s_st[0][0] = 0;
+        nd[0] = make_int4(-1, -1, -1, 0);
+    }
+    float ge = 0.f;                                   // lp[e_lane] of the coming frame
+    float qlse[D], qlpb[D], qlp[D];
+    int qtok[D];
+    auto request = [&](int j, int r) {                // (static j)
+        float a = 0.f, c = 0.f, p = -INFINITY;
+        int k = -1;
+        if (r < Tb) {
+            a = lse[row0 + r];
+            c = lpb[row0 + r];
+            if (lane < K) {
+                k = ctok[(row0 + r) * cand + lane];
+                p = clp[(row0 + r) * cand + lane];
+            }
+        }
+        qlse[j] = a; qlpb[j] = c; qtok[j] = k; qlp[j] = p;
+    };
+#pragma unroll
+    for (int j = 0; j < D; ++j) request(j, j);
+    __syncthreads();
+
+    for (int r0 = 0; r0 < Tb; r0 += D) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const int r = r0 + j;
+            if (r >= Tb) break;
+            const float cb = qlpb[j], lse_next = qlse[(j + 1) % D];
+            const int ctk = qtok[j];                  // candidate `lane` of this frame (-1: none)
+            if (lane < K) {
+                s_ctok[lane] = ctk;
+                s_clp[lane] = qlp[j];
+            }
+            request(j, r + D);
+            __syncthreads();
+            // ---- C: the extension items; lane (g, c) takes candidate c of the entries g, g + G, ...
+            const int N = nb * K;
+            {
+                const int c = lane & (Kp - 1);
+                const int tk = c < K ? s_ctok[c] : -1;
+                const double lpc = c < K ? (double)s_clp[c] : NEG;
+                for (int i = lane >> sh; i < nb; i += G) {
+                    if (c >= K) continue;
+                    double p = (tk == s_tok[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + lpc;
+                    if (tk < 0) p = NEG;
+                    if (BIAS && p > NEG) {
+                        const int s = bias_state(bt, s_st[cur][i]);
+                        const int n = bias_goto(bt, s, tk);
+                        p += s_bn[cur][i] + (bt.bias_held[n] - bt.bias_pend[s]);
+                    }
+                    s_sc[nb + i * K + c] = p;
+                }
+            }
+            // ---- B: the stays.  ci: where entry `lane`'s token stands in the candidate list (lane c holds candidate c:
+            // a ballot per entry), pi: where its parent stands in the beam; -1: not there
+            const bool stay = lane < nb;
+            const int tokj = stay ? s_tok[cur][lane] : -1, parj = stay ? s_par[cur][lane] : -2;
+            const int nodej = stay ? s_node[cur][lane] : -3;
+            int ci = -1, pi = -1;
+            for (int k = 0; k < nb; ++k) {          // (entry k's token and node out of lane k's registers)
+                const int tkk = __builtin_amdgcn_readlane(tokj, k), nk = __builtin_amdgcn_readlane(nodej, k);
+                const unsigned long long at = __ballot(ctk >= 0 && ctk == tkk);
+                if (lane == k && at) ci = __ffsll((long long)at) - 1;
+                if (parj == nk) pi = k;
+            }
+            __syncthreads();
+            if (stay) {
+                const double pbn = s_tot[cur][lane] + (double)cb;
+                double pnbn = NEG;
+                if (nodej != 0) {
+                    pnbn = s_pnb[cur][lane] + (double)(ci >= 0 ? s_clp[ci] : ge);
+                    if (ci >= 0 && pi >= 0) {
+                        const double pe = (tokj == s_tok[cur][pi] ? s_pb[cur][pi] : s_tot[cur][pi]) + (double)s_clp[ci];
+                        pnbn = log_add64(pnbn, pe);
+                        s_sc[nb + pi * K + ci] = NEG;
+                    }
+                }
+                s_pbn[lane] = pbn;
+                s_pnbn[lane] = pnbn;
+                double rk = log_add64(pbn, pnbn);
+                if (BIAS) rk += s_bn[cur][lane];
+                s_sc[lane] = rk;
+            }
+            __syncthreads();
+            // ---- D: select.  Lane l owns the items l, l + 64, ...: up to R of them in registers (W = 10 with 32
+            // candidates: 6), beyond that in LDS
+            const int NT = nb + N;
+            int nsel = 0, mysel = 0;
+            if (NT <= 64 * R) {
+                double loc[R];
+#pragma unroll
+                for (int k = 0; k < R; ++k) loc[k] = lane + 64 * k < NT ? s_sc[lane + 64 * k] : NEG;
+                for (int q = 0; q < W; ++q) {
+                    double bv = NEG;
+                    int bk = 0;
+#pragma unroll
+                    for (int k = 0; k < R; ++k)
+                        if (loc[k] > bv) { bv = loc[k]; bk = k; }
+                    double wv;
+                    const int wi = wave_pick(bv, bv > NEG ? lane + 64 * bk : CB_NONE, wv);
+                    if (wi == CB_NONE) break;         // (wave-uniform)
+                    if (lane == q) mysel = wi;
+#pragma unroll
+                    for (int k = 0; k < R; ++k)
+                        if (wi == lane + 64 * k) loc[k] = NEG;
+                    ++nsel;
+                }
+            } else {
+                double bv;
+                int bi;
+                auto rescan = [&]() {
+                    bv = NEG;
+                    bi = CB_NONE;
+                    for (int m = lane; m < NT; m += 64) {
+                        const double v = s_sc[m];
+                        if (v > bv) { bv = v; bi = m; }
+                    }
+                };
+                rescan();
+                for (int q = 0; q < W; ++q) {
+                    double wv;
+                    const int wi = wave_pick(bv, bi, wv);
+                    if (wi == CB_NONE) break;         // (wave-uniform)
+                    if (lane == q) mysel = wi;
+                    if ((wi & 63) == lane) {
+                        s_sc[wi] = NEG;
+                        rescan();
+                    }
+                    ++nsel;
+                }
+            }
+            // ---- E: the new beam
+            const int nxt = cur ^ 1;
+            const bool have = lane < nsel, fresh = have && mysel >= nb;
+            const unsigned long long mask = __ballot(fresh);
+            if (have) {
+                int node, tok, par, dep, st = 0;
+                double pb, pnb, bn = 0.0;
+                if (!fresh) {
+                    node = s_node[cur][mysel]; tok = s_tok[cur][mysel]; par = s_par[cur][mysel];
+                    dep = s_dep[cur][mysel]; st = s_st[cur][mysel]; bn = s_bn[cur][mysel];
+                    pb = s_pbn[mysel]; pnb = s_pnbn[mysel];
+                } else {
+                    const int m = mysel - nb, i = m / K, c = m - i * K;
+                    tok = s_ctok[c];
+                    node = nnodes + __popcll(mask & ((1ull << lane) - 1ull));
+                    par = s_node[cur][i];
+                    dep = s_dep[cur][i] + 1;
+                    pb = NEG;
+                    pnb = (tok == s_tok[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + (double)s_clp[c];
+                    if (BIAS) {
+                        const int s = bias_state(bt, s_st[cur][i]);
+                        st = bias_goto(bt, s, tok);
+                        bn = s_bn[cur][i] + (bt.bias_held[st] - bt.bias_pend[s]);
+                    }
+                    if (node < NC) nd[node] = make_int4(par, tok, r, __float_as_int(s_clp[c]));
+                }
+                s_node[nxt][lane] = node; s_tok[nxt][lane] = tok; s_par[nxt][lane] = par; s_dep[nxt][lane] = dep;
+                s_st[nxt][lane] = st; s_bn[nxt][lane] = bn;
+                s_pb[nxt][lane] = pb; s_pnb[nxt][lane] = pnb; s_tot[nxt][lane] = log_add64(pb, pnb);
+                if (r + 1 < Tb && tok >= 0 && tok < V)
+                    ge = ElemIO<T>::load(logits + (row0 + r + 1) * (long long)V + tok) - lse_next;
+            }
+            nnodes += __popcll(mask);
+            nb = nsel;
+            cur = nxt;
+            __syncthreads();
+        }
+    }
+    if (lane < W) {
+        const bool live = lane < nb;
+        fnode[b * W + lane] = live ? s_node[cur][lane] : -1;
+        fdepth[b * W + lane] = live ? s_dep[cur][lane] : 0;
+        logp[b * W + lane] = live ? s_tot[cur][lane] + (BIAS ? s_bn[cur][lane] : 0.0) : NEG;
+    }
+    if (lane == 0) n_hyp[b] = nb;
+}
+
+// ------------------------------------------------------------------ the read-out
+// blockIdx.x = b W + h.  tokens / frames / token_lp [B][W][Tm]: hypothesis h's tokens, their creation frames and their
+// log-softmax values on those frames, root to leaf; -1 / -1 / 0 behind ntok[b][h] (a hypothesis has at most T_b <= Tm
+// tokens: a node made on frame t is at depth <= t + 1).  The walk is a chain of dependent 16-byte loads, one lane's.
+__global__ __launch_bounds__(64) void ctc_beam_readout(const int4* __restrict__ nodes, int NC,
+                                                       const int32_t* __restrict__ fnode,
+                                                       const int32_t* __restrict__ fdepth, int Tm,
+                                                       int32_t* __restrict__ tokens, int32_t* __restrict__ frames,
+                                                       float* __restrict__ token_lp, int32_t* __restrict__ ntok, int W) {
+    const int bh = blockIdx.x, b = bh / W, lane = threadIdx.x;
+    const int dep = max(0, min(fdepth[bh], Tm));
+    const long long o = (long long)bh * Tm;
+    for (int pos = dep + lane; pos < Tm; pos += 64) {
+        tokens[o + pos] = -1;
+        frames[o + pos] = -1;
+        token_lp[o + pos] = 0.f;
+    }
+    if (lane != 0) return;
+    ntok[bh] = dep;
+    const int4* nd = nodes + (long long)b * NC;
+    int node = fnode[bh];
+    for (int pos = dep - 1; pos >= 0; --pos) {
+        int4 rec = make_int4(-1, -1, -1, 0);
+        if (node > 0 && node < NC) rec = nd[node];
+        tokens[o + pos] = rec.y;
+        frames[o + pos] = rec.z;
+        token_lp[o + pos] = __int_as_float(rec.w);
+        node = rec.x;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t edgedict_ctc_beam_workspace_bytes(int B, int T, int W, int cand) {
+    if (B <= 0 || T <= 0 || W < 1 || W > CB_MAXW || cand < 1 || cand > CB_MAXC) return 0;
+    return cb_ws(B, T, W, cand).total;
+}
+
+extern "C" int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V,
+                                        int blank, int W, int cand, const edgedict_beam_bias_t* bias, int32_t* tokens,
+                                        int32_t* frames, float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp,
+                                        void* workspace, void* stream_) {
+    ED_CHECK_ARG(B > 0 && T > 0, "ctc_beam_search: B, T must be positive (got %d, %d)", B, T);
+    ED_CHECK_ARG(V >= 2, "ctc_beam_search: V = %d, need at least the blank and one symbol", V);
+    ED_CHECK_ARG(blank >= 0 && blank < V, "ctc_beam_search: blank %d outside [0,%d)", blank, V);
+    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "ctc_beam_search: unsupported dtype code %d", dtype);
+    ED_CHECK_ARG(W >= 1 && W <= CB_MAXW, "ctc_beam_search: W = %d outside [1,%d]", W, CB_MAXW);
+    ED_CHECK_ARG(cand >= 1 && cand <= CB_MAXC, "ctc_beam_search: cand = %d outside [1,%d]", cand, CB_MAXC);
+    ED_CHECK_ARG(logits && act_lens && tokens && frames && token_lp && ntok && n_hyp && logp && workspace,
+                 "ctc_beam_search: null pointer argument");
+    ED_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
+    ED_CHECK_ARG((long long)B * W * T <= 0x7fffffffLL && (long long)B * T * cand <= 0x7fffffffLL,
+                 "ctc_beam_search: B x T x max(W, cand) = %d x %d x %d exceeds 2^31 - 1", B, T, max(W, cand));
+    CbBias bt{};
+    if (bias) {
+        ED_CHECK_ARG(bias->V == V, "ctc_beam_search: the bias list's vocabulary = %d differs from the head's V = %d",
+                     bias->V, V);
+        ED_CHECK_ARG(bias->S > 0 && bias->n_exc >= 0, "ctc_beam_search: bad bias automaton (S %d, exceptions %d)",
+                     bias->S, bias->n_exc);
+        ED_CHECK_ARG(bias->root_next && bias->held && bias->pend && bias->row_ptr && bias->exc_tok && bias->exc_next,
+                     "ctc_beam_search: null bias table pointer");
+        bt = CbBias{bias->root_next, bias->held, bias->pend, bias->row_ptr, bias->exc_tok, bias->exc_next, bias->S};
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const CbWs w = cb_ws(B, T, W, cand);
+    char* p = (char*)workspace;
+    float* lse = (float*)(p + w.off_lse);
+    float* lpb = (float*)(p + w.off_lpb);
+    int32_t* ctok = (int32_t*)(p + w.off_ctok);
+    float* clp = (float*)(p + w.off_clp);
+    int4* nodes = (int4*)(p + w.off_nodes);
+    int32_t* fnode = (int32_t*)(p + w.off_fnode);
+    int32_t* fdepth = (int32_t*)(p + w.off_fdepth);
+    const int K = min(cand, V - 1);
+    const int NC = (int)cb_node_capacity(T, W);
+
+    const size_t esz = dtype == ED_F32 ? 4 : 2;
+    const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)logits & 15) == 0);
+    const dim3 grid1(ed_grid_for(T, 4, max(1, 256 * 16 / B)), B);
+    if (dtype == ED_F32)
+        hipLaunchKernelGGL(ctc_beam_rows<float>, grid1, dim3(256), 0, stream, (const float*)logits, act_lens, T, V, blank,
+                           K, cand, lse, lpb, ctok, clp, vec_ok);
+    else
+        hipLaunchKernelGGL(ctc_beam_rows<bf16_t>, grid1, dim3(256), 0, stream, (const bf16_t*)logits, act_lens, T, V,
+                           blank, K, cand, lse, lpb, ctok, clp, vec_ok);
+    ED_CHECK_LAUNCH("ctc_beam_rows");
+#define ED_CB_WALK(TT, BB)                                                                                            \
+    hipLaunchKernelGGL((ctc_beam_walk<TT, BB>), dim3(B), dim3(64), 0, stream, (const TT*)logits, act_lens, T, V, W, K, \
+                       cand, lse, lpb, ctok, clp, nodes, NC, fnode, fdepth, n_hyp, logp, bt)
+    if (dtype == ED_F32) {
+        if (bias) ED_CB_WALK(float, true); else ED_CB_WALK(float, false);
+    } else {
+        if (bias) ED_CB_WALK(bf16_t, true); else ED_CB_WALK(bf16_t, false);
+    }
+#undef ED_CB_WALK
+    ED_CHECK_LAUNCH("ctc_beam_walk");
+    hipLaunchKernelGGL(ctc_beam_readout, dim3(B * W), dim3(64), 0, stream, (const int4*)nodes, NC, fnode, fdepth, T,
+                       tokens, frames, token_lp, ntok, W);
+    ED_CHECK_LAUNCH("ctc_beam_readout");
+    return ED_OK;
+}

@@ -12,6 +12,7 @@
 // (broadcast-add+tanh on one frame, row-wise pick, masked state commit).  Nothing returns to the
 // host between frames; token ids and scores stay on the device until the caller reads them.
 #include "decode_net.hpp"
+#include "bias_tables.hpp"
 
 #include <algorithm>
 #include <optional>
@@ -305,21 +306,7 @@ struct BeamPtrs {
     int bias_S;                     // states of the automaton: every state read from a table or a pool is clamped to it
 };
 
-// a state as the tables may be indexed with it (a stale or foreign state must not read out of range)
-__device__ __forceinline__ int bias_state(const BeamPtrs& p, int s) { return min(max(s, 0), p.bias_S - 1); }
-
-// goto(s, k) of the phrase automaton: the exception row of s (binary search), else the root's transition
-__device__ __forceinline__ int bias_goto(const BeamPtrs& p, int s, int k) {
-    s = bias_state(p, s);
-    int lo = p.bias_row_ptr[s], hi = p.bias_row_ptr[s + 1];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int t = p.bias_exc_tok[mid];
-        if (t == k) return bias_state(p, p.bias_exc_next[mid]);
-        if (t < k) lo = mid + 1; else hi = mid;
-    }
-    return bias_state(p, p.bias_root_next[k]);
-}
+// bias_state(p, s) / bias_goto(p, s, k), the automaton's lookup on these tables: bias_tables.hpp
 
 // (max, first position) of a workgroup's per-thread candidates: butterfly inside a wave, the four waves through LDS.
 // Ties go to the lower position, -inf candidates carry INT_MAX.  Every thread gets the result.

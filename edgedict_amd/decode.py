@@ -37,6 +37,10 @@ is not credited), an end-of-utterance retraction of a still-pending bonus, and t
 ``prefix=True`` with a bias list raises ``ValueError``, as with an LM.  ``bias=None``, an empty list and a list whose
 boosts are all 0 give tokens, scores and expansion counts bit-equal to the search without one (the first two run the
 plain kernels).  See ``edgedict_amd.bias``.
+
+``ctc_beam_search`` is the first pass from the encoder alone: a CTC prefix beam search on the CTC head's logits
+(``Transducer(ctc_weight > 0)``; csrc/ctc_decode.hip), all frames inside one launch, returning ranked ``NBestResult``
+lists; it takes ``bias=`` too.
 """
 import ctypes
 
@@ -414,6 +418,41 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
     _lib.check(rc, "beam_search_nbest")
     beam_search_batch.last_expansions = int(nexp.value)
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
+
+
+def ctc_beam_search(model, xs, xlen, W=10, cand=None, bias=None):
+    """First-pass N-best from the encoder alone: encoder, CTC head, ``loss.ctc_prefix_beam`` (the CTC prefix beam search
+    of csrc/ctc_decode.hip), then ONE read to the host - neither the prediction network nor the joint runs.  Returns a
+    list of ``NBestResult``, one per utterance, already ranked: ``logp`` is descending and entry 0 is the answer.
+
+    ``tokens[i]`` / ``frames[i]``: the prefix and the encoder frame on which each token's node was created (the first
+    frame the prefix could end on), so ``emission_times`` applies.  ``token_logp[i]``: the log-softmax value of each
+    token on that frame.  Unlike in the RNN-T searches ``token_logp`` is NOT an increment of ``logp``: CTC sums over all
+    paths of a prefix, so ``logp[i]`` is not the sum of per-token terms.  With ``bias`` (an
+    ``edgedict_amd.bias.ContextGraph``) ``logp`` includes the prefix' bias total ``bias.score(tokens)``; a frame's
+    candidate list (``cand``, default ``min(V - 1, 32)``) is cut before the bias is seen, so a boosted token outside it
+    is not rescued.  Raises ``RuntimeError`` on a model built without ``ctc_weight > 0``, as ``ctc_greedy_decode``."""
+    from .loss import ctc_prefix_beam
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+    _lib.require_cuda(xs)
+    with torch.no_grad():
+        xs = xs[:, :xlen.max()].contiguous()
+        h_enc, _ = model.encoder(xs)
+        act = model.scale_length(h_enc, xlen).to(device=h_enc.device, dtype=torch.int32).contiguous()
+        out = ctc_prefix_beam(model._ctc_logits(h_enc).contiguous(), act, W, model.blank, cand, bias)
+        B, Wn, T = out[0].shape
+        # one read: the int32 fields and token_lp as raw bits in one buffer, logp beside them
+        packed = torch.cat([out[0].reshape(B, -1), out[1].reshape(B, -1), out[2].view(torch.int32).reshape(B, -1),
+                            out[3], out[4].reshape(B, 1), out[5].view(torch.int32).reshape(B, -1)], dim=1).cpu().numpy()
+    n = Wn * T
+    tokens = packed[:, :n].reshape(B, Wn, T)
+    frames = packed[:, n:2 * n].reshape(B, Wn, T)
+    tlp = np.ascontiguousarray(packed[:, 2 * n:3 * n]).view(np.float32).reshape(B, Wn, T).astype(np.float64)
+    ntok = packed[:, 3 * n:3 * n + Wn]
+    nhyp = packed[:, 3 * n + Wn]
+    logp = np.ascontiguousarray(packed[:, 3 * n + Wn + 1:]).view(np.float64).reshape(B, Wn)
+    return _nbest_results(tokens, frames, tlp, ntok, nhyp, logp)
 
 
 class StreamingBeamSearch:

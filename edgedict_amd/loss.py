@@ -31,7 +31,9 @@ gradient - a ``'mean'`` or ``'sum'`` reduction is then ``+inf`` as well - decide
 joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`` under ``config.BAND_LATTICE``).
 
 ``CTCLoss`` / ``ctc_greedy`` (csrc/ctc_loss.hip) are the loss and the greedy decoder of the encoder's CTC auxiliary head
-(``Transducer(ctc_weight=...)``): raw head logits ``[B, T, V]``, not in the reference.
+(``Transducer(ctc_weight=...)``): raw head logits ``[B, T, V]``, not in the reference.  ``ctc_prefix_beam``
+(csrc/ctc_decode.hip) searches the same logits with a beam: ranked N-best prefixes with token frames, optionally biased
+towards a phrase list (``bias.ContextGraph``).
 """
 import ctypes
 import math
@@ -474,6 +476,72 @@ def ctc_greedy(logits, act_lens, blank=0):
     _lib.call("ctc_greedy", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, int(blank), tokens,
               counts, frames, neglogp, scratch)
     return tokens, counts, frames, neglogp
+
+
+CTC_BEAM_MAX_W = 32
+CTC_BEAM_MAX_CAND = 64
+
+
+@torch.no_grad()
+def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
+    """CTC prefix beam search of head logits ``[B, T, V]`` (float32 / bfloat16, contiguous, device), the counterpart of
+    ``ctc_greedy`` with a beam (csrc/ctc_decode.hip states the search): per frame ``t < act_lens[b]`` every prefix of
+    the beam stays or is extended with one of the ``min(cand, V - 1)`` most probable non-blank tokens of the frame, a
+    prefix's score is the sum over its paths (``pb`` / ``pnb``), the ``W`` best prefixes survive, ranked.
+
+    ``W`` in 1 .. 32, ``cand`` in 1 .. 64 (default ``min(V - 1, 32)``); anything else raises ``ValueError`` naming the
+    argument before a launch.  ``bias``: an ``edgedict_amd.bias.ContextGraph`` - every prefix then carries the phrase
+    automaton's state and its total bias ``graph.score(tokens)``, which enters the ranking and ``logp`` only.  The
+    candidate list is cut BEFORE the bias is seen: a boosted token outside a frame's top ``cand`` is not rescued.
+    ``bias=None`` and an empty graph run the plain kernel.
+
+    Returns device tensors ``(tokens, frames, token_lp, ntok, n_hyp, logp)``: ``tokens`` / ``frames`` int32
+    ``[B, W, T]`` (hypothesis h's tokens and the frame each token's node was created on; -1 behind ``ntok[b, h]``),
+    ``token_lp`` float32 ``[B, W, T]`` (``log_softmax(logits[b, frame])[token]``, 0 behind), ``ntok`` int32 ``[B, W]``,
+    ``n_hyp`` int32 ``[B]``, ``logp`` float64 ``[B, W]`` descending (-inf behind ``n_hyp[b]``; with a bias list it
+    includes the bias total).  Entry 0 is the answer; ``act_lens[b] == 0`` gives the empty prefix with ``logp`` 0.
+    No host sync."""
+    from .bias import active, check_bias_args
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+    if act_lens.dtype != torch.int32:
+        raise TypeError("act_lens must be int32, got %s" % act_lens.dtype)
+    if logits.dim() != 3:
+        raise ValueError("logits must have 3 dimensions [B,T,V], got %d" % logits.dim())
+    if not logits.is_contiguous() or not act_lens.is_contiguous():
+        raise ValueError("logits and act_lens must be contiguous")
+    if act_lens.dim() != 1 or act_lens.shape[0] != logits.shape[0]:
+        raise ValueError("must have a length per example (act_lens has %s, batch is %d)"
+                         % (tuple(act_lens.shape), logits.shape[0]))
+    B, T, V = logits.shape
+    W, blank = int(W), int(blank)
+    if B < 1 or T < 1:
+        raise ValueError("logits must hold at least one utterance and one frame (B = %d, T = %d)" % (B, T))
+    if V < 2:
+        raise ValueError("V = %d: need at least the blank and one symbol" % V)
+    if not 0 <= blank < V:
+        raise ValueError("blank %d outside [0, %d)" % (blank, V))
+    if not 1 <= W <= CTC_BEAM_MAX_W:
+        raise ValueError("W = %d outside [1, %d]" % (W, CTC_BEAM_MAX_W))
+    cand = min(V - 1, 32) if cand is None else int(cand)
+    if not 1 <= cand <= CTC_BEAM_MAX_CAND:
+        raise ValueError("cand = %d outside [1, %d]" % (cand, CTC_BEAM_MAX_CAND))
+    check_bias_args(bias, V, False)
+    _lib.require_cuda(logits, act_lens)
+    dev = logits.device
+    graph = active(bias)
+    bref = graph.ref(dev) if graph is not None else None
+    lib = _lib.load()
+    tokens = torch.empty(B, W, T, dtype=torch.int32, device=dev)
+    frames = torch.empty(B, W, T, dtype=torch.int32, device=dev)
+    token_lp = torch.empty(B, W, T, dtype=torch.float32, device=dev)
+    ntok = torch.empty(B, W, dtype=torch.int32, device=dev)
+    n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
+    logp = torch.empty(B, W, dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.edgedict_ctc_beam_workspace_bytes(B, T, W, cand), dtype=torch.uint8, device=dev)
+    _lib.call("ctc_beam_search", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, W, cand, bref,
+              tokens, frames, token_lp, ntok, n_hyp, logp, ws)
+    return tokens, frames, token_lp, ntok, n_hyp, logp
 
 
 def ctc_loss_debug(logits, labels, act_lens, label_lens, blank=0):

@@ -1142,6 +1142,14 @@ class Transducer(nn.Module):
         tokens, counts = tokens.cpu().numpy(), counts.cpu().numpy()
         return [tokens[b, :counts[b]].astype("int64") for b in range(tokens.shape[0])], neglogp
 
+    def ctc_beam_search(self, xs, xlen, W=10, cand=None, bias=None):
+        """First-pass N-best from the encoder alone: encoder, CTC head, the CTC prefix beam search
+        (``loss.ctc_prefix_beam``), one read to the host.  Returns a list of ``decode.NBestResult``, one per utterance,
+        ranked (``logp`` descending, entry 0 the answer); ``bias`` (an ``edgedict_amd.bias.ContextGraph``) boosts a
+        phrase list.  See ``decode.ctc_beam_search``.  Raises RuntimeError on a model built without ``ctc_weight > 0``."""
+        from .decode import ctc_beam_search
+        return ctc_beam_search(self, xs, xlen, W, cand, bias)
+
     def forward(self, xs, ys, xlen, ylen, *, windows=None):
         """The reference's forward (rnnt/models.py:209-241).  ``windows=(lo, hi)`` (keyword only): the
         alignment-restricted loss of ``loss.RNNTLoss`` on either loss path, in ENCODER frames as ``align`` counts them;

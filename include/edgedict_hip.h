@@ -1200,6 +1200,31 @@ int edgedict_ctc_greedy(const void* logits, int dtype, const int32_t* act_lens, 
                         int32_t* tokens, int32_t* counts, int32_t* frames, float* neglogp, void* scratch,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * CTC prefix beam search on the head's logits (csrc/ctc_decode.hip states the search): per utterance the W best
+ * prefixes after the last frame, ranked, with the frame each token's node was created on.  No prediction network and
+ * no joint: a row pass over [B, T, V] (log-sum-exp, lp[blank], the sorted top-cand list per frame), one launch that
+ * walks all frames of every utterance, one read-out launch.  No host sync; results bit-identical from run to run.
+ *
+ *   logits, dtype, act_lens, B, T, V, blank   as edgedict_ctc_greedy (rows t >= act_lens[b] are never read)
+ *   W          beam width, 1 .. 32
+ *   cand       candidates per frame, 1 .. 64: the min(cand, V - 1) most probable non-blank tokens of a frame are the
+ *              only ones a prefix is extended with (ties: the lower token id)
+ *   bias       nullable: a phrase automaton (edgedict_beam_bias_t above, bias->V == V).  A node carries the state after
+ *              its token and the total Bn = sum of D(s, k) from the root; Bn enters the ranking and logp only.  The
+ *              candidate list is cut BEFORE the bias is seen: a boosted token outside the top `cand` is not rescued.
+ *   tokens, frames [B, W, T] int32, token_lp [B, W, T] fp32: hypothesis h's tokens root to leaf, the frame each was
+ *              created on, log_softmax(logits[b, frame])[token]; -1 / -1 / 0 behind ntok[b, h]
+ *   ntok [B, W] int32, n_hyp [B] int32 (hypotheses h >= n_hyp[b]: ntok 0, logp -inf)
+ *   logp [B, W] fp64  logadd(pb, pnb) (+ Bn with a bias list), descending in h; act_lens[b] <= 0: the empty prefix, 0
+ *   workspace  edgedict_ctc_beam_workspace_bytes(B, T, W, cand) bytes, 16-byte aligned (0 for arguments out of range)
+ */
+size_t edgedict_ctc_beam_workspace_bytes(int B, int T, int W, int cand);
+int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V, int blank,
+                             int W, int cand, const edgedict_beam_bias_t* bias, int32_t* tokens, int32_t* frames,
+                             float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp, void* workspace,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
