@@ -557,8 +557,41 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const T* __restri
     float* yr = y + (long long)r * N;
     for (int i = tid; i < N; i += 256) yr[i] = (ElemIO<T>::load(xr + i) - m) - logs;
 }
+// its backward: dx[r, :] = dy[r, :] - exp(y[r, :]) * sum(dy[r, :]), dx in the logits' dtype; the same layout
+template <typename T>
+__global__ __launch_bounds__(256) void log_softmax_rows_bwd_kernel(const float* __restrict__ y,
+                                                                   const float* __restrict__ dy, long long lddy,
+                                                                   T* __restrict__ dx, int N) {
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* yr = y + (long long)r * N;
+    const float* dyr = dy + (long long)r * lddy;
+    __shared__ float part[4];
+    float a = 0.f;
+    for (int i = tid; i < N; i += 256) a += dyr[i];
+    a = wave_sum(a);
+    if (lane == 0) part[wave] = a;
+    __syncthreads();
+    const float sum = (part[0] + part[1]) + (part[2] + part[3]);
+    T* dxr = dx + (long long)r * N;
+    for (int i = tid; i < N; i += 256) ElemIO<T>::store(dxr + i, dyr[i] - expf(yr[i]) * sum);
+}
 
 }  // namespace
+
+extern "C" int edgedict_log_softmax_rows_bwd(const float* y, const float* dy, long long lddy, int dx_dtype, void* dx,
+                                             int M, int N, void* stream_) {
+    ED_CHECK_ARG(dx_dtype == ED_F32 || dx_dtype == ED_BF16, "log_softmax_rows_bwd: bad dtype");
+    ED_CHECK_ARG(M >= 0 && N > 0 && lddy >= N, "log_softmax_rows_bwd: bad shape (M %d, N %d, lddy %lld)", M, N, lddy);
+    if (M == 0) return ED_OK;
+    ED_CHECK_ARG(y && dy && dx, "log_softmax_rows_bwd: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    if (dx_dtype == ED_F32)
+        hipLaunchKernelGGL(log_softmax_rows_bwd_kernel<float>, dim3(M), dim3(256), 0, s, y, dy, lddy, (float*)dx, N);
+    else
+        hipLaunchKernelGGL(log_softmax_rows_bwd_kernel<bf16_t>, dim3(M), dim3(256), 0, s, y, dy, lddy, (bf16_t*)dx, N);
+    ED_CHECK_LAUNCH("log_softmax_rows_bwd");
+    return ED_OK;
+}
 
 extern "C" int edgedict_log_softmax_rows(int x_dtype, const void* x, long long ldx, float* y, int M, int N,
                                          void* stream_) {

@@ -34,6 +34,9 @@ joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`
 (``Transducer(ctc_weight=...)``): raw head logits ``[B, T, V]``, not in the reference.  ``ctc_prefix_beam``
 (csrc/ctc_decode.hip) searches the same logits with a beam: ranked N-best prefixes with token frames, optionally biased
 towards a phrase list (``bias.ContextGraph``).
+
+``SoftmaxNLLLoss`` / ``softmax_nll_rows`` (csrc/lm_loss.hip) are the language model's loss and sentence scorer:
+``log_softmax`` + ``NLLLoss(ignore_index)`` on raw logits ``[M, V]``, the gradient written into the logits in place.
 """
 import ctypes
 import math
@@ -570,3 +573,113 @@ def ctc_loss_debug(logits, labels, act_lens, label_lens, blank=0):
     S = 2 * U + 1
     return (costs, view(0, (B, T), torch.float32), view(1, (B, T, S), torch.float64),
             view(2, (B, T, S), torch.float64), view(3, (B, 2), torch.float64))
+
+
+# ------------------------------------------------------------------------------------------------ softmax NLL
+# The language model's loss (csrc/lm_loss.hip): log_softmax + NLLLoss(ignore_index) on raw logits [M, V] in two passes.
+
+
+def _nll_ld(logits):
+    M, V = logits.shape
+    return ctypes.c_longlong(int(logits.stride(0)) if M > 1 else V)
+
+
+def softmax_nll_rows(logits, targets, ignore_index=-100):
+    """Forward-only scoring: ``nll[m] = logsumexp(logits[m]) - logits[m, targets[m]]`` (fp32 ``[M]``; exactly 0 where
+    ``targets[m]`` equals ``ignore_index`` or lies outside ``[0, V)``).  ``logits`` float32 / bfloat16 ``[M, V]`` with
+    unit column stride, ``targets`` int32 ``[M]``, both on the device.  One kernel, no reduction, nothing else written;
+    not differentiable."""
+    _lib.require_cuda(logits, targets)
+    logits = logits.detach()
+    M, V = logits.shape
+    nll = torch.empty(M, dtype=torch.float32, device=logits.device)
+    _lib.call("softmax_nll_forward", _lib.dtype_code(logits.dtype), logits, _nll_ld(logits), targets, M, V,
+              int(ignore_index), None, nll, None, None, 0)
+    return nll
+
+
+class _SoftmaxNLLFn(torch.autograd.Function):
+    """forward: lse / nll per row and the fixed-order fp64 reduction; backward: the gradient overwrites the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, ignore_index, reduction):
+        _lib.require_cuda(logits, targets)
+        M, V = logits.shape
+        # one allocation: {sum, count} fp64 | reduced fp32 (+ pad) | lse [M] | nll [M]
+        ws = torch.empty(6 + 2 * M, dtype=torch.float32, device=logits.device)
+        stats, reduced, lse, nll = ws[:4].view(torch.float64), ws[4:5], ws[6:6 + M], ws[6 + M:]
+        z = logits.detach()
+        _lib.call("softmax_nll_forward", _lib.dtype_code(z.dtype), z, _nll_ld(z), targets, M, V, int(ignore_index),
+                  lse, nll, stats, reduced, reduction == "mean")
+        ctx.z = z                     # not save_for_backward: backward writes into it
+        ctx.rest = (targets, lse, stats)
+        ctx.cfg = (int(ignore_index), reduction)
+        return nll if reduction == "none" else reduced.view(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if ctx.z is None:
+            raise RuntimeError("edgedict_amd: this loss's logits were consumed by a previous backward (the gradient "
+                               "overwrote them; retain_graph is not supported)")
+        z, ctx.z = ctx.z, None
+        targets, lse, stats = ctx.rest
+        ignore_index, reduction = ctx.cfg
+        M, V = z.shape
+        go = grad_output
+        if go.dtype != torch.float32 or not go.is_contiguous():
+            go = go.contiguous().float()
+        _lib.call("softmax_nll_backward", _lib.dtype_code(z.dtype), z, _nll_ld(z), targets, M, V, ignore_index, lse, go,
+                  1 if reduction == "none" else 0, stats, reduction == "mean")
+        return z, None, None, None
+
+
+class SoftmaxNLLLoss(torch.nn.Module):
+    """``log_softmax`` + ``NLLLoss(ignore_index)`` on RAW logits, fused (csrc/lm_loss.hip): what
+    ``torch.nn.functional.cross_entropy(logits, targets, ignore_index=..., reduction=...)`` computes.
+
+    ``forward(logits, targets)``: ``logits`` float32 / bfloat16 ``[..., V]``, ``targets`` integer ``[...]`` (one per
+    row).  Device tensors only: there is no CPU fallback.  A row is ignored when its target equals ``ignore_index`` OR
+    lies outside ``[0, V)`` (torch raises for the latter; ``check_targets=True`` - one host read - raises ``ValueError``
+    for it here too, before anything is launched).  ``reduction``: ``'mean'`` (over the valid rows) and ``'sum'`` return
+    a 0-dim fp32 tensor, ``'none'`` fp32 of ``targets``' shape with exact zeros at ignored rows.
+
+    ``'mean'`` over ZERO valid rows is 0 with a zero gradient (torch returns NaN): a batch that happens to be all padding
+    must not poison the optimiser state, the reason ``CTCLoss`` departs from torch's reductions as well.
+
+    The loss CONSUMES its logits: backward writes the gradient into the logits' own buffer, in their dtype (no
+    ``[M, V]`` tensor is allocated in either pass), so the logits must not be read after ``backward`` and a second
+    backward raises.  Forward and backward make no host synchronisation; sum and count are added in a fixed order in
+    fp64, and loss and gradient are bit-identical from run to run."""
+
+    def __init__(self, ignore_index=-100, reduction="mean", check_targets=False):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+        self.check_targets = bool(check_targets)
+
+    def forward(self, logits, targets):
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+        if targets.dtype.is_floating_point or targets.dtype == torch.bool:
+            raise TypeError("targets must be an integer tensor, got %s" % targets.dtype)
+        if logits.dim() < 1 or tuple(targets.shape) != tuple(logits.shape[:-1]):
+            raise ValueError("targets %s must have the shape of logits %s without its last dimension"
+                             % (tuple(targets.shape), tuple(logits.shape)))
+        V = logits.shape[-1]
+        if V < 1:
+            raise ValueError("logits need at least one class")
+        if self.check_targets and targets.numel():     # one host read
+            bad = (targets != self.ignore_index) & ((targets < 0) | (targets >= V))
+            if bool(bad.any()):
+                raise ValueError("a target lies outside [0, %d) and is not ignore_index = %d" % (V, self.ignore_index))
+        _lib.require_cuda(logits, targets)
+        z = logits.reshape(-1, V)
+        if z.stride(1) != 1 or (z.shape[0] > 1 and z.stride(0) < V):
+            z = z.contiguous()
+        t = targets.reshape(-1)
+        if t.dtype != torch.int32 or not t.is_contiguous():      # int32 targets spare this cast kernel
+            t = t.to(torch.int32).contiguous()
+        out = _SoftmaxNLLFn.apply(z, t, self.ignore_index, self.reduction)
+        return out.view(targets.shape) if self.reduction == "none" else out

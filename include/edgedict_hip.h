@@ -1156,6 +1156,38 @@ int edgedict_beam_stream_advance_detail_bias(int dtype, const void* E1, long lon
  */
 int edgedict_log_softmax_rows(int x_dtype, const void* x, long long ldx, float* y, int M, int N,
                               void* stream);
+/* Its backward:  dx = dy - exp(y) * rowsum(dy).  y fp32 [M, N] contiguous (the forward's output), dy fp32 rows of
+ * leading dimension lddy, dx [M, N] contiguous in dx_dtype (the dtype the logits had). */
+int edgedict_log_softmax_rows_bwd(const float* y, const float* dy, long long lddy, int dx_dtype, void* dx, int M,
+                                  int N, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Softmax negative log-likelihood on raw logits (the LM's training loss and sentence scorer: log_softmax followed by
+ * NLLLoss(ignore_index) of cli/train_lm.py, csrc/lm_loss.hip).
+ *
+ *   logits   [M, V]  fp32 or bf16 (dtype code), rows of leading dimension ldx >= V.  16-byte accesses when the base
+ *                    pointer is 16-byte aligned and V and ldx are multiples of 16 / sizeof(dtype); otherwise a scalar
+ *                    path.
+ *   targets  [M]     int32.  Row m is IGNORED when targets[m] == ignore_index or lies outside [0, V).
+ *   lse      [M]     fp32 out (nullable): max + log(sum exp(z - max)), fp32 arithmetic
+ *   nll      [M]     fp32 out: lse - z[m, targets[m]], exactly 0 for an ignored row
+ *   stats    [2]     fp64 out (nullable): {sum of nll over the valid rows, number of valid rows}, added in a fixed
+ *                    order by one workgroup (no atomics).  NULL = forward-only scoring: nll (and lse) only.
+ *   reduced  [1]     fp32 out (nullable, needs stats): mean ? sum / count : sum; 'mean' over zero valid rows is 0.
+ *
+ * backward overwrites the logits IN PLACE, in their dtype, with d(loss)/d(logits): a valid row gets
+ * g_m * (exp(z - lse[m]) - onehot(targets[m])), an ignored row exact zeros (it is not read).  g_m = grad[m *
+ * grad_stride] (grad_stride 1: a gradient per row, reduction 'none'; 0: one device scalar), divided by stats[1] when
+ * mean != 0 (zero when no row is valid).  Everything is read on the device; neither call synchronises.
+ * Forward plus backward read the logits twice and write them once; loss, nll, lse and the gradient are bit-identical
+ * from run to run.
+ */
+int edgedict_softmax_nll_forward(int dtype, const void* logits, long long ldx, const int32_t* targets, int M, int V,
+                                 int ignore_index, float* lse, float* nll, double* stats, float* reduced, int mean,
+                                 void* stream);
+int edgedict_softmax_nll_backward(int dtype, void* logits, long long ldx, const int32_t* targets, int M, int V,
+                                  int ignore_index, const float* lse, const float* grad, int grad_stride,
+                                  const double* stats, int mean, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * CTC loss (Graves et al. 2006) on the encoder's auxiliary head, and the CTC greedy decoder.  Not in the
