@@ -635,6 +635,10 @@ extern "C" int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, 
     ED_CHECK_ARG(B > 0 && T > 0 && L > 0 && H % 32 == 0 && I0 % 8 == 0, "stream_encoder_step: need H %% 32 == 0 and "
                  "I0 %% 8 == 0 (B=%d T=%d I0=%d H=%d)", B, T, I0, H);
     ED_CHECK_ARG(x_dtype == ED_F32 || x_dtype == ED_BF16, "stream_encoder_step: bad input dtype");
+    // every argument is judged before the first launch: a refusal leaves the carried state of no layer advanced
+    // (`reduce` is a host array)
+    for (int l = 0; l < L; ++l)
+        ED_CHECK_ARG(reduce[l] == 1 || reduce[l] == 2, "stream_encoder_step: time reduction must be 1 or 2");
     hipStream_t s = (hipStream_t)stream_;
     const size_t D = (size_t)(I0 > H ? I0 : H);
     char* p = (char*)workspace;
@@ -657,7 +661,6 @@ extern "C" int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, 
         return rc;
     int Tl = T, K = I0;
     for (int l = 0; l < L; ++l) {
-        ED_CHECK_ARG(reduce[l] == 1 || reduce[l] == 2, "stream_encoder_step: time reduction must be 1 or 2");
         float* hl = h_state + (size_t)l * B * H;
         float* cl = c_state + (size_t)l * B * H;
         // the carried state is updated IN PLACE: a cell's c is read and written by the same thread, and the recurrent
