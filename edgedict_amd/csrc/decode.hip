@@ -176,6 +176,15 @@ SearchNet net_dims(int dtype, int B, int J, int V, int E, int L, int H, int P2) 
 
 }  // namespace
 
+// The beam searches' step composed from the general kernels, in the form of ed_decode_fused_beam_step (decode_fused.hip):
+// for the frame-synchronous search of decode_sync.hip, where ed_decode_fused_ok says no
+int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                 const StepBufs& u, hipStream_t s) {
+    if (int rc = composed_lstm_step(net.dtype, net.B, net.pred, u.pred, h_state, c_state, u, net.dtype, u.dec_new, s))
+        return rc;
+    return composed_joint(net, (const char*)E1t, u.dec_new, u, s);
+}
+
 extern "C" size_t edgedict_greedy_workspace_bytes(int dtype, int B, int J, int V, int E, int L,
                                                   int H, int P2) {
     if (B <= 0) return 0;

@@ -101,5 +101,8 @@ int ed_decode_fused_frame(const SearchNet& net, const void* E1t, float* h_state,
                           const GreedyOut& out, const StepBufs& u, hipStream_t s);
 int ed_decode_fused_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
                               const StepBufs& u, hipStream_t s);
+// decode.hip: the same step composed from the general kernels, for any shape
+int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                 const StepBufs& u, hipStream_t s);
 int ed_decode_fused_lm_step(int dtype, int B, const LstmNet& lm, const float* h_state, const float* c_state,
                             const StepBufs& u, hipStream_t s);

@@ -41,6 +41,11 @@ plain kernels).  See ``edgedict_amd.bias``.
 ``ctc_beam_search`` is the first pass from the encoder alone: a CTC prefix beam search on the CTC head's logits
 (``Transducer(ctc_weight > 0)``; csrc/ctc_decode.hip), all frames inside one launch, returning ranked ``NBestResult``
 lists; it takes ``bias=`` too.
+
+``sync_beam_search`` (``_nbest``, ``_enc``, ``_rows``) is a SECOND RNN-T beam search, frame-synchronous (at most one
+symbol per frame and hypothesis, all B x W hypotheses in one step per frame, equal sequences merged by log-add;
+csrc/decode_sync.hip).  A different algorithm from ``beam_search_batch``: it does not return the same hypotheses, and
+takes neither ``lm=`` nor ``bias=`` nor ``prefix=``.
 """
 import ctypes
 
@@ -417,6 +422,115 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
         rc = lib.edgedict_beam_search_nbest(*nb_args, *nb_tail)
     _lib.check(rc, "beam_search_nbest")
     beam_search_batch.last_expansions = int(nexp.value)
+    return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
+
+
+SYNC_BEAM_MAX_W = 32
+
+
+def _check_sync_width(W):
+    if not 1 <= int(W) <= SYNC_BEAM_MAX_W:
+        raise ValueError("sync_beam_search: beam width W = %r outside [1, %d]" % (W, SYNC_BEAM_MAX_W))
+
+
+def _sync_encode(model, xs, xlen, W):
+    """The argument rules of the ``sync_beam_search*`` entry points, then the encoder: (enc_out, lens)."""
+    _check_sync_width(W)
+    _lib.require_cuda(xs)
+    enc_out, _ = model.encoder(xs)
+    enc_out = enc_out.contiguous()
+    if xlen is None:
+        return enc_out, None
+    xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
+    return enc_out, model.scale_length(enc_out, xl).numpy().astype(np.int32)
+
+
+def _best_of(results):
+    """(seqs, scores) in ``beam_search_batch``'s types from ranked ``NBestResult`` lists: entry 0 of each."""
+    seqs = [r.tokens[0] for r in results]
+    return seqs, torch.from_numpy(np.array([-r.logp[0] for r in results], dtype=np.float64))
+
+
+def sync_beam_search(model, xs, xlen=None, W=10):
+    """Frame-synchronous beam search ("modified beam search"; csrc/decode_sync.hip): every hypothesis emits at most one
+    symbol per frame - the greedy search's rule - so all B x W hypotheses of the batch advance through ONE
+    prediction-network step and ONE joint per frame, with a fixed number of launches per frame and no wait for the host
+    inside the frame loop.  Hypotheses with the same token sequence are merged by log-add, so a hypothesis' log p sums
+    over its alignments inside the beam.  ``1 <= W <= 32``; ``W = 1`` is the greedy search with the blanks removed.
+
+    This is a different algorithm from ``beam_search_batch`` (the reference's best-first search, which may emit several
+    symbols per frame and never merges): the two do not return the same hypotheses.  It takes no ``lm=``, ``bias=`` or
+    ``prefix=`` and has no streaming form.
+
+    Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
+    utterance, in ``beam_search_batch``'s types."""
+    return _best_of(sync_beam_search_nbest(model, xs, xlen, W))
+
+
+def sync_beam_search_nbest(model, xs, xlen=None, W=10):
+    """``sync_beam_search`` returning, per utterance, the final beam as an ``NBestResult`` **already ranked**: ``logp``
+    descending (ties keep beam order), at most W hypotheses with distinct token sequences, entry 0 what
+    ``sync_beam_search`` returns.  ``frames[i]``: the encoder frame on which each token's tree node was created
+    (``emission_times`` applies); ``token_logp[i]``: the token's log-softmax value on that frame - NOT an increment of
+    ``logp``, which sums over alignments (as in ``ctc_beam_search``).  An utterance of 0 frames yields one empty
+    hypothesis with ``logp`` 0."""
+    enc_out, lens = _sync_encode(model, xs, xlen, W)
+    return sync_beam_search_nbest_enc(model, enc_out, lens, W)
+
+
+def sync_beam_search_enc(model, enc_out, lens=None, W=10):
+    """``sync_beam_search`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
+    encoder frames per utterance; None: all T)."""
+    return _best_of(sync_beam_search_nbest_enc(model, enc_out, lens, W))
+
+
+def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10):
+    """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``."""
+    _check_sync_width(W)
+    _lib.require_cuda(enc_out)
+    enc_out = enc_out.contiguous()
+    B, T, P = enc_out.shape
+    return sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W)
+
+
+def sync_beam_search_rows(model, E1, B, T, P, lens=None, W=10):
+    """``sync_beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
+    width P."""
+    return _best_of(sync_beam_search_nbest_rows(model, E1, B, T, P, lens, W))
+
+
+def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=None):
+    """``sync_beam_search_nbest_enc`` from the joint's encoder rows, as ``sync_beam_search_rows``.  ``max_tokens``
+    bounds a hypothesis' length (default T: one token per frame at most); a longer one raises, it is never cut."""
+    _check_sync_width(W)
+    _lib.require_cuda(E1)
+    W = int(W)
+    cd = E1.dtype
+    lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > T).any():
+        raise ValueError("sync_beam_search: lens must be [B] ints in [0, %d]" % T)
+    if T < 1:       # nothing to search: the empty hypothesis (the native call refuses T <= 0)
+        return [NBestResult([np.zeros(0, np.int64)], [np.zeros(0, np.int32)], [np.zeros(0)], [0.0]) for _ in range(B)]
+    net = _SearchNet(model, cd)
+    lib = _lib.load()
+    MT = T if max_tokens is None else int(max_tokens)
+    dev = E1.device
+    ws = torch.empty(lib.edgedict_sync_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H,
+                                                            net.P2, W), dtype=torch.uint8, device=dev)
+    result = torch.empty(lib.edgedict_sync_beam_result_bytes(B, W, MT), dtype=torch.uint8, device=dev)
+    tokens = np.empty((B, W, MT), dtype=np.int32)       # (only the used columns are written and read)
+    frames = np.empty((B, W, MT), dtype=np.int32)
+    tlogp = np.empty((B, W, MT), dtype=np.float64)
+    ntok = np.zeros((B, W), dtype=np.int32)
+    nhyp = np.zeros(B, dtype=np.int32)
+    logp = np.zeros((B, W), dtype=np.float64)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    from .tokenizer import BOS
+    rc = lib.edgedict_sync_beam_search(
+        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
+        *net.args(P), int(model.blank), int(BOS), W, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp),
+        _lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
+    _lib.check(rc, "sync_beam_search")
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
 
 

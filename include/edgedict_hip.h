@@ -1257,6 +1257,38 @@ int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_l
                              float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp, void* workspace,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Frame-synchronous batched RNN-T beam search (csrc/decode_sync.hip states the search): every hypothesis emits at most
+ * one symbol per frame, all B x W hypotheses advance through one prediction-network step and one joint per frame, equal
+ * token sequences are merged by log-add.  A second search beside edgedict_beam_search*, NOT the same algorithm: the two
+ * do not return the same hypotheses.  A fixed list of launches per frame, no host synchronisation inside the frame
+ * loop, no atomics; results are bit-identical from run to run.
+ *
+ *   operands   as edgedict_beam_search_nbest without max_expansions, prefix, expansions_host, lm and detail
+ *   W          beam width, 1 .. 32;  T > 0;  lens_host[b] in [0, T];  H a multiple of 4 (the LSTM kernels ask for 8)
+ *   tokens_host / frames_host  HOST int32 [B, W, max_tokens]: hypothesis h's tokens root to leaf and the frame each
+ *              token's node was created on;  token_logp_host HOST fp64 [B, W, max_tokens]: the token's log-softmax
+ *              value on that frame (NOT an increment of logp: logp sums over alignments)
+ *   ntokens_host HOST int32 [B, W];  nhyp_host HOST int32 [B] (= n <= W);  logp_host HOST fp64 [B, W], descending in h
+ *              Entries behind n / behind a hypothesis' length are not written.  An utterance of 0 frames has one empty
+ *              hypothesis with logp 0.  A hypothesis holds at most lens[b] tokens; one longer than max_tokens is an
+ *              error, never a truncation.
+ *   workspace  edgedict_sync_beam_workspace_bytes(...) bytes (0 for arguments out of range), 256-byte aligned
+ *   result     edgedict_sync_beam_result_bytes(B, W, max_tokens) bytes on the device
+ * Arguments are checked before anything is launched: a bad W, T <= 0, a null pointer give -1 and a message.
+ * Synchronises the stream once, at the end.
+ */
+size_t edgedict_sync_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2, int W);
+size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens);
+int edgedict_sync_beam_search(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+                              const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+                              const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+                              const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+                              const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
+                              int W, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
+                              int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                              void* workspace, void* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
