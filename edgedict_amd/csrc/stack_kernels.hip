@@ -1586,22 +1586,23 @@ __global__ __launch_bounds__(256) void stack_input_norm_bwd_kernel(
     const T* __restrict__ x, const bf16_t* __restrict__ dX, const float* __restrict__ mean_in,
     const float* __restrict__ rstd_in, float* __restrict__ dgamma, float* __restrict__ dbeta, int B,
     int Tn, int D, int rows_per_block) {
-    const int c = threadIdx.x;
-    if (c >= D) return;
     const long long rows = (long long)B * Tn;
     const long long r0 = (long long)blockIdx.x * rows_per_block;
     const long long r1 = min(rows, r0 + rows_per_block);
-    float ag = 0.f, ab = 0.f;
-    for (long long row = r0; row < r1; ++row) {   // row enumerates time-major (t, b)
-        const int t = (int)(row / B), b = (int)(row % B);
-        const long long xrow = (long long)b * Tn + t;
-        const float dy = bf16_to_f32(dX[row * D + c]);
-        const float xh = (ElemIO<T>::load(x + xrow * D + c) - mean_in[xrow]) * rstd_in[xrow];
-        ag += dy * xh;
-        ab += dy;
+    // (the block has at most 256 threads - the launch bound - and D goes up to 1024: a thread takes every 256th column)
+    for (int c = threadIdx.x; c < D; c += blockDim.x) {
+        float ag = 0.f, ab = 0.f;
+        for (long long row = r0; row < r1; ++row) {   // row enumerates time-major (t, b)
+            const int t = (int)(row / B), b = (int)(row % B);
+            const long long xrow = (long long)b * Tn + t;
+            const float dy = bf16_to_f32(dX[row * D + c]);
+            const float xh = (ElemIO<T>::load(x + xrow * D + c) - mean_in[xrow]) * rstd_in[xrow];
+            ag += dy * xh;
+            ab += dy;
+        }
+        atomicAdd(dgamma + c, ag);
+        atomicAdd(dbeta + c, ab);
     }
-    atomicAdd(dgamma + c, ag);
-    atomicAdd(dbeta + c, ab);
 }
 
 // Yx[0] <- bf16(h0), Cx[0] <- c0, fragment image of h0 (zeros when the states are null)
@@ -1791,7 +1792,7 @@ int ed_stack_input_norm_bwd(int x_dtype, const void* x, const bf16_t* dX, const 
     const long long rows = (long long)B * T;
     const int rpb = 64;
     const int grid = (int)((rows + rpb - 1) / rpb);
-    const int threads = (D + 63) / 64 * 64;
+    const int threads = min(256, (D + 63) / 64 * 64);     // the kernel's launch bound; it loops over the columns
     if (x_dtype == ED_F32)
         hipLaunchKernelGGL(stack_input_norm_bwd_kernel<float>, dim3(grid), dim3(threads), 0, s,
                            (const float*)x, dX, mean, rstd, dgamma, dbeta, B, T, D, rpb);
