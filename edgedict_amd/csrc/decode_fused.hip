@@ -698,6 +698,10 @@ bool ed_decode_fused_ok(int dtype, int emb_dtype, int J, int V, int E, int H, in
     return on && (dtype == ED_BF16 || (dtype == ED_F32 && emb_dtype == ED_F32)) && J % 32 == 0 && P2 % 32 == 0 &&
            E % 32 == 0 && H % 32 == 0 && V % 4 == 0;
 }
+// the same answer for callers outside the library (tests assert the route a shape takes)
+extern "C" int edgedict_decode_fused_ok(int dtype, int emb_dtype, int J, int V, int E, int H, int P2) {
+    return ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2) ? 1 : 0;
+}
 // slice partials of one frame: [B][ceil(V / 64)] PickPart (32 bytes each: V / 2 bytes per row - they fit the fp32
 // logits buffer of the composed path, which the fused frame never fills)
 size_t ed_decode_fused_ws_bytes(int B, int V) {

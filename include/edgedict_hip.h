@@ -734,6 +734,10 @@ int edgedict_greedy_decode(int dtype, const void* E1, long long e_row_stride,
                            const void* Wp, const float* bp, float* h_state, float* c_state,
                            void* dec_out, int blank, int unk, int32_t* tokens_out, int tok_stride,
                            float* score, void* workspace, void* stream);
+/* Route query: 1 where the searches run a frame / an expansion of these dimensions as the fused launches of
+ * csrc/decode_fused.hip, 0 where they compose it from the general kernels (csrc/decode.hip).  dtype = the search's
+ * compute dtype, emb_dtype = the embedding table's (ED_F32 / ED_BF16).  Touches no device. */
+int edgedict_decode_fused_ok(int dtype, int emb_dtype, int J, int V, int E, int H, int P2);
 
 /* ------------------------------------------------------------------------------------
  * GRU time recurrence (the module_type='GRU' encoder variant, ResLayerNormGRU rnnt/models.py:77-116;
