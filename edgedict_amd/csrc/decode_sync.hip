@@ -20,9 +20,12 @@
 // atomics: results are bit-identical from run to run.  Rows without a hypothesis (early frames, after merges) carry
 // logp = -inf, token BOS and a zero state; the rows of an utterance past its length keep its final beam and are left
 // alone by both kernels.  Rows flow through the step kernels either way and are row-independent there.
+//
+// Second half of the file: the streaming form (edgedict_sync_stream_*), the same frame loop on a persistent state.
 #include "decode_net.hpp"
 
 #include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -161,11 +164,30 @@ __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __
 // survivors close ranks, token children get their tree nodes, and the beam's small fields are rewritten in place (every
 // read of them comes before the first write, all inside this wave).  Then the whole workgroup gathers the states into
 // the other buffer: a blank child takes its parent's state before the token, a token child the state after it.
-__global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __restrict__ h_new,
-                                                   const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
-                                                   int H, int NODES, int blank, int bos) {
+// STREAM (the streaming search below, whose states outlive the call): a node's frame counts from the stream's reset,
+// frame0[b] + t, and an utterance past its length copies its rows' states through to the other buffer, so that every
+// stream's states are in the buffer the next frame reads whatever its own frame count.
+template <bool STREAM>
+__device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float* __restrict__ h_new,
+                                                 const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
+                                                 int H, int NODES, int blank, int bos,
+                                                 const int32_t* __restrict__ frame0) {
     const int b = blockIdx.x, tid = threadIdx.x, r0 = b * W;
-    if (t >= p.lens[b]) return;
+    if (t >= p.lens[b]) {
+        if constexpr (STREAM) {
+            const int H4 = H / 4, LH4 = L * H4;
+            const size_t BW = (size_t)B * W;
+            for (int idx = tid; idx < W * LH4; idx += 256) {
+                const int pos = idx / LH4, rem = idx % LH4, l = rem / H4, j = rem % H4;
+                const size_t at = ((size_t)l * BW + r0 + pos) * H4 + j;
+                ((float4*)p.hs[cur ^ 1])[at] = ((const float4*)p.hs[cur])[at];
+                ((float4*)p.cs[cur ^ 1])[at] = ((const float4*)p.cs[cur])[at];
+            }
+        }
+        return;
+    }
+    int frame = t;
+    if constexpr (STREAM) frame += frame0[b];
     __shared__ int s_src[SB_MAXW];      // per new place: the parent's place, | 0x100 for a token child; -1: no hypothesis
     __shared__ double s_score[SB_MAXW * SB_MAXW];       // the rows' sorted lists: the merge's loads are a dependent chain
     for (int i = tid; i < W * W; i += 256) s_score[i] = p.c_score[(size_t)r0 * W + i];
@@ -244,7 +266,7 @@ __global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __re
             } else {
                 if (nid < NODES) {
                     p.nodes[(size_t)b * NODES + nid] = make_int2(f_node, f_k);
-                    p.nd_frame[(size_t)b * NODES + nid] = t;
+                    p.nd_frame[(size_t)b * NODES + nid] = frame;
                     p.nd_lp[(size_t)b * NODES + nid] = f_lp;
                 }
                 p.node[row] = nid;
@@ -285,6 +307,19 @@ __global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __re
         ((float4*)hs_n)[dst] = hv;
         ((float4*)cs_n)[dst] = cv;
     }
+}
+
+__global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __restrict__ h_new,
+                                                   const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
+                                                   int H, int NODES, int blank, int bos) {
+    sync_select_body<false>(p, h_new, c_new, t, cur, W, B, L, H, NODES, blank, bos, nullptr);
+}
+
+__global__ __launch_bounds__(256) void sync_stream_select(SyncPtrs p, const float* __restrict__ h_new,
+                                                          const float* __restrict__ c_new, int t, int cur, int W, int B,
+                                                          int L, int H, int NODES, int blank, int bos,
+                                                          const int32_t* __restrict__ frame0) {
+    sync_select_body<true>(p, h_new, c_new, t, cur, W, B, L, H, NODES, blank, bos, frame0);
 }
 
 // Read-out: an utterance's beam ranked by logp descending (ties keep beam order), every path walked root to leaf into
@@ -506,6 +541,415 @@ extern "C" int edgedict_sync_beam_search(
                                       hipMemcpyDeviceToHost, s));
         ED_CHECK_HIP(hipMemcpy2DAsync(token_logp_host, MT * 8, rp + r.lp, MT * 8, (size_t)longest * 8, BW,
                                       hipMemcpyDeviceToHost, s));
+        ED_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    return ED_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Streaming form: the beams of S streams in a persistent STATE, advanced chunk by chunk (include/edgedict_hip.h states
+// the contract).  The state is what SyncPtrs holds per utterance - the W rows' small fields, both state buffers, the
+// token tree [S][NC] - plus per stream the frames since its reset and the tokens committed so far.  A frame is the
+// offline loop's four launches (sync_stream_select = sync_select with the frame offset and the pass-through); after the
+// last frame sync_stream_compact commits the path down to the live leaves' lowest common ancestor, re-roots the tree
+// there and renumbers the nodes that a live leaf still reaches into [0, n_live).  hash / len / pred are over the whole
+// sequence and stay as they are.  The beam stays in beam order; only the read-out (sync_read, unchanged) ranks it.
+namespace {
+
+struct SyncStreamState {
+    size_t logp, node, hash, len, pred, hs0, hs1, cs0, cs1, nodes, nd_frame, nd_lp, n_nodes, frames_done, n_committed,
+        total;
+};
+SyncStreamState sync_stream_state_layout(size_t S, size_t W, size_t L, size_t H, size_t NC) {
+    SyncStreamState a{};
+    const size_t SW = S * W;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    a.logp = take(SW * 8);
+    a.node = take(SW * 4);
+    a.hash = take(SW * 8);
+    a.len = take(SW * 4);
+    a.pred = take(SW * 4);
+    a.hs0 = take(SW * L * H * 4);
+    a.hs1 = take(SW * L * H * 4);
+    a.cs0 = take(SW * L * H * 4);
+    a.cs1 = take(SW * L * H * 4);
+    a.nodes = take(S * NC * 8);
+    a.nd_frame = take(S * NC * 4);
+    a.nd_lp = take(S * NC * 4);
+    a.n_nodes = take(S * 4);
+    a.frames_done = take(S * 4);
+    a.n_committed = take(S * 8);
+    a.total = o;
+    return a;
+}
+
+struct SyncStreamWs {
+    Ws step;
+    size_t step_at, e1g, c_score, c_k, c_lp, lens, remap, commit, total;
+};
+SyncStreamWs sync_stream_ws_layout(const SearchNet& rows, size_t S, size_t W, size_t NC) {
+    SyncStreamWs w{};
+    const size_t SW = S * W;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    w.step = ws_layout(rows);
+    w.step_at = take(w.step.total);
+    w.e1g = take(SW * rows.J * rows.esz);
+    w.c_score = take(SW * W * 8);
+    w.c_k = take(SW * W * 4);
+    w.c_lp = take(SW * W * 4);
+    w.lens = take(S * 4);
+    w.remap = take(S * NC * 4);
+    w.commit = take(S * (NC + 1) * 16);
+    w.total = o;
+    return w;
+}
+
+bool sync_stream_dims_ok(int S, int L, int H, int W, int NC) {
+    return S > 0 && L > 0 && H > 0 && H % 4 == 0 && W >= 1 && W <= SB_MAXW && NC >= W &&
+           (long long)S * W <= 0x7fffffff / 256 && (long long)S * ((long long)NC + 1) <= 0x7fffffff / 16;
+}
+
+// the state's part of SyncPtrs (the candidate lists and the lengths are per call: the workspace)
+SyncPtrs sync_stream_bind(char* st, const SyncStreamState& a) {
+    SyncPtrs q{};
+    q.logp = at<double>(st, a.logp);
+    q.node = at<int32_t>(st, a.node);
+    q.hash = at<unsigned long long>(st, a.hash);
+    q.len = at<int32_t>(st, a.len);
+    q.pred = at<int32_t>(st, a.pred);
+    q.hs[0] = at<float>(st, a.hs0); q.hs[1] = at<float>(st, a.hs1);
+    q.cs[0] = at<float>(st, a.cs0); q.cs[1] = at<float>(st, a.cs1);
+    q.nodes = at<int2>(st, a.nodes);
+    q.nd_frame = at<int32_t>(st, a.nd_frame);
+    q.nd_lp = at<float>(st, a.nd_lp);
+    q.n_nodes = at<int32_t>(st, a.n_nodes);
+    return q;
+}
+
+// One workgroup per stream s0 + blockIdx.x (mask: device int32 [S] or null): the empty hypothesis in row 0, zero states
+// in BOTH buffers (whichever the next advance reads), an empty tree, no frames, nothing committed.
+__global__ __launch_bounds__(256) void sync_stream_reset_kernel(SyncPtrs p, int32_t* __restrict__ frames_done,
+                                                                long long* __restrict__ n_committed,
+                                                                const int32_t* __restrict__ mask, int s0, int S, int W,
+                                                                int L, int H, int bos) {
+    const int b = s0 + blockIdx.x, tid = threadIdx.x, r0 = b * W;
+    if (b >= S || (mask && !mask[b])) return;
+    if (tid < W) {
+        p.logp[r0 + tid] = tid == 0 ? 0.0 : -(double)INFINITY;
+        p.node[r0 + tid] = -1;
+        p.hash[r0 + tid] = SB_HASH0;
+        p.len[r0 + tid] = 0;
+        p.pred[r0 + tid] = bos;
+    }
+    if (tid == 0) {
+        p.n_nodes[b] = 0;
+        frames_done[b] = 0;
+        n_committed[b] = 0;
+    }
+    const int H4 = H / 4, LH4 = L * H4;
+    const size_t SW = (size_t)S * W;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int idx = tid; idx < W * LH4; idx += 256) {
+        const int pos = idx / LH4, rem = idx % LH4, l = rem / H4, j = rem % H4;
+        const size_t at = ((size_t)l * SW + r0 + pos) * H4 + j;
+        ((float4*)p.hs[0])[at] = zero; ((float4*)p.hs[1])[at] = zero;
+        ((float4*)p.cs[0])[at] = zero; ((float4*)p.cs[1])[at] = zero;
+    }
+}
+
+// One wave per stream, once per advance, after the last frame.  Node ids grow with creation and a parent is older than
+// its child, which a dense renumbering in index order keeps: every walk towards the root strictly descends.
+//   1. lane j = row j: the depth of its leaf; all live rows climb to the smallest depth, then together until they
+//      stand on one node - the lowest common ancestor (the root, -1, as soon as one live row sits on it);
+//   2. lane 0 writes the path root -> ancestor into the commit records (token, frame, lp), record 0 = the counts;
+//   3. the nodes between a live leaf and the ancestor are marked, numbered by a running count over the marks, and moved
+//      down to their numbers with their parents renamed (the ancestor's children get parent -1); a chunk of 64 nodes
+//      is read whole before any of it is written, and a node never moves up, so nothing unread is overwritten;
+//   4. the rows' leaves are renamed, the stream's counters advance.
+// No atomics; the result depends on the tree alone.  `remap`: int32 [S][NC] scratch.
+__global__ __launch_bounds__(64) void sync_stream_compact(SyncPtrs p, int32_t* __restrict__ frames_done,
+                                                          long long* __restrict__ n_committed,
+                                                          int32_t* __restrict__ remap, int4* __restrict__ commit, int W,
+                                                          int NC) {
+    const int b = blockIdx.x, lane = threadIdx.x, r0 = b * W;
+    int2* tree = p.nodes + (size_t)b * NC;
+    int32_t* nfr = p.nd_frame + (size_t)b * NC;
+    float* nlp = p.nd_lp + (size_t)b * NC;
+    int32_t* map = remap + (size_t)b * NC;
+    int4* out = commit + (size_t)b * (NC + 1);
+    const int n = min(max(p.n_nodes[b], 0), NC);
+    const bool live = lane < W && p.logp[r0 + min(lane, W - 1)] != -(double)INFINITY;
+    int leaf = live ? p.node[r0 + lane] : -1;
+    if (leaf >= n) leaf = -1;               // (cannot happen on a state the advances wrote)
+    // 1.
+    int d = 0;
+    for (int nd = leaf; nd >= 0 && d < n; nd = tree[nd].x) ++d;
+    int dmin = live ? d : 0x7fffffff;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) dmin = min(dmin, __shfl_xor(dmin, off, 64));
+    const unsigned long long m_live = __ballot(live);
+    if (m_live == 0ull) dmin = 0;
+    int a = leaf;
+    for (int k = d; live && k > dmin && a >= 0; --k) a = tree[a].x;
+    const int first = m_live ? __ffsll((unsigned long long)m_live) - 1 : 0;
+    while (dmin > 0) {
+        const int a0 = __shfl(a, first, 64);
+        if (__ballot(live && a != a0) == 0ull) break;
+        if (live && a >= 0) a = tree[a].x;
+        --dmin;
+    }
+    const int lca = dmin > 0 ? __shfl(a, first, 64) : -1;
+    // 2.
+    if (lane == 0) {
+        int k = dmin;
+        for (int nd = lca; nd >= 0 && k > 0; nd = tree[nd].x) {
+            --k;
+            out[1 + k] = make_int4(tree[nd].y, nfr[nd], __float_as_int(nlp[nd]), 0);
+        }
+    }
+    // 3.
+    for (int i = lane; i < n; i += 64) map[i] = 0;
+    __syncthreads();
+    if (live) {
+        int steps = 0;
+        for (int nd = leaf; nd >= 0 && nd != lca && steps < n; nd = tree[nd].x, ++steps) map[nd] = 1;
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int n_live = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool m = i < n && map[i] != 0;
+        const unsigned long long bal = __ballot(m);
+        if (i < n) map[i] = m ? n_live + __popcll(bal & below) : -1;
+        n_live += __popcll(bal);
+    }
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const int id = i < n ? map[i] : -1;
+        int2 nd = make_int2(-1, 0);
+        int fr = 0;
+        float lp = 0.f;
+        if (id >= 0) {
+            nd = tree[i];
+            fr = nfr[i];
+            lp = nlp[i];
+            nd.x = (nd.x < 0 || nd.x == lca) ? -1 : map[nd.x];
+        }
+        __syncthreads();
+        if (id >= 0) {
+            tree[id] = nd;
+            nfr[id] = fr;
+            nlp[id] = lp;
+        }
+        __syncthreads();
+    }
+    // 4.
+    if (live) p.node[r0 + lane] = (leaf < 0 || leaf == lca) ? -1 : map[leaf];
+    if (lane == 0) {
+        p.n_nodes[b] = n_live;
+        frames_done[b] += p.lens[b];
+        n_committed[b] += dmin;
+        out[0] = make_int4(dmin, n_live, 0, 0);
+    }
+}
+
+}  // namespace
+
+extern "C" size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, int node_capacity) {
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity)) return 0;
+    return sync_stream_state_layout(S, W, L, H, node_capacity).total;
+}
+
+extern "C" size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                       int W, int node_capacity) {
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W)) return 0;
+    return sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
+}
+
+extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens) {
+    if (S <= 0 || W < 1 || W > SB_MAXW || max_tokens < 0) return 0;
+    return sync_result_layout(S, W, max_tokens).total;
+}
+
+#define SYNC_STREAM_CHECK_SHAPE(what, S, L, H, W, NC)                                                              \
+    do {                                                                                                           \
+        ED_CHECK_ARG(W >= 1 && W <= SB_MAXW, what ": beam width W = %d outside [1, %d]", W, SB_MAXW);              \
+        ED_CHECK_ARG(S > 0, what ": S = %d streams (must be > 0)", S);                                             \
+        ED_CHECK_ARG(NC >= W, what ": node_capacity = %d is too small (must be >= W = %d)", NC, W);                \
+        ED_CHECK_ARG(L > 0 && H > 0 && H % 4 == 0, what ": bad shape (H = %d must be a positive multiple of 4)", H); \
+        ED_CHECK_ARG(sync_stream_dims_ok(S, L, H, W, NC), what ": bad shape (too many rows or nodes)");            \
+    } while (0)
+
+extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                          int mask_on_host, void* state, void* stream_) {
+    SYNC_STREAM_CHECK_SHAPE("sync_stream_reset", S, L, H, W, node_capacity);
+    ED_CHECK_ARG(bos >= 0, "sync_stream_reset: bos = %d outside the vocabulary", bos);
+    ED_CHECK_ARG(state, "sync_stream_reset: null pointer (state)");
+    hipStream_t s = (hipStream_t)stream_;
+    char* st = (char*)state;
+    const SyncStreamState a = sync_stream_state_layout(S, W, L, H, node_capacity);
+    const SyncPtrs q = sync_stream_bind(st, a);
+    int32_t* frames_done = at<int32_t>(st, a.frames_done);
+    long long* n_committed = at<long long>(st, a.n_committed);
+    if (!mask || !mask_on_host) {
+        hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, frames_done, n_committed, mask, 0, S, W,
+                           L, H, bos);
+    } else {            // host mask: one launch per run of selected streams
+        for (int b = 0; b < S;) {
+            if (!mask[b]) { ++b; continue; }
+            int e = b;
+            while (e < S && mask[e]) ++e;
+            hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(e - b), dim3(256), 0, s, q, frames_done, n_committed,
+                               (const int32_t*)nullptr, b, S, W, L, H, bos);
+            b = e;
+        }
+    }
+    ED_CHECK_LAUNCH("sync_stream_reset");
+    return ED_OK;
+}
+
+extern "C" int edgedict_sync_stream_advance(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
+    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
+    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
+    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+    int max_commit, void* state, void* workspace, void* stream_) {
+    const int NC = node_capacity;
+    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_stream_advance: bad dtype");
+    SYNC_STREAM_CHECK_SHAPE("sync_stream_advance", S, L, H, W, NC);
+    ED_CHECK_ARG(T >= 0, "sync_stream_advance: T = %d frames (must be >= 0)", T);
+    ED_CHECK_ARG(sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) && max_commit >= 0, "sync_stream_advance: bad shape");
+    ED_CHECK_ARG((E1 || T == 0) && n_frames_host && W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp &&
+                     bp && live_host && parity_host && commit_host && state && workspace,
+                 "sync_stream_advance: null pointer");
+    for (int k = 0; k < L; ++k)
+        ED_CHECK_ARG(w_ih[k] && w_hh[k] && b_ih[k] && b_hh[k], "sync_stream_advance: null pointer (layer %d)", k);
+    ED_CHECK_ARG(emb_dtype == ED_F32 || emb_dtype == ED_BF16, "sync_stream_advance: bad embedding dtype");
+    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "sync_stream_advance: blank/bos outside the vocabulary");
+    ED_CHECK_ARG(*parity_host == 0 || *parity_host == 1, "sync_stream_advance: parity = %d (0 or 1)", *parity_host);
+    int maxlen = 0, cols = 0;
+    for (int b = 0; b < S; ++b) {
+        const int nf = n_frames_host[b];
+        ED_CHECK_ARG(nf >= 0 && nf <= T, "sync_stream_advance: n_frames[%d] = %d outside [0, %d]", b, nf, T);
+        ED_CHECK_ARG(live_host[b] >= 0 && live_host[b] <= NC, "sync_stream_advance: live[%d] = %d outside [0, %d]", b,
+                     live_host[b], NC);
+        ED_CHECK_ARG((long long)live_host[b] + (long long)nf * W <= NC,
+                     "sync_stream_advance: stream %d may need %lld token-tree nodes (%d live + %d frames x W = %d), "
+                     "node_capacity is %d",
+                     b, (long long)live_host[b] + (long long)nf * W, live_host[b], nf, W, NC);
+        maxlen = std::max(maxlen, nf);
+        cols = std::max(cols, std::min(NC, live_host[b] + nf));
+    }
+    ED_CHECK_ARG(cols <= max_commit, "sync_stream_advance: max_commit = %d, this advance may commit %d tokens",
+                 max_commit, cols);
+    hipStream_t s = (hipStream_t)stream_;
+    const int SW = S * W;
+    char* p = (char*)workspace;
+    char* st = (char*)state;
+    SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, nullptr, (long long)J, 0, SW, J, W1d, ldw1, b1, P2, W2, b2, V,
+                  {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, 0, NC};
+    const SyncStreamWs w = sync_stream_ws_layout(net, S, W, NC);
+    const SyncStreamState a = sync_stream_state_layout(S, W, L, H, NC);
+    StepBufs u = bind(p + w.step_at, w.step);
+    net.E1 = p + w.e1g;
+    SyncPtrs q = sync_stream_bind(st, a);
+    u.pred = q.pred;            // the step reads the rows' last tokens where the state keeps them
+    q.c_score = at<double>(p, w.c_score);
+    q.c_k = at<int32_t>(p, w.c_k);
+    q.c_lp = at<float>(p, w.c_lp);
+    q.lens = at<int32_t>(p, w.lens);
+    int32_t* frames_done = at<int32_t>(st, a.frames_done);
+
+    ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
+    const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    int cur = *parity_host;
+    for (int t = 0; t < maxlen; ++t) {
+        dispatch(dtype, [&](auto tag) {
+            using ET = decltype(tag);
+            hipLaunchKernelGGL(sync_gather<ET>, dim3(ed_grid_for((long long)SW * J, 256)), dim3(256), 0, s, (const ET*)E1,
+                               e_row_stride, e_frame_stride, t, (ET*)(p + w.e1g), SW, W, J);
+        });
+        int rc;
+        if (fused) rc = ed_decode_fused_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
+        else rc = ed_decode_composed_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
+        if (rc) return rc;
+        if (V <= 256 * SB_VPT) hipLaunchKernelGGL(sync_row_topw<true>, dim3(SW), dim3(256), 0, s, q, u.logits, t, W, V);
+        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(SW), dim3(256), 0, s, q, u.logits, t, W, V);
+        hipLaunchKernelGGL(sync_stream_select, dim3(S), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, S, L, H, NC,
+                           blank, bos, (const int32_t*)frames_done);
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(sync_stream_compact, dim3(S), dim3(64), 0, s, q, frames_done, at<long long>(st, a.n_committed),
+                       at<int32_t>(p, w.remap), at<int4>(p, w.commit), W, NC);
+    ED_CHECK_LAUNCH("sync_stream_advance");
+    *parity_host = cur;
+    // the one read of the advance: every stream's counts and the records this advance can have written
+    ED_CHECK_HIP(hipMemcpy2DAsync(commit_host, ((size_t)max_commit + 1) * 16, p + w.commit, ((size_t)NC + 1) * 16,
+                                  ((size_t)cols + 1) * 16, S, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    const int32_t* rec = (const int32_t*)commit_host;
+    for (int b = 0; b < S; ++b) live_host[b] = rec[(size_t)b * ((size_t)max_commit + 1) * 4 + 1];
+    return ED_OK;
+}
+
+extern "C" int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, const void* state, void* result,
+                                         int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
+                                         int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                         long long* ncommitted_host, long long* nframes_host, void* stream_) {
+    const int NC = node_capacity;
+    SYNC_STREAM_CHECK_SHAPE("sync_stream_read", S, L, H, W, NC);
+    ED_CHECK_ARG(max_tokens >= 0, "sync_stream_read: max_tokens = %d (must be >= 0)", max_tokens);
+    ED_CHECK_ARG(state && result && tokens_host && ntokens_host && nhyp_host && logp_host,
+                 "sync_stream_read: null pointer");
+    hipStream_t s = (hipStream_t)stream_;
+    char* st = (char*)state;            // (read only: sync_read writes the result alone)
+    const SyncStreamState a = sync_stream_state_layout(S, W, L, H, NC);
+    const SyncPtrs q = sync_stream_bind(st, a);
+    const SyncRes r = sync_result_layout(S, W, max_tokens);
+    char* rp = (char*)result;
+    const int SW = S * W;
+    hipLaunchKernelGGL(sync_read, dim3(S), dim3(64), 0, s, q, W, NC, max_tokens, at<int32_t>(rp, r.nhyp),
+                       at<int32_t>(rp, r.len), at<double>(rp, r.logp), at<int32_t>(rp, r.tok), at<int32_t>(rp, r.frame),
+                       at<double>(rp, r.lp));
+    ED_CHECK_LAUNCH("sync_stream_read");
+    ED_CHECK_HIP(hipMemcpyAsync(nhyp_host, rp + r.nhyp, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(ntokens_host, rp + r.len, (size_t)SW * 4, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipMemcpyAsync(logp_host, rp + r.logp, (size_t)SW * 8, hipMemcpyDeviceToHost, s));
+    std::vector<int32_t> fd;
+    if (nframes_host) {
+        fd.resize(S);
+        ED_CHECK_HIP(hipMemcpyAsync(fd.data(), st + a.frames_done, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (ncommitted_host)
+        ED_CHECK_HIP(hipMemcpyAsync(ncommitted_host, st + a.n_committed, (size_t)S * 8, hipMemcpyDeviceToHost, s));
+    ED_CHECK_HIP(hipStreamSynchronize(s));
+    if (nframes_host)
+        for (int b = 0; b < S; ++b) nframes_host[b] = fd[b];
+    int longest = 0;
+    for (int b = 0; b < S; ++b)
+        for (int j = 0; j < nhyp_host[b]; ++j) {
+            const int len = ntokens_host[(size_t)b * W + j];
+            ED_CHECK_ARG(len <= max_tokens, "sync_stream_read: tail of %d tokens exceeds max_tokens = %d", len, max_tokens);
+            longest = std::max(longest, len);
+        }
+    if (longest > 0) {
+        // the used columns only - or, where the rows are short (the caller sizes max_tokens by the live trees), the
+        // whole arrays in one piece each: a 2-D copy of S W short rows costs more than the bytes it saves
+        const size_t MT = (size_t)max_tokens;
+        const bool whole = (size_t)SW * MT * 8 <= ((size_t)1 << 20);
+        auto fetch = [&](void* dst, const char* src, size_t esz) -> hipError_t {
+            if (!dst) return hipSuccess;
+            if (whole) return hipMemcpyAsync(dst, src, (size_t)SW * MT * esz, hipMemcpyDeviceToHost, s);
+            return hipMemcpy2DAsync(dst, MT * esz, src, MT * esz, (size_t)longest * esz, SW, hipMemcpyDeviceToHost, s);
+        };
+        ED_CHECK_HIP(fetch(tokens_host, rp + r.tok, 4));
+        ED_CHECK_HIP(fetch(frames_host, rp + r.frame, 4));
+        ED_CHECK_HIP(fetch(token_logp_host, rp + r.lp, 8));
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;

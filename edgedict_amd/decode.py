@@ -45,7 +45,8 @@ lists; it takes ``bias=`` too.
 ``sync_beam_search`` (``_nbest``, ``_enc``, ``_rows``) is a SECOND RNN-T beam search, frame-synchronous (at most one
 symbol per frame and hypothesis, all B x W hypotheses in one step per frame, equal sequences merged by log-add;
 csrc/decode_sync.hip).  A different algorithm from ``beam_search_batch``: it does not return the same hypotheses, and
-takes neither ``lm=`` nor ``bias=`` nor ``prefix=``.
+takes neither ``lm=`` nor ``bias=`` nor ``prefix=``.  ``StreamingSyncBeamSearch`` runs it over encoder output that
+arrives chunk by chunk, carrying every stream's beam in a persistent device state, with the offline search's bits.
 """
 import ctypes
 
@@ -460,7 +461,7 @@ def sync_beam_search(model, xs, xlen=None, W=10):
 
     This is a different algorithm from ``beam_search_batch`` (the reference's best-first search, which may emit several
     symbols per frame and never merges): the two do not return the same hypotheses.  It takes no ``lm=``, ``bias=`` or
-    ``prefix=`` and has no streaming form.
+    ``prefix=``.  Its streaming form is ``StreamingSyncBeamSearch``.
 
     Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
     utterance, in ``beam_search_batch``'s types."""
@@ -875,6 +876,223 @@ class StreamingBeamSearch:
         hypothesis of ``nbest()`` that no later frame can change.  Needs ``detail=True``."""
         self._need_detail("committed_detail")
         return [(np.asarray(t, dtype=np.int64), np.asarray(f, dtype=np.int32), np.asarray(l, dtype=np.float64))
+                for t, f, l in zip(self._committed, self._committed_frames, self._committed_logp)]
+
+
+class StreamingSyncBeamSearch:
+    """The frame-synchronous beam search of ``sync_beam_search`` for S streams whose encoder output arrives chunk by
+    chunk (csrc/decode_sync.hip, ``edgedict_sync_stream_*``).
+
+    Every stream's beam - W rows with their log p, token-tree node, sequence hash, last token and prediction-network
+    state - lives in a persistent device state and stays in beam order between chunks, so ``advance`` over frames
+    [0, t1) and then [t1, t2) leaves exactly the beam the offline search has after t2 frames: after any chunk ``nbest()``
+    is bit for bit what ``sync_beam_search_nbest_rows`` over the stream's frames since its reset returns, and ``best()``
+    is its entry 0.  A frame is the offline search's launches (6 + L); nothing inside the frame loop waits for the
+    host.  A stream may take fewer frames of a chunk than the others, or none (``n_frames``).
+
+    After the last frame of an advance ONE launch compacts every stream's token tree: the tokens from the root down to
+    the lowest common ancestor of the live hypotheses' leaves are committed - no later frame can change them - and move
+    to a host-side log with their frames and log-probs, that ancestor becomes the root, and the nodes a live leaf still
+    reaches are renumbered densely.  The device tree therefore stays bounded by ``node_capacity`` however long a stream
+    runs.  The committed prefix is the TREE's common ancestor, not the longest common token prefix of the beam: a
+    sequence that was pruned and later created again has a second chain of nodes, so hypotheses that agree on their
+    first tokens can still hold them in different nodes, and those tokens are committed later (or, at the latest, never
+    lost: ``nbest()`` always returns whole hypotheses).  Per advance there is one device-to-host read (per stream the
+    commit count, the live node count and the committed records) and one stream synchronisation, after the compaction.
+
+    ``node_capacity`` (NC): token-tree nodes per stream.  An advance adds at most ``n_frames[s] * W`` nodes to stream s,
+    so one with ``live[s] + n_frames[s] * W > NC`` (``live[s]``: the stream's nodes after the previous advance's
+    compaction) raises ``RuntimeError`` before anything is launched and leaves the state as it was; nothing is ever
+    truncated.  Default ``NC = 32 * W + 1024``: room for chunks of 32 frames on top of a live tree of 1024 nodes.
+
+    ``1 <= W <= 32``.  There is no ``lm=``, ``bias=``, ``prefix=`` or ``max_expansions=``: the offline search has none.
+    A stream with no frames since its reset holds one empty hypothesis with ``logp`` 0."""
+
+    _EMPTY = (np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64))
+
+    def __init__(self, model, n_streams, W=10, node_capacity=None):
+        _check_sync_width(W)
+        if n_streams < 1:
+            raise ValueError("n_streams must be >= 1")
+        self.model = model
+        self.S = int(n_streams)
+        self.W = int(W)
+        self.NC = int(node_capacity) if node_capacity else 32 * self.W + 1024
+        if self.NC < self.W:
+            raise ValueError("node_capacity = %d is below W = %d: not even one frame fits" % (self.NC, self.W))
+        _lib.require_cuda(model.decoder.embed.weight)
+        from .stream import _compute_dtype
+        self.cd = _compute_dtype(model)
+        self.device = model.decoder.embed.weight.device
+        net = self._weights()
+        lib = _lib.load()
+        self._state = torch.empty(lib.edgedict_sync_stream_state_bytes(self.S, net.L, net.H, self.W, self.NC),
+                                  dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(lib.edgedict_sync_stream_workspace_bytes(
+            dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.NC),
+            dtype=torch.uint8, device=self.device)
+        if self._state.numel() == 0 or self._ws.numel() == 0:
+            raise ValueError("StreamingSyncBeamSearch: shapes out of range (H must be a multiple of 4)")
+        self._result, self._result_mt = None, -1
+        self._live = np.zeros(self.S, dtype=np.int32)        # token-tree nodes per stream after the last compaction
+        self._parity = ctypes.c_int32(0)                     # which state buffer the next frame reads
+        self._frames = np.zeros(self.S, dtype=np.int64)      # frames per stream since its reset
+        self._ncommitted = np.zeros(self.S, dtype=np.int64)  # tokens in its committed log
+        # the advance's read: [S][1 + NC] records {int32, int32, float32, int32}; record 0 = (commits, live nodes)
+        self._commit_buf = np.zeros((self.S, self.NC + 1, 4), dtype=np.int32)
+        # the committed log per stream, as arrays: (tokens int64, frames int32, token_logp float64)
+        self._committed = [self._EMPTY[0]] * self.S
+        self._committed_frames = [self._EMPTY[1]] * self.S
+        self._committed_logp = [self._EMPTY[2]] * self.S
+        self.reset()
+
+    def _weights(self):
+        return _SearchNet(self.model, self.cd)
+
+    def reset(self, mask=None):
+        """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log;
+        its frames count from 0 again."""
+        from .tokenizer import BOS
+        net = self._weights()
+        if mask is None:
+            sel = np.ones(self.S, dtype=bool)
+            mp, on_host = None, 0
+        else:
+            m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+            sel = m.astype(bool).reshape(self.S)
+            mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
+            mp = mh.ctypes.data_as(ctypes.c_void_p)
+        rc = _lib.load().edgedict_sync_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
+                                                    _lib.ptr(self._state), _lib.stream_ptr())
+        _lib.check(rc, "sync_stream_reset")
+        self._frames[sel] = 0
+        self._live[sel] = 0
+        self._ncommitted[sel] = 0
+        for s in np.nonzero(sel)[0]:
+            self._committed[s], self._committed_frames[s], self._committed_logp[s] = self._EMPTY
+
+    def joint_rows(self, enc_out):
+        """The rows ``advance`` reads for ``enc_out`` [S, T, P]: see ``joint_rows``."""
+        return self._weights().e1(enc_out)
+
+    def _n_frames(self, what, n_frames, T):
+        if n_frames is None:
+            return np.full(self.S, T, dtype=np.int32)
+        nf = np.ascontiguousarray(n_frames.cpu().numpy() if torch.is_tensor(n_frames) else n_frames, dtype=np.int32)
+        if nf.shape != (self.S,) or (nf < 0).any() or (nf > T).any():
+            raise ValueError("%s: n_frames must be [S] ints in [0, %d]" % (what, T))
+        return nf
+
+    def advance(self, enc_out, n_frames=None):
+        """Advance every stream over the first ``n_frames[s]`` frames (host ints, default all T; 0: the stream sits
+        this chunk out) of ``enc_out`` [S, T, P] (compute dtype, on the device)."""
+        _lib.require_cuda(enc_out)
+        if enc_out.dim() != 3 or enc_out.shape[0] != self.S:
+            raise ValueError("advance: enc_out must be [S=%d, T, P]" % self.S)
+        if enc_out.dtype != self.cd:
+            raise TypeError("advance: enc_out is %s, the model computes in %s" % (enc_out.dtype, self.cd))
+        enc_out = enc_out.contiguous()
+        S, T, P = enc_out.shape
+        nf = self._n_frames("advance", n_frames, T)
+        net = self._weights()
+        self._advance(net, net.e1(enc_out), T, P, nf)
+
+    def advance_rows(self, E1, P, n_frames=None):
+        """``advance`` from the joint's encoder rows ``E1`` [S * T, J] (``joint_rows``) of an encoder output of width
+        P: what ``advance`` runs after its first product."""
+        _lib.require_cuda(E1)
+        net = self._weights()
+        if E1.dim() != 2 or E1.shape[1] != net.J or E1.shape[0] % self.S or not E1.is_contiguous():
+            raise ValueError("advance_rows: E1 must be contiguous [S * T, J=%d]" % net.J)
+        if E1.dtype != self.cd:
+            raise TypeError("advance_rows: E1 is %s, the model computes in %s" % (E1.dtype, self.cd))
+        T = E1.shape[0] // self.S
+        self._advance(net, E1, T, P, self._n_frames("advance_rows", n_frames, T))
+
+    def _advance(self, net, E1, T, P, nf):
+        from .tokenizer import BOS
+        need = self._live.astype(np.int64) + nf.astype(np.int64) * self.W
+        if (need > self.NC).any():
+            s = int(np.argmax(need > self.NC))
+            raise RuntimeError("StreamingSyncBeamSearch: stream %d may need %d token-tree nodes (%d live + %d frames x "
+                               "W = %d), node_capacity is %d" % (s, need[s], self._live[s], nf[s], self.W, self.NC))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = _lib.load().edgedict_sync_stream_advance(
+            dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, T, vp(nf),
+            *net.args(P), int(self.model.blank), int(BOS), self.W, self.NC, vp(self._live),
+            ctypes.byref(self._parity), vp(self._commit_buf), self.NC, _lib.ptr(self._state), _lib.ptr(self._ws),
+            _lib.stream_ptr())
+        _lib.check(rc, "sync_stream_advance")
+        self._frames += nf
+        ncommit = self._commit_buf[:, 0, 0]
+        self._ncommitted += ncommit
+        for s in np.nonzero(ncommit)[0]:
+            rec = self._commit_buf[s, 1:1 + ncommit[s]]
+            lp = np.ascontiguousarray(rec[:, 2]).view(np.float32).astype(np.float64)
+            self._committed[s] = np.concatenate([self._committed[s], rec[:, 0].astype(np.int64)])
+            self._committed_frames[s] = np.concatenate([self._committed_frames[s], rec[:, 1]])
+            self._committed_logp[s] = np.concatenate([self._committed_logp[s], lp])
+
+    def live_nodes(self):
+        """int32 [S]: every stream's token-tree nodes after the last advance's compaction (what the capacity rule
+        counts)."""
+        return self._live.copy()
+
+    def _read(self, detail=True):
+        """The read-out: the ranked uncommitted tails of every stream as host arrays (``detail=False``: tokens only)."""
+        net = self._weights()
+        lib = _lib.load()
+        S, W = self.S, self.W
+        MT = max(1, int(self._live.max()))          # a tail holds at most the stream's live nodes
+        if self._result_mt < MT:
+            self._result = torch.empty(lib.edgedict_sync_stream_result_bytes(S, W, MT), dtype=torch.uint8,
+                                       device=self.device)
+            self._result_mt = MT
+        MT = self._result_mt
+        tokens = np.empty((S, W, MT), dtype=np.int32)       # (only the used columns are written and read)
+        frames = np.empty((S, W, MT), dtype=np.int32) if detail else None
+        tlogp = np.empty((S, W, MT), dtype=np.float64) if detail else None
+        ntok = np.zeros((S, W), dtype=np.int32)
+        nhyp = np.zeros(S, dtype=np.int32)
+        logp = np.zeros((S, W), dtype=np.float64)
+        ncom = np.zeros(S, dtype=np.int64)
+        nfr = np.zeros(S, dtype=np.int64)
+        vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        rc = lib.edgedict_sync_stream_read(S, net.L, net.H, W, self.NC, _lib.ptr(self._state), _lib.ptr(self._result),
+                                           vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp), vp(ncom),
+                                           vp(nfr), _lib.stream_ptr())
+        _lib.check(rc, "sync_stream_read")
+        bad = (ncom != self._ncommitted) | (nfr != self._frames)
+        if bad.any():
+            s = int(np.argmax(bad))
+            raise RuntimeError("sync_stream_read: stream %d has %d committed tokens and %d frames on the device, "
+                               "%d and %d on the host" % (s, ncom[s], nfr[s], self._ncommitted[s], self._frames[s]))
+        return tokens, frames, tlogp, ntok, nhyp, logp
+
+    def nbest(self):
+        """Per stream a ranked ``NBestResult`` (``logp`` descending, ties keep beam order): the beam as
+        ``sync_beam_search_nbest`` over the stream's frames since its reset returns it, every hypothesis the committed log
+        followed by its uncommitted tail, in tokens, frames and ``token_logp`` alike.  Does not modify the state."""
+        prefix = list(zip(self._committed, self._committed_frames, self._committed_logp))
+        return _nbest_results(*self._read(), prefix)
+
+    def best(self):
+        """Per stream the best hypothesis of the current beam - entry 0 of ``nbest()`` -, as ``sync_beam_search`` returns
+        it: ``(list of int64 arrays (tokens, no blanks), fp64 tensor [S] = -log p)``."""
+        tokens, _, _, ntok, _, logp = self._read(detail=False)
+        tails, n = tokens[:, 0].astype(np.int64), ntok[:, 0].tolist()
+        seqs = [np.concatenate([c, tails[s, :n[s]]]) if len(c) else tails[s, :n[s]].copy()
+                for s, c in enumerate(self._committed)]
+        return seqs, torch.from_numpy(-logp[:, 0])
+
+    def committed(self):
+        """Per stream the committed tokens (int64 arrays): a prefix of every hypothesis of ``nbest()`` that no later
+        frame can change."""
+        return [c.copy() for c in self._committed]
+
+    def committed_detail(self):
+        """Per stream ``(tokens int64, frames int32, token_logp float64)`` of the committed log."""
+        return [(t.copy(), f.copy(), l.copy())
                 for t, f, l in zip(self._committed, self._committed_frames, self._committed_logp)]
 
 

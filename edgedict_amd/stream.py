@@ -375,6 +375,73 @@ class BatchedStreamBeamDecoder(StreamTransducerDecoder):
         return self.search.committed_detail()
 
 
+class BatchedStreamSyncBeamDecoder(StreamTransducerDecoder):
+    """S streams decoded concurrently with the frame-synchronous beam search (``Transducer.sync_beam_search``).
+
+    Same chunk geometry (``chunk_geometry``), feature transform and carried encoder (h, c) as
+    ``BatchedStreamBeamDecoder``; the search is ``decode.StreamingSyncBeamSearch``, which keeps every stream's beam from
+    chunk to chunk, so after any chunk a stream's ``best()`` / ``nbest()`` is what the offline frame-synchronous search
+    over its audio so far returns.  ``1 <= W <= 32``; no ``lm=``, ``bias=``, ``prefix=`` or ``max_expansions=``, as the
+    offline search; ``node_capacity`` as ``decode.StreamingSyncBeamSearch``."""
+
+    def __init__(self, transducer, flags, n_streams, W=10, node_capacity=None, dither=None):
+        from .decode import StreamingSyncBeamSearch
+        self.model = transducer.eval()
+        self.flags = flags
+        self.S = n_streams
+        dev = transducer.decoder.embed.weight.device
+        self.device = dev
+        self.search = StreamingSyncBeamSearch(transducer, n_streams, W=W, node_capacity=node_capacity)
+        self.transform = StackedLogFbank(
+            n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
+            hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,
+            dither=1e-5 if dither is None else dither).to(dev)
+        self.reset_profile()
+        self.reset()
+
+    @torch.no_grad()
+    def reset(self, mask=None):
+        """Reset every stream, or only those where ``mask[s]`` is true."""
+        enc = self.model.encoder.lstm
+        L, H = len(enc.lstms), enc.hidden_size
+        if mask is None or not hasattr(self, "enc_h"):
+            self.enc_h = torch.zeros(L, self.S, H, device=self.device)
+            self.enc_c = torch.zeros(L, self.S, H, device=self.device)
+            self.search.reset()
+            return
+        m = torch.as_tensor(mask).to(self.device).bool()
+        self.enc_h[:, m] = 0
+        self.enc_c[:, m] = 0
+        self.search.reset(m)
+
+    @torch.no_grad()
+    def decode(self, frames):
+        """frames: float32 [S, win_size] on the device -> ``(list of int64 arrays, fp64 tensor [S])``: every stream's
+        best hypothesis over its audio so far (tokens without blanks, -log p), as ``best()`` returns it."""
+        t0 = time.time()
+        encoder_stack.check_wsr_error()
+        xs, _ = self.transform(frames)
+        enc_out, (self.enc_h, self.enc_c) = self.model.encoder(xs, (self.enc_h, self.enc_c))
+        self.encoder_elapsed.append(time.time() - t0)
+        t0 = time.time()
+        self.search.advance(enc_out.contiguous())
+        out = self.search.best()
+        self.joint_elapsed.append(time.time() - t0)
+        return out
+
+    def best(self):
+        return self.search.best()
+
+    def committed(self):
+        return self.search.committed()
+
+    def nbest(self):
+        return self.search.nbest()
+
+    def committed_detail(self):
+        return self.search.committed_detail()
+
+
 class PytorchStreamDecoder(StreamTransducerDecoder):
     """Single-stream decoder with the reference's constructor: ``PytorchStreamDecoder(FLAGS)``
     loads ``logs/<FLAGS.name>/models/<FLAGS.model_name>`` (or ``logs/<name>/<model_name>``) and

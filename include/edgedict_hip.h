@@ -1293,6 +1293,69 @@ int edgedict_sync_beam_search(int dtype, const void* E1, long long e_row_stride,
                               int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
                               void* workspace, void* result, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Streaming form of the frame-synchronous search: the beams of S streams live in a persistent device STATE, so that
+ * advancing over frames [0, t1) and then [t1, t2) leaves exactly the beam edgedict_sync_beam_search has after t2 frames,
+ * and sync_stream_read after any advance returns what that search returns over the frames since the stream's reset.
+ * Per stream the state holds the W rows (fp64 logp, token-tree node, sequence hash and length, last token), the rows'
+ * prediction-network (h, c) [L][S*W][H] in two buffers (read / written alternately per frame), the token tree
+ * (parent, token, frame, lp) [node_capacity] with its node count, the frames since the reset and the committed tokens.
+ * A frame is the offline search's launches; a stream that is past its n_frames copies its rows' states through to the
+ * other buffer, so every stream finds its states where the next frame reads.  After the last frame ONE launch per
+ * advance compacts every stream's tree: the path from the root to the lowest common ancestor of the live rows' leaves
+ * is COMMITTED (no later frame can change it) and returned, that ancestor becomes the root, the nodes still reachable
+ * from a live leaf are renumbered densely.  The committed path is the TREE's common ancestor: a sequence that was
+ * pruned and created again has a second node chain, so it can be shorter than the beam's common token prefix.
+ *
+ *   node_capacity  token-tree nodes per stream, >= W.  An advance adds at most n_frames[s] * W nodes to stream s:
+ *                  one with live[s] + n_frames[s] * W > node_capacity fails before anything is launched
+ *   sync_stream_state_bytes      device bytes of the state (contents undefined until a reset of all streams)
+ *   sync_stream_workspace_bytes  device bytes of the per-call workspace of sync_stream_advance
+ *   sync_stream_result_bytes     device bytes of sync_stream_read's result buffer
+ *                  (all three: 0 for arguments out of range; buffers 256-byte aligned)
+ *   sync_stream_reset    streams with mask[s] != 0 (mask null: all; mask_on_host: HOST int32 [S], else device) -> the
+ *                  empty hypothesis, zero states, an empty tree, no frames, nothing committed
+ *   sync_stream_advance  operands as edgedict_sync_beam_search; E1 holds this chunk's T frames per stream.
+ *                  n_frames_host HOST int32 [S] in [0, T] (0: the stream sits the chunk out, its beam unchanged)
+ *                  live_host   HOST int32 [S], in and out: every stream's live tree nodes - 0 after its reset, else
+ *                              what the previous advance wrote
+ *                  parity_host HOST int32, in and out: which state buffer holds the states; 0 before the first
+ *                              advance on a state, then what the previous advance wrote (resets leave it alone)
+ *                  commit_host HOST [S][1 + max_commit] records of 16 bytes {int32, int32, float, int32}: record 0 =
+ *                              {tokens committed by this advance, live nodes, -, -}, record 1 + k = {token, frame
+ *                              (counted from the stream's reset), the token's log-softmax value on that frame, -}.
+ *                              max_commit >= min(node_capacity, max over s of live[s] + n_frames[s])
+ *                  One device-to-host copy and one stream synchronisation, after the compaction; nothing inside the
+ *                  frame loop waits for the host.  After an error other than an argument or capacity error the
+ *                  advanced streams' state is undefined (reset them).
+ *   sync_stream_read     as edgedict_sync_beam_search's outputs, for the UNCOMMITTED tails: ranked by logp descending
+ *                  (ties keep beam order); a full hypothesis is the stream's committed log followed by its tail.
+ *                  frames_host / token_logp_host are nullable (tokens only); entries behind a tail's length are
+ *                  undefined.  ncommitted_host / nframes_host HOST int64 [S], nullable: committed tokens and frames
+ *                  since the reset.  Does not modify the state.  A tail longer than max_tokens is an error (a tail holds at
+ *                  most live[s] tokens).  Synchronises the stream.
+ * Every entry point checks its arguments before any launch (W outside [1, 32], S <= 0, node_capacity < W, null
+ * pointers, dtypes, blank / bos, n_frames, H % 4) and returns -1 with a message.
+ */
+size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, int node_capacity);
+size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
+                                            int node_capacity);
+size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens);
+int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                               int mask_on_host, void* state, void* stream);
+int edgedict_sync_stream_advance(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S,
+                                 int T, const int32_t* n_frames_host, int J, const void* W1d, long long ldw1,
+                                 const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
+                                 int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+                                 const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
+                                 const float* bp, int blank, int bos, int W, int node_capacity, int32_t* live_host,
+                                 int32_t* parity_host, void* commit_host, int max_commit, void* state,
+                                 void* workspace, void* stream);
+int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, const void* state, void* result,
+                              int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
+                              int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                              long long* ncommitted_host, long long* nframes_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
