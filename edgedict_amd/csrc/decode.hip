@@ -185,6 +185,14 @@ int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const fl
     return composed_joint(net, (const char*)E1t, u.dec_new, u, s);
 }
 
+// One LM step for `rows` rows (decode_net.hpp): shared by the best-first searches here and the frame-synchronous one
+int ed_decode_lm_step(int dtype, int rows, const LstmNet& lm, const float* h_state, const float* c_state,
+                      const StepBufs& u, hipStream_t s) {
+    if (ed_decode_fused_lm_ok(dtype, lm.emb_dtype, lm.V, lm.E, lm.H))
+        return ed_decode_fused_lm_step(dtype, rows, lm, h_state, c_state, u, s);
+    return composed_lstm_step(dtype, rows, lm, u.pred, h_state, c_state, u, ED_F32, u.logits, s);
+}
+
 extern "C" size_t edgedict_greedy_workspace_bytes(int dtype, int B, int J, int V, int E, int L,
                                                   int H, int P2) {
     if (B <= 0) return 0;
@@ -1040,8 +1048,7 @@ BeamBufs bind_beam_ptrs(char* p, const BeamWs* w, char* st, const BeamStreamStat
     }
     bb.lm = lm;
     if (!lm) return bb;
-    bb.lm_net = LstmNet{lm->emb, lm->emb_dtype, lm->V, lm->E, lm->L, lm->w_ih, lm->w_hh, lm->b_ih, lm->b_hh, lm->H, lm->Wo,
-                        lm->bo, lm->V};
+    bb.lm_net = lm_net_of(*lm);
     q.lm_L = lm->L;
     q.lm_H = lm->H;
     q.lm_bos = lm->bos;
@@ -1233,11 +1240,7 @@ struct PrefixMerge {
 
 // one LM step for every row: token lm_pred[b] from (lm_h_state, lm_c_state) -> new state, fp32 logits [B, V]
 int lm_step(int dtype, int B, const BeamBufs& bb, hipStream_t s) {
-    const LstmNet& n = bb.lm_net;
-    const BeamPtrs& q = bb.q;
-    if (ed_decode_fused_lm_ok(dtype, n.emb_dtype, n.V, n.E, n.H))
-        return ed_decode_fused_lm_step(dtype, B, n, q.lm_h_state, q.lm_c_state, bb.lmu, s);
-    return composed_lstm_step(dtype, B, n, q.lm_pred, q.lm_h_state, q.lm_c_state, bb.lmu, ED_F32, bb.lmu.logits, s);
+    return ed_decode_lm_step(dtype, B, bb.lm_net, bb.q.lm_h_state, bb.q.lm_c_state, bb.lmu, s);
 }
 
 // The frame loop shared by the offline search and the streaming one: frames [0, maxlen), utterance b taking part in
@@ -1439,6 +1442,13 @@ struct NBestOut {
     NBestHost host;
 };
 }  // namespace
+
+int ed_decode_lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what) {
+    return lm_check(lm, V, prefix, what);
+}
+int ed_decode_bias_check(const edgedict_beam_bias_t* bias, int V, int prefix, const char* what) {
+    return bias_check(bias, V, prefix, what);
+}
 
 extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
 extern "C" size_t edgedict_beam_bias_struct_bytes(void) { return sizeof(edgedict_beam_bias_t); }

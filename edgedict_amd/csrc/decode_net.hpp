@@ -27,6 +27,11 @@ struct LstmNet {
     int O;
 };
 
+// the fusion LM as an LstmNet (its decoder is the output layer, O = V)
+static inline LstmNet lm_net_of(const edgedict_beam_lm_t& lm) {
+    return LstmNet{lm.emb, lm.emb_dtype, lm.V, lm.E, lm.L, lm.w_ih, lm.w_hh, lm.b_ih, lm.b_hh, lm.H, lm.Wo, lm.bo, lm.V};
+}
+
 // Weights and shapes of one search call, as the extern "C" searches take them (include/edgedict_hip.h)
 struct SearchNet {
     int dtype, esz;
@@ -106,3 +111,10 @@ int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const fl
                                  const StepBufs& u, hipStream_t s);
 int ed_decode_fused_lm_step(int dtype, int B, const LstmNet& lm, const float* h_state, const float* c_state,
                             const StepBufs& u, hipStream_t s);
+// decode.hip: one LM step for `rows` rows, token u.pred[r] from (h_state, c_state) [L, rows, H] -> u.h_new / u.c_new and
+// fp32 logits u.logits [rows, V]: the fused step where ed_decode_fused_lm_ok holds, the composed one otherwise
+int ed_decode_lm_step(int dtype, int rows, const LstmNet& lm, const float* h_state, const float* c_state,
+                      const StepBufs& u, hipStream_t s);
+// decode.hip: an LM / a bias list that a search over the vocabulary V can use: ED_OK, or a status with a message
+int ed_decode_lm_check(const edgedict_beam_lm_t* lm, int V, int prefix, const char* what);
+int ed_decode_bias_check(const edgedict_beam_bias_t* bias, int V, int prefix, const char* what);

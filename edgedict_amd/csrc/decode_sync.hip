@@ -21,10 +21,18 @@
 // logp = -inf, token BOS and a zero state; the rows of an utterance past its length keep its final beam and are left
 // alone by both kernels.  Rows flow through the step kernels either way and are row-independent there.
 //
+// LM shallow fusion and a bias list (the *_fusion entry points, the *_fused kernels): a row also carries the LM state
+// from before its last token and the phrase automaton's state after its sequence; a frame gains the LM step on all
+// B * W rows (ed_decode_lm_step, behind the prediction-network step), and a non-blank candidate scores
+//   ((logp_i + (double) lp_i[k]) + (lm_w * (double) lp_lm_i[k] + lm_b)) + (held[goto(s_i, k)] - pend[s_i])
+// where a term is absent when its feature is.  Without either the plain kernels run, launch for launch.
+//
 // Second half of the file: the streaming form (edgedict_sync_stream_*), the same frame loop on a persistent state.
+#include "bias_tables.hpp"
 #include "decode_net.hpp"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -48,6 +56,25 @@ struct SyncPtrs {
     float* nd_lp;               // [B][NODES] its token's log-softmax value on that frame
     int32_t* n_nodes;           // [B]
     int32_t* lens;              // [B]
+};
+
+// What LM shallow fusion and a bias list add to the rows: the second argument block of the *_fused kernels (the plain
+// kernels never see it).  Row r carries the LM state from BEFORE its last token, as it carries the prediction network's,
+// the token the LM steps on (lm_bos for the empty sequence) and the phrase automaton's state after its sequence.
+struct SyncFuse {
+    float* lm_hs[2];            // [lm_L][B*W][lm_H], double-buffered per frame as hs / cs
+    float* lm_cs[2];
+    int32_t* lm_pred;           // [B*W]  len == 0 ? lm_bos : pred (the LM step's symbol)
+    int lm_L, lm_H, lm_bos;
+    double lm_w, lm_b;          // weight, length bonus
+    int32_t* bias_st;           // [B*W]  0: the automaton's root
+    const int32_t* bias_root_next;      // the tables of edgedict_beam_bias_t (bias_tables.hpp)
+    const double* bias_held;
+    const double* bias_pend;
+    const int32_t* bias_row_ptr;
+    const int32_t* bias_exc_tok;
+    const int32_t* bias_exc_next;
+    int bias_S, bias_V;
 };
 
 __device__ __forceinline__ float sb_block_sum_max(float x, bool is_max, float* s_f) {
@@ -89,8 +116,16 @@ __global__ void sync_gather(const T* __restrict__ E1, long long row_stride, long
 // CACHED (V <= 256 * SB_VPT): a thread keeps its SB_VPT scores in registers over the passes instead of reading the
 // logits again; the arithmetic and the order are the same either way.
 constexpr int SB_VPT = 8;
-template <bool CACHED>
-__global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __restrict__ logits, int t, int W, int V) {
+// LM / BIAS (sync_row_topw_fused): a non-blank candidate k scores
+//   ((base + (double)lp[k]) + (lm_w * (double)lp_lm[k] + lm_b)) + (held[goto(s, k)] - pend[s])
+// in fp64, in this order, without contraction (as beam_expand_body of decode.hip); lp_lm is the same fp32 log-softmax
+// over the row's LM logits, s the row's automaton state.  A term is absent when its feature is; blank keeps
+// base + lp[blank]; c_lp stays lp[k].  goto is bias_goto's binary search in s's (short) exception row, once per
+// candidate in the CACHED form and once per candidate and pass in the other.
+template <bool CACHED, bool LM, bool BIAS>
+__device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const SyncFuse& f,
+                                                   const float* __restrict__ logits,
+                                                   const float* __restrict__ lm_logits, int t, int W, int V, int blank) {
     const int r = blockIdx.x, tid = threadIdx.x;
     if (t >= p.lens[r / W]) return;
     const double base = p.logp[r];
@@ -106,12 +141,40 @@ __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __
     for (int v = tid; v < V; v += 256) s += expf(z[v] - m);
     s = sb_block_sum_max(s, false, sf);
     const float logs = logf(s);
+    const float* zl = nullptr;
+    float ml = 0.f, logsl = 0.f;
+    if constexpr (LM) {
+        zl = lm_logits + (size_t)r * V;
+        ml = -INFINITY;
+        for (int v = tid; v < V; v += 256) ml = fmaxf(ml, zl[v]);
+        ml = sb_block_sum_max(ml, true, sf);
+        float sl = 0.f;
+        for (int v = tid; v < V; v += 256) sl += expf(zl[v] - ml);
+        sl = sb_block_sum_max(sl, false, sf);
+        logsl = logf(sl);
+    }
+    int st = 0;
+    double pend_s = 0.0;
+    if constexpr (BIAS) {
+        st = bias_state(f, f.bias_st[r]);
+        pend_s = f.bias_pend[st];
+    }
+    auto score = [&](int v) -> double {
+        double c = base + (double)((z[v] - m) - logs);
+        if constexpr (LM) {
+            if (v != blank) c = c + __dadd_rn(__dmul_rn(f.lm_w, (double)((zl[v] - ml) - logsl)), f.lm_b);
+        }
+        if constexpr (BIAS) {
+            if (v != blank) c = __dadd_rn(c, __dsub_rn(f.bias_held[bias_goto(f, st, v)], pend_s));
+        }
+        return c;
+    };
     double sc[SB_VPT];
     if constexpr (CACHED) {
 #pragma unroll
         for (int i = 0; i < SB_VPT; ++i) {
             const int v = tid + 256 * i;
-            sc[i] = v < V ? base + (double)((z[v] - m) - logs) : -(double)INFINITY;
+            sc[i] = v < V ? score(v) : -(double)INFINITY;
         }
     }
     double prev = (double)INFINITY, my_best = -(double)INFINITY;
@@ -128,7 +191,7 @@ __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __
             }
         } else {
             for (int v = tid; v < V; v += 256) {
-                const double c = base + (double)((z[v] - m) - logs);
+                const double c = score(v);
                 if ((c < prev || (c == prev && v > prev_k)) && c > best) { best = c; arg = v; }
             }
         }
@@ -159,6 +222,18 @@ __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __
     }
 }
 
+template <bool CACHED>
+__global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __restrict__ logits, int t, int W, int V) {
+    sync_row_topw_body<CACHED, false, false>(p, SyncFuse{}, logits, nullptr, t, W, V, -1);
+}
+
+template <bool CACHED, bool LM, bool BIAS>
+__global__ __launch_bounds__(256) void sync_row_topw_fused(SyncPtrs p, SyncFuse f, const float* __restrict__ logits,
+                                                           const float* __restrict__ lm_logits, int t, int W, int V,
+                                                           int blank) {
+    sync_row_topw_body<CACHED, LM, BIAS>(p, f, logits, lm_logits, t, W, V, blank);
+}
+
 // One workgroup per utterance.  Wave 0, lane j = the j-th kept candidate: a W-way merge of the rows' sorted lists picks
 // the W best in order (ties: the lower row, inside a row the list's order), equal sequences are paired and folded, the
 // survivors close ranks, token children get their tree nodes, and the beam's small fields are rewritten in place (every
@@ -167,9 +242,37 @@ __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __
 // STREAM (the streaming search below, whose states outlive the call): a node's frame counts from the stream's reset,
 // frame0[b] + t, and an utterance past its length copies its rows' states through to the other buffer, so that every
 // stream's states are in the buffer the next frame reads whatever its own frame count.
-template <bool STREAM>
-__device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float* __restrict__ h_new,
-                                                 const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
+// LM / BIAS (the *_fused kernels): a token child also takes the LM state after its parent's token (lm_h_new / lm_c_new,
+// the LM step's output) and the automaton state goto(s, k); a blank child or a folded pair keeps the parent's (the two
+// partners hold the same sequence, so the same states); a row left without a hypothesis gets a zero LM state and the
+// root.  The automaton state and the LM's next symbol are small fields of wave 0; the LM states are gathered by the
+// whole workgroup through the same s_src table, and copied through where the prediction network's are.
+
+// the rows [r0, r0 + W) of a [L][BW][H] state: src < 0 zero, src & 0x100 from the step's output, else from the old buffer
+__device__ __forceinline__ void sb_gather_rows(const int* s_src, const float* __restrict__ old_h,
+                                               const float* __restrict__ old_c, const float* __restrict__ new_h,
+                                               const float* __restrict__ new_c, float* __restrict__ out_h,
+                                               float* __restrict__ out_c, int r0, int W, size_t BW, int L, int H) {
+    const int H4 = H / 4, LH4 = L * H4;
+    for (int idx = threadIdx.x; idx < W * LH4; idx += 256) {
+        const int pos = idx / LH4, rem = idx % LH4, l = rem / H4, j = rem % H4;
+        const int src = s_src ? s_src[pos] : pos;
+        const size_t dst = ((size_t)l * BW + r0 + pos) * H4 + j;
+        float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), cv = hv;
+        if (src >= 0) {
+            const size_t so = ((size_t)l * BW + r0 + (src & 0xff)) * H4 + j;
+            hv = ((const float4*)((src & 0x100) ? new_h : old_h))[so];
+            cv = ((const float4*)((src & 0x100) ? new_c : old_c))[so];
+        }
+        ((float4*)out_h)[dst] = hv;
+        ((float4*)out_c)[dst] = cv;
+    }
+}
+
+template <bool STREAM, bool LM, bool BIAS>
+__device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFuse& f, const float* __restrict__ h_new,
+                                                 const float* __restrict__ c_new, const float* __restrict__ lm_h_new,
+                                                 const float* __restrict__ lm_c_new, int t, int cur, int W, int B, int L,
                                                  int H, int NODES, int blank, int bos,
                                                  const int32_t* __restrict__ frame0) {
     const int b = blockIdx.x, tid = threadIdx.x, r0 = b * W;
@@ -183,6 +286,9 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float*
                 ((float4*)p.hs[cur ^ 1])[at] = ((const float4*)p.hs[cur])[at];
                 ((float4*)p.cs[cur ^ 1])[at] = ((const float4*)p.cs[cur])[at];
             }
+            if constexpr (LM)
+                sb_gather_rows(nullptr, f.lm_hs[cur], f.lm_cs[cur], nullptr, nullptr, f.lm_hs[cur ^ 1], f.lm_cs[cur ^ 1],
+                               r0, W, (size_t)B * W, f.lm_L, f.lm_H);
         }
         return;
     }
@@ -225,7 +331,11 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float*
         const int par_node = p.node[r0 + sel_i], par_tok = p.pred[r0 + sel_i], par_len = p.len[r0 + sel_i];
         const unsigned long long par_hash = p.hash[r0 + sel_i];
         const int n_nodes0 = p.n_nodes[b];
+        int par_st = 0;
+        if constexpr (BIAS) par_st = f.bias_st[r0 + sel_i];
         const int is_blank = k == blank;
+        int c_st = 0;
+        if constexpr (BIAS) c_st = (is_blank || k < 0 || k >= f.bias_V) ? par_st : bias_goto(f, par_st, k);
         const unsigned long long c_hash = is_blank ? par_hash : (par_hash ^ (unsigned long long)(k + 1)) * SB_PRIME;
         const int c_len = is_blank ? par_len : par_len + 1;
         // the other kept candidate with the same sequence, if there is one
@@ -249,6 +359,8 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float*
         const int f_i = __shfl(sel_i, src, 64), f_k = __shfl(k, src, 64), f_blank = __shfl(is_blank, src, 64);
         const int f_node = __shfl(par_node, src, 64), f_tok = __shfl(par_tok, src, 64);
         const float f_lp = __shfl(lp, src, 64);
+        int f_st = 0;
+        if constexpr (BIAS) f_st = __shfl(c_st, src, 64);
         const unsigned long long below = (1ull << lane) - 1ull;
         const unsigned long long m_alive = __ballot(alive);
         const unsigned long long m_new = __ballot(alive && !f_blank);
@@ -273,9 +385,13 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float*
                 p.pred[row] = f_k;
                 s_src[pos] = f_i | 0x100;
             }
+            if constexpr (LM) f.lm_pred[row] = c_len == 0 ? f.lm_bos : (f_blank ? f_tok : f_k);
+            if constexpr (BIAS) f.bias_st[row] = f_st;
         }
         if (lane >= n_new && lane < W) {
             const int row = r0 + lane;
+            if constexpr (LM) f.lm_pred[row] = f.lm_bos;
+            if constexpr (BIAS) f.bias_st[row] = 0;
             p.logp[row] = -(double)INFINITY;
             p.hash[row] = SB_HASH0;
             p.len[row] = 0;
@@ -307,19 +423,42 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const float*
         ((float4*)hs_n)[dst] = hv;
         ((float4*)cs_n)[dst] = cv;
     }
+    if constexpr (LM)
+        sb_gather_rows(s_src, f.lm_hs[cur], f.lm_cs[cur], lm_h_new, lm_c_new, f.lm_hs[cur ^ 1], f.lm_cs[cur ^ 1], r0, W,
+                       BW, f.lm_L, f.lm_H);
 }
 
 __global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __restrict__ h_new,
                                                    const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
                                                    int H, int NODES, int blank, int bos) {
-    sync_select_body<false>(p, h_new, c_new, t, cur, W, B, L, H, NODES, blank, bos, nullptr);
+    sync_select_body<false, false, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
+                                          bos, nullptr);
 }
 
 __global__ __launch_bounds__(256) void sync_stream_select(SyncPtrs p, const float* __restrict__ h_new,
                                                           const float* __restrict__ c_new, int t, int cur, int W, int B,
                                                           int L, int H, int NODES, int blank, int bos,
                                                           const int32_t* __restrict__ frame0) {
-    sync_select_body<true>(p, h_new, c_new, t, cur, W, B, L, H, NODES, blank, bos, frame0);
+    sync_select_body<true, false, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
+                                         bos, frame0);
+}
+
+template <bool STREAM, bool LM, bool BIAS>
+__global__ __launch_bounds__(256) void sync_select_fused(SyncPtrs p, SyncFuse f, const float* __restrict__ h_new,
+                                                         const float* __restrict__ c_new,
+                                                         const float* __restrict__ lm_h_new,
+                                                         const float* __restrict__ lm_c_new, int t, int cur, int W, int B,
+                                                         int L, int H, int NODES, int blank, int bos,
+                                                         const int32_t* __restrict__ frame0) {
+    sync_select_body<STREAM, LM, BIAS>(p, f, h_new, c_new, lm_h_new, lm_c_new, t, cur, W, B, L, H, NODES, blank, bos, frame0);
+}
+
+// the fused forms' part of sync_init: the LM steps on lm_bos, the automaton stands on its root
+__global__ void sync_init_fused(SyncFuse f, int BW) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= BW) return;
+    if (f.lm_pred) f.lm_pred[r] = f.lm_bos;
+    if (f.bias_st) f.bias_st[r] = 0;
 }
 
 // Read-out: an utterance's beam ranked by logp descending (ties keep beam order), every path walked root to leaf into
@@ -423,12 +562,151 @@ bool sync_dims_ok(int dtype, int B, int T, int J, int V, int E, int L, int H, in
            H % 4 == 0 && P2 > 0 && W >= 1 && W <= SB_MAXW && (long long)B * W <= 0x7fffffff / 256;
 }
 
+// LM fusion / a bias list, host side.  Both parts are APPENDED behind a plain layout (offsets from `base`, a multiple of
+// 256), so every plain offset holds in every form.  The rows' part - what SyncFuse points at - lives in the offline
+// workspace or in the streams' persistent state; the LM step's buffers are always workspace.
+struct SyncFuseRows {
+    size_t lm_hs0, lm_hs1, lm_cs0, lm_cs1, lm_pred, bias_st, total;
+};
+SyncFuseRows sync_fuse_rows_layout(size_t base, size_t rows, const edgedict_beam_lm_t* lm,
+                                   const edgedict_beam_bias_t* bias) {
+    SyncFuseRows a{};
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    if (lm) {
+        const size_t st = rows * (size_t)lm->L * lm->H * 4;
+        a.lm_hs0 = take(st);
+        a.lm_hs1 = take(st);
+        a.lm_cs0 = take(st);
+        a.lm_cs1 = take(st);
+        a.lm_pred = take(rows * 4);
+    }
+    if (bias) a.bias_st = take(rows * 4);
+    a.total = o;
+    return a;
+}
+struct SyncFuseStep {
+    size_t x, G, Hprev, Y0, Y1, Cst, h_new, c_new, logits, total;
+};
+SyncFuseStep sync_fuse_step_layout(size_t base, size_t rows, size_t esz, size_t V, const edgedict_beam_lm_t* lm) {
+    SyncFuseStep w{};
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    if (lm) {
+        const size_t H = lm->H, LH = (size_t)lm->L * lm->H;
+        w.x = take(rows * lm->E * esz);
+        w.G = take(rows * 4 * H * esz);
+        w.Hprev = take(rows * H * esz);
+        w.Y0 = take(rows * H * esz);
+        w.Y1 = take(rows * H * esz);
+        w.Cst = take(rows * H * 4);
+        w.h_new = take(rows * LH * 4);
+        w.c_new = take(rows * LH * 4);
+        w.logits = take(rows * V * 4);
+    }
+    w.total = o;
+    return w;
+}
+
+// an LM / a bias list this search can use (checked before anything is launched)
+int sync_fuse_check(const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, int V, const char* what) {
+    if (int rc = ed_decode_lm_check(lm, V, 0, what)) return rc;
+    ED_CHECK_ARG(!lm || lm->H % 4 == 0, "%s: the LM's hidden width H = %d must be a multiple of 4", what, lm->H);
+    return ed_decode_bias_check(bias, V, 0, what);
+}
+bool sync_fuse_dims_ok(const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, int V) {
+    return (!lm || (lm->V == V && lm->L > 0 && lm->E > 0 && lm->H > 0 && lm->H % 4 == 0)) && (!bias || bias->S > 0);
+}
+
+// One search call's fusion: the kernels' block, the LM as a network and its step's buffers
+struct SyncFusion {
+    bool lm, bias;
+    SyncFuse f;
+    LstmNet lm_net;
+    StepBufs lmu;
+};
+// rows_base + ra: where the rows' part lives;  ws + wa: the LM step's buffers
+SyncFusion sync_fuse_bind(char* rows_base, const SyncFuseRows& ra, char* ws, const SyncFuseStep* wa,
+                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias) {
+    SyncFusion u{};
+    u.lm = lm != nullptr;
+    u.bias = bias != nullptr;
+    SyncFuse& f = u.f;
+    if (lm) {
+        f.lm_hs[0] = at<float>(rows_base, ra.lm_hs0); f.lm_hs[1] = at<float>(rows_base, ra.lm_hs1);
+        f.lm_cs[0] = at<float>(rows_base, ra.lm_cs0); f.lm_cs[1] = at<float>(rows_base, ra.lm_cs1);
+        f.lm_pred = at<int32_t>(rows_base, ra.lm_pred);
+        f.lm_L = lm->L; f.lm_H = lm->H; f.lm_bos = lm->bos;
+        f.lm_w = lm->weight; f.lm_b = lm->length_bonus;
+        u.lm_net = lm_net_of(*lm);
+        if (wa)
+            u.lmu = StepBufs{nullptr, nullptr, at<float>(ws, wa->logits), f.lm_pred, ws + wa->x, ws + wa->G,
+                             ws + wa->Hprev, {ws + wa->Y0, ws + wa->Y1}, at<float>(ws, wa->Cst), at<float>(ws, wa->h_new),
+                             at<float>(ws, wa->c_new), nullptr};
+    }
+    if (bias) {
+        f.bias_st = at<int32_t>(rows_base, ra.bias_st);
+        f.bias_root_next = bias->root_next;
+        f.bias_held = bias->held;
+        f.bias_pend = bias->pend;
+        f.bias_row_ptr = bias->row_ptr;
+        f.bias_exc_tok = bias->exc_tok;
+        f.bias_exc_next = bias->exc_next;
+        f.bias_S = bias->S;
+        f.bias_V = bias->V;
+    }
+    return u;
+}
+
+// The frame's last two launches: the per-row top-W and the select / merge / gather.  fu null: the plain kernels.
+template <bool STREAM>
+void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u, int t, int cur, int W, int B, int L,
+                      int H, int NODES, int V, int blank, int bos, const int32_t* frame0, hipStream_t s) {
+    const int BW = B * W;
+    const bool cached = V <= 256 * SB_VPT;
+    if (!fu) {
+        if (cached) hipLaunchKernelGGL(sync_row_topw<true>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
+        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
+        if constexpr (STREAM)
+            hipLaunchKernelGGL(sync_stream_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H,
+                               NODES, blank, bos, frame0);
+        else
+            hipLaunchKernelGGL(sync_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H, NODES,
+                               blank, bos);
+        return;
+    }
+    auto go = [&](auto lm_tag, auto bias_tag) {
+        constexpr bool LM = decltype(lm_tag)::value, BIAS = decltype(bias_tag)::value;
+        const float* lz = fu->lmu.logits;
+        if (cached)
+            hipLaunchKernelGGL((sync_row_topw_fused<true, LM, BIAS>), dim3(BW), dim3(256), 0, s, q, fu->f, u.logits, lz, t,
+                               W, V, blank);
+        else
+            hipLaunchKernelGGL((sync_row_topw_fused<false, LM, BIAS>), dim3(BW), dim3(256), 0, s, q, fu->f, u.logits, lz,
+                               t, W, V, blank);
+        hipLaunchKernelGGL((sync_select_fused<STREAM, LM, BIAS>), dim3(B), dim3(256), 0, s, q, fu->f, u.h_new, u.c_new,
+                           (const float*)fu->lmu.h_new, (const float*)fu->lmu.c_new, t, cur, W, B, L, H, NODES, blank,
+                           bos, frame0);
+    };
+    if (fu->lm && fu->bias) go(std::true_type{}, std::true_type{});
+    else if (fu->lm) go(std::true_type{}, std::false_type{});
+    else go(std::false_type{}, std::true_type{});
+}
+
 }  // namespace
+
+extern "C" size_t edgedict_sync_beam_workspace_bytes_fusion(int dtype, int B, int T, int J, int V, int E, int L, int H,
+                                                            int P2, int W, const edgedict_beam_lm_t* lm,
+                                                            const edgedict_beam_bias_t* bias) {
+    if (!sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W) || !sync_fuse_dims_ok(lm, bias, V)) return 0;
+    const size_t BW = (size_t)B * W;
+    const size_t plain = sync_layout(sync_dims(dtype, B * W, J, V, E, L, H, P2), B, W, T).total;
+    return sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, dtype == ED_F32 ? 4 : 2, V, lm).total, BW, lm, bias).total;
+}
 
 extern "C" size_t edgedict_sync_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
                                                      int W) {
-    if (!sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W)) return 0;
-    return sync_layout(sync_dims(dtype, B * W, J, V, E, L, H, P2), B, W, T).total;
+    return edgedict_sync_beam_workspace_bytes_fusion(dtype, B, T, J, V, E, L, H, P2, W, nullptr, nullptr);
 }
 
 extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) {
@@ -436,14 +714,16 @@ extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) 
     return sync_result_layout(B, W, max_tokens).total;
 }
 
-extern "C" int edgedict_sync_beam_search(
+// lm / bias null: the plain search, launch for launch
+extern "C" int edgedict_sync_beam_search_fusion(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
     const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
     const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
     const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
     const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
     int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
-    int32_t* nhyp_host, double* logp_host, void* workspace, void* result, void* stream_) {
+    int32_t* nhyp_host, double* logp_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+    void* workspace, void* result, void* stream_) {
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_beam_search: bad dtype");
     ED_CHECK_ARG(W >= 1 && W <= SB_MAXW, "sync_beam_search: beam width W = %d outside [1, %d]", W, SB_MAXW);
     ED_CHECK_ARG(T > 0, "sync_beam_search: T = %d frames (must be > 0)", T);
@@ -462,6 +742,7 @@ extern "C" int edgedict_sync_beam_search(
                      lens_host[b], T);
         maxlen = std::max(maxlen, lens_host[b]);
     }
+    if (int rc = sync_fuse_check(lm, bias, V, "sync_beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     const int BW = B * W, NODES = T * W;
     // the step's network: B * W rows whose joint rows are gathered per frame, J apart
@@ -496,6 +777,22 @@ extern "C" int edgedict_sync_beam_search(
     ED_CHECK_HIP(hipMemsetAsync(q.cs[0], 0, st, s));
     ED_CHECK_HIP(hipMemsetAsync(q.cs[1], 0, st, s));
     hipLaunchKernelGGL(sync_init, dim3((BW + 255) / 256), dim3(256), 0, s, q, B, W, bos);
+    SyncFusion fusion{};
+    const SyncFusion* fu = nullptr;
+    if (lm || bias) {
+        const SyncFuseStep wa = sync_fuse_step_layout(w.total, BW, net.esz, V, lm);
+        const SyncFuseRows ra = sync_fuse_rows_layout(wa.total, BW, lm, bias);
+        fusion = sync_fuse_bind(p, ra, p, &wa, lm, bias);
+        fu = &fusion;
+        if (lm) {       // the empty sequence's LM state is zero, in both buffers as the prediction network's
+            const size_t lst = (size_t)BW * lm->L * lm->H * 4;
+            ED_CHECK_HIP(hipMemsetAsync(fusion.f.lm_hs[0], 0, lst, s));
+            ED_CHECK_HIP(hipMemsetAsync(fusion.f.lm_hs[1], 0, lst, s));
+            ED_CHECK_HIP(hipMemsetAsync(fusion.f.lm_cs[0], 0, lst, s));
+            ED_CHECK_HIP(hipMemsetAsync(fusion.f.lm_cs[1], 0, lst, s));
+        }
+        hipLaunchKernelGGL(sync_init_fused, dim3((BW + 255) / 256), dim3(256), 0, s, fusion.f, BW);
+    }
     const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
     int cur = 0;
     for (int t = 0; t < maxlen; ++t) {
@@ -508,10 +805,10 @@ extern "C" int edgedict_sync_beam_search(
         if (fused) rc = ed_decode_fused_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
         else rc = ed_decode_composed_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
         if (rc) return rc;
-        if (V <= 256 * SB_VPT) hipLaunchKernelGGL(sync_row_topw<true>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
-        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
-        hipLaunchKernelGGL(sync_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H, NODES, blank,
-                           bos);
+        if (fu && fu->lm &&
+            (rc = ed_decode_lm_step(dtype, BW, fu->lm_net, fu->f.lm_hs[cur], fu->f.lm_cs[cur], fu->lmu, s)))
+            return rc;
+        sync_launch_pick<false>(q, fu, u, t, cur, W, B, L, H, NODES, V, blank, bos, nullptr, s);
         cur ^= 1;
     }
     // results: one read at the end - lengths and scores first, then only the used columns
@@ -544,6 +841,20 @@ extern "C" int edgedict_sync_beam_search(
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;
+}
+
+extern "C" int edgedict_sync_beam_search(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
+    int32_t* nhyp_host, double* logp_host, void* workspace, void* result, void* stream_) {
+    return edgedict_sync_beam_search_fusion(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
+                                            W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
+                                            W, tokens_host, frames_host, token_logp_host, max_tokens, ntokens_host,
+                                            nhyp_host, logp_host, nullptr, nullptr, workspace, result, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -659,6 +970,28 @@ __global__ __launch_bounds__(256) void sync_stream_reset_kernel(SyncPtrs p, int3
     }
 }
 
+// The fused forms' part of a reset, for the same streams: zero LM states in both buffers, the LM's next symbol lm_bos,
+// the automaton's root.
+__global__ __launch_bounds__(256) void sync_stream_reset_fused_kernel(SyncFuse f, const int32_t* __restrict__ mask,
+                                                                      int s0, int S, int W) {
+    const int b = s0 + blockIdx.x, tid = threadIdx.x, r0 = b * W;
+    if (b >= S || (mask && !mask[b])) return;
+    if (tid < W) {
+        if (f.lm_pred) f.lm_pred[r0 + tid] = f.lm_bos;
+        if (f.bias_st) f.bias_st[r0 + tid] = 0;
+    }
+    if (!f.lm_pred) return;
+    const int H4 = f.lm_H / 4, LH4 = f.lm_L * H4;
+    const size_t SW = (size_t)S * W;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int idx = tid; idx < W * LH4; idx += 256) {
+        const int pos = idx / LH4, rem = idx % LH4, l = rem / H4, j = rem % H4;
+        const size_t at = ((size_t)l * SW + r0 + pos) * H4 + j;
+        ((float4*)f.lm_hs[0])[at] = zero; ((float4*)f.lm_hs[1])[at] = zero;
+        ((float4*)f.lm_cs[0])[at] = zero; ((float4*)f.lm_cs[1])[at] = zero;
+    }
+}
+
 // One wave per stream, once per advance, after the last frame.  Node ids grow with creation and a parent is older than
 // its child, which a dense renumbering in index order keeps: every walk towards the root strictly descends.
 //   1. lane j = row j: the depth of its leaf; all live rows climb to the smallest depth, then together until they
@@ -759,15 +1092,33 @@ __global__ __launch_bounds__(64) void sync_stream_compact(SyncPtrs p, int32_t* _
 
 }  // namespace
 
+// The fused forms append the rows' LM (h, c) in both buffers, the LM's next symbols and the automaton states behind the
+// plain state, and the LM step's buffers behind the plain workspace: edgedict_sync_stream_read serves every form.
+// (V is not known to the state query: the LM's own V sizes nothing there.)
+extern "C" size_t edgedict_sync_stream_state_bytes_fusion(int S, int L, int H, int W, int node_capacity,
+                                                          const edgedict_beam_lm_t* lm,
+                                                          const edgedict_beam_bias_t* bias) {
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_fuse_dims_ok(lm, bias, lm ? lm->V : 0)) return 0;
+    return sync_fuse_rows_layout(sync_stream_state_layout(S, W, L, H, node_capacity).total, (size_t)S * W, lm, bias).total;
+}
+
 extern "C" size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, int node_capacity) {
-    if (!sync_stream_dims_ok(S, L, H, W, node_capacity)) return 0;
-    return sync_stream_state_layout(S, W, L, H, node_capacity).total;
+    return edgedict_sync_stream_state_bytes_fusion(S, L, H, W, node_capacity, nullptr, nullptr);
+}
+
+extern "C" size_t edgedict_sync_stream_workspace_bytes_fusion(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                              int W, int node_capacity, const edgedict_beam_lm_t* lm,
+                                                              const edgedict_beam_bias_t* bias) {
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) ||
+        !sync_fuse_dims_ok(lm, bias, V))
+        return 0;
+    const size_t plain = sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
+    return sync_fuse_step_layout(plain, (size_t)S * W, dtype == ED_F32 ? 4 : 2, V, lm).total;
 }
 
 extern "C" size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
                                                        int W, int node_capacity) {
-    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W)) return 0;
-    return sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
+    return edgedict_sync_stream_workspace_bytes_fusion(dtype, S, J, V, E, L, H, P2, W, node_capacity, nullptr, nullptr);
 }
 
 extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens) {
@@ -784,20 +1135,28 @@ extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens
         ED_CHECK_ARG(sync_stream_dims_ok(S, L, H, W, NC), what ": bad shape (too many rows or nodes)");            \
     } while (0)
 
-extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                          int mask_on_host, void* state, void* stream_) {
+// lm / bias null: the plain reset.  (The LM's and the list's vocabulary are the advance's to check: V is not known here.)
+extern "C" int edgedict_sync_stream_reset_fusion(int S, int L, int H, int W, int node_capacity, int bos,
+                                                 const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
+                                                 const edgedict_beam_bias_t* bias, void* state, void* stream_) {
     SYNC_STREAM_CHECK_SHAPE("sync_stream_reset", S, L, H, W, node_capacity);
     ED_CHECK_ARG(bos >= 0, "sync_stream_reset: bos = %d outside the vocabulary", bos);
     ED_CHECK_ARG(state, "sync_stream_reset: null pointer (state)");
+    if (int rc = sync_fuse_check(lm, bias, lm ? lm->V : (bias ? bias->V : 0), "sync_stream_reset")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     char* st = (char*)state;
     const SyncStreamState a = sync_stream_state_layout(S, W, L, H, node_capacity);
     const SyncPtrs q = sync_stream_bind(st, a);
     int32_t* frames_done = at<int32_t>(st, a.frames_done);
     long long* n_committed = at<long long>(st, a.n_committed);
+    SyncFusion fusion{};
+    if (lm || bias)
+        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, (size_t)S * W, lm, bias), nullptr, nullptr, lm, bias);
     if (!mask || !mask_on_host) {
         hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, frames_done, n_committed, mask, 0, S, W,
                            L, H, bos);
+        if (lm || bias)
+            hipLaunchKernelGGL(sync_stream_reset_fused_kernel, dim3(S), dim3(256), 0, s, fusion.f, mask, 0, S, W);
     } else {            // host mask: one launch per run of selected streams
         for (int b = 0; b < S;) {
             if (!mask[b]) { ++b; continue; }
@@ -805,6 +1164,9 @@ extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_c
             while (e < S && mask[e]) ++e;
             hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(e - b), dim3(256), 0, s, q, frames_done, n_committed,
                                (const int32_t*)nullptr, b, S, W, L, H, bos);
+            if (lm || bias)
+                hipLaunchKernelGGL(sync_stream_reset_fused_kernel, dim3(e - b), dim3(256), 0, s, fusion.f,
+                                   (const int32_t*)nullptr, b, S, W);
             b = e;
         }
     }
@@ -812,13 +1174,21 @@ extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_c
     return ED_OK;
 }
 
-extern "C" int edgedict_sync_stream_advance(
+extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                          int mask_on_host, void* state, void* stream_) {
+    return edgedict_sync_stream_reset_fusion(S, L, H, W, node_capacity, bos, mask, mask_on_host, nullptr, nullptr, state,
+                                             stream_);
+}
+
+// lm / bias null: the plain advance, launch for launch
+extern "C" int edgedict_sync_stream_advance_fusion(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
     const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
     const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
     const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
     int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-    int max_commit, void* state, void* workspace, void* stream_) {
+    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* workspace,
+    void* stream_) {
     const int NC = node_capacity;
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_stream_advance: bad dtype");
     SYNC_STREAM_CHECK_SHAPE("sync_stream_advance", S, L, H, W, NC);
@@ -847,6 +1217,7 @@ extern "C" int edgedict_sync_stream_advance(
     }
     ED_CHECK_ARG(cols <= max_commit, "sync_stream_advance: max_commit = %d, this advance may commit %d tokens",
                  max_commit, cols);
+    if (int rc = sync_fuse_check(lm, bias, V, "sync_stream_advance")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     const int SW = S * W;
     char* p = (char*)workspace;
@@ -864,6 +1235,13 @@ extern "C" int edgedict_sync_stream_advance(
     q.c_lp = at<float>(p, w.c_lp);
     q.lens = at<int32_t>(p, w.lens);
     int32_t* frames_done = at<int32_t>(st, a.frames_done);
+    SyncFusion fusion{};
+    const SyncFusion* fu = nullptr;
+    if (lm || bias) {
+        const SyncFuseStep wa = sync_fuse_step_layout(w.total, SW, net.esz, V, lm);
+        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, SW, lm, bias), p, &wa, lm, bias);
+        fu = &fusion;
+    }
 
     ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
     const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
@@ -878,10 +1256,10 @@ extern "C" int edgedict_sync_stream_advance(
         if (fused) rc = ed_decode_fused_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
         else rc = ed_decode_composed_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
         if (rc) return rc;
-        if (V <= 256 * SB_VPT) hipLaunchKernelGGL(sync_row_topw<true>, dim3(SW), dim3(256), 0, s, q, u.logits, t, W, V);
-        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(SW), dim3(256), 0, s, q, u.logits, t, W, V);
-        hipLaunchKernelGGL(sync_stream_select, dim3(S), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, S, L, H, NC,
-                           blank, bos, (const int32_t*)frames_done);
+        if (fu && fu->lm &&
+            (rc = ed_decode_lm_step(dtype, SW, fu->lm_net, fu->f.lm_hs[cur], fu->f.lm_cs[cur], fu->lmu, s)))
+            return rc;
+        sync_launch_pick<true>(q, fu, u, t, cur, W, S, L, H, NC, V, blank, bos, (const int32_t*)frames_done, s);
         cur ^= 1;
     }
     hipLaunchKernelGGL(sync_stream_compact, dim3(S), dim3(64), 0, s, q, frames_done, at<long long>(st, a.n_committed),
@@ -895,6 +1273,19 @@ extern "C" int edgedict_sync_stream_advance(
     const int32_t* rec = (const int32_t*)commit_host;
     for (int b = 0; b < S; ++b) live_host[b] = rec[(size_t)b * ((size_t)max_commit + 1) * 4 + 1];
     return ED_OK;
+}
+
+extern "C" int edgedict_sync_stream_advance(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
+    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
+    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
+    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+    int max_commit, void* state, void* workspace, void* stream_) {
+    return edgedict_sync_stream_advance_fusion(dtype, E1, e_row_stride, e_frame_stride, S, T, n_frames_host, J, W1d, ldw1,
+                                               b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
+                                               blank, bos, W, node_capacity, live_host, parity_host, commit_host,
+                                               max_commit, nullptr, nullptr, state, workspace, stream_);
 }
 
 extern "C" int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, const void* state, void* result,

@@ -434,6 +434,14 @@ def _check_sync_width(W):
         raise ValueError("sync_beam_search: beam width W = %r outside [1, %d]" % (W, SYNC_BEAM_MAX_W))
 
 
+def _check_sync_fusion(model, lm, lm_weight, bias):
+    """The fusion argument rules of the ``sync_beam_search*`` entry points (raised before anything is launched)."""
+    from .bias import check_bias_args
+    from .lm import check_fusion_args
+    check_fusion_args(lm, lm_weight, _vocab(model), False)
+    check_bias_args(bias, _vocab(model), False)
+
+
 def _sync_encode(model, xs, xlen, W):
     """The argument rules of the ``sync_beam_search*`` entry points, then the encoder: (enc_out, lens)."""
     _check_sync_width(W)
@@ -460,49 +468,87 @@ def sync_beam_search(model, xs, xlen=None, W=10):
     over its alignments inside the beam.  ``1 <= W <= 32``; ``W = 1`` is the greedy search with the blanks removed.
 
     This is a different algorithm from ``beam_search_batch`` (the reference's best-first search, which may emit several
-    symbols per frame and never merges): the two do not return the same hypotheses.  It takes no ``lm=``, ``bias=`` or
-    ``prefix=``.  Its streaming form is ``StreamingSyncBeamSearch``.
+    symbols per frame and never merges): the two do not return the same hypotheses.  It takes no ``prefix=`` or
+    ``max_expansions=``.  Its streaming form is ``StreamingSyncBeamSearch``.  This function is the plain search and keeps
+    its signature (no ``lm=``, ``bias=``): LM fusion and biasing are ``sync_beam_search_fusion``, below, the ``_nbest`` /
+    ``_enc`` / ``_rows`` forms and ``Transducer.sync_beam_search``, which take the keywords.
 
     Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
     utterance, in ``beam_search_batch``'s types."""
     return _best_of(sync_beam_search_nbest(model, xs, xlen, W))
 
 
-def sync_beam_search_nbest(model, xs, xlen=None, W=10):
+def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
+                            bias=None):
+    """``sync_beam_search`` with LM shallow fusion and contextual biasing (without either: ``sync_beam_search`` itself,
+    launch for launch).
+
+    ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos``: LM shallow fusion with ``beam_search_batch``'s arguments and
+    rules (``lm`` needs ``lm_weight``; an LM of another vocabulary raises ``ValueError``).  Every row carries its LM state
+    as it carries the prediction network's and all B x W rows step the LM once per frame (``lm.nlayers + 1`` more
+    launches on the fused LM step); a non-blank candidate k of hypothesis i scores
+    ``((logp_i + lp_i[k]) + (lm_weight * lp_lm_i[k] + length_bonus)) + D(s_i, k)`` in fp64, blank ``logp_i + lp_i[blank]``.
+    ``bias``: a contextual-biasing list (``edgedict_amd.bias.ContextGraph``); ``D(s, k) = held[goto(s, k)] - pend[s]`` is
+    its increment from the row's automaton state, so a partial match that breaks gives its bonus back, and nothing is
+    settled at the end of an utterance (as in ``beam_search_batch`` and ``ContextGraph.score``).  Selection, merging and
+    ranking act on the fused score, which is what the returned score is; ``lm_weight = 0, length_bonus = 0`` and an
+    empty list are bit-equal to the plain search, and without ``lm`` / ``bias`` the plain kernels run.
+
+    Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
+    utterance, in ``beam_search_batch``'s types."""
+    return _best_of(sync_beam_search_nbest(model, xs, xlen, W,
+                                           lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
+
+
+def sync_beam_search_nbest(model, xs, xlen=None, W=10,
+                           *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``sync_beam_search`` returning, per utterance, the final beam as an ``NBestResult`` **already ranked**: ``logp``
     descending (ties keep beam order), at most W hypotheses with distinct token sequences, entry 0 what
     ``sync_beam_search`` returns.  ``frames[i]``: the encoder frame on which each token's tree node was created
     (``emission_times`` applies); ``token_logp[i]``: the token's log-softmax value on that frame - NOT an increment of
-    ``logp``, which sums over alignments (as in ``ctc_beam_search``).  An utterance of 0 frames yields one empty
-    hypothesis with ``logp`` 0."""
+    ``logp``, which sums over alignments (as in ``ctc_beam_search``), and with an LM or a bias list still the RNN-T
+    value alone while ``logp`` is the fused score.  An utterance of 0 frames yields one empty hypothesis with ``logp`` 0."""
+    _check_sync_fusion(model, lm, lm_weight, bias)
     enc_out, lens = _sync_encode(model, xs, xlen, W)
-    return sync_beam_search_nbest_enc(model, enc_out, lens, W)
+    return sync_beam_search_nbest_enc(model, enc_out, lens, W,
+                                      lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
-def sync_beam_search_enc(model, enc_out, lens=None, W=10):
+def sync_beam_search_enc(model, enc_out, lens=None, W=10,
+                         *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``sync_beam_search`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
     encoder frames per utterance; None: all T)."""
-    return _best_of(sync_beam_search_nbest_enc(model, enc_out, lens, W))
+    return _best_of(sync_beam_search_nbest_enc(model, enc_out, lens, W,
+                                               lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
 
 
-def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10):
+def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10,
+                               *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``."""
+    _check_sync_fusion(model, lm, lm_weight, bias)
     _check_sync_width(W)
     _lib.require_cuda(enc_out)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
-    return sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W)
+    return sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W,
+                                                         lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
-def sync_beam_search_rows(model, E1, B, T, P, lens=None, W=10):
+def sync_beam_search_rows(model, E1, B, T, P, lens=None, W=10,
+                          *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``sync_beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
     width P."""
-    return _best_of(sync_beam_search_nbest_rows(model, E1, B, T, P, lens, W))
+    return _best_of(sync_beam_search_nbest_rows(model, E1, B, T, P, lens, W,
+                                                lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
 
 
-def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=None):
+def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=None,
+                                *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
     """``sync_beam_search_nbest_enc`` from the joint's encoder rows, as ``sync_beam_search_rows``.  ``max_tokens``
     bounds a hypothesis' length (default T: one token per frame at most); a longer one raises, it is never cut."""
+    from .bias import active
+    from .lm import FusionLM
+    _check_sync_fusion(model, lm, lm_weight, bias)
     _check_sync_width(W)
     _lib.require_cuda(E1)
     W = int(W)
@@ -516,8 +562,16 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     lib = _lib.load()
     MT = T if max_tokens is None else int(max_tokens)
     dev = E1.device
-    ws = torch.empty(lib.edgedict_sync_beam_workspace_bytes(dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H,
-                                                            net.P2, W), dtype=torch.uint8, device=dev)
+    flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
+    bref = active(bias).ref(dev) if active(bias) is not None else None
+    fused = flm is not None or bref is not None         # else: the plain entry points, untouched
+    fargs = (flm.ref() if flm is not None else None, bref)
+    dims = (dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W)
+    nbytes = (lib.edgedict_sync_beam_workspace_bytes_fusion(*dims, *fargs) if fused
+              else lib.edgedict_sync_beam_workspace_bytes(*dims))
+    if fused and nbytes == 0:
+        raise ValueError("sync_beam_search: shapes out of range (the LM's hidden width must be a multiple of 4)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     result = torch.empty(lib.edgedict_sync_beam_result_bytes(B, W, MT), dtype=torch.uint8, device=dev)
     tokens = np.empty((B, W, MT), dtype=np.int32)       # (only the used columns are written and read)
     frames = np.empty((B, W, MT), dtype=np.int32)
@@ -527,10 +581,14 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     logp = np.zeros((B, W), dtype=np.float64)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     from .tokenizer import BOS
-    rc = lib.edgedict_sync_beam_search(
-        dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
-        *net.args(P), int(model.blank), int(BOS), W, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp),
-        _lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
+    args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
+            *net.args(P), int(model.blank), int(BOS), W, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp),
+            vp(logp))
+    tail = (_lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
+    if fused:
+        rc = lib.edgedict_sync_beam_search_fusion(*args, *fargs, *tail)
+    else:
+        rc = lib.edgedict_sync_beam_search(*args, *tail)
     _lib.check(rc, "sync_beam_search")
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
 
@@ -905,12 +963,19 @@ class StreamingSyncBeamSearch:
     compaction) raises ``RuntimeError`` before anything is launched and leaves the state as it was; nothing is ever
     truncated.  Default ``NC = 32 * W + 1024``: room for chunks of 32 frames on top of a live tree of 1024 nodes.
 
-    ``1 <= W <= 32``.  There is no ``lm=``, ``bias=``, ``prefix=`` or ``max_expansions=``: the offline search has none.
+    ``1 <= W <= 32``.  The constructor keeps the plain search's signature: there is no ``lm=``, ``bias=``, ``prefix=``
+    or ``max_expansions=`` here.  LM shallow fusion and contextual biasing are ``StreamingSyncFusionBeamSearch``, the
+    same class with a wider constructor; ``set_bias`` gives a search built here a bias list between utterances.
     A stream with no frames since its reset holds one empty hypothesis with ``logp`` 0."""
 
     _EMPTY = (np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64))
 
     def __init__(self, model, n_streams, W=10, node_capacity=None):
+        self._setup(model, n_streams, W, node_capacity)
+
+    def _setup(self, model, n_streams, W, node_capacity, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+        from .bias import active
+        _check_sync_fusion(model, lm, lm_weight, bias)
         _check_sync_width(W)
         if n_streams < 1:
             raise ValueError("n_streams must be >= 1")
@@ -924,15 +989,10 @@ class StreamingSyncBeamSearch:
         from .stream import _compute_dtype
         self.cd = _compute_dtype(model)
         self.device = model.decoder.embed.weight.device
-        net = self._weights()
-        lib = _lib.load()
-        self._state = torch.empty(lib.edgedict_sync_stream_state_bytes(self.S, net.L, net.H, self.W, self.NC),
-                                  dtype=torch.uint8, device=self.device)
-        self._ws = torch.empty(lib.edgedict_sync_stream_workspace_bytes(
-            dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.NC),
-            dtype=torch.uint8, device=self.device)
-        if self._state.numel() == 0 or self._ws.numel() == 0:
-            raise ValueError("StreamingSyncBeamSearch: shapes out of range (H must be a multiple of 4)")
+        self.lm = lm
+        self._lm_args = (lm_weight, length_bonus, lm_bos)
+        self.bias = active(bias)
+        self._alloc()
         self._result, self._result_mt = None, -1
         self._live = np.zeros(self.S, dtype=np.int32)        # token-tree nodes per stream after the last compaction
         self._parity = ctypes.c_int32(0)                     # which state buffer the next frame reads
@@ -949,6 +1009,65 @@ class StreamingSyncBeamSearch:
     def _weights(self):
         return _SearchNet(self.model, self.cd)
 
+    def _fusion(self):
+        """(FusionLM or None, (lm, bias) of the ``_fusion`` entry points, or None for the plain ones).  The FusionLM is
+        returned so that it outlives the call that reads its struct."""
+        from .lm import FusionLM
+        flm = None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args)
+        bref = None if self.bias is None else self.bias.ref(self.device)
+        if flm is None and bref is None:
+            return None, None
+        return flm, (flm.ref() if flm is not None else None, bref)
+
+    def _alloc(self):
+        """The persistent state and the workspace, sized for the current forms (LM, bias list)."""
+        net = self._weights()
+        lib = _lib.load()
+        flm, fargs = self._fusion()
+        sdims = (self.S, net.L, net.H, self.W, self.NC)
+        wdims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.NC)
+        if fargs is None:
+            sbytes, wbytes = lib.edgedict_sync_stream_state_bytes(*sdims), lib.edgedict_sync_stream_workspace_bytes(*wdims)
+        else:
+            sbytes = lib.edgedict_sync_stream_state_bytes_fusion(*sdims, *fargs)
+            wbytes = lib.edgedict_sync_stream_workspace_bytes_fusion(*wdims, *fargs)
+        if sbytes == 0 or wbytes == 0:
+            raise ValueError("StreamingSyncBeamSearch: shapes out of range (H and the LM's hidden width must be "
+                             "multiples of 4)")
+        self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+
+    def set_bias(self, graph, mask=None):
+        """Swap the bias list (a ``ContextGraph``, or None / an empty one for "no bias"), with
+        ``StreamingBeamSearch.set_bias``'s rules: the list is shared by all streams and the rows of a stream in
+        mid-utterance hold states of the old automaton, so EVERY stream must be fresh - no frames since its reset - or
+        ``ValueError`` is raised.  ``mask`` (None: all) only names the streams the caller swaps the list for: a stream in
+        it that has frames is reported as such, one outside it as being in the middle of an utterance.  Nothing is
+        launched when the state keeps its size (a fresh stream stands on state 0, the root of every automaton) and the
+        next ``advance`` reads the new tables; where the gain or loss of a list changes the state's size, the state is
+        allocated anew and reset."""
+        from .bias import active, check_bias_args
+        check_bias_args(graph, _vocab(self.model), False)
+        if mask is None:
+            sel = np.ones(self.S, dtype=bool)
+        else:
+            m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+            sel = m.astype(bool).reshape(self.S)
+        busy = np.nonzero(self._frames > 0)[0]
+        for s in busy:
+            if sel[s]:
+                raise ValueError("set_bias: stream %d has advanced over %d frames since its reset (reset it first)"
+                                 % (s, self._frames[s]))
+        if len(busy):
+            raise ValueError("set_bias: the bias list is shared by all streams and stream %d, outside the mask, is in "
+                             "the middle of an utterance" % busy[0])
+        had = self.bias is not None
+        self.bias = active(graph)
+        if had != (self.bias is not None):
+            self._alloc()
+            self._parity = ctypes.c_int32(0)
+            self.reset()
+
     def reset(self, mask=None):
         """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log;
         its frames count from 0 again."""
@@ -962,8 +1081,13 @@ class StreamingSyncBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
             mp = mh.ctypes.data_as(ctypes.c_void_p)
-        rc = _lib.load().edgedict_sync_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
-                                                    _lib.ptr(self._state), _lib.stream_ptr())
+        flm, fargs = self._fusion()
+        if fargs is None:
+            rc = _lib.load().edgedict_sync_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
+                                                        _lib.ptr(self._state), _lib.stream_ptr())
+        else:
+            rc = _lib.load().edgedict_sync_stream_reset_fusion(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp,
+                                                               on_host, *fargs, _lib.ptr(self._state), _lib.stream_ptr())
         _lib.check(rc, "sync_stream_reset")
         self._frames[sel] = 0
         self._live[sel] = 0
@@ -1017,11 +1141,15 @@ class StreamingSyncBeamSearch:
             raise RuntimeError("StreamingSyncBeamSearch: stream %d may need %d token-tree nodes (%d live + %d frames x "
                                "W = %d), node_capacity is %d" % (s, need[s], self._live[s], nf[s], self.W, self.NC))
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        rc = _lib.load().edgedict_sync_stream_advance(
-            dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, T, vp(nf),
-            *net.args(P), int(self.model.blank), int(BOS), self.W, self.NC, vp(self._live),
-            ctypes.byref(self._parity), vp(self._commit_buf), self.NC, _lib.ptr(self._state), _lib.ptr(self._ws),
-            _lib.stream_ptr())
+        args = (dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, T,
+                vp(nf), *net.args(P), int(self.model.blank), int(BOS), self.W, self.NC, vp(self._live),
+                ctypes.byref(self._parity), vp(self._commit_buf), self.NC)
+        tail = (_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
+        flm, fargs = self._fusion()
+        if fargs is None:
+            rc = _lib.load().edgedict_sync_stream_advance(*args, *tail)
+        else:
+            rc = _lib.load().edgedict_sync_stream_advance_fusion(*args, *fargs, *tail)
         _lib.check(rc, "sync_stream_advance")
         self._frames += nf
         ncommit = self._commit_buf[:, 0, 0]
@@ -1094,6 +1222,22 @@ class StreamingSyncBeamSearch:
         """Per stream ``(tokens int64, frames int32, token_logp float64)`` of the committed log."""
         return [(t.copy(), f.copy(), l.copy())
                 for t, f, l in zip(self._committed, self._committed_frames, self._committed_logp)]
+
+
+class StreamingSyncFusionBeamSearch(StreamingSyncBeamSearch):
+    """``StreamingSyncBeamSearch`` with ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` / ``bias``: LM shallow
+    fusion and contextual biasing as in ``sync_beam_search_fusion``, every method the base class's.  After any chunk
+    ``nbest()`` is bit for bit ``sync_beam_search_nbest_rows(..., lm=, bias=)`` over the stream's frames since its reset.
+
+    The rows' LM states (both buffers) and automaton states live in the persistent state behind the plain layout, are
+    cleared by ``reset`` and untouched by compaction; the LM's root token is ``lm_bos`` for the empty sequence only
+    (``len`` counts committed tokens too).  The bias list is shared by all streams; ``set_bias`` swaps it between
+    utterances.  Without an LM and without a list (or with an empty one) the plain kernels run until ``set_bias`` gives
+    the search a list.  With an LM a frame is ``6 + L + lm.nlayers + 1`` launches on the fused steps."""
+
+    def __init__(self, model, n_streams, W=10, node_capacity=None, *, lm=None, lm_weight=None, length_bonus=0.0,
+                 lm_bos=1, bias=None):
+        self._setup(model, n_streams, W, node_capacity, lm, lm_weight, length_bonus, lm_bos, bias)
 
 
 def emission_times(frames, flags, time_reduction=2):

@@ -1339,19 +1339,24 @@ class Transducer(nn.Module):
                                  length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
     @torch.no_grad()
-    def sync_beam_search(self, xs, xlen=None, W=10):
+    def sync_beam_search(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
         """Frame-synchronous beam search (one symbol per frame at most, all B x W hypotheses in one step per frame,
         equal sequences merged by log-add; ``1 <= W <= 32``): a different algorithm from ``beam_search``, several times
-        fewer launches.  Returns ``(seqs, scores)`` in ``beam_search``'s types.  See ``decode.sync_beam_search``."""
-        from .decode import sync_beam_search
-        return sync_beam_search(self, xs, xlen, W)
+        fewer launches.  ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` / ``bias``: LM shallow fusion and
+        contextual biasing, as ``beam_search`` takes them.  Returns ``(seqs, scores)`` in ``beam_search``'s types.  See
+        ``decode.sync_beam_search_fusion``."""
+        from .decode import sync_beam_search_fusion
+        return sync_beam_search_fusion(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                       lm_bos=lm_bos, bias=bias)
 
     @torch.no_grad()
-    def sync_beam_search_nbest(self, xs, xlen=None, W=10):
+    def sync_beam_search_nbest(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
+                               bias=None):
         """``sync_beam_search`` returning per utterance the final beam as a ranked ``decode.NBestResult``; entry 0 is
         what ``sync_beam_search`` returns.  See ``decode.sync_beam_search_nbest``."""
         from .decode import sync_beam_search_nbest
-        return sync_beam_search_nbest(self, xs, xlen, W)
+        return sync_beam_search_nbest(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                      lm_bos=lm_bos, bias=bias)
 
 
 class _CausalConvFn(torch.autograd.Function):

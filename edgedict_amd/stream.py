@@ -381,17 +381,22 @@ class BatchedStreamSyncBeamDecoder(StreamTransducerDecoder):
     Same chunk geometry (``chunk_geometry``), feature transform and carried encoder (h, c) as
     ``BatchedStreamBeamDecoder``; the search is ``decode.StreamingSyncBeamSearch``, which keeps every stream's beam from
     chunk to chunk, so after any chunk a stream's ``best()`` / ``nbest()`` is what the offline frame-synchronous search
-    over its audio so far returns.  ``1 <= W <= 32``; no ``lm=``, ``bias=``, ``prefix=`` or ``max_expansions=``, as the
-    offline search; ``node_capacity`` as ``decode.StreamingSyncBeamSearch``."""
+    over its audio so far returns.  ``1 <= W <= 32``; no ``lm=``, ``bias=``, ``prefix=`` or ``max_expansions=`` in this
+    constructor, which keeps the plain search's signature (LM fusion and biasing: ``BatchedStreamSyncFusionBeamDecoder``,
+    the same class with a wider constructor); ``node_capacity`` as ``decode.StreamingSyncBeamSearch``."""
 
     def __init__(self, transducer, flags, n_streams, W=10, node_capacity=None, dither=None):
-        from .decode import StreamingSyncBeamSearch
+        self._setup(transducer, flags, n_streams, W, node_capacity, dither, {})
+
+    def _setup(self, transducer, flags, n_streams, W, node_capacity, dither, fusion):
+        """``fusion``: the keywords ``decode.StreamingSyncFusionBeamSearch`` takes beyond the plain search's."""
+        from .decode import StreamingSyncFusionBeamSearch
         self.model = transducer.eval()
         self.flags = flags
         self.S = n_streams
         dev = transducer.decoder.embed.weight.device
         self.device = dev
-        self.search = StreamingSyncBeamSearch(transducer, n_streams, W=W, node_capacity=node_capacity)
+        self.search = StreamingSyncFusionBeamSearch(transducer, n_streams, W=W, node_capacity=node_capacity, **fusion)
         self.transform = StackedLogFbank(
             n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
             hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,
@@ -440,6 +445,18 @@ class BatchedStreamSyncBeamDecoder(StreamTransducerDecoder):
 
     def committed_detail(self):
         return self.search.committed_detail()
+
+
+class BatchedStreamSyncFusionBeamDecoder(BatchedStreamSyncBeamDecoder):
+    """``BatchedStreamSyncBeamDecoder`` with ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` (LM shallow fusion)
+    and ``bias`` (a contextual-biasing list, ``edgedict_amd.bias.ContextGraph``), as in
+    ``decode.StreamingSyncFusionBeamSearch``; ``self.search.set_bias`` swaps the list between utterances.  After any
+    chunk ``nbest()`` is what the offline fused search over the stream's audio so far returns."""
+
+    def __init__(self, transducer, flags, n_streams, W=10, node_capacity=None, dither=None, *, lm=None, lm_weight=None,
+                 length_bonus=0.0, lm_bos=1, bias=None):
+        self._setup(transducer, flags, n_streams, W, node_capacity, dither,
+                    dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
 
 
 class PytorchStreamDecoder(StreamTransducerDecoder):

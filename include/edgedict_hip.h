@@ -1356,6 +1356,69 @@ int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, con
                               int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
                               long long* ncommitted_host, long long* nframes_host, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * LM shallow fusion and contextual biasing in the frame-synchronous search, offline and streaming.  The *_fusion entry
+ * points take the plain ones' arguments with `lm` and `bias` in front of the trailing state / workspace / result /
+ * stream; either may be null, and with both null they ARE the plain calls (same kernels, same layouts, same bits).
+ *
+ * Every row carries, beside its prediction-network state, the LM state from BEFORE its last token and the phrase
+ * automaton's state s after its sequence (root: 0).  Per frame every row steps the LM on its last token - a row with
+ * the empty sequence on lm->bos from a zero state - which gives fp32 LM logits; lp_lm is their log-softmax in the
+ * formula of the RNN-T row.  Candidate (i, k) scores
+ *   blank:      logp_i + (double)lp_i[blank]
+ *   non-blank:  ((logp_i + (double)lp_i[k]) + (weight * (double)lp_lm_i[k] + length_bonus)) + (held[goto(s_i, k)] - pend[s_i])
+ * in fp64, in this order, without contraction; a term is absent when its feature is.  Selection, merging and the final
+ * ranking are the plain search's on these scores: a token child takes the LM state after its parent's token and the
+ * state goto(s_i, k), a blank child or a folded pair keeps the parent's, a row left empty gets zeros and the root.
+ * logp is the fused score; token_logp and frames are what the plain search returns (the RNN-T log-softmax value on the
+ * node's creation frame).  No pending bonus is settled at the end of an utterance.  weight = length_bonus = 0 is
+ * bit-equal to the plain search.  A frame is the plain search's launches plus the LM step on all B * W rows
+ * (lm->L + 1 launches on the fused step); a bias list adds none.
+ *
+ *   sync_beam_workspace_bytes_fusion     the plain workspace + the LM step's buffers + the rows' LM (h, c) [lm->L][B*W][lm->H]
+ *                                        in two buffers, the LM's next symbols and the automaton states
+ *   sync_stream_state_bytes_fusion       the plain state with the rows' LM (h, c) in both buffers, the LM's next symbols
+ *                                        and the automaton states APPENDED: edgedict_sync_stream_read serves every form.
+ *                                        A state sized with an LM / a list must be reset and advanced with one
+ *   sync_stream_workspace_bytes_fusion   the plain workspace + the LM step's buffers
+ *   sync_stream_reset_fusion             the plain reset; the selected streams' LM states are zeroed, their automaton
+ *                                        states set to the root (the list may change at a reset)
+ *   sync_stream_advance_fusion           the plain advance on the fused scores; compaction is unchanged
+ * Checked before anything is launched (-1 and a message): the LM's ntoken and the list's vocabulary equal V, lm->H a
+ * multiple of 4, lm->bos inside the vocabulary, finite weight / length_bonus, non-null weights and tables, bias->S > 0.
+ * The size queries return 0 for arguments out of range.
+ */
+size_t edgedict_sync_beam_workspace_bytes_fusion(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
+                                                 int W, const edgedict_beam_lm_t* lm,
+                                                 const edgedict_beam_bias_t* bias);
+int edgedict_sync_beam_search_fusion(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B,
+                                     int T, const int32_t* lens_host, int J, const void* W1d, long long ldw1,
+                                     const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
+                                     int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+                                     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
+                                     const float* bp, int blank, int bos, int W, int32_t* tokens_host,
+                                     int32_t* frames_host, double* token_logp_host, int max_tokens,
+                                     int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                     const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* workspace,
+                                     void* result, void* stream);
+size_t edgedict_sync_stream_state_bytes_fusion(int S, int L, int H, int W, int node_capacity,
+                                               const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias);
+size_t edgedict_sync_stream_workspace_bytes_fusion(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
+                                                   int node_capacity, const edgedict_beam_lm_t* lm,
+                                                   const edgedict_beam_bias_t* bias);
+int edgedict_sync_stream_reset_fusion(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
+                                      int mask_on_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                      void* state, void* stream);
+int edgedict_sync_stream_advance_fusion(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride,
+                                        int S, int T, const int32_t* n_frames_host, int J, const void* W1d,
+                                        long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+                                        const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+                                        const void* const* w_hh, const float* const* b_ih, const float* const* b_hh,
+                                        int H, const void* Wp, const float* bp, int blank, int bos, int W,
+                                        int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+                                        int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                        void* state, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
