@@ -47,6 +47,13 @@ symbol per frame and hypothesis, all B x W hypotheses in one step per frame, equ
 csrc/decode_sync.hip).  A different algorithm from ``beam_search_batch``: it does not return the same hypotheses, and
 takes neither ``lm=`` nor ``bias=`` nor ``prefix=``.  ``StreamingSyncBeamSearch`` runs it over encoder output that
 arrives chunk by chunk, carrying every stream's beam in a persistent device state, with the offline search's bits.
+
+``skip_blank=threshold`` (keyword only, on ``beam_search_batch``, ``beam_search_nbest``, ``sync_beam_search_fusion`` and
+``sync_beam_search_nbest``; needs ``Transducer(ctc_weight > 0)``): the search runs only on the encoder frames whose CTC
+blank posterior is at most ``threshold`` (``skip_blank_frames``: the head's logits, ``loss.ctc_blank_skip``, one read
+to the host, ``gather_frames``; csrc/frame_skip.hip), through the ``_enc`` form on the compacted output, and the N-best
+forms report ``frames`` in the original numbering.  Everything else passes through; ``prefix=True`` raises
+``ValueError``.  Not for the greedy search, the streaming searches or ``ctc_beam_search``.  None launches nothing new.
 """
 import ctypes
 
@@ -119,8 +126,97 @@ def _vocab(model):
     return model.joint.joint[2].weight.shape[0]
 
 
+class SkippedFrames:
+    """What ``skip_blank_frames`` returns: ``enc_out`` [B, Tc, P] (the kept frames of every utterance compacted to the
+    front, zero rows behind ``lens[b]``), ``lens`` int32 numpy [B] (kept frames per utterance, ``Tc = lens.max()``) and
+    ``frame_map`` int32 numpy [B, T] (the original index of the j-th kept frame, -1 behind ``lens[b]``)."""
+
+    def __init__(self, enc_out, lens, frame_map):
+        self.enc_out = enc_out
+        self.lens = lens
+        self.frame_map = frame_map
+
+    def restore(self, results):
+        """Rewrite ``frames`` of the ``NBestResult`` list of a search over ``enc_out`` into the original frame numbers
+        (in place; returns the list)."""
+        for b, r in enumerate(results):
+            r.frames = [self.frame_map[b, np.asarray(f, dtype=np.int64)].astype(np.int32) for f in r.frames]
+        return results
+
+
+def _check_skip(model, skip_blank, prefix=False):
+    """The argument rules of ``skip_blank=`` (raised before anything touches the device): the threshold as a float."""
+    from .loss import check_skip_threshold
+    thr = check_skip_threshold(skip_blank)
+    if prefix:
+        raise ValueError("skip_blank with prefix=True is not supported: the prefix variant's sums are defined over all "
+                         "frames of an utterance")
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+    return thr
+
+
+def gather_frames(enc_out, frame_map, kept, Tc, out=None):
+    """``out[b, j] = enc_out[b, frame_map[b, j]]`` for ``j < kept[b]``, zero rows for ``kept[b] <= j < Tc``
+    (csrc/frame_skip.hip): ``enc_out`` [B, T, P] float32 / bfloat16, contiguous; ``frame_map`` int32 [B, T] and ``kept``
+    int32 [B] on the device, as ``loss.ctc_blank_skip`` returns them; ``1 <= Tc <= T`` a host int.  ``out``: a contiguous
+    [B, Tc, P] tensor of ``enc_out``'s dtype to write into (default: a new one).  No host sync."""
+    if enc_out.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("enc_out must be float32 or bfloat16, got %s" % enc_out.dtype)
+    if enc_out.dim() != 3 or not enc_out.is_contiguous():
+        raise ValueError("enc_out must be contiguous [B, T, P]")
+    B, T, P = enc_out.shape
+    Tc = int(Tc)
+    if frame_map.dtype != torch.int32 or kept.dtype != torch.int32:
+        raise TypeError("frame_map and kept must be int32")
+    if tuple(frame_map.shape) != (B, T) or tuple(kept.shape) != (B,) or not frame_map.is_contiguous() \
+            or not kept.is_contiguous():
+        raise ValueError("frame_map must be contiguous [B, T] = [%d, %d] and kept [B]" % (B, T))
+    if B < 1 or P < 1 or not 1 <= Tc <= T:
+        raise ValueError("need B, P >= 1 and 1 <= Tc <= T (B = %d, P = %d, Tc = %d, T = %d)" % (B, P, Tc, T))
+    if out is None:
+        out = torch.empty(B, Tc, P, dtype=enc_out.dtype, device=enc_out.device)
+    elif out.dtype != enc_out.dtype or tuple(out.shape) != (B, Tc, P) or not out.is_contiguous():
+        raise ValueError("out must be contiguous [B, Tc, P] of enc_out's dtype")
+    _lib.require_cuda(enc_out, frame_map, kept, out)
+    _lib.call("frame_skip_gather", enc_out.detach(), dtype_code(enc_out.dtype), frame_map, kept, B, T, P, Tc, out)
+    return out
+
+
+@torch.no_grad()
+def skip_blank_frames(model, enc_out, lens, threshold):
+    """Drop the encoder frames on which the model's CTC head is sure nothing is emitted: frame ``t < lens[b]`` of
+    ``enc_out`` [B, T, P] (compute dtype, device; ``lens`` host ints or None for all T) is kept iff the head's blank
+    posterior on it is at most ``threshold`` (in (0, 1]; ``loss.ctc_blank_skip``).  The head's logits, the decision and
+    the compaction run on the device; ONE read brings the kept counts and the frame map to the host, which sizes the
+    gather.  Returns a ``SkippedFrames``: run an ``_enc`` search on its ``enc_out`` with its ``lens`` and pass an N-best
+    result through its ``restore``.  ``Tc = 0`` (every frame of every utterance dropped) is legal.  Raises
+    ``RuntimeError`` on a model built without ``ctc_weight > 0``."""
+    from .loss import ctc_blank_skip
+    thr = _check_skip(model, threshold)
+    _lib.require_cuda(enc_out)
+    enc_out = enc_out.contiguous()
+    B, T, P = enc_out.shape
+    if T < 1:
+        return SkippedFrames(enc_out, np.zeros(B, dtype=np.int32), np.zeros((B, 0), dtype=np.int32))
+    lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > T).any():
+        raise ValueError("skip_blank_frames: lens must be [B] ints in [0, %d]" % T)
+    act = torch.from_numpy(lens).to(enc_out.device)
+    frame_map, kept, _ = ctc_blank_skip(model._ctc_logits(enc_out).contiguous(), act, thr, model.blank)
+    host = torch.cat([kept[:, None], frame_map], dim=1).cpu().numpy()
+    kept_h, map_h = np.ascontiguousarray(host[:, 0]), np.ascontiguousarray(host[:, 1:])
+    Tc = int(kept_h.max())
+    out = gather_frames(enc_out, frame_map, kept, Tc) if Tc > 0 else enc_out.new_zeros(B, 0, P)
+    return SkippedFrames(out, kept_h, map_h)
+
+
+def _empty_nbest(B):
+    return [NBestResult([np.zeros(0, np.int64)], [np.zeros(0, np.int32)], [np.zeros(0)], [0.0]) for _ in range(B)]
+
+
 def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=False, *, lm=None, lm_weight=None,
-                      length_bonus=0.0, lm_bos=1, bias=None):
+                      length_bonus=0.0, lm_bos=1, bias=None, skip_blank=None):
     """Graves (2012) beam search as the reference's legacy ``Transducer.beam_search`` runs it
     (models.py:121-202), batched: every utterance keeps its own A / B sets and all open utterances
     advance one expansion per lockstep iteration on the device.  ``prefix=True`` is the reference's
@@ -136,11 +232,17 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     ``lm_weight``; ``prefix=True`` with an LM and an LM of another vocabulary raise ``ValueError``).
 
     ``bias``: a contextual-biasing list (``edgedict_amd.bias.ContextGraph``), see the module docstring; the same two
-    cases raise ``ValueError``."""
+    cases raise ``ValueError``.
+
+    ``skip_blank``: a threshold in (0, 1] - the search then runs only on the encoder frames whose CTC blank posterior
+    is at most the threshold (``skip_blank_frames``; the model needs a CTC head, ``prefix=True`` raises ``ValueError``).
+    None: nothing of this runs."""
     from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), prefix)
     check_bias_args(bias, _vocab(model), prefix)
+    if skip_blank is not None:
+        _check_skip(model, skip_blank, prefix)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -152,6 +254,12 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
     else:
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
+    if skip_blank is not None:
+        sk = skip_blank_frames(model, enc_out, lens, skip_blank)
+        if sk.enc_out.shape[1] == 0:        # every frame dropped: the empty hypothesis, nothing to launch
+            beam_search_batch.last_expansions = 0
+            return [np.zeros(0, np.int64) for _ in range(B)], torch.zeros(B, dtype=torch.float64)
+        enc_out, lens = sk.enc_out, sk.lens
     return beam_search_enc(model, enc_out, lens, W, max_expansions, prefix, lm=lm, lm_weight=lm_weight,
                            length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
@@ -335,18 +443,21 @@ def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
 
 
 def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                      lm_bos=1, bias=None):
+                      lm_bos=1, bias=None, skip_blank=None):
     """``beam_search_batch`` (``prefix=False``) returning, per utterance, an ``NBestResult``: all ``n <= W`` hypotheses
     of the last frame's list B in B's order, each with its tokens, the encoder frame every token was emitted on and the
     score increment every token added, and ``logp`` (log p, not negated).  Entry 0 is exactly what ``beam_search_batch``
     returns (same tokens, ``logp[0] == -score`` bit for bit), and ``beam_search_batch.last_expansions`` is set as there.
     An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.  The prefix-sum variant is not available
     here: its merge changes a score at frame starts, so the increments would no longer add up.  With ``bias`` (module
-    docstring) ``token_logp`` and ``logp`` include the bias increments."""
+    docstring) ``token_logp`` and ``logp`` include the bias increments.  ``skip_blank``: as in ``beam_search_batch``;
+    ``frames`` stay in the original frame numbering."""
     from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), False)
     check_bias_args(bias, _vocab(model), False)
+    if skip_blank is not None:
+        _check_skip(model, skip_blank)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -357,6 +468,14 @@ def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=Non
     else:
         xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
         lens = model.scale_length(enc_out, xl).numpy().astype(np.int32)
+    if skip_blank is not None:
+        sk = skip_blank_frames(model, enc_out, lens, skip_blank)
+        if sk.enc_out.shape[1] == 0:        # every frame dropped: the empty hypothesis, nothing to launch
+            beam_search_batch.last_expansions = 0
+            return _empty_nbest(enc_out.shape[0])
+        return sk.restore(beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, max_expansions, lm=lm,
+                                                lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos,
+                                                bias=bias))
     return beam_search_nbest_enc(model, enc_out, lens, W, max_expansions, lm=lm, lm_weight=lm_weight,
                                  length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
@@ -479,7 +598,7 @@ def sync_beam_search(model, xs, xlen=None, W=10):
 
 
 def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
-                            bias=None):
+                            bias=None, skip_blank=None):
     """``sync_beam_search`` with LM shallow fusion and contextual biasing (without either: ``sync_beam_search`` itself,
     launch for launch).
 
@@ -494,22 +613,33 @@ def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=No
     ranking act on the fused score, which is what the returned score is; ``lm_weight = 0, length_bonus = 0`` and an
     empty list are bit-equal to the plain search, and without ``lm`` / ``bias`` the plain kernels run.
 
+    ``skip_blank``: a threshold in (0, 1] - the search then runs only on the encoder frames whose CTC blank posterior
+    is at most the threshold (``skip_blank_frames``; the model needs a CTC head).  None: nothing of this runs.
+
     Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
     utterance, in ``beam_search_batch``'s types."""
-    return _best_of(sync_beam_search_nbest(model, xs, xlen, W,
-                                           lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
+    return _best_of(sync_beam_search_nbest(model, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                           lm_bos=lm_bos, bias=bias, skip_blank=skip_blank))
 
 
 def sync_beam_search_nbest(model, xs, xlen=None, W=10,
-                           *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+                           *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, skip_blank=None):
     """``sync_beam_search`` returning, per utterance, the final beam as an ``NBestResult`` **already ranked**: ``logp``
     descending (ties keep beam order), at most W hypotheses with distinct token sequences, entry 0 what
     ``sync_beam_search`` returns.  ``frames[i]``: the encoder frame on which each token's tree node was created
     (``emission_times`` applies); ``token_logp[i]``: the token's log-softmax value on that frame - NOT an increment of
     ``logp``, which sums over alignments (as in ``ctc_beam_search``), and with an LM or a bias list still the RNN-T
-    value alone while ``logp`` is the fused score.  An utterance of 0 frames yields one empty hypothesis with ``logp`` 0."""
+    value alone while ``logp`` is the fused score.  An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.
+    ``skip_blank``: as in ``sync_beam_search_fusion``; ``frames`` stay in the original frame numbering, and an utterance
+    whose frames are all dropped is an utterance of 0 frames."""
     _check_sync_fusion(model, lm, lm_weight, bias)
+    if skip_blank is not None:
+        _check_skip(model, skip_blank)
     enc_out, lens = _sync_encode(model, xs, xlen, W)
+    if skip_blank is not None:
+        sk = skip_blank_frames(model, enc_out, lens, skip_blank)
+        return sk.restore(sync_beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, lm=lm, lm_weight=lm_weight,
+                                                     length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
     return sync_beam_search_nbest_enc(model, enc_out, lens, W,
                                       lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 

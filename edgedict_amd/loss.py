@@ -33,7 +33,8 @@ joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`
 ``CTCLoss`` / ``ctc_greedy`` (csrc/ctc_loss.hip) are the loss and the greedy decoder of the encoder's CTC auxiliary head
 (``Transducer(ctc_weight=...)``): raw head logits ``[B, T, V]``, not in the reference.  ``ctc_prefix_beam``
 (csrc/ctc_decode.hip) searches the same logits with a beam: ranked N-best prefixes with token frames, optionally biased
-towards a phrase list (``bias.ContextGraph``).
+towards a phrase list (``bias.ContextGraph``).  ``ctc_blank_skip`` (csrc/frame_skip.hip) marks the frames whose blank
+posterior is at most a threshold and compacts their indices: the front of ``decode.skip_blank_frames``.
 
 ``SoftmaxNLLLoss`` / ``softmax_nll_rows`` (csrc/lm_loss.hip) are the language model's loss and sentence scorer:
 ``log_softmax`` + ``NLLLoss(ignore_index)`` on raw logits ``[M, V]``, the gradient written into the logits in place.
@@ -479,6 +480,58 @@ def ctc_greedy(logits, act_lens, blank=0):
     _lib.call("ctc_greedy", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, int(blank), tokens,
               counts, frames, neglogp, scratch)
     return tokens, counts, frames, neglogp
+
+
+def check_skip_threshold(threshold):
+    """The blank-skip threshold as a float in (0, 1], else ``ValueError`` (a NaN fails both comparisons)."""
+    try:
+        thr = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError("the blank-skip threshold must be a number in (0, 1], got %r" % (threshold,)) from None
+    if not 0.0 < thr <= 1.0:
+        raise ValueError("the blank-skip threshold must lie in (0, 1], got %r" % (threshold,))
+    return thr
+
+
+@torch.no_grad()
+def ctc_blank_skip(logits, act_lens, threshold, blank=0):
+    """Which frames of head logits ``[B, T, V]`` (float32 / bfloat16, contiguous, device) CTC is NOT sure are blank
+    (csrc/frame_skip.hip): with ``lp_blank[b, t] = log_softmax(logits[b, t])[blank]`` frame ``t < act_lens[b]`` is kept
+    iff ``lp_blank[b, t] <= float32(log(threshold))``, i.e. the blank holds at most ``threshold`` of the frame's mass.
+    ``threshold`` in (0, 1], else ``ValueError``; 1.0 keeps every frame.  Returns device tensors
+    ``(frame_map, kept, lp_blank)``: ``frame_map`` int32 ``[B, T]`` (the original index of the j-th kept frame, ascending,
+    -1 behind ``kept[b]``), ``kept`` int32 ``[B]``, ``lp_blank`` float32 ``[B, T]`` (clamped to <= 0; 0 behind
+    ``act_lens[b]``).  No host sync."""
+    thr = check_skip_threshold(threshold)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+    if act_lens.dtype != torch.int32:
+        raise TypeError("act_lens must be int32, got %s" % act_lens.dtype)
+    if logits.dim() != 3:
+        raise ValueError("logits must have 3 dimensions [B,T,V], got %d" % logits.dim())
+    if not logits.is_contiguous() or not act_lens.is_contiguous():
+        raise ValueError("logits and act_lens must be contiguous")
+    if act_lens.dim() != 1 or act_lens.shape[0] != logits.shape[0]:
+        raise ValueError("must have a length per example (act_lens has %s, batch is %d)"
+                         % (tuple(act_lens.shape), logits.shape[0]))
+    B, T, V = logits.shape
+    blank = int(blank)
+    if B < 1 or T < 1:
+        raise ValueError("logits must hold at least one utterance and one frame (B = %d, T = %d)" % (B, T))
+    if V < 2:
+        raise ValueError("V = %d: need at least the blank and one symbol" % V)
+    if not 0 <= blank < V:
+        raise ValueError("blank %d outside [0, %d)" % (blank, V))
+    _lib.require_cuda(logits, act_lens)
+    dev = logits.device
+    # the comparison's right-hand side is formed once, here, in the precision the kernel compares in
+    log_thr = ctypes.c_float(math.log(thr)).value
+    frame_map = torch.empty(B, T, dtype=torch.int32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    lp_blank = torch.empty(B, T, dtype=torch.float32, device=dev)
+    _lib.call("frame_skip_scan", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, log_thr,
+              lp_blank, frame_map, kept)
+    return frame_map, kept, lp_blank
 
 
 CTC_BEAM_MAX_W = 32

@@ -1262,6 +1262,31 @@ int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_l
                              void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Blank-frame skipping ahead of the RNN-T beam searches (csrc/frame_skip.hip): the CTC head's blank posterior decides
+ * which encoder frames a search sees.  No host sync inside either call, no atomics; results bit-identical from run to
+ * run.
+ *
+ * edgedict_frame_skip_scan (two launches: a row pass, one wave per utterance for the compaction):
+ *   logits, dtype, act_lens, B, T, V, blank   as edgedict_ctc_greedy (rows t >= act_lens[b] are never read)
+ *   log_thr    (float)log(threshold) of a threshold in (0, 1], formed once on the host: finite, <= 0
+ *   lp_blank   [B, T] fp32 out: min(logits[b,t,blank] - lse(logits[b,t,:]), 0) for t < act_lens[b], 0 behind
+ *   frame_map  [B, T] int32 out: the original index of the j-th kept frame in ascending order, -1 behind kept[b];
+ *              frame t < act_lens[b] is kept iff lp_blank[b,t] <= log_thr (log_thr = 0 keeps every frame)
+ *   kept       [B] int32 out
+ *
+ * edgedict_frame_skip_gather (one launch):
+ *   enc_out    [B, T, P] contiguous, dtype code; out [B, Tc, P] of the same dtype, 1 <= Tc <= T
+ *   out[b,j,:] = enc_out[b, frame_map[b,j], :] for j < min(kept[b], Tc), zeros for the other rows (and for a map entry
+ *   outside [0, T)).  16-byte copies when P * sizeof(dtype) is a multiple of 16 and both pointers are 16-byte aligned,
+ *   element copies otherwise.
+ * Limits: B <= 65535, B x T <= 2^31 - 1, V >= 2.
+ */
+int edgedict_frame_skip_scan(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V, int blank,
+                             float log_thr, float* lp_blank, int32_t* frame_map, int32_t* kept, void* stream);
+int edgedict_frame_skip_gather(const void* enc_out, int dtype, const int32_t* frame_map, const int32_t* kept, int B,
+                               int T, int P, int Tc, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Frame-synchronous batched RNN-T beam search (csrc/decode_sync.hip states the search): every hypothesis emits at most
  * one symbol per frame, all B x W hypotheses advance through one prediction-network step and one joint per frame, equal
  * token sequences are merged by log-add.  A second search beside edgedict_beam_search*, NOT the same algorithm: the two
