@@ -55,7 +55,7 @@ class _ChunkPlan:
     argument conversion, a dozen tensor allocations - costs 0.33 ms per chunk step, more than the ~0.2 ms of kernels
     behind it at 256 streams.  The plan keeps every intermediate buffer and every converted argument; per chunk only the
     caller's frame pointer, the dither seed and the token buffer change.  Same kernels, same arguments, same order:
-    bit-identical to the module path (tests/test_stream_gpu.py).  Rebuilt when a parameter changes (version counters,
+    bit-identical to the module path (tests/test_stream_gpu.py; at other chunk lengths tests/test_stream_geometry_gpu.py).  Rebuilt when a parameter changes (version counters,
     the engine's parameter epoch), the frames' shape changes or the model moves."""
 
     def __init__(self, dec, frames):

@@ -17,9 +17,16 @@ filled with
 Only the texts the reference returns per chunk are stored, for single streams and for S independent
 streams with resets (the fixture of the batched decoder).  Asserts oracle/stream_ref.py reproduces them.
 
+tests/golden/stream.npz holds CASES, all at the native chunk (win 320, hop 200, 3 stacked frames, 2 steps: 1320 / 1200
+samples, 2 stacked frames of 240 features).  tests/golden/stream_geometry.npz holds GEOMETRY_CASES: the same loop at the
+chunk geometries of GEOMETRIES, where a chunk carries 1, 3, 13, 23 or 24 stacked frames of 80 .. 320 features - an odd
+count is zero-padded by the encoder's time reduction in EVERY chunk, which offline decoding of the same audio does not
+do.  The reference's FilterbankFeatures / Downsample are then built with the case's hop_length / downsample.
+
     python oracle/make_golden_stream.py        # needs /root/reference
 """
 import ast
+import collections
 import os
 import sys
 import time
@@ -54,6 +61,61 @@ CASES = {
 }
 WIN, HOP = 1320, 1200      # stream.py:71-77 at E6D2 framing: win 320, hop 200, downsample 3, 2 frames
 
+# Chunk geometries beyond the native one (win_length 320, n_fft 512, 80 filters throughout).  win / hop: samples of a chunk
+# (stream.py:71-77 of the reference); T0 x I0: stacked frames per chunk and their width, (1 + win // hop_length) //
+# downsample frames of 80 * downsample features (Downsample(ds, pad_to_divisible=False) truncates); T_out: encoder frames
+# per chunk behind the body's one time reduction by 2, which rounds up.  tests/test_oracle_stream.py checks the last five
+# columns against oracle.features_ref.
+Geometry = collections.namedtuple("Geometry", "hop_length downsample step_n_frame win hop T0 I0 T_out")
+GEOMETRIES = {
+    "native": Geometry(200, 3, 2, 1320, 1200, 2, 240, 1),
+    "hop640": Geometry(160, 2, 2, 800, 640, 3, 160, 2),             # the benched 40 ms chunk: odd T0
+    "one_frame": Geometry(200, 3, 1, 720, 600, 1, 240, 1),          # a lone frame, halved by the reduction every chunk
+    "narrow": Geometry(200, 1, 2, 520, 400, 3, 80, 2),
+    "wide": Geometry(200, 4, 2, 1720, 1600, 2, 320, 1),
+    "long": Geometry(160, 2, 12, 4000, 3840, 13, 160, 7),
+    "stack_below": Geometry(160, 2, 22, 7200, 7040, 23, 160, 12),   # the two sides of config.STACK_MIN_FRAMES = 24
+    "stack_at": Geometry(160, 2, 23, 7520, 7360, 24, 160, 12),
+}
+
+
+def body(base, geometry, **kw):
+    """``base`` with the input width of ``geometry`` (and any other override)."""
+    return dict(base, input_size=GEOMETRIES[geometry].I0, **kw)
+
+
+GeometryCase = collections.namedtuple("GeometryCase", "geometry cfg wseed xseed S n_chunks resets bias")
+# the bias pairs are found per case by the scan CASES' pairs came from (StreamOracle over the case's audio; CASES' own
+# pairs give all blanks or no blank here): blanks and symbols both occur in every case - the generator asserts it
+GEOMETRY_CASES = {
+    "hop640": GeometryCase("hop640", body(SMALL, "hop640"), 5, 10, 1, 8, {}, (0.475, 1.9)),
+    "hop640_multi": GeometryCase("hop640", body(SMALL, "hop640"), 5, 11, 5, 6, {3: [1, 4]}, (0.45, 1.9)),
+    # the body of the 256-stream test (tests/test_stream_geometry_gpu.py): H = 128, the multi-stream case's streams and reset
+    "hop640_mid": GeometryCase("hop640", body(SMALL, "hop640", enc_hidden_size=128), 5, 19, 5, 6, {3: [1, 4]}, (0.425, 1.9)),
+    "one_frame": GeometryCase("one_frame", body(SMALL, "one_frame"), 6, 12, 1, 8, {4: [0]}, (0.3, 1.9)),
+    "narrow": GeometryCase("narrow", body(SMALL, "narrow", enc_hidden_size=96), 7, 13, 2, 8, {5: [1]}, (0.5, 1.9)),   # I0 < H
+    "wide": GeometryCase("wide", body(SMALL, "wide"), 8, 14, 2, 6, {}, (0.275, 1.9)),                                     # I0 > H
+    "wide96": GeometryCase("wide", body(SMALL, "wide", enc_hidden_size=96), 8, 15, 1, 6, {}, (0.2, 1.9)),
+    "long": GeometryCase("long", body(SMALL, "long"), 9, 16, 2, 5, {2: [0]}, (0.2, 1.9)),
+    "stack_below": GeometryCase("stack_below", body(SMALL, "stack_below"), 10, 17, 3, 3, {2: [1]}, (0.375, 1.9)),
+    "stack_at": GeometryCase("stack_at", body(SMALL, "stack_at"), 10, 17, 3, 3, {2: [1]}, (0.375, 1.9)),
+    "E6D2_hop640": GeometryCase("hop640", body(E6D2, "hop640"), 31, 18, 3, 6, {}, (0.65, 1.9)),
+}
+
+
+def geometry_flags(geometry):
+    """The E6D2 flags with the framing of GEOMETRIES[geometry]."""
+    from edgedict_amd.flags import make_flags
+    g = GEOMETRIES[geometry]
+    return make_flags("E6D2", hop_length=g.hop_length, downsample=g.downsample)
+
+
+def case_wave(case):
+    """The audio of a GeometryCase: float32 [S, win + n_chunks * hop]; chunk c is [:, c * hop:c * hop + win]."""
+    g = GEOMETRIES[case.geometry]
+    gen = torch.Generator(device="cpu").manual_seed(case.xseed)
+    return 0.1 * torch.randn(case.S, g.win + case.n_chunks * g.hop, generator=gen)
+
 
 def state_dict(cfg, seed, bias=(0.8, 2.05)):
     """Seeded weights with the joint's output bias raised for blank (id 0) and '<unk>' (id 3)."""
@@ -79,15 +141,15 @@ def reference_decoder_class():
     return ns["PytorchStreamDecoder"]
 
 
-def reference_stream(cfg, sd, Decoder, RF, DS):
+def reference_stream(cfg, sd, Decoder, RF, DS, hop_length=200, downsample=3):
     m = reference_model(cfg, sd)
     d = object.__new__(Decoder)                      # __init__ bypassed, see the module docstring
     d.FLAGS = types.SimpleNamespace(enc_layers=cfg["enc_layers"], enc_hidden_size=cfg["enc_hidden_size"],
                                     dec_layers=cfg["dec_layers"], dec_hidden_size=cfg["dec_hidden_size"])
     d.tokenizer = types.SimpleNamespace(tokenizer=StubVocab())
-    fb = RF(n_filt=80, n_fft=512, win_length=320, hop_length=200)
+    fb = RF(n_filt=80, n_fft=512, win_length=320, hop_length=hop_length)
     fb.dither = 0.0
-    d.transform = torch.nn.Sequential(fb, DS(3, False))
+    d.transform = torch.nn.Sequential(fb, DS(downsample, False))
     d.encoder, d.decoder, d.joint = m.encoder, m.decoder, m.joint
     d.reset_profile()
     d.reset()
@@ -98,8 +160,45 @@ def ids_of(text):
     return [int(t[1:]) for t in text.split(" ") if t]
 
 
-def main():
+def run_case(name, cfg, sd, flags, wave, win, hop, n_chunks, resets, Decoder, RF, DS, out):
+    """The reference's decoder and StreamOracle side by side over ``wave``; the texts go to ``out``."""
     from oracle.stream_ref import StreamOracle
+    S = wave.shape[0]
+    refs = [reference_stream(cfg, sd, Decoder, RF, DS, flags.hop_length, flags.downsample) for _ in range(S)]
+    oracles = [StreamOracle(sd, flags) for _ in range(S)]
+    texts = np.empty((S, n_chunks), dtype=object)
+    emitted = blanks = 0
+    for c in range(n_chunks):
+        for s in resets.get(c, []):
+            refs[s].reset()
+            oracles[s].reset()
+        for s in range(S):
+            chunk = wave[s:s + 1, c * hop:c * hop + win]
+            text = refs[s].decode(chunk.clone())
+            full = oracles[s].decode(chunk.clone())
+            want = [t for t in full if t != 0]
+            assert ids_of(text) == want, (name, c, s, text, want)
+            texts[s, c] = text
+            emitted += len(want)
+            blanks += len(full) - len(want)
+    assert emitted > 0 and blanks > 0, name
+    assert len(refs[0].encoder_elapsed) == n_chunks
+    out[name + "_texts"] = texts.astype(str)
+    print("%s: %d streams x %d chunks, %d symbols + %d blanks, oracle == reference" % (name, S, n_chunks, emitted, blanks))
+
+
+def save(name, out):
+    path = os.path.join(ROOT, "tests", "golden", name)
+    if os.path.exists(path):           # an archive's bytes hold timestamps: a file whose arrays are unchanged is left alone
+        old = np.load(path)
+        if sorted(old.files) == sorted(out) and all(np.array_equal(old[k], out[k]) for k in out):
+            print("unchanged", path)
+            return
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
+def main():
     from edgedict_amd.flags import make_flags
     torch.set_num_threads(8)
     Decoder = reference_decoder_class()
@@ -110,31 +209,17 @@ def main():
         sd = state_dict(cfg, wseed, bias)
         g = torch.Generator(device="cpu").manual_seed(xseed)
         wave = 0.1 * torch.randn(S, WIN + n_chunks * HOP, generator=g)
-        refs = [reference_stream(cfg, sd, Decoder, RF, DS) for _ in range(S)]
-        oracles = [StreamOracle(sd, flags) for _ in range(S)]
-        texts = np.empty((S, n_chunks), dtype=object)
-        emitted = blanks = 0
-        for c in range(n_chunks):
-            for s in resets.get(c, []):
-                refs[s].reset()
-                oracles[s].reset()
-            for s in range(S):
-                chunk = wave[s:s + 1, c * HOP:c * HOP + WIN]
-                text = refs[s].decode(chunk.clone())
-                full = oracles[s].decode(chunk.clone())
-                want = [t for t in full if t != 0]
-                assert ids_of(text) == want, (name, c, s, text, want)
-                texts[s, c] = text
-                emitted += len(want)
-                blanks += len(full) - len(want)
-        assert emitted > 0 and blanks > 0, name
-        assert len(refs[0].encoder_elapsed) == n_chunks
-        out[name + "_texts"] = texts.astype(str)
+        run_case(name, cfg, sd, flags, wave, WIN, HOP, n_chunks, resets, Decoder, RF, DS, out)
         out[name + "_cfg"] = np.array([wseed, xseed, S, n_chunks])
-        print("%s: %d streams x %d chunks, %d symbols + %d blanks, oracle == reference" % (name, S, n_chunks, emitted, blanks))
-    path = os.path.join(ROOT, "tests", "golden", "stream.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    save("stream.npz", out)
+    out = {}
+    for name, case in GEOMETRY_CASES.items():
+        geo = GEOMETRIES[case.geometry]
+        sd = state_dict(case.cfg, case.wseed, case.bias)
+        run_case(name, case.cfg, sd, geometry_flags(case.geometry), case_wave(case), geo.win, geo.hop, case.n_chunks,
+                 case.resets, Decoder, RF, DS, out)
+        out[name + "_cfg"] = np.array([case.wseed, case.xseed, case.S, case.n_chunks])
+    save("stream_geometry.npz", out)
 
 
 if __name__ == "__main__":

@@ -191,3 +191,60 @@ def replay(name, store=None):
         sd, x, hid = problem(name)
         _REPLAYS[key] = encoder_steps64(sd, x, hid, CASES[name].red, store=store)
     return _REPLAYS[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# chunks of a stream: the replay chained over consecutive chunks with carried (h, c), as stream.BatchedStreamDecoder
+# drives the encoder (tests/test_stream_geometry_gpu.py), and four mistakes in HOW a chunk is fed and its state carried
+CHUNK_MUTATIONS = ("no_pad", "state_after_pad", "state_reset", "wrong_stride")
+
+
+def kernel_weights(sd):
+    """The encoder's parameters as the bf16 kernels read them: the LSTM matrices rounded to bf16, the rest as given."""
+    return {k: (v.to(BF16).to(v.dtype) if k.endswith(("weight_ih_l0", "weight_hh_l0")) else v)
+            for k, v in sd.items() if k.startswith("encoder.") and not k.startswith("encoder.proj.")}
+
+
+def chunk_step64(sd, xs, hiddens, time_reductions=(1,), store=None, mutate=None):
+    """encoder_steps64 on ONE chunk xs [B,T0,I0] with the carried ``hiddens``, or with one mistake:
+
+    no_pad           an odd frame count under a time reduction is not zero-padded: the lone last frame leaves the
+                     reduction as it is instead of as its mean with a zero frame (the encoder_steps64 mutation
+                     'lone_not_halved'); the reference pads inside every chunk (rnnt/models.py TimeReduction)
+    state_after_pad  the chunk is padded to an even frame count at its INPUT, so that the layers up to the first time
+                     reduction run one step more than the chunk has frames: their carried (h, c) is the state after the
+                     pad frame, not after the last real one.  The chunk's own output is left right - only the next
+                     chunk sees it
+    state_reset      the carried state is dropped: the chunk starts from zeros
+    wrong_stride     stacked frame t is read at t * (I0 - 8) of the row instead of t * I0
+    Returns a Replay."""
+    assert mutate is None or mutate in CHUNK_MUTATIONS, mutate
+    B, T0, I0 = xs.shape
+    if mutate == "state_reset":
+        hiddens = None
+    if mutate == "wrong_stride":
+        flat = xs.reshape(B, T0 * I0)
+        xs = torch.stack([flat[:, t * (I0 - 8):t * (I0 - 8) + I0] for t in range(T0)], 1)
+    good = encoder_steps64(sd, xs, hiddens, time_reductions, store=store, mutate="lone_not_halved" if mutate == "no_pad" else None)
+    if mutate == "state_after_pad" and T0 % 2 and len(time_reductions):
+        padded = encoder_steps64(sd, torch.cat([xs, torch.zeros_like(xs[:, :1])], 1), hiddens, time_reductions, store=store)
+        upto = min(time_reductions) + 1
+        good = good._replace(h=torch.cat([padded.h[:upto], good.h[upto:]]), c=torch.cat([padded.c[:upto], good.c[upto:]]))
+    return good
+
+
+def chunk_mutation_applies(mutation, T0, n_chunks):
+    """Is the mistake one at all for chunks of T0 frames (one time reduction)?"""
+    return {"no_pad": T0 % 2 == 1, "state_after_pad": T0 % 2 == 1 and n_chunks > 1, "state_reset": n_chunks > 1,
+            "wrong_stride": T0 > 1}[mutation]
+
+
+def chain64(sd, chunks, time_reductions=(1,), store=None, mutate=None):
+    """chunk_step64 over ``chunks`` (a list of [B,T0,I0]), each fed the (h, c) the previous one returned, from zeros.
+    Returns the list of Replays."""
+    out, hid = [], None
+    for xs in chunks:
+        r = chunk_step64(sd, xs, hid, time_reductions, store=store, mutate=mutate)
+        out.append(r)
+        hid = (r.h, r.c)
+    return out

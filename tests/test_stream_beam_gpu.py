@@ -200,16 +200,21 @@ STREAM_CFG = dict(vocab_embed_size=16, vocab_size=64, input_size=240, enc_hidden
                   enc_proj_size=48, dec_hidden_size=32, dec_layers=2, dec_proj_size=32, joint_size=64)
 
 
-def test_audio_level_decoder_equals_offline_search_over_the_module_path(hip_lib):
+@pytest.mark.parametrize("geometry", ["native", "hop640", "one_frame"])
+def test_audio_level_decoder_equals_offline_search_over_the_module_path(hip_lib, geometry):
+    """native: 2 stacked frames of 240 features per chunk; hop640: 3 of 160, the odd count zero-padded by the time
+    reduction in every chunk; one_frame: a lone frame of 240 (oracle.make_golden_stream.GEOMETRIES)."""
     from edgedict_amd import decode
-    from edgedict_amd.flags import make_flags
     from edgedict_amd.stream import BatchedStreamBeamDecoder, chunk_geometry
-    flags = make_flags("E6D2")
-    sd = M.make_state_dict(STREAM_CFG, 5)
+    from oracle.make_golden_stream import GEOMETRIES, geometry_flags
+    geo, flags = GEOMETRIES[geometry], geometry_flags(geometry)
+    cfg = dict(STREAM_CFG, input_size=geo.I0)
+    sd = M.make_state_dict(cfg, 5)
     sd["joint.joint.2.bias"][0] += 1.0
-    m = _engine(sd, "fp32", STREAM_CFG)
+    m = _engine(sd, "fp32", cfg)
     S, W = 3, 4
-    win, hop = chunk_geometry(flags, 2)
+    win, hop = chunk_geometry(flags, geo.step_n_frame)
+    assert (win, hop) == (geo.win, geo.hop)
     g = torch.Generator().manual_seed(0)
     wave = (0.1 * torch.randn(S, win + 5 * hop, generator=g)).cuda()
     dec = BatchedStreamBeamDecoder(m, flags, S, W=W, dither=0)
@@ -222,8 +227,10 @@ def test_audio_level_decoder_equals_offline_search_over_the_module_path(hip_lib)
             chunk = wave[:, k * hop:k * hop + win].contiguous()
             got, gsc = dec.decode(chunk.clone())
             xs, _ = dec.transform(chunk.clone())
+            assert tuple(xs.shape) == (S, geo.T0, geo.I0)
             enc, (h, c) = m.encoder(xs, (h, c))
             enc = enc.contiguous()
+            assert enc.shape[1] == geo.T_out
             rows.append(decode.joint_rows(m, enc).reshape(S, enc.shape[1], -1))
             want, wsc, _ = _offline(m, rows, enc.shape[2], W, max(16, 8 * W))
             _same(got, gsc, want, wsc)

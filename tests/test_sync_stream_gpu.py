@@ -303,17 +303,22 @@ def test_two_runs_over_the_same_chunks_give_the_same_bits(hip_lib, name, dtype):
 
 
 # ------------------------------------------------------------------------------------------- 8. audio-level decoder
-def test_audio_level_decoder_equals_the_search_over_the_module_path(hip_lib):
+@pytest.mark.parametrize("geometry", ["native", "hop640", "one_frame"])
+def test_audio_level_decoder_equals_the_search_over_the_module_path(hip_lib, geometry):
+    """native: 2 stacked frames of 240 features per chunk; hop640: 3 of 160, the odd count zero-padded by the time
+    reduction in every chunk; one_frame: a lone frame of 240 (oracle.make_golden_stream.GEOMETRIES)."""
     from edgedict_amd import decode
-    from edgedict_amd.flags import make_flags
     from edgedict_amd.stream import chunk_geometry
+    from oracle.make_golden_stream import GEOMETRIES, geometry_flags
     from test_stream_beam_gpu import STREAM_CFG
-    flags = make_flags("E6D2")
-    sd = M.make_state_dict(STREAM_CFG, 5)
+    geo, flags = GEOMETRIES[geometry], geometry_flags(geometry)
+    cfg = dict(STREAM_CFG, input_size=geo.I0)
+    sd = M.make_state_dict(cfg, 5)
     sd["joint.joint.2.bias"][0] += 1.0
-    m = _engine(sd, STREAM_CFG, "fp32")
+    m = _engine(sd, cfg, "fp32")
     Sn, W = 3, 4
-    win, hop = chunk_geometry(flags, 2)
+    win, hop = chunk_geometry(flags, geo.step_n_frame)
+    assert (win, hop) == (geo.win, geo.hop)
     g = torch.Generator().manual_seed(0)
     wave = (0.1 * torch.randn(Sn, win + 5 * hop, generator=g)).cuda()
     dec = BatchedStreamSyncBeamDecoder(m, flags, Sn, W=W, dither=0)
@@ -327,8 +332,10 @@ def test_audio_level_decoder_equals_the_search_over_the_module_path(hip_lib):
             chunk = wave[:, k * hop:k * hop + win].contiguous()
             got, gsc = dec.decode(chunk.clone())
             xs, _ = dec.transform(chunk.clone())
+            assert tuple(xs.shape) == (Sn, geo.T0, geo.I0)
             enc, (h, c) = m.encoder(xs, (h, c))
             enc = enc.contiguous()
+            assert enc.shape[1] == geo.T_out
             sb.advance(enc)
             rows.append(decode.joint_rows(m, enc).reshape(Sn, enc.shape[1], -1))
             all_rows = torch.cat(rows, dim=1)
