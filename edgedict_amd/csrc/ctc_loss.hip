@@ -22,6 +22,8 @@
 //   ctc_alpha_beta  : ONE WAVE per (utterance, direction), a lane owns C consecutive states, all lanes walk the frames
 //                     in lock step; the two values a lane needs from its left neighbour arrive by DPP moves (no LDS,
 //                     no barrier).  fp64 carry, log_add64 of common.hpp.                              latency-bound.
+//                     <C, VIT = true>: the forced aligner's Viterbi walk, one wave per utterance, max for the log-add.
+//   ctc_viterbi_backtrace : one wave per utterance, one lane walks the best path back: each label's first / last frame.
 //   ctc_costs       : costs, the zero_infinity rule, the dead-utterance flags, the reduction.
 //   ctc_grad        : one wave64 per row again; reads the logits once, writes the gradient once.      HBM-bound.
 //   ctc_argmax / ctc_collapse : the greedy decoder (arg max per frame, then drop repeats and blanks).
@@ -120,7 +122,12 @@ __global__ __launch_bounds__(256) void ctc_label_chain(const int32_t* __restrict
 // log-probabilities (the blank's, and the lane's C / 2 labels') are requested D rows ahead.
 // No sum below has +inf as an operand, so no -inf - (-inf) is ever formed; an utterance with T_b < U_b + repeats never
 // reaches its last two states and gets ll = -inf from the recursion itself.
-template <int C>
+// VIT = true is the Viterbi walk of the forced aligner (edgedict_ctc_align): ONE wave per utterance (blockIdx.x = b,
+// direction 0 only), ONE fmax per predecessor in place of the log-add, then the same add:
+//   v(t,s) = max(v(t-1,s), v(t-1,s-1), [skip(s)] v(t-1,s-2)) + (double)lp(t,s)       (row 0: 0.0 + lp for s <= 1)
+// written where the alphas go, and the best path's score max(v(T_b-1,S_b-1), v(T_b-1,S_b-2)) into ll[2 b]; the beta
+// plane and ll[2 b + 1] are not written.  The VIT = false instantiation is the kernel as it was.
+template <int C, bool VIT = false>
 __global__ __launch_bounds__(64) void ctc_alpha_beta(const float* __restrict__ lpb, const float* __restrict__ lpl,
                                                      const int32_t* __restrict__ labels,
                                                      const int32_t* __restrict__ act_lens,
@@ -130,7 +137,8 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta(const float* __restrict__ l
     static_assert(C >= 2 && (C & 1) == 0, "a lane owns an even number of states");
     constexpr int H = C / 2;                         // label states per lane (the odd slots)
     constexpr int D = C <= 2 ? 8 : (C <= 4 ? 4 : (C <= 8 ? 2 : 1));
-    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1;
+    const int b = VIT ? blockIdx.x : blockIdx.x >> 1;
+    const int dir = VIT ? 0 : blockIdx.x & 1;
     const int lane = threadIdx.x;
     // clamped as rnnt_alpha_beta clamps them; an empty utterance has likelihood 0
     const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U));
@@ -196,8 +204,8 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta(const float* __restrict__ l
                 } else {
                     const double a1 = c >= 1 ? prev[c >= 1 ? c - 1 : 0] : s1;
                     const double a2 = c >= 2 ? prev[c >= 2 ? c - 2 : 0] : (c == 1 ? s1 : s2);
-                    p = log_add64(prev[c], a1);
-                    if ((c & 1) && ((skip >> c) & 1)) p = log_add64(p, a2);
+                    p = VIT ? fmax(prev[c], a1) : log_add64(prev[c], a1);
+                    if ((c & 1) && ((skip >> c) & 1)) p = VIT ? fmax(p, a2) : log_add64(p, a2);
                 }
                 const double carry = p + (double)((c & 1) ? cl[c >> 1] : cb);
                 if (dir == 0) alphas[base + m] = carry;
@@ -215,7 +223,69 @@ __global__ __launch_bounds__(64) void ctc_alpha_beta(const float* __restrict__ l
     }
     v1 = __shfl(v1, (S - 1) / C, 64);
     v2 = __shfl(v2, S >= 2 ? (S - 2) / C : 0, 64);
-    if (lane == 0) ll[2 * b + dir] = S >= 2 ? log_add64(v1, v2) : v1;
+    if (lane == 0) ll[2 * b + dir] = S >= 2 ? (VIT ? fmax(v1, v2) : log_add64(v1, v2)) : v1;
+}
+
+// Back-trace of the Viterbi walk (ctc_alpha_beta<C, true>): one wave per utterance.  Lane 0 starts in the better of the
+// last two states of frame T_b - 1 and walks down to frame 0: T_b - 1 dependent steps of up to three loads of
+// v(t-1, .) (and the two labels the skip rule compares).  All three predecessors of (t,s) get the same lp(t,s) added, so
+// the one the maximum came from is found by comparing v(t-1, .) directly - no back-pointers are stored and no sum is
+// re-formed.  TIE RULE (the later emission wins, as rnnt_viterbi_backtrace waits): the walk starts in state S_b - 2
+// when v(T_b-1,S_b-2) >= v(T_b-1,S_b-1), and among the predecessors whose v(t-1, .) equals the maximum it takes s - 2
+// (where the skip is allowed), else s - 1, else s.  On a row with a path every cell of the walk has a finite v, so the
+// maximum is finite and the walk ends in state 0 or 1 having passed every label.  frames[b][u] / ends[b][u] = the first
+// / last frame the path spends in label u's state; the other lanes write the -1 padding behind U_b.  A row without a
+// path (T_b = 0, or fewer frames than labels plus adjacent repeats: score -inf): -1 everywhere.
+__global__ __launch_bounds__(64) void ctc_viterbi_backtrace(const double* __restrict__ v, const double* __restrict__ ll,
+                                                            const int32_t* __restrict__ labels,
+                                                            const int32_t* __restrict__ act_lens,
+                                                            const int32_t* __restrict__ label_lens, int Tm, int U,
+                                                            int32_t* __restrict__ frames, int32_t* __restrict__ ends,
+                                                            float* __restrict__ scores) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int Tb = max(0, min(act_lens[b], Tm)), Ub = max(0, min(label_lens[b], U));   // as ctc_alpha_beta
+    const double NEG = -(double)INFINITY;
+    const double L = ll[2 * b];                      // -inf for an empty utterance
+    const bool none = Tb == 0 || L == NEG;
+    int32_t* fr = frames + (long long)b * U;
+    int32_t* en = ends + (long long)b * U;
+    for (int u = (none ? 0 : Ub) + lane; u < U; u += 64) {
+        fr[u] = -1;
+        en[u] = -1;
+    }
+    if (lane != 0) return;
+    scores[b] = (float)L;
+    if (none) return;
+    const int S = 2 * Ub + 1, Sm = 2 * U + 1;
+    const long long row0 = (long long)b * Tm;
+    const int32_t* y = labels + (long long)b * U;
+    int t = Tb - 1, s = S - 1;
+    if (S >= 2) {
+        const double* last = v + (row0 + t) * Sm;
+        if (last[S - 2] >= last[S - 1]) s = S - 2;
+    }
+    if (s & 1) en[s >> 1] = t;
+    for (; t > 0; --t) {
+        const double* pr = v + (row0 + t - 1) * Sm;
+        const double a0 = pr[s];
+        const double a1 = s >= 1 ? pr[s - 1] : NEG;
+        double a2 = NEG;
+        bool skip = false;
+        if ((s & 1) && s >= 3) {
+            a2 = pr[s - 2];
+            skip = y[s >> 1] != y[(s >> 1) - 1];
+        }
+        if (!skip) a2 = NEG;
+        const double m = fmax(fmax(a0, a1), a2);
+        // (the index tests keep a row of NaN logits, where m may be -inf, inside the plane)
+        const int from = (skip && a2 == m) ? s - 2 : ((s >= 1 && a1 == m) ? s - 1 : s);
+        if (from != s) {
+            if (s & 1) fr[s >> 1] = t;
+            if (from & 1) en[from >> 1] = t - 1;
+            s = from;
+        }
+    }
+    if (s & 1) fr[s >> 1] = 0;
 }
 
 // single block: costs[b] = -ll_alpha[b]; zero_infinity turns a non-finite cost into 0; dead[b] = 1 marks the
@@ -384,6 +454,38 @@ inline int ctc_check(const char* who, int B, int T, int U, int V, int blank, int
     return ED_OK;
 }
 
+// the first two stages of the loss and of the aligner: the row pass, then the lattice walk - one wave per
+// (utterance, direction) (VIT: per utterance), C = max(2, ceil(S / 64)) states per lane (rounded up to a power of two)
+inline void ctc_launch_rows(const void* logits, int dtype, const int32_t* labels, const int32_t* act_lens,
+                            const int32_t* label_lens, int B, int T, int U, int V, int blank, float* lse, float* lpb,
+                            float* lpl, hipStream_t stream) {
+    const size_t esz = dtype == ED_F32 ? 4 : 2;
+    const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)logits & 15) == 0);
+    const dim3 grid1(ed_grid_for(T, 4, max(1, 256 * 16 / B)), B);
+    if (dtype == ED_F32)
+        hipLaunchKernelGGL(ctc_lse_gather<float>, grid1, dim3(256), 0, stream, (const float*)logits, labels, act_lens,
+                           label_lens, T, U, V, blank, lse, lpb, lpl, vec_ok);
+    else
+        hipLaunchKernelGGL(ctc_lse_gather<bf16_t>, grid1, dim3(256), 0, stream, (const bf16_t*)logits, labels, act_lens,
+                           label_lens, T, U, V, blank, lse, lpb, lpl, vec_ok);
+}
+
+template <bool VIT>
+inline void ctc_launch_walk(const float* lpb, const float* lpl, const int32_t* labels, const int32_t* act_lens,
+                            const int32_t* label_lens, int B, int T, int U, double* alphas, double* betas, double* ll,
+                            hipStream_t stream) {
+#define ED_CTC_AB(CC)                                                                                                 \
+    hipLaunchKernelGGL((ctc_alpha_beta<CC, VIT>), dim3(VIT ? B : 2 * B), dim3(64), 0, stream, lpb, lpl, labels, act_lens, \
+                       label_lens, T, U, alphas, betas, ll)
+    const int per_lane = (2 * U + 1 + 63) / 64;
+    if (per_lane <= 2) ED_CTC_AB(2);
+    else if (per_lane <= 4) ED_CTC_AB(4);
+    else if (per_lane <= 8) ED_CTC_AB(8);
+    else if (per_lane <= 16) ED_CTC_AB(16);
+    else ED_CTC_AB(32);
+#undef ED_CTC_AB
+}
+
 }  // namespace
 
 extern "C" size_t edgedict_ctc_workspace_bytes(int B, int T, int U) {
@@ -427,35 +529,45 @@ extern "C" int edgedict_ctc_loss_forward(const void* logits, int dtype, const in
     int32_t* dead = (int32_t*)(p + w.off_flag);
     int32_t* chain = (int32_t*)(p + w.off_chain);
 
-    const size_t esz = dtype == ED_F32 ? 4 : 2;
-    const int vec_ok = ((V * esz) % 16 == 0) && (((uintptr_t)logits & 15) == 0);
-    const dim3 grid1(ed_grid_for(T, 4, max(1, 256 * 16 / B)), B);
-    if (dtype == ED_F32)
-        hipLaunchKernelGGL(ctc_lse_gather<float>, grid1, dim3(256), 0, stream, (const float*)logits, labels, act_lens,
-                           label_lens, T, U, V, blank, lse, lpb, lpl, vec_ok);
-    else
-        hipLaunchKernelGGL(ctc_lse_gather<bf16_t>, grid1, dim3(256), 0, stream, (const bf16_t*)logits, labels, act_lens,
-                           label_lens, T, U, V, blank, lse, lpb, lpl, vec_ok);
+    ctc_launch_rows(logits, dtype, labels, act_lens, label_lens, B, T, U, V, blank, lse, lpb, lpl, stream);
     ED_CHECK_LAUNCH("ctc_lse_gather");
     if (U > 0) {
         hipLaunchKernelGGL(ctc_label_chain, dim3(B), dim3(256), 0, stream, labels, label_lens, U, chain);
         ED_CHECK_LAUNCH("ctc_label_chain");
     }
-    // one wave per (utterance, direction), C = max(2, ceil(S / 64)) states per lane (rounded up to a power of two)
-#define ED_CTC_AB(CC)                                                                                             \
-    hipLaunchKernelGGL(ctc_alpha_beta<CC>, dim3(2 * B), dim3(64), 0, stream, lpb, lpl, labels, act_lens, label_lens, \
-                       T, U, alphas, betas, ll)
-    const int per_lane = (2 * U + 1 + 63) / 64;
-    if (per_lane <= 2) ED_CTC_AB(2);
-    else if (per_lane <= 4) ED_CTC_AB(4);
-    else if (per_lane <= 8) ED_CTC_AB(8);
-    else if (per_lane <= 16) ED_CTC_AB(16);
-    else ED_CTC_AB(32);
-#undef ED_CTC_AB
+    ctc_launch_walk<false>(lpb, lpl, labels, act_lens, label_lens, B, T, U, alphas, betas, ll, stream);
     ED_CHECK_LAUNCH("ctc_alpha_beta");
     hipLaunchKernelGGL(ctc_costs, dim3(1), dim3(256), 0, stream, ll, costs, B, zero_infinity ? 1 : 0, dead, reduced,
                        reduce_scale);
     ED_CHECK_LAUNCH("ctc_costs");
+    return ED_OK;
+}
+
+// The forced aligner: the row pass of the loss, the Viterbi walk, its back-trace.  ctc_label_chain, the beta walk and
+// ctc_costs are not launched; the workspace is the loss's (v where the alphas go).
+extern "C" int edgedict_ctc_align(const void* logits, int dtype, const int32_t* labels, const int32_t* act_lens,
+                                  const int32_t* label_lens, int B, int T, int U, int V, int blank, int32_t* frames,
+                                  int32_t* ends, float* scores, void* workspace, void* stream_) {
+    if (int rc = ctc_check("ctc_align", B, T, U, V, blank, dtype)) return rc;
+    ED_CHECK_ARG(logits && (labels || U == 0) && act_lens && label_lens && (frames || U == 0) && (ends || U == 0) &&
+                     scores && workspace,
+                 "ctc_align: null pointer argument");
+    ED_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "ctc_align: workspace must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const CtcWs w = ctc_ws(B, T, U);
+    char* p = (char*)workspace;
+    float* lse = (float*)(p + w.off_lse);
+    float* lpb = (float*)(p + w.off_lpb);
+    float* lpl = (float*)(p + w.off_lpl);
+    double* v = (double*)(p + w.off_alpha);
+    double* ll = (double*)(p + w.off_ll);
+    ctc_launch_rows(logits, dtype, labels, act_lens, label_lens, B, T, U, V, blank, lse, lpb, lpl, stream);
+    ED_CHECK_LAUNCH("ctc_lse_gather");
+    ctc_launch_walk<true>(lpb, lpl, labels, act_lens, label_lens, B, T, U, v, nullptr, ll, stream);
+    ED_CHECK_LAUNCH("ctc_alpha_beta (viterbi)");
+    hipLaunchKernelGGL(ctc_viterbi_backtrace, dim3(B), dim3(64), 0, stream, v, ll, labels, act_lens, label_lens, T, U,
+                       frames, ends, scores);
+    ED_CHECK_LAUNCH("ctc_viterbi_backtrace");
     return ED_OK;
 }
 

@@ -35,6 +35,9 @@ joint and the loss onto those cells (``BandPlan``; used by ``Transducer.forward`
 (csrc/ctc_decode.hip) searches the same logits with a beam: ranked N-best prefixes with token frames, optionally biased
 towards a phrase list (``bias.ContextGraph``).  ``ctc_blank_skip`` (csrc/frame_skip.hip) marks the frames whose blank
 posterior is at most a threshold and compacts their indices: the front of ``decode.skip_blank_frames``.
+``ctc_align`` (csrc/ctc_loss.hip) is the head's forced aligner - Viterbi over the loss's lattice: per label the first and
+the last frame of the best path, from the encoder alone.  Its ``frames`` are an "outside aligner's" for
+``alignment_windows`` (``Transducer.ctc_windows``): windows for the restricted RNN-T loss that need no trained joint.
 
 ``SoftmaxNLLLoss`` / ``softmax_nll_rows`` (csrc/lm_loss.hip) are the language model's loss and sentence scorer:
 ``log_softmax`` + ``NLLLoss(ignore_index)`` on raw logits ``[M, V]``, the gradient written into the logits in place.
@@ -598,6 +601,64 @@ def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
     _lib.call("ctc_beam_search", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, W, cand, bref,
               tokens, frames, token_lp, ntok, n_hyp, logp, ws)
     return tokens, frames, token_lp, ntok, n_hyp, logp
+
+
+def _ctc_align_call(logits, labels, act_lens, label_lens, blank, ws):
+    B, T, V = logits.shape
+    U = labels.shape[1]
+    frames = torch.empty(B, U, dtype=torch.int32, device=logits.device)
+    ends = torch.empty(B, U, dtype=torch.int32, device=logits.device)
+    scores = torch.empty(B, dtype=torch.float32, device=logits.device)
+    _lib.call("ctc_align", logits.detach(), _lib.dtype_code(logits.dtype), labels if U else None, act_lens, label_lens,
+              B, T, U, V, int(blank), frames if U else None, ends if U else None, scores, ws)
+    return frames, ends, scores
+
+
+@torch.no_grad()
+def ctc_align(logits, labels, act_lens, label_lens, blank=0, *, check_lengths=True):
+    """CTC forced alignment of the transcripts ``labels`` on head logits: the single most probable path of the loss's
+    lattice (Viterbi over the ``2 U + 1`` states, float64 carry on the loss's float32 log-probabilities).  Arguments as
+    ``CTCLoss.forward`` (validated the same way; ``check_lengths=True`` is its one host sync).  Returns device tensors
+    ``(frames, ends, scores)``: ``frames`` / ``ends`` int32 ``[B, U]``, the first and the last frame the path spends in
+    label ``u``'s state (``0 <= frames[u] <= ends[u] < frames[u+1]``, ``ends[U_b-1] <= T_b - 1``; -1 behind
+    ``label_lens[b]``), ``scores`` float32 ``[B]``, the path's log-probability (``<= -cost``).  ``frames`` is what
+    ``alignment_windows`` and ``decode.emission_times`` take; ``frames`` and ``ends`` together are a label's span.
+
+    Unlike the loss's lengths check, a row without a path (``act_lens[b] == 0``, or fewer frames than labels plus
+    adjacent repeats) is not an error: its score is ``-inf`` and its frames and ends are all -1; the other rows are
+    unaffected.  Tie rule (the later emission wins, as ``rnnt_align`` waits): the path ends in the last label's state
+    when that scores at least the final blank's, and among the equally good predecessors of a state it comes from the
+    label two states back (where CTC allows the skip), else from the state before, else it stays."""
+    _certify_ctc_inputs(logits, labels, act_lens, label_lens, check_lengths)
+    _lib.require_cuda(logits, labels, act_lens, label_lens)
+    B, T, _ = logits.shape
+    ws = torch.empty(_lib.load().edgedict_ctc_workspace_bytes(B, T, labels.shape[1]), dtype=torch.uint8,
+                     device=logits.device)
+    return _ctc_align_call(logits, labels, act_lens, label_lens, blank, ws)
+
+
+def ctc_align_debug(logits, labels, act_lens, label_lens, blank=0):
+    """Test hook: run ``ctc_align`` and return (frames, ends, scores, lp_blank [B,T] f32, lp_label [B,T,U] f32,
+    v [B,T,2U+1] f64) - clones; entries outside an utterance's ``[T_b, U_b]`` / ``[T_b, 2 U_b + 1]`` box are zeros."""
+    _lib.require_cuda(logits, labels, act_lens, label_lens)
+    B, T, V = logits.shape
+    U = labels.shape[1]
+    lib = _lib.load()
+    ws = torch.zeros(lib.edgedict_ctc_workspace_bytes(B, T, U), dtype=torch.uint8, device=logits.device)
+    frames, ends, scores = _ctc_align_call(logits, labels, act_lens, label_lens, blank, ws)
+    base = ws.data_ptr()
+
+    def view(which, shape, dtype):
+        p = lib.edgedict_ctc_workspace_view(_lib.ptr(ws), B, T, U, which)
+        esz = 8 if dtype == torch.float64 else 4
+        off = (p - base) // esz
+        n = 1
+        for s in shape:
+            n *= s
+        return ws.view(dtype)[off:off + n].view(*shape).clone()
+
+    return (frames, ends, scores, view(4, (B, T), torch.float32), view(5, (B, T, U), torch.float32),
+            view(1, (B, T, 2 * U + 1), torch.float64))
 
 
 def ctc_loss_debug(logits, labels, act_lens, label_lens, blank=0):

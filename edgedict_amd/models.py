@@ -1142,6 +1142,56 @@ class Transducer(nn.Module):
         tokens, counts = tokens.cpu().numpy(), counts.cpu().numpy()
         return [tokens[b, :counts[b]].astype("int64") for b in range(tokens.shape[0])], neglogp
 
+    def _ctc_align(self, xs, ys, xlen, ylen):
+        """encoder, head, ``loss.ctc_align``: (frames, ends, scores, act_lens, label_lens), the lengths int32 on the
+        device as the aligner read them."""
+        from ._staging import to_device
+        from .loss import ctc_align
+        if getattr(self, "ctc_head", None) is None:
+            raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+        xs = xs[:, :xlen.max()].contiguous()
+        ys = ys[:, :ylen.max()].contiguous()
+        h_enc, _ = self.encoder(xs)
+        dev = h_enc.device
+
+        def lens(t):
+            if t.is_cuda:
+                return t.to(device=dev, dtype=torch.int32).contiguous()
+            return to_device(t.to(torch.int32), dev)
+
+        act, lab = lens(self.scale_length(h_enc, xlen)), lens(ylen)
+        labels = ys.to(device=dev, dtype=torch.int32).contiguous()
+        frames, ends, scores = ctc_align(self._ctc_logits(h_enc).contiguous(), labels, act, lab, self.blank,
+                                         check_lengths=False)
+        return frames, ends, scores, act, lab
+
+    @torch.no_grad()
+    def ctc_align(self, xs, ys, xlen, ylen):
+        """Forced alignment of the transcripts ``ys`` by the CTC head (encoder, head, ``loss.ctc_align`` - neither the
+        prediction network nor the joint runs, no ``T x U x V`` lattice is formed): returns ``(frames, ends, scores)``,
+        ``frames`` / ``ends`` int32 ``[B, U]`` with the first and the last ENCODER frame (after the time reductions, as
+        ``scale_length`` counts them) the best CTC path spends in each label, -1 behind ``ylen[b]``; ``scores`` float32
+        ``[B]``, that path's log-probability.  A row without a CTC path (fewer encoder frames than labels plus adjacent
+        repeats) has score -inf and frames / ends of all -1.  ``decode.emission_times`` turns either into seconds.
+        Arguments as ``forward``; no host sync.  Leaves no state behind: run it in ``eval()`` mode, or dropout takes
+        part.  Raises RuntimeError on a model built without ``ctc_weight > 0``."""
+        return self._ctc_align(xs, ys, xlen, ylen)[:3]
+
+    @torch.no_grad()
+    def ctc_windows(self, xs, ys, xlen, ylen, left, right):
+        """Emission windows from the CTC head alone: ``ctc_align`` followed by ``loss.alignment_windows(frames, act,
+        ylen, left, right)``.  Returns ``(lo, hi)`` int32 ``[B, U]`` on the device, ready for ``forward(...,
+        windows=)``, ``align(..., windows=)`` and ``TrainEngine.train_step(..., windows=)``.  A CTC alignment's frames
+        are strictly increasing and at most ``T_b - 1``, so windows that contain them always admit an RNN-T alignment
+        (which needs them non-decreasing only).  A row without a CTC path (frames of -1) gets ``lo = 0, hi = T - 1`` in
+        every column - the padding rule of ``alignment_windows``, ``T = max(act_lens)`` - so it stays unrestricted
+        rather than dead.  Remarks of ``ctc_align`` (``eval()``, the missing head) apply."""
+        from .loss import alignment_windows
+        frames, _, scores, act, lab = self._ctc_align(xs, ys, xlen, ylen)
+        # a row without a path counts as having no labels: alignment_windows then pads every column of it
+        lab = torch.where(scores == float("-inf"), torch.zeros_like(lab), lab)
+        return alignment_windows(frames, act, lab, left, right)
+
     def ctc_beam_search(self, xs, xlen, W=10, cand=None, bias=None):
         """First-pass N-best from the encoder alone: encoder, CTC head, the CTC prefix beam search
         (``loss.ctc_prefix_beam``), one read to the host.  Returns a list of ``decode.NBestResult``, one per utterance,

@@ -1222,6 +1222,19 @@ int edgedict_softmax_nll_backward(int dtype, void* logits, long long ldx, const 
  * k_t != blank and (t == 0 or k_t != k_{t-1}).  tokens / frames [B, T] int32: the kept symbols and their frame
  * indices, -1 behind counts[b]; neglogp [B] fp32 = -sum over kept frames of log_softmax(logits[b,t])[k_t];
  * scratch: 8 * B * T bytes.
+ *
+ * edgedict_ctc_align: the forced aligner of the head - Viterbi over the loss's lattice, fp64 carry,
+ *   v(t,s) = max(v(t-1,s), v(t-1,s-1), [skip(s)] v(t-1,s-2)) + (double)lp(t,s),  lp the loss's fp32 log-probabilities.
+ *   frames, ends [B, U] int32  out: the first / last frame the best path spends in label u's state; strictly
+ *                              increasing in u, ends[u] < frames[u+1], at most act_lens[b] - 1; -1 behind label_lens[b]
+ *                              (both nullable when U == 0)
+ *   scores       [B] fp32      out: the best path's log-probability (<= -cost)
+ *   A row without a path (act_lens[b] <= 0, or fewer frames than labels + adjacent repeats): score -inf, frames and
+ *   ends all -1; the other rows are unaffected.  TIE RULE: the later emission wins - the path ends in the last label's
+ *   state when that scores >= the final blank, and among the equal best predecessors of a state it comes from s - 2
+ *   (where the skip is allowed), else s - 1, else s.  Three launches (the loss's row pass, the walk, the back-trace),
+ *   no host sync, no atomics, bit-identical from run to run.  The workspace (size and layout of the loss's, 16-byte
+ *   aligned) is scratch: v lies where the alphas go (view 1), the beta plane is not written.
  */
 size_t edgedict_ctc_workspace_bytes(int B, int T, int U);
 const void* edgedict_ctc_workspace_view(const void* workspace, int B, int T, int U, int which);
@@ -1235,6 +1248,9 @@ int edgedict_ctc_loss_backward(const void* logits, int dtype, void* grads, const
 int edgedict_ctc_greedy(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V, int blank,
                         int32_t* tokens, int32_t* counts, int32_t* frames, float* neglogp, void* scratch,
                         void* stream);
+int edgedict_ctc_align(const void* logits, int dtype, const int32_t* labels, const int32_t* act_lens,
+                       const int32_t* label_lens, int B, int T, int U, int V, int blank, int32_t* frames,
+                       int32_t* ends, float* scores, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * CTC prefix beam search on the head's logits (csrc/ctc_decode.hip states the search): per utterance the W best
