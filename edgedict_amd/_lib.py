@@ -58,6 +58,7 @@ def load():
         lib.edgedict_rnnt_workspace_view.restype = ctypes.c_void_p
         lib.edgedict_ctc_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_ctc_workspace_view.restype = ctypes.c_void_p
+        lib.edgedict_ctc_score_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_ctc_beam_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_greedy_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_beam_workspace_bytes.restype = ctypes.c_size_t

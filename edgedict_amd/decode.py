@@ -54,6 +54,15 @@ blank posterior is at most ``threshold`` (``skip_blank_frames``: the head's logi
 to the host, ``gather_frames``; csrc/frame_skip.hip), through the ``_enc`` form on the compacted output, and the N-best
 forms report ``frames`` in the original numbering.  Everything else passes through; ``prefix=True`` raises
 ``ValueError``.  Not for the greedy search, the streaming searches or ``ctc_beam_search``.  None launches nothing new.
+
+``ctc_rescore=weight`` (keyword only, on ``beam_search_nbest``, ``sync_beam_search_nbest`` and their ``_enc`` forms;
+needs ``Transducer(ctc_weight > 0)``): joint CTC / transducer rescoring, the cheap second pass.  The list the search
+returns is scored by the CTC head (``ctc_rescore``: the head's logits, ``loss.ctc_score_nbest`` on all hypotheses of
+the batch at once, one read to the host; csrc/ctc_score.hip), ``logp`` becomes ``logp + weight * ctc_logp`` and the list
+is sorted by it; the CTC score itself is kept in ``NBestResult.ctc_logp``.  With ``skip_blank=`` the head scores the
+UNSKIPPED encoder output.  ``Transducer.rescore_nbest`` does the same to lists obtained elsewhere (``ctc_beam_search``,
+a streaming search's ``nbest()``).  No length normalisation, no LM term, no CTC prefix score inside the frame loop.
+None launches nothing new.
 """
 import ctypes
 
@@ -386,16 +395,22 @@ class NBestResult:
                        the fused increment ``lp_rnnt + (lm_weight lp_lm + length_bonus)``, with a bias list plus the
                        automaton's increment ``D``); ``logp[i]`` minus their sum is what the hypothesis' blanks
                        contributed
-    ``logp``           float64 [n]: log p per hypothesis (fused log p with an LM; plus the total bias with a list)
+    ``logp``           float64 [n]: log p per hypothesis (fused log p with an LM; plus the total bias with a list);
+                       after ``ctc_rescore`` the combined score ``logp + weight * ctc_logp``
+    ``ctc_logp``       None, or float64 [n]: the CTC head's log-likelihood of each hypothesis' tokens (``ctc_rescore``
+                       fills it; -inf: the head has no path for them)
     """
 
-    def __init__(self, tokens, frames, token_logp, logp):
+    def __init__(self, tokens, frames, token_logp, logp, ctc_logp=None):
         self.tokens = list(tokens)
         self.frames = list(frames)
         self.token_logp = list(token_logp)
         self.logp = np.asarray(logp, dtype=np.float64)
+        self.ctc_logp = None if ctc_logp is None else np.asarray(ctc_logp, dtype=np.float64)
         if not (len(self.tokens) == len(self.frames) == len(self.token_logp) == self.logp.shape[0]):
             raise ValueError("NBestResult: fields of different lengths")
+        if self.ctc_logp is not None and self.ctc_logp.shape != self.logp.shape:
+            raise ValueError("NBestResult: ctc_logp must have one value per hypothesis")
 
     def __len__(self):
         return len(self.tokens)
@@ -404,7 +419,9 @@ class NBestResult:
         """A new ``NBestResult`` sorted by ``logp`` descending, stably (ties keep B's order).  ``merge=True`` first folds
         entries with identical token sequences into one with log-add (the legacy search keeps them apart: the same
         sequence can be in B twice, reached with different emission frames); the folded entry keeps the frames and
-        increments of its most probable member (the first one on ties) and stands at that member's place in B."""
+        increments of its most probable member (the first one on ties) and stands at that member's place in B.
+        ``ctc_logp`` is carried along; a folded entry keeps its kept member's value (equal token sequences have equal
+        CTC scores, so the log-add of combined scores is the combined score of the log-add)."""
         idx = list(range(len(self)))
         logp = self.logp.copy()
         if merge:
@@ -421,7 +438,8 @@ class NBestResult:
             idx.sort()
         order = sorted(idx, key=lambda i: -logp[i])          # sorted() is stable
         return NBestResult([self.tokens[i] for i in order], [self.frames[i] for i in order],
-                           [self.token_logp[i] for i in order], logp[order] if order else np.zeros(0))
+                           [self.token_logp[i] for i in order], logp[order] if order else np.zeros(0),
+                           None if self.ctc_logp is None else (self.ctc_logp[order] if order else np.zeros(0)))
 
 
 def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
@@ -442,8 +460,102 @@ def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
     return out
 
 
+CTC_RESCORE_MAX_N = 32
+
+
+def _check_rescore(model, weight):
+    """The argument rules of ``ctc_rescore=`` (raised before anything touches the device): the weight as a float."""
+    try:
+        w = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError("the CTC rescoring weight must be a finite number >= 0, got %r" % (weight,)) from None
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("the CTC rescoring weight must be finite and >= 0, got %r" % (weight,))
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+    return w
+
+
+def combine_ctc(logp, ctc_logp, weight):
+    """The combine-and-sort rule of ``ctc_rescore`` on one list (host, float64): ``(combined, order)`` with
+    ``combined = logp + weight * ctc_logp`` evaluated as exactly that expression - for ``weight == 0`` ``logp`` itself,
+    so no ``0 * inf`` is formed - and ``order`` the stable sort of ``combined``, descending.  A ``ctc_logp`` of -inf
+    with ``weight > 0`` gives -inf, which sorts last."""
+    logp = np.asarray(logp, dtype=np.float64)
+    ctc_logp = np.asarray(ctc_logp, dtype=np.float64)
+    combined = logp + weight * ctc_logp if weight > 0 else logp.copy()
+    return combined, np.argsort(-combined, kind="stable")
+
+
+@torch.no_grad()
+def ctc_score_lists(model, enc_out, lens, lists):
+    """The CTC head's log-likelihood of token sequences: ``lists[b]`` holds the sequences (int arrays without blanks)
+    to score on utterance ``b`` of ``enc_out`` [B, T, P] (compute dtype, device; ``lens`` host ints, encoder frames per
+    utterance, or None for all T).  The head's logits (``model._ctc_logits``), ONE int32 upload holding all tokens as
+    ``[B, N, U]`` (``N`` the longest list, at most 32; ``U`` the longest sequence) with the lengths behind them, ONE
+    ``loss.ctc_score_nbest`` call and ONE read to the host.  Returns a list of float64 arrays, one value per sequence
+    (-inf: no CTC path).  Raises ``RuntimeError`` on a model built without ``ctc_weight > 0``."""
+    from .loss import ctc_score_nbest
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+    _lib.require_cuda(enc_out)
+    enc_out = enc_out.contiguous()
+    B, T, _ = enc_out.shape
+    lists = [[np.asarray(t, dtype=np.int64).reshape(-1) for t in seqs] for seqs in lists]
+    if len(lists) != B:
+        raise ValueError("ctc_score_lists: %d lists for a batch of %d utterances" % (len(lists), B))
+    lens = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > T).any():
+        raise ValueError("ctc_score_lists: lens must be [B] ints in [0, %d]" % T)
+    N = max([len(seqs) for seqs in lists], default=0)
+    U = max([t.size for seqs in lists for t in seqs], default=0)
+    if N > CTC_RESCORE_MAX_N:
+        raise ValueError("ctc_score_lists: a list of %d hypotheses exceeds the supported maximum of %d"
+                         % (N, CTC_RESCORE_MAX_N))
+    if N == 0 or T < 1:             # nothing to score / no frame: no sequence has a path
+        return [np.full(len(seqs), -np.inf) for seqs in lists]
+    # one upload: hyps [B, N, U], hyp_lens [B, N], n_hyp [B], act_lens [B], back to back
+    nh, nl = B * N * U, B * N
+    host = np.zeros(nh + nl + 2 * B, dtype=np.int32)
+    hyps, hyp_lens = host[:nh].reshape(B, N, U), host[nh:nh + nl].reshape(B, N)
+    for b, seqs in enumerate(lists):
+        host[nh + nl + b] = len(seqs)
+        for n, t in enumerate(seqs):
+            hyps[b, n, :t.size] = t
+            hyp_lens[b, n] = t.size
+    host[nh + nl + B:] = lens
+    dev = torch.from_numpy(host).to(enc_out.device)
+    scores = ctc_score_nbest(model._ctc_logits(enc_out).contiguous(), dev[nh + nl + B:], dev[:nh].view(B, N, U),
+                             dev[nh:nh + nl].view(B, N), dev[nh + nl:nh + nl + B], model.blank).cpu().numpy()
+    return [scores[b, :len(seqs)].copy() for b, seqs in enumerate(lists)]
+
+
+def ctc_rescore(model, enc_out, lens, results, weight):
+    """Rescore N-best lists with the model's CTC head: ``results`` (one ``NBestResult`` per utterance of ``enc_out``
+    [B, T, P], compute dtype, device; ``lens`` host ints, encoder frames per utterance, or None for all T) from any
+    search over this encoder output.  All hypotheses of the batch are scored by ``ctc_score_lists``: one upload, one
+    ``loss.ctc_score_nbest`` call, one read to the host.
+
+    Returns new ``NBestResult`` objects: ``ctc_logp`` is the head's log-likelihood of each hypothesis' tokens, ``logp``
+    the combined score ``logp + weight * ctc_logp`` (float64 on the host, exactly that expression), the entries sorted
+    by it descending, stably, with ``tokens``, ``frames`` and ``token_logp`` permuted along.  ``weight`` must be finite
+    and ``>= 0`` (``ValueError``); for ``weight == 0`` the combined score is ``logp`` itself and the order its stable
+    sort.  A hypothesis without a CTC path (``ctc_logp`` -inf) gets -inf for ``weight > 0`` and sorts last.  An empty
+    list stays empty.  Equal token sequences are NOT merged here: chain ``.ranked(merge=True)``.  No length
+    normalisation, no LM term.  Raises ``RuntimeError`` on a model built without ``ctc_weight > 0``."""
+    w = _check_rescore(model, weight)
+    results = list(results)
+    scores = ctc_score_lists(model, enc_out, lens, [r.tokens for r in results])
+    out = []
+    for r, ctc in zip(results, scores):
+        combined, order = combine_ctc(r.logp, ctc, w)
+        out.append(NBestResult([r.tokens[i] for i in order], [r.frames[i] for i in order],
+                               [r.token_logp[i] for i in order], combined[order], ctc[order]))
+    return out
+
+
 def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                      lm_bos=1, bias=None, skip_blank=None):
+                      lm_bos=1, bias=None, skip_blank=None, ctc_rescore=None):
     """``beam_search_batch`` (``prefix=False``) returning, per utterance, an ``NBestResult``: all ``n <= W`` hypotheses
     of the last frame's list B in B's order, each with its tokens, the encoder frame every token was emitted on and the
     score increment every token added, and ``logp`` (log p, not negated).  Entry 0 is exactly what ``beam_search_batch``
@@ -451,13 +563,17 @@ def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=Non
     An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.  The prefix-sum variant is not available
     here: its merge changes a score at frame starts, so the increments would no longer add up.  With ``bias`` (module
     docstring) ``token_logp`` and ``logp`` include the bias increments.  ``skip_blank``: as in ``beam_search_batch``;
-    ``frames`` stay in the original frame numbering."""
+    ``frames`` stay in the original frame numbering.  ``ctc_rescore``: a weight ``>= 0`` - the list then goes through
+    ``ctc_rescore`` (the module-level function; on the unskipped encoder output) before it is returned: ``ctc_logp``
+    filled, ``logp`` the combined score, sorted by it.  None: nothing of this runs."""
     from .bias import check_bias_args
     from .lm import check_fusion_args
     check_fusion_args(lm, lm_weight, _vocab(model), False)
     check_bias_args(bias, _vocab(model), False)
     if skip_blank is not None:
         _check_skip(model, skip_blank)
+    if ctc_rescore is not None:
+        _check_rescore(model, ctc_rescore)
     _lib.require_cuda(xs)
     if W < 1:
         raise ValueError("beam width must be >= 1")
@@ -472,24 +588,34 @@ def beam_search_nbest(model, xs, xlen=None, W=10, max_expansions=None, *, lm=Non
         sk = skip_blank_frames(model, enc_out, lens, skip_blank)
         if sk.enc_out.shape[1] == 0:        # every frame dropped: the empty hypothesis, nothing to launch
             beam_search_batch.last_expansions = 0
-            return _empty_nbest(enc_out.shape[0])
-        return sk.restore(beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, max_expansions, lm=lm,
-                                                lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos,
-                                                bias=bias))
+            return _rescored(model, enc_out, lens, _empty_nbest(enc_out.shape[0]), ctc_rescore)
+        return _rescored(model, enc_out, lens,
+                         sk.restore(beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, max_expansions, lm=lm,
+                                                          lm_weight=lm_weight, length_bonus=length_bonus,
+                                                          lm_bos=lm_bos, bias=bias)), ctc_rescore)
     return beam_search_nbest_enc(model, enc_out, lens, W, max_expansions, lm=lm, lm_weight=lm_weight,
-                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
+                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, ctc_rescore=ctc_rescore)
+
+
+def _rescored(model, enc_out, lens, results, weight):
+    """``results`` as they are for ``weight`` None, else through ``ctc_rescore`` on ``enc_out``."""
+    return results if weight is None else ctc_rescore(model, enc_out, lens, results, weight)
 
 
 def beam_search_nbest_enc(model, enc_out, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
-                          length_bonus=0.0, lm_bos=1, prefix=False, bias=None):
+                          length_bonus=0.0, lm_bos=1, prefix=False, bias=None, ctc_rescore=None):
     """``beam_search_nbest`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
-    encoder frames per utterance; None: all T)."""
+    encoder frames per utterance; None: all T).  ``ctc_rescore``: as there, the head scoring this ``enc_out``."""
     from .bias import check_bias_args
     check_bias_args(bias, _vocab(model), prefix)
+    if ctc_rescore is not None:
+        _check_rescore(model, ctc_rescore)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
-    return beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, lm=lm,
-                                  lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, prefix=prefix, bias=bias)
+    return _rescored(model, enc_out, lens,
+                     beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, max_expansions, lm=lm,
+                                            lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos,
+                                            prefix=prefix, bias=bias), ctc_rescore)
 
 
 def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, *, lm=None, lm_weight=None,
@@ -622,8 +748,8 @@ def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=No
                                            lm_bos=lm_bos, bias=bias, skip_blank=skip_blank))
 
 
-def sync_beam_search_nbest(model, xs, xlen=None, W=10,
-                           *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, skip_blank=None):
+def sync_beam_search_nbest(model, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
+                           bias=None, skip_blank=None, ctc_rescore=None):
     """``sync_beam_search`` returning, per utterance, the final beam as an ``NBestResult`` **already ranked**: ``logp``
     descending (ties keep beam order), at most W hypotheses with distinct token sequences, entry 0 what
     ``sync_beam_search`` returns.  ``frames[i]``: the encoder frame on which each token's tree node was created
@@ -631,17 +757,23 @@ def sync_beam_search_nbest(model, xs, xlen=None, W=10,
     ``logp``, which sums over alignments (as in ``ctc_beam_search``), and with an LM or a bias list still the RNN-T
     value alone while ``logp`` is the fused score.  An utterance of 0 frames yields one empty hypothesis with ``logp`` 0.
     ``skip_blank``: as in ``sync_beam_search_fusion``; ``frames`` stay in the original frame numbering, and an utterance
-    whose frames are all dropped is an utterance of 0 frames."""
+    whose frames are all dropped is an utterance of 0 frames.  ``ctc_rescore``: a weight ``>= 0`` - the ranked list
+    then goes through ``ctc_rescore`` (the module-level function; on the unskipped encoder output) before it is
+    returned: ``ctc_logp`` filled, ``logp`` the combined score, ranked by it.  None: nothing of this runs."""
     _check_sync_fusion(model, lm, lm_weight, bias)
     if skip_blank is not None:
         _check_skip(model, skip_blank)
+    if ctc_rescore is not None:
+        _check_rescore(model, ctc_rescore)
     enc_out, lens = _sync_encode(model, xs, xlen, W)
     if skip_blank is not None:
         sk = skip_blank_frames(model, enc_out, lens, skip_blank)
-        return sk.restore(sync_beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, lm=lm, lm_weight=lm_weight,
-                                                     length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
-    return sync_beam_search_nbest_enc(model, enc_out, lens, W,
-                                      lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
+        return _rescored(model, enc_out, lens,
+                         sk.restore(sync_beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, lm=lm,
+                                                               lm_weight=lm_weight, length_bonus=length_bonus,
+                                                               lm_bos=lm_bos, bias=bias)), ctc_rescore)
+    return sync_beam_search_nbest_enc(model, enc_out, lens, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                      lm_bos=lm_bos, bias=bias, ctc_rescore=ctc_rescore)
 
 
 def sync_beam_search_enc(model, enc_out, lens=None, W=10,
@@ -653,15 +785,20 @@ def sync_beam_search_enc(model, enc_out, lens=None, W=10,
 
 
 def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10,
-                               *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
-    """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``."""
+                               *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, ctc_rescore=None):
+    """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``.  ``ctc_rescore``: as there,
+    the head scoring this ``enc_out``."""
     _check_sync_fusion(model, lm, lm_weight, bias)
     _check_sync_width(W)
+    if ctc_rescore is not None:
+        _check_rescore(model, ctc_rescore)
     _lib.require_cuda(enc_out)
     enc_out = enc_out.contiguous()
     B, T, P = enc_out.shape
-    return sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W,
-                                                         lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
+    return _rescored(model, enc_out, lens,
+                     sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, lm=lm,
+                                                 lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos,
+                                                 bias=bias), ctc_rescore)
 
 
 def sync_beam_search_rows(model, E1, B, T, P, lens=None, W=10,

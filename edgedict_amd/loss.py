@@ -38,6 +38,9 @@ posterior is at most a threshold and compacts their indices: the front of ``deco
 ``ctc_align`` (csrc/ctc_loss.hip) is the head's forced aligner - Viterbi over the loss's lattice: per label the first and
 the last frame of the best path, from the encoder alone.  Its ``frames`` are an "outside aligner's" for
 ``alignment_windows`` (``Transducer.ctc_windows``): windows for the restricted RNN-T loss that need no trained joint.
+``ctc_score_nbest`` (csrc/ctc_score.hip) scores N-best lists with the head: the CTC log-likelihood of up to 32
+hypotheses per utterance, one log-sum-exp per frame shared by all of them, no lattice plane stored - the device side of
+``decode.ctc_rescore``.
 
 ``SoftmaxNLLLoss`` / ``softmax_nll_rows`` (csrc/lm_loss.hip) are the language model's loss and sentence scorer:
 ``log_softmax`` + ``NLLLoss(ignore_index)`` on raw logits ``[M, V]``, the gradient written into the logits in place.
@@ -659,6 +662,77 @@ def ctc_align_debug(logits, labels, act_lens, label_lens, blank=0):
 
     return (frames, ends, scores, view(4, (B, T), torch.float32), view(5, (B, T, U), torch.float32),
             view(1, (B, T, 2 * U + 1), torch.float64))
+
+
+CTC_SCORE_MAX_N = 32
+CTC_SCORE_MAX_U = 1023
+
+
+def _certify_ctc_score_inputs(logits, act_lens, hyps, hyp_lens, n_hyp, blank):
+    # error classes / wording of _certify_ctc_inputs
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+    named = (("act_lens", act_lens), ("hyps", hyps), ("hyp_lens", hyp_lens), ("n_hyp", n_hyp))
+    for name, t in named:
+        if t is not None and t.dtype != torch.int32:
+            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
+    for name, t in (("logits", logits),) + named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if logits.dim() != 3:
+        raise ValueError("logits must have 3 dimensions [B,T,V], got %d" % logits.dim())
+    if hyps.dim() != 3:
+        raise ValueError("hyps must have 3 dimensions [B,N,U], got %d" % hyps.dim())
+    if hyp_lens.dim() != 2:
+        raise ValueError("hyp_lens must have 2 dimensions [B,N], got %d" % hyp_lens.dim())
+    if act_lens.dim() != 1 or (n_hyp is not None and n_hyp.dim() != 1):
+        raise ValueError("act_lens and n_hyp must have 1 dimension")
+    B, T, V = logits.shape
+    N, U = hyps.shape[1], hyps.shape[2]
+    if act_lens.shape[0] != B:
+        raise ValueError("must have a length per example (act_lens has %d, batch is %d)" % (act_lens.shape[0], B))
+    if hyps.shape[0] != B or tuple(hyp_lens.shape) != (B, N):
+        raise ValueError("must have a hypothesis length per slot (hyps is %s, hyp_lens %s, batch is %d)"
+                         % (tuple(hyps.shape), tuple(hyp_lens.shape), B))
+    if n_hyp is not None and n_hyp.shape[0] != B:
+        raise ValueError("must have a hypothesis count per example (n_hyp has %d, batch is %d)" % (n_hyp.shape[0], B))
+    if B < 1 or T < 1:
+        raise ValueError("logits must hold at least one utterance and one frame (B = %d, T = %d)" % (B, T))
+    if V < 2:
+        raise ValueError("V = %d: need at least the blank and one symbol" % V)
+    if not 0 <= blank < V:
+        raise ValueError("blank %d outside [0, %d)" % (blank, V))
+    if not 1 <= N <= CTC_SCORE_MAX_N:
+        raise ValueError("N = %d hypotheses per utterance outside [1, %d]" % (N, CTC_SCORE_MAX_N))
+    if U > CTC_SCORE_MAX_U:
+        raise ValueError("U = %d exceeds the supported maximum of %d tokens per hypothesis" % (U, CTC_SCORE_MAX_U))
+
+
+@torch.no_grad()
+def ctc_score_nbest(logits, act_lens, hyps, hyp_lens, n_hyp=None, blank=0):
+    """CTC log-likelihoods of N-best lists on head logits (csrc/ctc_score.hip): ``logits`` float32 / bfloat16
+    ``[B, T, V]`` raw and contiguous, ``act_lens`` int32 ``[B]``, ``hyps`` int32 ``[B, N, U]`` (token sequences without
+    blanks, ``1 <= N <= 32``, ``U <= 1023``; ``U = 0``: every hypothesis is empty), ``hyp_lens`` int32 ``[B, N]``,
+    ``n_hyp`` int32 ``[B]`` (live slots per utterance; None: all ``N``).  Device tensors only.  Returns a float64
+    ``[B, N]`` device tensor: ``scores[b, n]`` is the log of the total probability of all CTC paths of
+    ``hyps[b, n, :hyp_lens[b, n]]`` over the frames ``t < act_lens[b]`` - minus what ``CTCLoss(reduction='none')`` costs
+    that transcript, in the loss's arithmetic (float32 log-sum-exp per frame, float64 carry).  ``-inf``: a hypothesis
+    without a path (``act_lens[b] == 0``, fewer frames than tokens plus adjacent repeats, a token outside ``[0, V)``)
+    and every slot ``n >= n_hyp[b]``.  Tokens behind ``hyp_lens`` and slots behind ``n_hyp`` are never read.
+
+    The frame's log-sum-exp is computed once per utterance, not once per hypothesis, and nothing is stored per lattice
+    state: the workspace is two float32 ``[B, T]`` arrays.  No gradient, no host sync."""
+    blank = int(blank)
+    _certify_ctc_score_inputs(logits, act_lens, hyps, hyp_lens, n_hyp, blank)
+    _lib.require_cuda(logits, act_lens, hyps, hyp_lens, n_hyp)
+    B, T, V = logits.shape
+    N, U = hyps.shape[1], hyps.shape[2]
+    dev = logits.device
+    scores = torch.empty(B, N, dtype=torch.float64, device=dev)
+    ws = torch.empty(_lib.load().edgedict_ctc_score_workspace_bytes(B, T, N, U), dtype=torch.uint8, device=dev)
+    _lib.call("ctc_score_nbest", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, hyps if U else None,
+              hyp_lens, n_hyp, B, T, N, U, V, blank, scores, ws)
+    return scores
 
 
 def ctc_loss_debug(logits, labels, act_lens, label_lens, blank=0):

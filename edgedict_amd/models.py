@@ -1200,6 +1200,44 @@ class Transducer(nn.Module):
         from .decode import ctc_beam_search
         return ctc_beam_search(self, xs, xlen, W, cand, bias)
 
+    def _ctc_encode(self, xs, xlen):
+        """The encoder as the N-best searches run it: (enc_out contiguous, host int32 frame counts or None)."""
+        if getattr(self, "ctc_head", None) is None:
+            raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+        from . import _lib
+        _lib.require_cuda(xs)
+        enc_out, _ = self.encoder(xs)
+        enc_out = enc_out.contiguous()
+        if xlen is None:
+            return enc_out, None
+        xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
+        return enc_out, self.scale_length(enc_out, xl).numpy().astype("int32")
+
+    @torch.no_grad()
+    def ctc_score(self, xs, xlen, hyps):
+        """The CTC head's log-likelihood of given token sequences: ``hyps[b]`` is a list of sequences (ints, no blanks;
+        at most 32 per utterance) to score on utterance ``b``.  Encoder, head, ``loss.ctc_score_nbest`` on all of them
+        at once, one read to the host - neither the prediction network nor the joint runs.  Returns a list of float64
+        numpy arrays, one value per sequence: minus the CTC cost of that transcript over the utterance's encoder
+        frames, -inf where the head has no path for it (fewer frames than tokens plus adjacent repeats).  ``xlen`` as
+        the beam searches take it (None: all frames).  Raises RuntimeError on a model built without
+        ``ctc_weight > 0``."""
+        from .decode import ctc_score_lists
+        enc_out, lens = self._ctc_encode(xs, xlen)
+        return ctc_score_lists(self, enc_out, lens, hyps)
+
+    @torch.no_grad()
+    def rescore_nbest(self, xs, xlen, results, weight):
+        """Joint CTC / transducer rescoring of N-best lists obtained elsewhere (``ctc_beam_search``, a streaming
+        search's ``nbest()``, a list read from disk): the encoder, then ``decode.ctc_rescore`` - ``ctc_logp`` filled,
+        ``logp`` replaced by ``logp + weight * ctc_logp``, every list sorted by it.  What ``beam_search_nbest(...,
+        ctc_rescore=weight)`` does to its own lists.  ``weight`` finite and ``>= 0``, else ``ValueError``.  Raises
+        RuntimeError on a model built without ``ctc_weight > 0``."""
+        from .decode import _check_rescore, ctc_rescore
+        _check_rescore(self, weight)
+        enc_out, lens = self._ctc_encode(xs, xlen)
+        return ctc_rescore(self, enc_out, lens, results, weight)
+
     def forward(self, xs, ys, xlen, ylen, *, windows=None):
         """The reference's forward (rnnt/models.py:209-241).  ``windows=(lo, hi)`` (keyword only): the
         alignment-restricted loss of ``loss.RNNTLoss`` on either loss path, in ENCODER frames as ``align`` counts them;
@@ -1381,14 +1419,17 @@ class Transducer(nn.Module):
                                  length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, skip_blank=skip_blank)
 
     def beam_search_nbest(self, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                          lm_bos=1, bias=None, skip_blank=None):
+                          lm_bos=1, bias=None, skip_blank=None, ctc_rescore=None):
         """``beam_search`` (``prefix=False``) returning per utterance a ``decode.NBestResult``: the whole list B of the
         last frame in B's order, every hypothesis with its tokens, the encoder frame each token was emitted on, each
         token's score increment, and its log p; entry 0 is what ``beam_search`` returns.  ``skip_blank``: as in
-        ``beam_search``, the frames reported in the original numbering.  See ``decode.beam_search_nbest``."""
+        ``beam_search``, the frames reported in the original numbering.  ``ctc_rescore`` (a weight ``>= 0``; needs the
+        CTC head): the list is rescored by the head - ``ctc_logp`` filled, ``logp = logp + weight * ctc_logp``, sorted
+        by it (``decode.ctc_rescore``).  See ``decode.beam_search_nbest``."""
         from .decode import beam_search_nbest
         return beam_search_nbest(self, xs, xlen, W, max_expansions, lm=lm, lm_weight=lm_weight,
-                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, skip_blank=skip_blank)
+                                 length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, skip_blank=skip_blank,
+                                 ctc_rescore=ctc_rescore)
 
     @torch.no_grad()
     def sync_beam_search(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None,
@@ -1404,12 +1445,14 @@ class Transducer(nn.Module):
 
     @torch.no_grad()
     def sync_beam_search_nbest(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
-                               bias=None, skip_blank=None):
+                               bias=None, skip_blank=None, ctc_rescore=None):
         """``sync_beam_search`` returning per utterance the final beam as a ranked ``decode.NBestResult``; entry 0 is
-        what ``sync_beam_search`` returns.  See ``decode.sync_beam_search_nbest``."""
+        what ``sync_beam_search`` returns.  ``ctc_rescore`` (a weight ``>= 0``; needs the CTC head): the list is
+        rescored by the head and ranked by ``logp + weight * ctc_logp`` (``decode.ctc_rescore``).  See
+        ``decode.sync_beam_search_nbest``."""
         from .decode import sync_beam_search_nbest
         return sync_beam_search_nbest(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                      lm_bos=lm_bos, bias=bias, skip_blank=skip_blank)
+                                      lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ctc_rescore=ctc_rescore)
 
 
 class _CausalConvFn(torch.autograd.Function):

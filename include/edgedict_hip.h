@@ -1253,6 +1253,29 @@ int edgedict_ctc_align(const void* logits, int dtype, const int32_t* labels, con
                        int32_t* ends, float* scores, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * CTC scores of N-best lists (csrc/ctc_score.hip): the CTC log-likelihood of up to 32 hypotheses per utterance on the
+ * head's logits - what rescoring the transducer's N-best lists with the head needs, without the loss's planes.
+ *   logits   [B, T, V]  dtype     raw head logits, contiguous
+ *   act_lens [B]        int32     frames per utterance (clamped to [0, T])
+ *   hyps     [B, N, U]  int32     token sequences without blanks (nullable when U == 0); entries behind hyp_lens[b, n]
+ *                                 and the slots n >= n_hyp[b] are never read
+ *   hyp_lens [B, N]     int32     tokens per hypothesis (clamped to [0, U])
+ *   n_hyp    [B]        int32     live slots per utterance (clamped to [0, N]); null: all N are live
+ *   scores   [B, N]     fp64 out  ll of hyps[b, n, :hyp_lens[b, n]] over the frames t < act_lens[b], as the loss defines
+ *                                 it (-cost); -inf for a hypothesis without a path (act_lens[b] <= 0, fewer frames than
+ *                                 tokens + adjacent repeats, a token outside [0, V)) and for the slots n >= n_hyp[b]
+ * Two launches: a row pass (log-sum-exp and lp[blank] per frame, once per utterance) and ONE wave per (b, n) that walks
+ * the alpha recursion with the loss's arithmetic (fp64 carry) reading the labels' logits directly; nothing is stored
+ * per lattice state.  No host sync, no atomics, bit-identical from run to run.  1 <= N <= 32, U <= 1023 (U == 0: every
+ * hypothesis is empty and scores the sum of lp[blank]), V >= 2.  The workspace (16-byte aligned, scratch) holds two
+ * [B, T] fp32 arrays: edgedict_ctc_score_workspace_bytes depends on B and T only (0 for arguments out of range).
+ */
+size_t edgedict_ctc_score_workspace_bytes(int B, int T, int N, int U);
+int edgedict_ctc_score_nbest(const void* logits, int dtype, const int32_t* act_lens, const int32_t* hyps,
+                             const int32_t* hyp_lens, const int32_t* n_hyp, int B, int T, int N, int U, int V,
+                             int blank, double* scores, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CTC prefix beam search on the head's logits (csrc/ctc_decode.hip states the search): per utterance the W best
  * prefixes after the last frame, ranked, with the frame each token's node was created on.  No prediction network and
  * no joint: a row pass over [B, T, V] (log-sum-exp, lp[blank], the sorted top-cand list per frame), one launch that
