@@ -15,6 +15,8 @@ rnnt/models.py:150-157 Decoder.forward                        ``Decoder.forward`
 rnnt/models.py:169-179 Joint.forward                          ``_JointFn``
 rnnt/models.py:223-241 Transducer.scale_length / forward      ``Transducer``
 rnnt/models.py:243-269 Transducer.greedy_decode               ``Transducer.greedy_decode``
+cli/train.py:294-319   Trainer.evaluate_step (behind the      ``Transducer.evaluate_step``
+                       front-end)
 =====================  =====================================  ==============================
 
 PyTorch is the container/plumbing layer only: ``nn.Parameter`` holds the fp32 master weights,
@@ -1453,6 +1455,52 @@ class Transducer(nn.Module):
         from .decode import sync_beam_search_nbest
         return sync_beam_search_nbest(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
                                       lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ctc_rescore=ctc_rescore)
+
+    EVALUATE_SEARCHES = ("greedy", "ctc_greedy", "beam", "sync_beam")
+    last_error_rate = None       # the metrics.ErrorRateResult of the last evaluate_step
+
+    @torch.no_grad()
+    def evaluate_step(self, xs, ys, xlen, ylen, *, search="greedy", tokenizer=None, **search_kwargs):
+        """One validation batch, as the reference's ``evaluate_step`` runs it behind its front-end (cli/train.py:
+        294-319): the loss (``forward``), a decode, and the batch's error rate - under ``torch.no_grad()`` in the
+        model's CURRENT mode (call ``eval()`` first, or dropout takes part; ``TrainEngine.evaluate_step`` does).
+        ``search``: ``"greedy"`` (``greedy_decode``, the reference's choice, blanks removed), ``"ctc_greedy"``
+        (``ctc_greedy_decode``), ``"beam"`` (``beam_search``) or ``"sync_beam"`` (``sync_beam_search``, its top
+        hypothesis); ``search_kwargs`` go to the two beam searches (``W=``, ``lm=``, ``skip_blank=``, ...).  ``ys`` is cut
+        at ``ylen`` row by row.  Returns the reference's tuple ``(loss_float, rate, pred, true)``: without a tokenizer
+        ``rate`` is the batch's token error rate and ``pred`` / ``true`` are lists of int64 token arrays; with a
+        tokenizer (anything with the reference's ``decode_plus``) ``rate`` is the batch's word error rate
+        (``metrics.word_error_rate``: summed errors over summed reference words) and ``pred`` / ``true`` are the
+        strings ``decode_plus`` returns.  The full ``metrics.ErrorRateResult`` of the call stays in
+        ``self.last_error_rate``.  Needs ``output_loss=True``."""
+        import numpy as np
+        from . import metrics
+        if search not in self.EVALUATE_SEARCHES:
+            raise ValueError("search must be one of %s, got %r" % (", ".join(self.EVALUATE_SEARCHES), search))
+        if search_kwargs and search in ("greedy", "ctc_greedy"):
+            raise ValueError("search=%r takes no search arguments (got %s)" % (search, ", ".join(sorted(search_kwargs))))
+        if not self.output_loss:
+            raise ValueError("evaluate_step needs output_loss=True")
+        loss = float(self.forward(xs, ys, xlen, ylen))
+        if search == "greedy":
+            seqs, _ = self.greedy_decode(xs, xlen)
+            pred = [s[s != self.blank] for s in seqs]
+        elif search == "ctc_greedy":
+            pred, _ = self.ctc_greedy_decode(xs, xlen)
+        elif search == "beam":
+            pred, _ = self.beam_search(xs, xlen, **search_kwargs)
+        else:
+            pred, _ = self.sync_beam_search(xs, xlen, **search_kwargs)
+        pred = [np.asarray(s, dtype=np.int64) for s in pred]
+        ys_h, ylen_h = ys.detach().cpu().numpy(), ylen.detach().cpu().numpy()
+        true = [ys_h[b, :int(ylen_h[b])].astype(np.int64) for b in range(ys_h.shape[0])]
+        if tokenizer is None:
+            record = metrics.token_error_rate(pred, true, xs.device)
+        else:
+            pred, true = tokenizer.decode_plus(pred), tokenizer.decode_plus(true)
+            record = metrics.word_error_rate(pred, true, xs.device)
+        self.last_error_rate = record
+        return loss, record.rate, pred, true
 
 
 class _CausalConvFn(torch.autograd.Function):

@@ -9,6 +9,9 @@ MI355X-motivated: the log-mel front-end runs on the GPU inside the step (the ref
 it in DataLoader workers on the CPU), gradients live in one flat buffer, data parallelism is one
 process per GPU with bucketed RCCL all-reduce overlapped with the backward pass, and Adam is a
 single kernel.
+
+``evaluate`` / ``evaluate_step`` are the reference's validation loop (cli/train.py:273-319) on the same
+front-end, with the error rate from ``edgedict_amd.metrics`` in place of the third-party ``jiwer``.
 """
 import torch
 import torch.distributed as dist
@@ -187,6 +190,53 @@ class TrainEngine:
         """Call with the validation loss after each evaluation (cli/train.py:182-184,206-208)."""
         if self.sched is not None:
             self.sched.step(val_loss)
+
+    last_eval = None             # the corpus-level metrics.ErrorRateResult of the last evaluate()
+
+    def evaluate_step(self, wave, wave_len, ys, ylen, **kw):
+        """One validation batch from waveforms: the engine's front-end WITHOUT SpecAugment and without dither (the
+        caller's waveform is not modified and the training run's dither sequence does not advance: evaluation is
+        deterministic), then ``Transducer.evaluate_step(xs, ys, xlen, ylen, **kw)`` in ``eval()`` mode - the model's
+        mode is put back afterwards.  Returns its tuple ``(loss_float, rate, pred, true)`` (the reference's
+        ``evaluate_step``, cli/train.py:294-319).  The prefetched next batch, ``step_count``, the optimiser and the
+        gradients are left untouched: a ``train_step`` after it computes what it would have computed without it."""
+        fbank = self.features.fbank
+        dither, fbank.dither = fbank.dither, 0.0
+        try:
+            xs, xlen = self.features(wave, wave_len)
+        finally:
+            fbank.dither = dither
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return self.model.evaluate_step(xs, ys, xlen, ylen, **kw)
+        finally:
+            self.model.train(was_training)
+
+    def evaluate(self, batches, sample_size=None, **kw):
+        """The reference's validation loop (cli/train.py:273-292) over ``batches``, an iterable of ``(wave, wave_len,
+        ys, ylen)``: ``evaluate_step`` on each.  Returns ``(loss, rate, pred_seqs, true_seqs)`` with ``loss`` the MEAN
+        OF THE BATCH LOSSES and ``rate`` the MEAN OF THE BATCH RATES - exactly the reference's averaging (``np.mean``
+        of its per-batch lists; ``nan`` without a batch) - and the first ``sample_size`` predictions / references (None:
+        all of them).  The mean of batch rates weighs every batch alike, so it differs from the corpus-level rate -
+        summed errors over summed reference length - whenever batches hold different amounts of reference text; that
+        figure, as a ``metrics.ErrorRateResult`` over all batches, stays in ``self.last_eval``.  Pass the returned loss
+        to ``validation_end``."""
+        import numpy as np
+        from .metrics import _record
+        losses, rates, pred_seqs, true_seqs = [], [], [], []
+        totals = [0] * 7
+        for wave, wave_len, ys, ylen in batches:
+            loss, rate, pred, true = self.evaluate_step(wave, wave_len, ys, ylen, **kw)
+            losses.append(loss)
+            rates.append(rate)
+            room = None if sample_size is None else max(0, sample_size - len(pred_seqs))
+            pred_seqs.extend(pred[:room])
+            true_seqs.extend(true[:room])
+            totals = [a + b for a, b in zip(totals, self.model.last_error_rate[5:])]
+        self.last_eval = _record(*totals)
+        nan = float("nan")
+        return (float(np.mean(losses)) if losses else nan, float(np.mean(rates)) if rates else nan, pred_seqs, true_seqs)
 
     def train_step(self, wave, wave_len, ys, ylen, next_batch=None, *, windows=None):
         """wave f32[B,N] (device), wave_len i32[B] samples (or None), ys i32[B,U], ylen i32[B].

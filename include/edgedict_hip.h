@@ -1276,6 +1276,29 @@ int edgedict_ctc_score_nbest(const void* logits, int dtype, const int32_t* act_l
                              int blank, double* scores, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Batched edit distance (csrc/edit_distance.hip): the error counts of up to 32 hypotheses per utterance against the
+ * utterance's reference - the integers every error rate is made of (the reference's validation loop, cli/train.py:
+ * 273-319, takes its WER from a third-party package; edgedict_amd/metrics.py builds the rates on this).
+ *   hyps     [B, N, Uh] int32     hypothesis tokens (nullable when Uh == 0); entries behind hyp_lens[b, n] and the slots
+ *                                 n >= n_hyp[b] are never read.  Plain pairs: N = 1
+ *   hyp_lens [B, N]     int32     tokens per hypothesis (clamped to [0, Uh])
+ *   n_hyp    [B]        int32     live slots per utterance (clamped to [0, N]); null: all N are live
+ *   refs     [B, Ur]    int32     reference tokens (nullable when Ur == 0); entries behind ref_lens[b] are never read
+ *   ref_lens [B]        int32     tokens per reference (clamped to [0, Ur])
+ *   out      [B, N, 4]  int32 out (dist, sub, del, ins); -1 in all four for the slots n >= n_hyp[b]
+ * Symbols are compared with == only: every int32 value is a symbol.  d(i, j), the cheapest way to turn ref[:j] into
+ * hyp[:i], has the integer edge costs hit 0, substitution K, deletion (a reference element without a hypothesis
+ * element) K, insertion (a hypothesis element without a reference element) K + 1, K = 4096, d(0, j) = j K, d(i, 0) =
+ * i (K + 1).  v = d(H, R): dist = v / K is the Levenshtein distance, ins = v % K the insertions of the minimum-distance
+ * alignment with the FEWEST insertions (hence the fewest deletions and the most substitutions), del = ins - (H - R),
+ * sub = dist - ins - del; hits = R - sub - del.
+ * One launch, one wave64 per (b, n); no workspace, no host sync, no atomics, bit-identical from run to run.
+ * B >= 1, 1 <= N <= 32, 0 <= Uh, Ur <= 1023; arguments are validated before anything is launched.
+ */
+int edgedict_edit_distance(const int32_t* hyps, const int32_t* hyp_lens, const int32_t* n_hyp, const int32_t* refs,
+                           const int32_t* ref_lens, int B, int N, int Uh, int Ur, int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CTC prefix beam search on the head's logits (csrc/ctc_decode.hip states the search): per utterance the W best
  * prefixes after the last frame, ranked, with the frame each token's node was created on.  No prediction network and
  * no joint: a row pass over [B, T, V] (log-sum-exp, lp[blank], the sorted top-cand list per frame), one launch that
