@@ -92,6 +92,10 @@ def load():
         lib.edgedict_stack_struct_bytes.restype = ctypes.c_size_t
         lib.edgedict_aux_stream.restype = ctypes.c_void_p
         lib.edgedict_stack_error_words.restype = ctypes.c_void_p
+        # the one entry point with double arguments: declared, so that Python floats arrive as doubles
+        vp, ci, cdb = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+        lib.edgedict_mwer_risk.argtypes = [vp, vp, ci, vp, vp, ci, ci, cdb, cdb, vp, vp, vp, vp, vp]
+        lib.edgedict_mwer_risk.restype = ci
         for name in declared_symbols():
             if not hasattr(lib, name):
                 raise RuntimeError("edgedict_amd: %s lacks symbol %s declared in the header"

@@ -44,10 +44,17 @@ hypotheses per utterance, one log-sum-exp per frame shared by all of them, no la
 
 ``SoftmaxNLLLoss`` / ``softmax_nll_rows`` (csrc/lm_loss.hip) are the language model's loss and sentence scorer:
 ``log_softmax`` + ``NLLLoss(ignore_index)`` on raw logits ``[M, V]``, the gradient written into the logits in place.
+
+``mwer_risk`` / ``MWERLoss`` (csrc/mwer.hip) are the risk layer of minimum word error rate training: the expected number
+of errors of an N-best list under the list's own renormalised posterior, differentiable in the hypotheses' costs.
+``mwer_rows`` packs the lists for the two consumers of one upload - the lattice batch whose per-row costs the packed
+joint returns, and ``metrics.edit_distance``; ``Transducer.mwer_loss`` puts the pieces together.
 """
+import collections
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -871,3 +878,240 @@ class SoftmaxNLLLoss(torch.nn.Module):
             t = t.to(torch.int32).contiguous()
         out = _SoftmaxNLLFn.apply(z, t, self.ignore_index, self.reduction)
         return out.view(targets.shape) if self.reduction == "none" else out
+
+
+# ------------------------------------------------------------------------------------------------ MWER
+# The risk layer of minimum word error rate training (csrc/mwer.hip): N-best costs and error counts in, the expected
+# number of errors and its derivative with respect to the costs out.
+
+MWER_MAX_N = 32
+
+
+def _certify_mwer_inputs(costs, errs, n_hyp, ref_costs):
+    # error classes / wording of _certify_ctc_score_inputs.  Returns the element stride of errs.
+    named = (("costs", costs), ("errs", errs), ("n_hyp", n_hyp), ("ref_costs", ref_costs))
+    for name, t in named:
+        if t is not None and not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (name, type(t).__name__))
+    for name, t in (("costs", costs), ("ref_costs", ref_costs)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    for name, t in (("errs", errs), ("n_hyp", n_hyp)):
+        if t is not None and t.dtype != torch.int32:
+            raise TypeError("%s must be int32, got %s" % (name, t.dtype))
+    for name, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if costs.dim() != 2:
+        raise ValueError("costs must have 2 dimensions [B,N], got %d" % costs.dim())
+    if errs.dim() not in (2, 3):
+        raise ValueError("errs must have 2 dimensions [B,N] or 3, [B,N,4] as metrics.edit_distance returns them, got %d"
+                         % errs.dim())
+    if (n_hyp is not None and n_hyp.dim() != 1) or (ref_costs is not None and ref_costs.dim() != 1):
+        raise ValueError("n_hyp and ref_costs must have 1 dimension")
+    B, N = costs.shape
+    if tuple(errs.shape[:2]) != (B, N) or (errs.dim() == 3 and errs.shape[2] != 4):
+        raise ValueError("must have an error count per slot (costs is %s, errs %s)"
+                         % (tuple(costs.shape), tuple(errs.shape)))
+    if n_hyp is not None and n_hyp.shape[0] != B:
+        raise ValueError("must have a hypothesis count per example (n_hyp has %d, batch is %d)" % (n_hyp.shape[0], B))
+    if ref_costs is not None and ref_costs.shape[0] != B:
+        raise ValueError("must have a reference cost per example (ref_costs has %d, batch is %d)"
+                         % (ref_costs.shape[0], B))
+    if B < 1:
+        raise ValueError("costs must hold at least one utterance (B = %d)" % B)
+    if not 1 <= N <= MWER_MAX_N:
+        raise ValueError("N = %d hypotheses per utterance outside [1, %d]" % (N, MWER_MAX_N))
+    return 4 if errs.dim() == 3 else 1
+
+
+def check_nll_weight(value):
+    """``float(value)``; ValueError unless it is finite and >= 0."""
+    w = float(value)
+    if not (w >= 0.0 and math.isfinite(w)):
+        raise ValueError("nll_weight must be finite and >= 0, got %r" % (value,))
+    return w
+
+
+class _MWERRiskFn(torch.autograd.Function):
+    """forward: one ``edgedict_mwer_risk`` call that leaves the risk, the posterior, the coefficients ``d(scale risk_b) /
+    d costs[b, n]`` and (unless ``reduction == 'none'``) the reduced value; backward: the coefficients times the incoming
+    gradient.  Returns ``(risk [B], post)`` for ``reduction == 'none'``, else ``(reduced (1,), post, risk)``; only the first is
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, costs, errs, n_hyp, ref_costs, nll_weight, reduction, stride):
+        _lib.require_cuda(costs, errs, n_hyp, ref_costs)
+        B, N = costs.shape
+        dev = costs.device
+        risk = torch.empty(B, dtype=torch.float32, device=dev)
+        post = torch.empty(B, N, dtype=torch.float32, device=dev)
+        coef = torch.empty(B, N, dtype=torch.float32, device=dev)
+        reduced = None if reduction == "none" else torch.empty(1, dtype=torch.float32, device=dev)
+        scale = 1.0 / B if reduction == "mean" else 1.0
+        _lib.call("mwer_risk", costs.detach(), errs, stride, n_hyp, None if ref_costs is None else ref_costs.detach(), B,
+                  N, ctypes.c_double(nll_weight), ctypes.c_double(scale), risk, post, coef, reduced)
+        ctx.save_for_backward(coef)
+        ctx.ref_grad = scale * nll_weight if ref_costs is not None else None
+        ctx.per_row = reduced is None
+        if reduced is None:
+            ctx.mark_non_differentiable(post)
+            return risk, post
+        ctx.mark_non_differentiable(post, risk)              # (one call: a second one replaces the first)
+        return reduced, post, risk
+
+    @staticmethod
+    def backward(ctx, grad_out, *_unused):
+        coef, = ctx.saved_tensors
+        go = grad_out.float()
+        grad_costs = (go[:, None] if ctx.per_row else go) * coef
+        grad_ref = None
+        if ctx.ref_grad is not None and ctx.needs_input_grad[3]:
+            grad_ref = (go * ctx.ref_grad).expand(coef.shape[0])
+        return grad_costs, None, None, grad_ref, None, None, None
+
+
+def mwer_risk(costs, errs, n_hyp=None):
+    """The MWER risk of N-best lists (csrc/mwer.hip): ``costs`` float32 ``[B, N]``, the negative log-likelihood of every
+    hypothesis (finite, or ``+inf`` for a slot to leave out; ``1 <= N <= 32``), ``errs`` int32 ``[B, N]`` or the
+    ``[B, N, 4]`` of ``metrics.edit_distance`` (its ``dist`` is read in place), ``n_hyp`` int32 ``[B]`` (live slots; None:
+    all ``N``).  Contiguous device tensors.  Returns ``(risk [B], post [B, N])`` float32: ``post`` is the softmax of
+    ``-costs`` over the live slots (0 on the others), ``risk[b] = sum_n post[b, n] * errs[b, n]`` the expected number of
+    errors (0 for an utterance without a live slot).  ``risk`` is differentiable in ``costs``: ``d risk[b] /
+    d costs[b, n] = -post[b, n] (errs[b, n] - risk[b])``, formed in fp64 by the kernel with the errors taken relative to
+    the list's minimum - exactly 0 where all live hypotheses have the same error count; ``post`` carries no gradient.
+    One launch, no host sync, bit-identical from run to run."""
+    stride = _certify_mwer_inputs(costs, errs, n_hyp, None)
+    return _MWERRiskFn.apply(costs, errs, n_hyp, None, 0.0, "none", stride)
+
+
+class MWERLoss(torch.nn.Module):
+    """Minimum word error rate loss on N-best lists (Prabhavalkar et al. 2018): ``mean_b risk_b + nll_weight *
+    mean_b ref_costs_b`` with ``risk`` as ``mwer_risk`` defines it.
+
+    ``forward(costs, errs, n_hyp=None, ref_costs=None)``: ``costs`` / ``errs`` / ``n_hyp`` as ``mwer_risk`` takes them,
+    ``ref_costs`` float32 ``[B]`` the negative log-likelihood of the reference transcripts - the interpolated
+    cross-entropy term that keeps the posterior from drifting; it receives the gradient ``scale * nll_weight``.
+    ``nll_weight > 0`` without ``ref_costs`` is a ``ValueError``.  ``reduction``: ``'mean'`` (default; ``sum / B`` with
+    shape ``(1,)``, as ``RNNTLoss``), ``'sum'`` (shape ``(1,)``) or ``'none'`` (shape ``(B,)``).  Sums run in a fixed order
+    in fp64 on the device; no host sync.  The per-utterance risk and the posterior of the last call stay in
+    ``last_risk`` / ``last_posterior`` (detached device tensors)."""
+
+    def __init__(self, nll_weight=0.0, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+        self.nll_weight = check_nll_weight(nll_weight)
+        self.reduction = reduction
+        self.last_risk = self.last_posterior = None
+
+    def forward(self, costs, errs, n_hyp=None, ref_costs=None):
+        if self.nll_weight > 0 and ref_costs is None:
+            raise ValueError("nll_weight = %g needs ref_costs" % self.nll_weight)
+        stride = _certify_mwer_inputs(costs, errs, n_hyp, ref_costs)
+        if self.reduction == "none":
+            risk, post = _MWERRiskFn.apply(costs, errs, n_hyp, None, 0.0, "none", stride)
+            self.last_risk, self.last_posterior = risk.detach(), post
+            return risk if ref_costs is None else risk + self.nll_weight * ref_costs
+        out, post, risk = _MWERRiskFn.apply(costs, errs, n_hyp, ref_costs, self.nll_weight, self.reduction, stride)
+        self.last_risk, self.last_posterior = risk, post
+        return out
+
+
+class MWERRows:
+    """What ``mwer_rows`` packed: ONE host int32 buffer ``host`` holding, back to back, the arrays ``views()`` names.
+
+    The lattice batch (a row per live hypothesis in ``(b, n)`` order - the first ``Rh`` rows - then, with references,
+    a row per utterance; ``R`` rows in all):
+      ``labels`` ``[R, Umax]`` (0 behind a row's length; ``Umax >= 1``), ``label_lens`` ``[R]``, ``row_utt`` ``[R]`` (the
+      utterance of each row), ``row_slot`` ``[R]`` (its slot ``n`` in the dense layout, -1 for a reference row),
+      ``row_dense`` ``[R]`` (``b * N + n``, -1 for a reference row);
+    the layout of ``metrics.edit_distance``:
+      ``hyps`` ``[B, N, Uh]``, ``hyp_lens`` ``[B, N]``, ``n_hyp`` ``[B]``, ``refs`` ``[B, Ur]``, ``ref_lens`` ``[B]``.
+    ``lists[b]``: the distinct token sequences of utterance ``b`` (int64 arrays), slot by slot."""
+
+    def __init__(self, host, R, Rh, Umax, B, N, Uh, Ur, lists):
+        self.host, self.lists = host, lists
+        self.R, self.Rh, self.Umax, self.B, self.N, self.Uh, self.Ur = R, Rh, Umax, B, N, Uh, Ur
+
+    def _shapes(self):
+        R, B, N = self.R, self.B, self.N
+        return (("labels", (R, self.Umax)), ("label_lens", (R,)), ("row_utt", (R,)), ("row_slot", (R,)),
+                ("row_dense", (R,)), ("hyps", (B, N, self.Uh)), ("hyp_lens", (B, N)), ("n_hyp", (B,)),
+                ("refs", (B, self.Ur)), ("ref_lens", (B,)))
+
+    def size(self):
+        return sum(int(np.prod(shape)) for _, shape in self._shapes())
+
+    def views(self, buf=None):
+        """The named arrays as views of ``buf``: the host buffer (None), or its copy on a device (a 1-D tensor)."""
+        buf = self.host if buf is None else buf
+        out, o = {}, 0
+        for name, shape in self._shapes():
+            n = int(np.prod(shape))
+            out[name] = buf[o:o + n].reshape(shape)
+            o += n
+        return out
+
+
+def mwer_rows(lists, ys, ylen, with_reference):
+    """The host-side packer of MWER training, one int32 upload like ``metrics.edit_distance_lists``'s: ``lists[b]`` the
+    token sequences (ints, no blanks) hypothesised for utterance ``b``, ``ys`` ``[B, U]`` / ``ylen`` ``[B]`` the reference
+    labels (host arrays or CPU tensors).  Sequences are de-duplicated (the first occurrence keeps its place); an empty
+    list stands for the single empty hypothesis (as in ``metrics.oracle_error_rate``); more than 32 distinct sequences
+    per utterance raise ``ValueError``.  Only live hypotheses become lattice rows; ``with_reference`` adds one row per
+    utterance holding its reference.  Returns an ``MWERRows``."""
+    from .metrics import EDIT_MAX_U, _seq
+    ys = np.asarray(ys.detach().cpu() if torch.is_tensor(ys) else ys)
+    ylen = np.asarray(ylen.detach().cpu() if torch.is_tensor(ylen) else ylen).reshape(-1)
+    if ys.ndim != 2 or ys.shape[0] != ylen.shape[0]:
+        raise ValueError("mwer_rows: ys must be [B, U] with one length per row (ys is %s, ylen has %d)"
+                         % (tuple(ys.shape), ylen.shape[0]))
+    B = ys.shape[0]
+    if len(lists) != B:
+        raise ValueError("mwer_rows: %d lists for %d references" % (len(lists), B))
+    if B < 1:
+        raise ValueError("mwer_rows: need at least one utterance")
+    refs = [_seq(ys[b, :max(0, min(int(ylen[b]), ys.shape[1]))], "a reference") for b in range(B)]
+    distinct = []
+    for b, seqs in enumerate(lists):
+        seen, own = set(), []
+        for t in seqs:
+            t = _seq(t, "a hypothesis")
+            key = t.tobytes()
+            if key not in seen:
+                seen.add(key)
+                own.append(t)
+        if not own:
+            own.append(np.zeros(0, dtype=np.int64))
+        if len(own) > MWER_MAX_N:
+            raise ValueError("mwer_rows: utterance %d has %d distinct hypotheses, more than the supported %d"
+                             % (b, len(own), MWER_MAX_N))
+        distinct.append(own)
+    N = max(len(own) for own in distinct)
+    Rh = sum(len(own) for own in distinct)
+    R = Rh + (B if with_reference else 0)
+    Uh = max(t.size for own in distinct for t in own)
+    Ur = max(r.size for r in refs)
+    Umax = max(1, Uh, Ur if with_reference else 0)
+    assert Umax <= EDIT_MAX_U
+    rows = MWERRows(None, R, Rh, Umax, B, N, Uh, Ur, distinct)
+    rows.host = np.zeros(rows.size(), dtype=np.int32)
+    v = rows.views()
+    r = 0
+    for b, own in enumerate(distinct):
+        v["n_hyp"][b] = len(own)
+        v["refs"][b, :refs[b].size] = refs[b]
+        v["ref_lens"][b] = refs[b].size
+        for n, t in enumerate(own):
+            v["hyps"][b, n, :t.size] = t
+            v["hyp_lens"][b, n] = t.size
+            v["labels"][r, :t.size] = t
+            v["label_lens"][r], v["row_utt"][r], v["row_slot"][r], v["row_dense"][r] = t.size, b, n, b * N + n
+            r += 1
+    if with_reference:
+        for b in range(B):
+            v["labels"][r, :refs[b].size] = refs[b]
+            v["label_lens"][r], v["row_utt"][r], v["row_slot"][r], v["row_dense"][r] = refs[b].size, b, -1, -1
+            r += 1
+    return rows

@@ -432,11 +432,15 @@ class _JointLossFn(torch.autograd.Function):
     M; the dense workspace planes of the loss get -inf log-probabilities on the dead cells of the boxes, which is what
     the lattice walks saw of them before (an alpha or a beta of -inf), so the loss is the box path's.  With
     ``plan.rows == 0`` (no utterance has an alignment) nothing is launched: the loss is +inf, every gradient zero.
-    ``ops.LAST["joint_packed_rows"]`` is the number of rows materialised (``joint_rows`` without a plan)."""
+    ``ops.LAST["joint_packed_rows"]`` is the number of rows materialised (``joint_rows`` without a plan).
+    ``row_costs=True`` (MWER training, ``Transducer.mwer_loss``): the same forward, but the per-row costs ``[B]`` are
+    returned instead of their mean, differentiable - backward hands the incoming ``[B]`` gradient to the packed gradient
+    kernels as their per-utterance scale (stride 1, host scale 1).  The batch's rows need not reach ``T`` and ``U``
+    (they are an N-best list's hypotheses).  Not with windows, a band plan or FastEmit: ``ValueError``."""
 
     @staticmethod
     def forward(ctx, enc, dec, w1, b1, w2, b2, labels, act_lens, label_lens, blank, cd, fastemit_lambda=0.0,
-                win_lo=None, win_hi=None, plan=None):
+                win_lo=None, win_hi=None, plan=None, row_costs=False):
         from ._staging import to_device
         B, T, P = enc.shape
         U1, P2 = dec.shape[1], dec.shape[2]
@@ -444,7 +448,13 @@ class _JointLossFn(torch.autograd.Function):
         dev = enc.device
         al = act_lens.to(torch.int64).cpu()
         ll = label_lens.to(torch.int64).cpu()
-        if int(al.max()) != T or int(ll.max()) != U1 - 1 or int(al.min()) < 1 or int(ll.min()) < 0:
+        ctx.row_costs = bool(row_costs)
+        if row_costs:
+            if win_lo is not None or win_hi is not None or plan is not None or float(fastemit_lambda) != 0.0:
+                raise ValueError("per-row costs of the packed joint take no windows, no band plan and no FastEmit")
+            if int(al.max()) > T or int(ll.max()) > U1 - 1 or int(al.min()) < 1 or int(ll.min()) < 0:
+                raise ValueError("Input length mismatch")
+        elif int(al.max()) != T or int(ll.max()) != U1 - 1 or int(al.min()) < 1 or int(ll.min()) < 0:
             raise ValueError("Input length mismatch")     # wording of warprnnt_pytorch's checks
         rows = al * (ll + 1)
         off = torch.zeros(B, dtype=torch.int64)
@@ -511,13 +521,15 @@ class _JointLossFn(torch.autograd.Function):
             else:
                 _lib.call("rnnt_loss_forward_packed", logits, _lib.dtype_code(cd), labels, al_d, ll_d, off_d,
                           B, T, U1, V, int(blank), costs, reduced, 1.0 / B, ws)
-        ops.LAST["joint_costs"] = costs       # per-utterance costs of the last packed joint + loss ([B], device)
+        # per-utterance costs of the last packed joint + loss ([B], device; detached: the returned tensor of the
+        # row_costs form carries this node, and a reference to it would keep the lattice alive)
+        ops.LAST["joint_costs"] = costs.detach()
         ctx.save_for_backward(enc2, dec2, w1, w2, hid, logits, labels, al_d, ll_d, off_d, ws)
         ctx.b1, ctx.b2 = b1, b2
         ctx.cfg = (cd, B, T, U1, P, P2, J, V, M, int(blank))
         ctx.fastemit_lambda = float(fastemit_lambda)
         ctx.restricted = restricted
-        return reduced
+        return costs if row_costs else reduced
 
     @staticmethod
     def _forward_band(ctx, enc, dec, w1, b1, w2, b2, labels, al_d, ll_d, blank, cd, fastemit_lambda, win_lo, win_hi,
@@ -579,7 +591,7 @@ class _JointLossFn(torch.autograd.Function):
     def _backward_band(ctx, gout):
         plan = ctx.plan
         cd, B, T, U1, P, P2, J, V, M, blank = ctx.cfg
-        tail = (None,) * 9
+        tail = (None,) * 10
         if M == 0:
             enc2, dec2, w1, w2 = ctx.saved_tensors
             with side.WeightGrads(ctx, 2, (w1, ctx.b1, w2, ctx.b2)) as wg:
@@ -634,6 +646,8 @@ class _JointLossFn(torch.autograd.Function):
         cd, B, T, U1, P, P2, J, V, M, blank = ctx.cfg
         dl = torch.empty_like(logits)
         gscale = gout.contiguous().float()
+        # the mean: one scale for the batch, times 1 / B on the host; per-row costs: a scale per utterance, as it came
+        gs_host, gs_stride = (1.0, 1) if ctx.row_costs else (1.0 / B, 0)
         w1c = WEIGHTS.get(w1, cd)
         w2t = WEIGHTS.get(w2, cd, transposed=True)
         dE1 = torch.empty(B, T, J, dtype=F32, device=dl.device)
@@ -650,23 +664,23 @@ class _JointLossFn(torch.autograd.Function):
                 # gradient kernels with the dead-cell test (the windows are in the workspace)
                 if db2_parts is not None:
                     _lib.call("rnnt_loss_backward_packed_colsum_ar", logits, _lib.dtype_code(cd), dl, labels, al_d,
-                              ll_d, off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, lam)
+                              ll_d, off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride, db2_parts, lam)
                 else:
                     _lib.call("rnnt_loss_backward_packed_ar", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
-                              off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, lam)
+                              off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride, lam)
             elif lam != 0.0:
                 if db2_parts is not None:
                     _lib.call("rnnt_loss_backward_packed_colsum_fe", logits, _lib.dtype_code(cd), dl, labels, al_d,
-                              ll_d, off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts, lam)
+                              ll_d, off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride, db2_parts, lam)
                 else:
                     _lib.call("rnnt_loss_backward_packed_fe", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
-                              off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, lam)
+                              off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride, lam)
             elif db2_parts is not None:
                 _lib.call("rnnt_loss_backward_packed_colsum", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
-                          off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0, db2_parts)
+                          off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride, db2_parts)
             else:
                 _lib.call("rnnt_loss_backward_packed", logits, _lib.dtype_code(cd), dl, labels, al_d, ll_d,
-                          off_d, B, T, U1, V, blank, ws, 1.0 / B, gscale, 0)
+                          off_d, B, T, U1, V, blank, ws, gs_host, gscale, gs_stride)
         del logits
         with ops.timed("joint_dhid_gemm"):
             dhid = ops.gemm(dl, w2t)
@@ -685,7 +699,7 @@ class _JointLossFn(torch.autograd.Function):
             wg.gemm(0, dD1c.t(), dec2.t(), cols=slice(P, None), split_k=ops.pick_split_k(J, P2, B * U1))
             wg.colsum(1, dD1.view(B * U1, J))
         ops.mark("joint_bwd:exit")
-        return (denc, ddec, *wg.grads, None, None, None, None, None, None, None, None, None)
+        return (denc, ddec, *wg.grads, None, None, None, None, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -1501,6 +1515,83 @@ class Transducer(nn.Module):
             record = metrics.word_error_rate(pred, true, xs.device)
         self.last_error_rate = record
         return loss, record.rate, pred, true
+
+    MWER_SEARCHES = ("sync_beam", "beam")
+    last_mwer = None             # what the last mwer_loss call worked on (see there)
+
+    def mwer_loss(self, xs, ys, xlen, ylen, *, W=4, search="sync_beam", nbest=None, nll_weight=0.0, **search_kwargs):
+        """Minimum word error rate loss of a batch (Prabhavalkar et al. 2018; Guo et al. 2020): the expected number of
+        token errors of every utterance's N-best list under the list's renormalised posterior, ``mean_b risk_b +
+        nll_weight * mean_b nll_ref_b`` as a ``(1,)`` tensor, differentiable in every parameter (``loss.MWERLoss``).
+
+        The encoder runs once, with gradient, in the model's current mode.  The lists: ``nbest`` (one entry per
+        utterance: a ``decode.NBestResult`` or a list of token arrays), else a search on the detached encoder output
+        under ``torch.no_grad()`` - ``search="sync_beam"``: ``decode.sync_beam_search_nbest_enc``, ``"beam"``:
+        ``decode.beam_search_nbest_enc`` with ``.ranked(merge=True)`` - of width ``W``; ``search_kwargs`` (``lm=``,
+        ``bias=``, ...) go to the search.  Equal sequences count once, an empty list is the empty hypothesis, more than
+        32 distinct sequences per utterance raise.  Every hypothesis (and, with ``nll_weight > 0``, every reference) is a
+        row of ONE packed joint + loss call whose per-row costs are the hypotheses' negative log-likelihoods; the
+        encoder rows are gathered with ``index_select`` (torch adds the gradients back), the errors come from
+        ``metrics.edit_distance`` on the same upload.
+
+        No CTC term, and ``fastemit_lambda`` is NOT applied: the hypotheses' costs are plain negative log-likelihoods.
+        Needs a device model and host-side ``xlen`` / ``ylen`` (they size the lattice), else ``ValueError``.  Apart from
+        the search's own read nothing waits for the device as long as ``ys`` is a host tensor (a device ``ys`` is read
+        back once, behind the search).  Leaves ``self.last_mwer``: ``lists`` (the distinct sequences used), and the
+        device tensors ``errors`` ``[B, N, 4]``, ``costs`` ``[B, N]`` (+inf on empty slots), ``posterior`` ``[B, N]``,
+        ``risk`` ``[B]`` and ``n_hyp`` ``[B]``."""
+        import numpy as np
+        from . import decode, metrics
+        from ._staging import to_device
+        from .loss import MWERLoss, check_nll_weight, mwer_rows
+        if search not in self.MWER_SEARCHES:
+            raise ValueError("search must be one of %s, got %r" % (", ".join(self.MWER_SEARCHES), search))
+        nll_weight = check_nll_weight(nll_weight)
+        if not (torch.is_tensor(xs) and xs.is_cuda and xs.dim() == 3):
+            raise ValueError("mwer_loss needs a device batch xs [B, T, F]")
+        if xlen.is_cuda or ylen.is_cuda:
+            raise ValueError("mwer_loss needs xlen and ylen on the host: they size the packed lattice")
+        B = xs.shape[0]
+        if nbest is not None and len(nbest) != B:
+            raise ValueError("nbest must hold one list per utterance (got %d for a batch of %d)" % (len(nbest), B))
+        xs = xs[:, :xlen.max()].contiguous()
+        cd = self.compute_dtype
+        h_enc, _ = self.encoder(xs)
+        h_enc = _to_cd(h_enc, cd)
+        act = self.scale_length(h_enc, xlen)                 # host int32 [B]
+        if nbest is None:
+            with torch.no_grad():
+                lens = act.numpy().astype(np.int32)
+                if search == "sync_beam":
+                    found = decode.sync_beam_search_nbest_enc(self, h_enc.detach(), lens, W, **search_kwargs)
+                else:
+                    found = [r.ranked(merge=True)
+                             for r in decode.beam_search_nbest_enc(self, h_enc.detach(), lens, W, **search_kwargs)]
+            lists = [r.tokens for r in found]
+        else:
+            lists = [r.tokens if isinstance(r, decode.NBestResult) else list(r) for r in nbest]
+        rows = mwer_rows(lists, ys, ylen, nll_weight > 0)
+        dev = h_enc.device
+        v = rows.views(to_device(torch.from_numpy(rows.host), dev))
+        host = rows.views()
+        l1, l2 = self.joint.joint[0], self.joint.joint[2]
+        ops.mark("joint:enter")
+        enc_rows = h_enc.index_select(0, v["row_utt"])
+        h_dec, _ = self.decoder(v["labels"])
+        act_rows = act[torch.from_numpy(host["row_utt"].astype(np.int64))]
+        row_costs = _JointLossFn.apply(enc_rows, _to_cd(h_dec, cd), l1.weight, l1.bias, l2.weight, l2.bias, v["labels"],
+                                       act_rows, torch.from_numpy(host["label_lens"]), self.blank, cd, 0.0, None, None,
+                                       None, True)
+        ops.mark("joint:exit")
+        errors = metrics.edit_distance(v["hyps"], v["hyp_lens"], v["refs"], v["ref_lens"], v["n_hyp"])
+        N, Rh = rows.N, rows.Rh
+        dense = torch.full((B * N,), float("inf"), dtype=F32, device=dev)
+        dense = dense.index_copy(0, v["row_dense"][:Rh].long(), row_costs[:Rh]).view(B, N)
+        crit = MWERLoss(nll_weight)
+        loss = crit(dense, errors, v["n_hyp"], row_costs[Rh:] if nll_weight > 0 else None)
+        self.last_mwer = dict(lists=rows.lists, errors=errors, costs=dense.detach(), posterior=crit.last_posterior,
+                              risk=crit.last_risk, n_hyp=v["n_hyp"])
+        return loss
 
 
 class _CausalConvFn(torch.autograd.Function):

@@ -302,3 +302,45 @@ class TrainEngine:
             gc.collect()
             gc.freeze()
         return total
+
+    def mwer_step(self, wave, wave_len, ys, ylen, *, W=4, nll_weight=0.0, **kw):
+        """One optimiser step on the MWER criterion (``Transducer.mwer_loss``): ``train_step``'s loop - front-end,
+        ``sub_batch_size`` slices, backward, gradient exchange, Adam, next step's weight images - around ``mwer_loss``
+        instead of ``forward``; arguments as ``train_step``'s, ``W`` / ``nll_weight`` / ``kw`` (``search=``, ``lm=``, ...)
+        as ``mwer_loss``'s (``nbest=`` is cut per slice).  No prefetch of a next batch and no windows.  ``mwer_loss`` needs
+        the lengths on the host: without ``wave_len`` every utterance has all frames, a device ``wave_len`` / ``ylen``
+        is read back once.  Returns the mean loss of the local batch as a device tensor."""
+        from . import ops
+        ops.mark("step:enter")
+        self.step_count += 1
+        self.warmup.step(self.step_count)
+        self.model.train()
+        self.optim.zero_grad()
+        B = wave.shape[0]
+        sub = self.sub_batch_size or B
+        starts = list(range(0, B, sub))
+        ylen = ylen.cpu() if ylen.is_cuda else ylen
+        nbest = kw.pop("nbest", None)
+        total = None
+        for s in starts:
+            e = min(B, s + sub)
+            self.reducer.armed = (s == starts[-1])   # exchange once, after the last accumulation
+            xs, xlen = self._front_end(wave[s:e], None if wave_len is None else wave_len[s:e])
+            if xlen.is_cuda:
+                xlen = torch.full((e - s,), xs.shape[1], dtype=torch.int32) if wave_len is None else xlen.cpu()
+            loss = self.model.mwer_loss(xs, ys[s:e], xlen, ylen[s:e], W=W, nll_weight=nll_weight,
+                                        nbest=None if nbest is None else nbest[s:e], **kw)
+            loss = loss / len(starts)
+            ops.mark("backward:enter")
+            loss.backward()
+            ops.mark("backward:exit")
+            total = loss.detach() if total is None else total + loss.detach()
+        scale = self.reducer.finish()
+        self.optim.step(grad_scale=scale, guard=self._guard)
+        if self.compute_dtype == torch.bfloat16 and config.USE_ENCODER_STACK:
+            from . import encoder_stack, side
+            aux = side.stream(self.device)
+            aux.wait_stream(torch.cuda.current_stream(self.device))
+            encoder_stack.prepack(self.model.encoder, aux)
+        ops.mark("step:exit")
+        return total

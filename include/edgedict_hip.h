@@ -1299,6 +1299,30 @@ int edgedict_edit_distance(const int32_t* hyps, const int32_t* hyp_lens, const i
                            const int32_t* ref_lens, int B, int N, int Uh, int Ur, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The risk layer of MWER training (csrc/mwer.hip): the expected number of errors of an N-best list under its own
+ * renormalised posterior, and its derivative with respect to every hypothesis' cost.
+ *   costs      [B, N]  fp32      negative log-likelihood of every hypothesis, finite or +inf
+ *   errs               int32     errors of every hypothesis, element (b N + n) * err_stride: err_stride 1 reads a
+ *                                [B, N] array, 4 reads `dist` out of edgedict_edit_distance's [B, N, 4]
+ *   n_hyp      [B]     int32     live slots per utterance (clamped to [0, N]); null: all N
+ *   ref_costs  [B]     fp32      nullable: negative log-likelihood of the reference, for the nll_weight term of `reduced`
+ *   risk       [B]     fp32 out  e_min + sum_n p_n d_n
+ *   post       [B, N]  fp32 out  p
+ *   coef       [B, N]  fp32 out  scale p_n (dbar - d_n) = d(scale risk[b]) / d costs[b, n]
+ *   reduced    [1]     fp32 out  nullable: scale * sum_b (risk[b] + nll_weight * ref_costs[b]), the stored risk values
+ *                                added in a fixed order in fp64; without ref_costs the second term is absent
+ * Slot n is live iff n < n_hyp[b] and costs[b, n] < +inf.  Over the live slots, in fp64: m = min c, w = exp(-(c - m)),
+ * p = w / sum w, e_min = min errs, d = errs - e_min (an integer difference), dbar = sum p d.  Dead slots have post =
+ * coef = 0, an utterance without a live slot has risk 0; live hypotheses that all have the same error count give
+ * coefficients of exactly 0.  One wave64 per utterance plus one wave for `reduced`; no workspace, no host sync, no
+ * atomics, bit-identical from run to run.  B >= 1, 1 <= N <= 32, err_stride 1 or 4, B * N < 2^31; arguments are
+ * validated before anything is launched (-1 with a message; needs no device).
+ */
+int edgedict_mwer_risk(const float* costs, const int32_t* errs, int err_stride, const int32_t* n_hyp,
+                       const float* ref_costs, int B, int N, double nll_weight, double scale, float* risk, float* post,
+                       float* coef, float* reduced, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CTC prefix beam search on the head's logits (csrc/ctc_decode.hip states the search): per utterance the W best
  * prefixes after the last frame, ranked, with the frame each token's node was created on.  No prediction network and
  * no joint: a row pass over [B, T, V] (log-sum-exp, lp[blank], the sorted top-cand list per frame), one launch that
