@@ -84,6 +84,9 @@ def load():
         lib.edgedict_sync_beam_workspace_bytes_fusion.restype = ctypes.c_size_t
         lib.edgedict_sync_stream_state_bytes_fusion.restype = ctypes.c_size_t
         lib.edgedict_sync_stream_workspace_bytes_fusion.restype = ctypes.c_size_t
+        lib.edgedict_sync_beam_workspace_bytes_ilme.restype = ctypes.c_size_t
+        lib.edgedict_sync_stream_workspace_bytes_ilme.restype = ctypes.c_size_t
+        lib.edgedict_ilm_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_stream_encoder_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_blaslt_calls.restype = ctypes.c_longlong
         lib.edgedict_gelu_groupnorm_bwd_workspace_bytes.restype = ctypes.c_size_t

@@ -185,6 +185,38 @@ int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const fl
     return composed_joint(net, (const char*)E1t, u.dec_new, u, s);
 }
 
+// The internal LM's logits composed from the general kernels: the joint on the all-zero encoder row `zero_row` [J] for
+// every row, from D1 = dec W1d^T + b1 [B, J] as composed_joint left it (d1) - hid = tanh(0 + D1) into `hid`, then the
+// logits product into `logits` (fp32 [B, V]).  Two launches.
+static int composed_ilm_tail(const SearchNet& net, const void* zero_row, const void* d1, void* hid, float* logits,
+                             hipStream_t s) {
+    const int B = net.B, J = net.J;
+    dispatch(net.dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(add_tanh_rows<T>, dim3(ed_grid_for((long long)B * J, 256)), dim3(256), 0, s,
+                           (const T*)zero_row, 0ll, (const T*)d1, (T*)hid, B, J);
+    });
+    return edgedict_gemm(net.dtype, ED_F32, hid, J, 1, net.W2, J, 1, logits, net.V, B, net.V, J, net.b2, nullptr, 0, 1, s);
+}
+
+// ed_decode_composed_beam_step, then the internal LM's logits of the same rows (ilm_logits, fp32 [B, V]; ilm_hid [B, J]
+// scratch): two launches more
+int ed_decode_composed_beam_step_ilm(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                     const StepBufs& u, const void* zero_row, void* ilm_hid, float* ilm_logits,
+                                     hipStream_t s) {
+    if (int rc = ed_decode_composed_beam_step(net, E1t, h_state, c_state, u, s)) return rc;
+    return composed_ilm_tail(net, zero_row, u.D1, ilm_hid, ilm_logits, s);
+}
+
+// the internal LM's logits alone for B rows of prediction-network output `dec` [B, P2]: three launches
+int ed_decode_composed_ilm_logits(const SearchNet& net, const void* dec, const void* zero_row, void* d1, void* hid,
+                                  float* logits, hipStream_t s) {
+    if (int rc = edgedict_gemm(net.dtype, net.dtype, dec, net.P2, 1, net.W1d, net.ldw1, 1, d1, net.J, net.B, net.J, net.P2,
+                               net.b1, nullptr, 0, 1, s))
+        return rc;
+    return composed_ilm_tail(net, zero_row, d1, hid, logits, s);
+}
+
 // One LM step for `rows` rows (decode_net.hpp): shared by the best-first searches here and the frame-synchronous one
 int ed_decode_lm_step(int dtype, int rows, const LstmNet& lm, const float* h_state, const float* c_state,
                       const StepBufs& u, hipStream_t s) {

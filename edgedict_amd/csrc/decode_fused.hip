@@ -148,6 +148,45 @@ __global__ __launch_bounds__(256) void dec_joint_hidden(const ET* __restrict__ E
     Md::st4(hid + (long long)row * J + c, h[0], h[1], h[2], h[3]);
 }
 
+// The same tile with TWO epilogues, for internal-LM estimation (decode_sync.hip, ILME): the product dec_out W1d^T is shared
+// between the transducer's hidden vector and the internal LM's - the joint on an all-zero encoder row - so it is formed
+// once and written twice into hid [2 B, J]:
+//   hid[b]     = tanh(E1[b, t] + act(acc + b1))     bit for bit dec_joint_hidden's (same operand order, same act rounding)
+//   hid[B + b] = tanh(act(acc + b1))
+// DUAL false (the teacher-forced scorer, ilm_score.hip): the second form alone, into hid [B, J]; E1t is not read.
+template <typename ET, bool DUAL>
+__global__ __launch_bounds__(256) void dec_joint_hidden_ilm(const ET* __restrict__ E1t, long long e_row_stride,
+                                                            const ET* __restrict__ dec_out, int P2,
+                                                            const ET* __restrict__ W1d, long long ldw1,
+                                                            const float* __restrict__ b1, ET* __restrict__ hid,
+                                                            int B, int J) {
+    typedef Mode<ET> Md;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r16 = lane & 15, q = lane >> 4;
+    const int row = blockIdx.x * 16 + r16, col0 = blockIdx.y * 64 + wave * 16;
+    if (col0 >= J) return;
+    const int c = min(col0 + q * 4, J - 4);
+    float ev[4] = {0.f, 0.f, 0.f, 0.f}, h[4], g[4];
+    if constexpr (DUAL) Md::ld4(E1t + (long long)min(row, B - 1) * e_row_stride + c, ev);
+    const float4 bv = *reinterpret_cast<const float4*>(b1 + c);
+    f32x4_t acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    wave_product<ET, 20>(acc, dec_out + (long long)min(row, B - 1) * P2 + q * Md::LK,
+                         W1d + (long long)min(col0 + r16, J - 1) * ldw1 + q * Md::LK, P2);
+    if (row >= B || col0 + q * 4 >= J) return;
+    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float d = Md::act(acc[i] + bb[i]);
+        h[i] = tanhf(ev[i] + d);
+        g[i] = tanhf(d);
+    }
+    if constexpr (DUAL) {
+        Md::st4(hid + (long long)row * J + c, h[0], h[1], h[2], h[3]);
+        Md::st4(hid + ((long long)B + row) * J + c, g[0], g[1], g[2], g[3]);
+    } else {
+        Md::st4(hid + (long long)row * J + c, g[0], g[1], g[2], g[3]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- 2
 // per row and 64-column slice of the logits: (max, first arg-max), the same without column `unk`, sum of
 // exp(z - max).  4 waves = 4 x 16 columns of 16 rows.  With logits_out the logits are written instead (fp32 [B, V]:
@@ -758,6 +797,46 @@ int ed_decode_fused_beam_step(const SearchNet& net, const void* E1t, const float
                            (const ET*)net.W2, net.b2, net.V, -1, 0, (PickPart*)nullptr, u.logits, B);
     });
     ED_CHECK_LAUNCH("decode_fused_beam_step");
+    return ED_OK;
+}
+
+// The same step with internal-LM estimation: dec_joint_hidden_ilm writes hid2 [2 B, J] (the frame's rows, then the same
+// rows on a zero encoder row), dec_logits_pick runs unchanged on 2 B rows into logits2 (fp32 [2 B, V]): the RNN-T logits,
+// bit for bit those of the step above, then the internal LM's.  The same 3 + L launches.
+int ed_decode_fused_beam_step_ilm(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                  const StepBufs& u, void* hid2, float* logits2, hipStream_t s) {
+    const LstmNet& pn = net.pred;
+    const int B = net.B, RB = (B + 15) / 16, RB2 = (2 * B + 15) / 16;
+    dispatch(net.dtype, [&](auto tag) {
+        using ET = decltype(tag);
+        launch_lstm_steps<ET>(2, pn, nullptr, -1, NO_PICK, h_state, c_state, u, B, s);
+        hipLaunchKernelGGL(dec_proj_commit<ET>, dim3(RB, (net.P2 + 63) / 64), dim3(256), 0, s,
+                           (const ET*)u.Y[(pn.L - 1) & 1], pn.H, (const ET*)pn.Wo, pn.bo, net.P2, (const int32_t*)nullptr, 0,
+                           (ET*)u.dec_new, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (const float*)nullptr,
+                           pn.L, B);
+        hipLaunchKernelGGL((dec_joint_hidden_ilm<ET, true>), dim3(RB, (net.J + 63) / 64), dim3(256), 0, s, (const ET*)E1t,
+                           net.e_row_stride, (const ET*)u.dec_new, net.P2, (const ET*)net.W1d, net.ldw1, net.b1,
+                           (ET*)hid2, B, net.J);
+        hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB2, (net.V + 63) / 64), dim3(256), 0, s, (const ET*)hid2, net.J,
+                           (const ET*)net.W2, net.b2, net.V, -1, 0, (PickPart*)nullptr, logits2, 2 * B);
+    });
+    ED_CHECK_LAUNCH("decode_fused_beam_step_ilm");
+    return ED_OK;
+}
+
+// the internal LM's logits alone for B rows of prediction-network output `dec` [B, P2]: hid [B, J] scratch, logits fp32
+// [B, V]; two launches
+int ed_decode_fused_ilm_logits(const SearchNet& net, const void* dec, void* hid, float* logits, hipStream_t s) {
+    const int B = net.B, RB = (B + 15) / 16;
+    dispatch(net.dtype, [&](auto tag) {
+        using ET = decltype(tag);
+        hipLaunchKernelGGL((dec_joint_hidden_ilm<ET, false>), dim3(RB, (net.J + 63) / 64), dim3(256), 0, s,
+                           (const ET*)nullptr, 0ll, (const ET*)dec, net.P2, (const ET*)net.W1d, net.ldw1, net.b1, (ET*)hid,
+                           B, net.J);
+        hipLaunchKernelGGL(dec_logits_pick<ET>, dim3(RB, (net.V + 63) / 64), dim3(256), 0, s, (const ET*)hid, net.J,
+                           (const ET*)net.W2, net.b2, net.V, -1, 0, (PickPart*)nullptr, logits, B);
+    });
+    ED_CHECK_LAUNCH("decode_fused_ilm_logits");
     return ED_OK;
 }
 

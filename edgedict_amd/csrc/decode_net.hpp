@@ -109,6 +109,19 @@ int ed_decode_fused_beam_step(const SearchNet& net, const void* E1t, const float
 // decode.hip: the same step composed from the general kernels, for any shape
 int ed_decode_composed_beam_step(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
                                  const StepBufs& u, hipStream_t s);
+// Internal-LM estimation (decode_sync.hip, ilm_score.hip).  The internal LM's logits of a row are the joint on an
+// all-zero encoder row.  The *_step_ilm forms are the beam step plus those logits for the same rows: fused, hid2 [2 B, J]
+// and logits2 fp32 [2 B, V] hold the step's rows and then the internal LM's (u.hid / u.logits are not written); composed,
+// u.logits as ever and ilm_logits fp32 [B, V] (zero_row: J zero elements, ilm_hid [B, J] scratch).  The *_ilm_logits
+// forms are the internal LM's logits alone for net.B rows of prediction-network output `dec` [B, P2].
+int ed_decode_fused_beam_step_ilm(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                  const StepBufs& u, void* hid2, float* logits2, hipStream_t s);
+int ed_decode_composed_beam_step_ilm(const SearchNet& net, const void* E1t, const float* h_state, const float* c_state,
+                                     const StepBufs& u, const void* zero_row, void* ilm_hid, float* ilm_logits,
+                                     hipStream_t s);
+int ed_decode_fused_ilm_logits(const SearchNet& net, const void* dec, void* hid, float* logits, hipStream_t s);
+int ed_decode_composed_ilm_logits(const SearchNet& net, const void* dec, const void* zero_row, void* d1, void* hid,
+                                  float* logits, hipStream_t s);
 int ed_decode_fused_lm_step(int dtype, int B, const LstmNet& lm, const float* h_state, const float* c_state,
                             const StepBufs& u, hipStream_t s);
 // decode.hip: one LM step for `rows` rows, token u.pred[r] from (h_state, c_state) [L, rows, H] -> u.h_new / u.c_new and

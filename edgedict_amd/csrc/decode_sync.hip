@@ -27,11 +27,20 @@
 //   ((logp_i + (double) lp_i[k]) + (lm_w * (double) lp_lm_i[k] + lm_b)) + (held[goto(s_i, k)] - pend[s_i])
 // where a term is absent when its feature is.  Without either the plain kernels run, launch for launch.
 //
+// Internal-LM estimation (ILME; the *_ilme entry points, sync_row_topw_ilm): the prior the transducer learned from its
+// training transcripts is subtracted while an external LM is added.  The internal LM's logits of a row are the step's
+// joint on an all-zero encoder row, z_ilm = tanh(act(d W1d^T + b1)) W2^T + b2 for the row's prediction-network output d;
+// lp_ilm is their fp32 log-softmax over the NON-BLANK symbols, and a non-blank candidate's score gains
+// - ilm_w * (double) lp_ilm[k] behind the LM term and in front of the list's.  ILME carries no per-row state: the select
+// kernels and the persistent state are untouched.  On the fused step the frame keeps its launch count (the joint-hidden
+// kernel writes both hidden vectors from one product, the logits kernel runs on 2 B W rows); composed, two launches more.
+//
 // Second half of the file: the streaming form (edgedict_sync_stream_*), the same frame loop on a persistent state.
 #include "bias_tables.hpp"
 #include "decode_net.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <vector>
 
@@ -122,10 +131,13 @@ constexpr int SB_VPT = 8;
 // over the row's LM logits, s the row's automaton state.  A term is absent when its feature is; blank keeps
 // base + lp[blank]; c_lp stays lp[k].  goto is bias_goto's binary search in s's (short) exception row, once per
 // candidate in the CACHED form and once per candidate and pass in the other.
-template <bool CACHED, bool LM, bool BIAS>
+// ILM (sync_row_topw_ilm): a third max / sum pass over the row's internal-LM logits that skips `blank`, and behind the LM
+// term  c = c - ilm_w * (double)lp_ilm[k]  (__dsub_rn / __dmul_rn: no contraction), so ilm_w = 0 leaves every bit.
+template <bool CACHED, bool LM, bool BIAS, bool ILM = false>
 __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const SyncFuse& f,
                                                    const float* __restrict__ logits,
-                                                   const float* __restrict__ lm_logits, int t, int W, int V, int blank) {
+                                                   const float* __restrict__ lm_logits, int t, int W, int V, int blank,
+                                                   const float* __restrict__ ilm_logits = nullptr, double ilm_w = 0.0) {
     const int r = blockIdx.x, tid = threadIdx.x;
     if (t >= p.lens[r / W]) return;
     const double base = p.logp[r];
@@ -153,6 +165,20 @@ __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const Sync
         sl = sb_block_sum_max(sl, false, sf);
         logsl = logf(sl);
     }
+    const float* zi = nullptr;
+    float mi = 0.f, logsi = 0.f;
+    if constexpr (ILM) {
+        zi = ilm_logits + (size_t)r * V;
+        mi = -INFINITY;
+        for (int v = tid; v < V; v += 256)
+            if (v != blank) mi = fmaxf(mi, zi[v]);
+        mi = sb_block_sum_max(mi, true, sf);
+        float si = 0.f;
+        for (int v = tid; v < V; v += 256)
+            if (v != blank) si += expf(zi[v] - mi);
+        si = sb_block_sum_max(si, false, sf);
+        logsi = logf(si);
+    }
     int st = 0;
     double pend_s = 0.0;
     if constexpr (BIAS) {
@@ -163,6 +189,9 @@ __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const Sync
         double c = base + (double)((z[v] - m) - logs);
         if constexpr (LM) {
             if (v != blank) c = c + __dadd_rn(__dmul_rn(f.lm_w, (double)((zl[v] - ml) - logsl)), f.lm_b);
+        }
+        if constexpr (ILM) {
+            if (v != blank) c = __dsub_rn(c, __dmul_rn(ilm_w, (double)((zi[v] - mi) - logsi)));
         }
         if constexpr (BIAS) {
             if (v != blank) c = __dadd_rn(c, __dsub_rn(f.bias_held[bias_goto(f, st, v)], pend_s));
@@ -232,6 +261,14 @@ __global__ __launch_bounds__(256) void sync_row_topw_fused(SyncPtrs p, SyncFuse 
                                                            const float* __restrict__ lm_logits, int t, int W, int V,
                                                            int blank) {
     sync_row_topw_body<CACHED, LM, BIAS>(p, f, logits, lm_logits, t, W, V, blank);
+}
+
+template <bool CACHED, bool LM, bool BIAS>
+__global__ __launch_bounds__(256) void sync_row_topw_ilm(SyncPtrs p, SyncFuse f, const float* __restrict__ logits,
+                                                         const float* __restrict__ lm_logits,
+                                                         const float* __restrict__ ilm_logits, double ilm_w, int t, int W,
+                                                         int V, int blank) {
+    sync_row_topw_body<CACHED, LM, BIAS, true>(p, f, logits, lm_logits, t, W, V, blank, ilm_logits, ilm_w);
 }
 
 // One workgroup per utterance.  Wave 0, lane j = the j-th kept candidate: a W-way merge of the rows' sorted lists picks
@@ -658,21 +695,106 @@ SyncFusion sync_fuse_bind(char* rows_base, const SyncFuseRows& ra, char* ws, con
     return u;
 }
 
-// The frame's last two launches: the per-row top-W and the select / merge / gather.  fu null: the plain kernels.
+// ILME, host side: the buffers behind every other part of a workspace (offsets from `base`), sized for either step -
+// fused: hid2 [2 rows, J] and logits2 fp32 [2 rows, V]; composed: their first halves and the zero encoder row.
+struct SyncIlmWs {
+    size_t hid2, logits2, zero_row, total;
+};
+SyncIlmWs sync_ilm_layout(size_t base, size_t rows, size_t esz, size_t J, size_t V, bool on) {
+    SyncIlmWs w{};
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
+    if (on) {
+        w.hid2 = take(2 * rows * J * esz);
+        w.logits2 = take(2 * rows * V * 4);
+        w.zero_row = take(J * esz);
+    }
+    w.total = o;
+    return w;
+}
+// a usable weight: finite and >= 0 (null: ILME is off)
+bool sync_ilm_ok(const double* ilm_weight) { return !ilm_weight || (std::isfinite(*ilm_weight) && *ilm_weight >= 0.0); }
+int sync_ilm_check(const double* ilm_weight, const char* what) {
+    ED_CHECK_ARG(sync_ilm_ok(ilm_weight), "%s: ilm_weight = %g (must be finite and >= 0)", what, *ilm_weight);
+    return ED_OK;
+}
+// One call's ILME: the weight, where the internal LM's logits of the rows are, the step's extra buffers
+struct SyncIlm {
+    double w;
+    const float* logits;
+    void* hid2;
+    float* logits2;
+    const void* zero_row;
+};
+// the step of one frame: u.logits holds the rows' RNN-T logits afterwards (with ILME on the fused step: u = ui, whose
+// logits point into logits2)
+int sync_step(bool fused, const SearchNet& net, const float* hs, const float* cs, const StepBufs& u, const SyncIlm* il,
+              hipStream_t s) {
+    if (!il) {
+        if (fused) return ed_decode_fused_beam_step(net, net.E1, hs, cs, u, s);
+        return ed_decode_composed_beam_step(net, net.E1, hs, cs, u, s);
+    }
+    if (fused) return ed_decode_fused_beam_step_ilm(net, net.E1, hs, cs, u, il->hid2, il->logits2, s);
+    return ed_decode_composed_beam_step_ilm(net, net.E1, hs, cs, u, il->zero_row, il->hid2, il->logits2, s);
+}
+// binds ILME's buffers at p + a; `u` is the step's bundle, whose logits move into logits2 on the fused step
+SyncIlm sync_ilm_bind(char* p, const SyncIlmWs& a, double w, bool fused, size_t rows, size_t V, StepBufs& u) {
+    SyncIlm il{w, nullptr, p + a.hid2, at<float>(p, a.logits2), p + a.zero_row};
+    if (fused) {
+        u.logits = il.logits2;
+        il.logits = il.logits2 + rows * V;
+    } else {
+        il.logits = il.logits2;
+    }
+    return il;
+}
+
+// The frame's last two launches: the per-row top-W and the select / merge / gather.  fu and il null: the plain kernels.
+// ILME alone has no per-row state: its top-W kernel, then the plain select.
 template <bool STREAM>
 void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u, int t, int cur, int W, int B, int L,
-                      int H, int NODES, int V, int blank, int bos, const int32_t* frame0, hipStream_t s) {
+                      int H, int NODES, int V, int blank, int bos, const int32_t* frame0, hipStream_t s,
+                      const SyncIlm* il = nullptr) {
     const int BW = B * W;
     const bool cached = V <= 256 * SB_VPT;
-    if (!fu) {
-        if (cached) hipLaunchKernelGGL(sync_row_topw<true>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
-        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
+    auto plain_select = [&] {
         if constexpr (STREAM)
             hipLaunchKernelGGL(sync_stream_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H,
                                NODES, blank, bos, frame0);
         else
             hipLaunchKernelGGL(sync_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H, NODES,
                                blank, bos);
+    };
+    if (il) {
+        const SyncFuse none{};
+        const SyncFuse& f = fu ? fu->f : none;
+        auto go = [&](auto lm_tag, auto bias_tag) {
+            constexpr bool LM = decltype(lm_tag)::value, BIAS = decltype(bias_tag)::value;
+            const float* lz = fu ? fu->lmu.logits : nullptr;
+            if (cached)
+                hipLaunchKernelGGL((sync_row_topw_ilm<true, LM, BIAS>), dim3(BW), dim3(256), 0, s, q, f, u.logits, lz,
+                                   il->logits, il->w, t, W, V, blank);
+            else
+                hipLaunchKernelGGL((sync_row_topw_ilm<false, LM, BIAS>), dim3(BW), dim3(256), 0, s, q, f, u.logits, lz,
+                                   il->logits, il->w, t, W, V, blank);
+            if constexpr (LM || BIAS)
+                hipLaunchKernelGGL((sync_select_fused<STREAM, LM, BIAS>), dim3(B), dim3(256), 0, s, q, f, u.h_new, u.c_new,
+                                   (const float*)fu->lmu.h_new, (const float*)fu->lmu.c_new, t, cur, W, B, L, H, NODES,
+                                   blank, bos, frame0);
+            else
+                plain_select();
+        };
+        const bool lm = fu && fu->lm, bias = fu && fu->bias;
+        if (lm && bias) go(std::true_type{}, std::true_type{});
+        else if (lm) go(std::true_type{}, std::false_type{});
+        else if (bias) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+        return;
+    }
+    if (!fu) {
+        if (cached) hipLaunchKernelGGL(sync_row_topw<true>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
+        else hipLaunchKernelGGL(sync_row_topw<false>, dim3(BW), dim3(256), 0, s, q, u.logits, t, W, V);
+        plain_select();
         return;
     }
     auto go = [&](auto lm_tag, auto bias_tag) {
@@ -695,13 +817,22 @@ void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u
 
 }  // namespace
 
+// ilm_weight null: the size of the _fusion form; else ILME's buffers behind it
+extern "C" size_t edgedict_sync_beam_workspace_bytes_ilme(int dtype, int B, int T, int J, int V, int E, int L, int H,
+                                                          int P2, int W, const edgedict_beam_lm_t* lm,
+                                                          const edgedict_beam_bias_t* bias, const double* ilm_weight) {
+    if (!sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W) || !sync_fuse_dims_ok(lm, bias, V) || !sync_ilm_ok(ilm_weight))
+        return 0;
+    const size_t BW = (size_t)B * W, esz = dtype == ED_F32 ? 4 : 2;
+    const size_t plain = sync_layout(sync_dims(dtype, B * W, J, V, E, L, H, P2), B, W, T).total;
+    const size_t fuse = sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, esz, V, lm).total, BW, lm, bias).total;
+    return sync_ilm_layout(fuse, BW, esz, J, V, ilm_weight != nullptr).total;
+}
+
 extern "C" size_t edgedict_sync_beam_workspace_bytes_fusion(int dtype, int B, int T, int J, int V, int E, int L, int H,
                                                             int P2, int W, const edgedict_beam_lm_t* lm,
                                                             const edgedict_beam_bias_t* bias) {
-    if (!sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W) || !sync_fuse_dims_ok(lm, bias, V)) return 0;
-    const size_t BW = (size_t)B * W;
-    const size_t plain = sync_layout(sync_dims(dtype, B * W, J, V, E, L, H, P2), B, W, T).total;
-    return sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, dtype == ED_F32 ? 4 : 2, V, lm).total, BW, lm, bias).total;
+    return edgedict_sync_beam_workspace_bytes_ilme(dtype, B, T, J, V, E, L, H, P2, W, lm, bias, nullptr);
 }
 
 extern "C" size_t edgedict_sync_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
@@ -714,8 +845,8 @@ extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) 
     return sync_result_layout(B, W, max_tokens).total;
 }
 
-// lm / bias null: the plain search, launch for launch
-extern "C" int edgedict_sync_beam_search_fusion(
+// lm / bias / ilm_weight null: the plain search, launch for launch;  ilm_weight null: the _fusion search, launch for launch
+extern "C" int edgedict_sync_beam_search_ilme(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
     const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
     const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
@@ -723,7 +854,7 @@ extern "C" int edgedict_sync_beam_search_fusion(
     const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
     int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
     int32_t* nhyp_host, double* logp_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-    void* workspace, void* result, void* stream_) {
+    const double* ilm_weight, void* workspace, void* result, void* stream_) {
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_beam_search: bad dtype");
     ED_CHECK_ARG(W >= 1 && W <= SB_MAXW, "sync_beam_search: beam width W = %d outside [1, %d]", W, SB_MAXW);
     ED_CHECK_ARG(T > 0, "sync_beam_search: T = %d frames (must be > 0)", T);
@@ -743,6 +874,7 @@ extern "C" int edgedict_sync_beam_search_fusion(
         maxlen = std::max(maxlen, lens_host[b]);
     }
     if (int rc = sync_fuse_check(lm, bias, V, "sync_beam_search")) return rc;
+    if (int rc = sync_ilm_check(ilm_weight, "sync_beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     const int BW = B * W, NODES = T * W;
     // the step's network: B * W rows whose joint rows are gathered per frame, J apart
@@ -750,7 +882,7 @@ extern "C" int edgedict_sync_beam_search_fusion(
     SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, nullptr, (long long)J, 0, BW, J, W1d, ldw1, b1, P2, W2, b2, V,
                   {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, 0, NODES};
     const SyncWs w = sync_layout(net, B, W, T);
-    const StepBufs u = bind(p + w.step_at, w.step);
+    StepBufs u = bind(p + w.step_at, w.step);
     net.E1 = p + w.e1g;
     SyncPtrs q{};
     q.logp = at<double>(p, w.logp);
@@ -794,6 +926,16 @@ extern "C" int edgedict_sync_beam_search_fusion(
         hipLaunchKernelGGL(sync_init_fused, dim3((BW + 255) / 256), dim3(256), 0, s, fusion.f, BW);
     }
     const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    SyncIlm ilm{};
+    const SyncIlm* il = nullptr;
+    if (ilm_weight) {
+        const size_t fuse_end =
+            sync_fuse_rows_layout(sync_fuse_step_layout(w.total, BW, net.esz, V, lm).total, BW, lm, bias).total;
+        const SyncIlmWs ia = sync_ilm_layout(fuse_end, BW, net.esz, J, V, true);
+        ilm = sync_ilm_bind(p, ia, *ilm_weight, fused, BW, V, u);
+        il = &ilm;
+        ED_CHECK_HIP(hipMemsetAsync(p + ia.zero_row, 0, (size_t)J * net.esz, s));
+    }
     int cur = 0;
     for (int t = 0; t < maxlen; ++t) {
         dispatch(dtype, [&](auto tag) {
@@ -801,14 +943,12 @@ extern "C" int edgedict_sync_beam_search_fusion(
             hipLaunchKernelGGL(sync_gather<ET>, dim3(ed_grid_for((long long)BW * J, 256)), dim3(256), 0, s, (const ET*)E1,
                                e_row_stride, e_frame_stride, t, (ET*)(p + w.e1g), BW, W, J);
         });
-        int rc;
-        if (fused) rc = ed_decode_fused_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
-        else rc = ed_decode_composed_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
+        int rc = sync_step(fused, net, q.hs[cur], q.cs[cur], u, il, s);
         if (rc) return rc;
         if (fu && fu->lm &&
             (rc = ed_decode_lm_step(dtype, BW, fu->lm_net, fu->f.lm_hs[cur], fu->f.lm_cs[cur], fu->lmu, s)))
             return rc;
-        sync_launch_pick<false>(q, fu, u, t, cur, W, B, L, H, NODES, V, blank, bos, nullptr, s);
+        sync_launch_pick<false>(q, fu, u, t, cur, W, B, L, H, NODES, V, blank, bos, nullptr, s, il);
         cur ^= 1;
     }
     // results: one read at the end - lengths and scores first, then only the used columns
@@ -841,6 +981,21 @@ extern "C" int edgedict_sync_beam_search_fusion(
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;
+}
+
+extern "C" int edgedict_sync_beam_search_fusion(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
+    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
+    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
+    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
+    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
+    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
+    int32_t* nhyp_host, double* logp_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+    void* workspace, void* result, void* stream_) {
+    return edgedict_sync_beam_search_ilme(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
+                                          W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
+                                          W, tokens_host, frames_host, token_logp_host, max_tokens, ntokens_host,
+                                          nhyp_host, logp_host, lm, bias, nullptr, workspace, result, stream_);
 }
 
 extern "C" int edgedict_sync_beam_search(
@@ -1106,14 +1261,22 @@ extern "C" size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, i
     return edgedict_sync_stream_state_bytes_fusion(S, L, H, W, node_capacity, nullptr, nullptr);
 }
 
+// ilm_weight null: the size of the _fusion form; else ILME's buffers behind it.  (The persistent state has no ILME part.)
+extern "C" size_t edgedict_sync_stream_workspace_bytes_ilme(int dtype, int S, int J, int V, int E, int L, int H, int P2,
+                                                            int W, int node_capacity, const edgedict_beam_lm_t* lm,
+                                                            const edgedict_beam_bias_t* bias, const double* ilm_weight) {
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) ||
+        !sync_fuse_dims_ok(lm, bias, V) || !sync_ilm_ok(ilm_weight))
+        return 0;
+    const size_t SW = (size_t)S * W, esz = dtype == ED_F32 ? 4 : 2;
+    const size_t plain = sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
+    return sync_ilm_layout(sync_fuse_step_layout(plain, SW, esz, V, lm).total, SW, esz, J, V, ilm_weight != nullptr).total;
+}
+
 extern "C" size_t edgedict_sync_stream_workspace_bytes_fusion(int dtype, int S, int J, int V, int E, int L, int H, int P2,
                                                               int W, int node_capacity, const edgedict_beam_lm_t* lm,
                                                               const edgedict_beam_bias_t* bias) {
-    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) ||
-        !sync_fuse_dims_ok(lm, bias, V))
-        return 0;
-    const size_t plain = sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
-    return sync_fuse_step_layout(plain, (size_t)S * W, dtype == ED_F32 ? 4 : 2, V, lm).total;
+    return edgedict_sync_stream_workspace_bytes_ilme(dtype, S, J, V, E, L, H, P2, W, node_capacity, lm, bias, nullptr);
 }
 
 extern "C" size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
@@ -1180,15 +1343,15 @@ extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_c
                                              stream_);
 }
 
-// lm / bias null: the plain advance, launch for launch
-extern "C" int edgedict_sync_stream_advance_fusion(
+// lm / bias / ilm_weight null: the plain advance, launch for launch;  ilm_weight null: the _fusion advance
+extern "C" int edgedict_sync_stream_advance_ilme(
     int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
     const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
     const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
     const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
     int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* workspace,
-    void* stream_) {
+    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, const double* ilm_weight, void* state,
+    void* workspace, void* stream_) {
     const int NC = node_capacity;
     ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_stream_advance: bad dtype");
     SYNC_STREAM_CHECK_SHAPE("sync_stream_advance", S, L, H, W, NC);
@@ -1218,6 +1381,7 @@ extern "C" int edgedict_sync_stream_advance_fusion(
     ED_CHECK_ARG(cols <= max_commit, "sync_stream_advance: max_commit = %d, this advance may commit %d tokens",
                  max_commit, cols);
     if (int rc = sync_fuse_check(lm, bias, V, "sync_stream_advance")) return rc;
+    if (int rc = sync_ilm_check(ilm_weight, "sync_stream_advance")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     const int SW = S * W;
     char* p = (char*)workspace;
@@ -1245,6 +1409,15 @@ extern "C" int edgedict_sync_stream_advance_fusion(
 
     ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
     const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    SyncIlm ilm{};
+    const SyncIlm* il = nullptr;
+    if (ilm_weight) {
+        const SyncIlmWs ia =
+            sync_ilm_layout(sync_fuse_step_layout(w.total, SW, net.esz, V, lm).total, SW, net.esz, J, V, true);
+        ilm = sync_ilm_bind(p, ia, *ilm_weight, fused, SW, V, u);
+        il = &ilm;
+        if (maxlen > 0) ED_CHECK_HIP(hipMemsetAsync(p + ia.zero_row, 0, (size_t)J * net.esz, s));
+    }
     int cur = *parity_host;
     for (int t = 0; t < maxlen; ++t) {
         dispatch(dtype, [&](auto tag) {
@@ -1252,14 +1425,12 @@ extern "C" int edgedict_sync_stream_advance_fusion(
             hipLaunchKernelGGL(sync_gather<ET>, dim3(ed_grid_for((long long)SW * J, 256)), dim3(256), 0, s, (const ET*)E1,
                                e_row_stride, e_frame_stride, t, (ET*)(p + w.e1g), SW, W, J);
         });
-        int rc;
-        if (fused) rc = ed_decode_fused_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
-        else rc = ed_decode_composed_beam_step(net, net.E1, q.hs[cur], q.cs[cur], u, s);
+        int rc = sync_step(fused, net, q.hs[cur], q.cs[cur], u, il, s);
         if (rc) return rc;
         if (fu && fu->lm &&
             (rc = ed_decode_lm_step(dtype, SW, fu->lm_net, fu->f.lm_hs[cur], fu->f.lm_cs[cur], fu->lmu, s)))
             return rc;
-        sync_launch_pick<true>(q, fu, u, t, cur, W, S, L, H, NC, V, blank, bos, (const int32_t*)frames_done, s);
+        sync_launch_pick<true>(q, fu, u, t, cur, W, S, L, H, NC, V, blank, bos, (const int32_t*)frames_done, s, il);
         cur ^= 1;
     }
     hipLaunchKernelGGL(sync_stream_compact, dim3(S), dim3(64), 0, s, q, frames_done, at<long long>(st, a.n_committed),
@@ -1273,6 +1444,20 @@ extern "C" int edgedict_sync_stream_advance_fusion(
     const int32_t* rec = (const int32_t*)commit_host;
     for (int b = 0; b < S; ++b) live_host[b] = rec[(size_t)b * ((size_t)max_commit + 1) * 4 + 1];
     return ED_OK;
+}
+
+extern "C" int edgedict_sync_stream_advance_fusion(
+    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
+    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
+    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
+    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* workspace,
+    void* stream_) {
+    return edgedict_sync_stream_advance_ilme(dtype, E1, e_row_stride, e_frame_stride, S, T, n_frames_host, J, W1d, ldw1,
+                                             b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
+                                             blank, bos, W, node_capacity, live_host, parity_host, commit_host,
+                                             max_commit, lm, bias, nullptr, state, workspace, stream_);
 }
 
 extern "C" int edgedict_sync_stream_advance(

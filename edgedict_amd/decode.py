@@ -63,6 +63,13 @@ is sorted by it; the CTC score itself is kept in ``NBestResult.ctc_logp``.  With
 UNSKIPPED encoder output.  ``Transducer.rescore_nbest`` does the same to lists obtained elsewhere (``ctc_beam_search``,
 a streaming search's ``nbest()``).  No length normalisation, no LM term, no CTC prefix score inside the frame loop.
 None launches nothing new.
+
+``ilm_weight=weight`` (keyword only, on ``sync_beam_search_fusion``, ``sync_beam_search_nbest``, the ``_enc`` / ``_rows``
+forms and ``StreamingSyncFusionBeamSearch``): internal-LM estimation.  The log-probabilities of the transducer's own
+prior - the log-softmax over the non-blank symbols of the joint on an all-zero encoder row - are subtracted from every
+non-blank candidate's score inside the frame loop (csrc/decode_sync.hip, csrc/decode_fused.hip), with or without
+``lm=`` / ``bias=``.  ``ilm_logits`` is the raw kernel call, ``Transducer.ilm_logprobs`` / ``ilm_score`` score a text
+with the internal LM (csrc/ilm_score.hip).  Not for the best-first searches.  None launches nothing new.
 """
 import ctypes
 
@@ -687,6 +694,73 @@ def _check_sync_fusion(model, lm, lm_weight, bias):
     check_bias_args(bias, _vocab(model), False)
 
 
+def _check_ilm_weight(ilm_weight):
+    """``ilm_weight`` of the ``sync_beam_search*`` entry points: None (no internal-LM estimation) or a finite number
+    ``>= 0``, else ``ValueError`` (raised before anything is launched).  Returns None or the weight as a ``c_double``."""
+    if ilm_weight is None:
+        return None
+    ok = isinstance(ilm_weight, (int, float, np.integer, np.floating)) and not isinstance(ilm_weight, bool)
+    if not ok or not np.isfinite(ilm_weight) or ilm_weight < 0:
+        raise ValueError("sync_beam_search: ilm_weight = %r must be a finite number >= 0 (or None)" % (ilm_weight,))
+    return ctypes.c_double(float(ilm_weight))
+
+
+def _no_ilm(ilm_weight, what):
+    """The best-first searches have another expand kernel: internal-LM estimation is the frame-synchronous search's."""
+    if ilm_weight is not None:
+        raise ValueError("%s: ilm_weight is not supported here (internal-LM estimation is in sync_beam_search*)" % what)
+
+
+def ilm_logits(model, dec_rows):
+    """The internal LM's logits, fp32 [R, V], of R rows of prediction-network output ``dec_rows`` [R, P2] (compute dtype,
+    on the device): the joint evaluated on an all-zero encoder row, ``tanh(act(d W1d^T + b1)) W2^T + b2``, by the kernels
+    the frame-synchronous search's step uses for this model (csrc/ilm_score.hip).  The raw kernel call behind
+    ``Transducer.ilm_logprobs`` and what ``sync_beam_search*(ilm_weight=)`` subtracts (there as a log-softmax over the
+    non-blank symbols)."""
+    _lib.require_cuda(dec_rows)
+    net = _SearchNet(model, dec_rows.dtype)
+    if dec_rows.dim() != 2 or dec_rows.shape[1] != net.P2:
+        raise ValueError("ilm_logits: dec_rows must be [R, P2=%d]" % net.P2)
+    dec_rows = dec_rows.contiguous()
+    R = dec_rows.shape[0]
+    out = torch.empty(R, net.V, dtype=torch.float32, device=dec_rows.device)
+    if R == 0:
+        return out
+    lib = _lib.load()
+    cdc = dtype_code(dec_rows.dtype)
+    ws = torch.empty(lib.edgedict_ilm_workspace_bytes(cdc, R, net.J), dtype=torch.uint8, device=dec_rows.device)
+    w1d = net.w1c[:, net.w1c.shape[1] - net.P2:]
+    rc = lib.edgedict_ilm_logits(cdc, _lib.ptr(dec_rows), R, net.P2, net.J, _lib.ptr(w1d),
+                                 ctypes.c_longlong(net.w1c.stride(0)), _lib.ptr(net.b1), _lib.ptr(net.w2c),
+                                 _lib.ptr(net.b2), net.V, dtype_code(net.emb.dtype), net.E, net.H, _lib.ptr(out),
+                                 _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(rc, "ilm_logits")
+    return out
+
+
+def ilm_logprobs(model, ys, ylen):
+    """``Transducer.ilm_logprobs``: fp32 [B, U] on the device, nothing read back."""
+    dev = model.decoder.embed.weight.device
+    ys = torch.as_tensor(ys)
+    if ys.dim() != 2:
+        raise ValueError("ilm_logprobs: ys must be [B, U] token ids")
+    B, U = ys.shape
+    ylen = torch.as_tensor(ylen)
+    if ylen.shape != (B,):
+        raise ValueError("ilm_logprobs: ylen must be [B]")
+    out = torch.zeros(B, U, dtype=torch.float32, device=dev)
+    if B == 0 or U == 0:
+        return out
+    tgt = ys.to(device=dev, dtype=torch.int32).contiguous()
+    yl = ylen.to(device=dev, dtype=torch.int32).contiguous()
+    h_dec, _ = model.decoder(tgt)                       # BOS in front: row u is the network's output after y_<u
+    logits = ilm_logits(model, h_dec[:, :U].reshape(B * U, -1))
+    rc = _lib.load().edgedict_ilm_logprobs(_lib.ptr(logits), _lib.ptr(tgt), _lib.ptr(yl), B, U, logits.shape[1],
+                                           int(model.blank), _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "ilm_logprobs")
+    return out
+
+
 def _sync_encode(model, xs, xlen, W):
     """The argument rules of the ``sync_beam_search*`` entry points, then the encoder: (enc_out, lens)."""
     _check_sync_width(W)
@@ -724,7 +798,7 @@ def sync_beam_search(model, xs, xlen=None, W=10):
 
 
 def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
-                            bias=None, skip_blank=None):
+                            bias=None, skip_blank=None, ilm_weight=None):
     """``sync_beam_search`` with LM shallow fusion and contextual biasing (without either: ``sync_beam_search`` itself,
     launch for launch).
 
@@ -742,14 +816,23 @@ def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=No
     ``skip_blank``: a threshold in (0, 1] - the search then runs only on the encoder frames whose CTC blank posterior
     is at most the threshold (``skip_blank_frames``; the model needs a CTC head).  None: nothing of this runs.
 
+    ``ilm_weight``: internal-LM estimation (ILME; a finite number ``>= 0``, with or without ``lm`` / ``bias``).  The
+    transducer's prediction network and joint hold a language model of the training transcripts; its log-probabilities
+    ``lp_ilm_i`` - the log-softmax over the NON-BLANK symbols of the joint evaluated on an all-zero encoder row - are
+    subtracted while an external LM is added: a non-blank candidate scores
+    ``(((logp_i + lp_i[k]) + (lm_weight * lp_lm_i[k] + length_bonus)) - ilm_weight * lp_ilm_i[k]) + D(s_i, k)``.
+    ``Transducer.ilm_score`` gives the internal LM's score of a text, to choose the weight by.  No launch more per frame
+    on the fused step, two more on the composed one.  ``ilm_weight=0.0`` runs the ILME kernels and is bit-equal to the
+    call without it; None (the default) launches exactly the kernels of the call without it.
+
     Returns ``(list of int64 arrays (tokens, no blanks), fp64 tensor [B] = -log p)`` of the best hypothesis per
     utterance, in ``beam_search_batch``'s types."""
     return _best_of(sync_beam_search_nbest(model, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                           lm_bos=lm_bos, bias=bias, skip_blank=skip_blank))
+                                           lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ilm_weight=ilm_weight))
 
 
 def sync_beam_search_nbest(model, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
-                           bias=None, skip_blank=None, ctc_rescore=None):
+                           bias=None, skip_blank=None, ctc_rescore=None, ilm_weight=None):
     """``sync_beam_search`` returning, per utterance, the final beam as an ``NBestResult`` **already ranked**: ``logp``
     descending (ties keep beam order), at most W hypotheses with distinct token sequences, entry 0 what
     ``sync_beam_search`` returns.  ``frames[i]``: the encoder frame on which each token's tree node was created
@@ -759,8 +842,10 @@ def sync_beam_search_nbest(model, xs, xlen=None, W=10, *, lm=None, lm_weight=Non
     ``skip_blank``: as in ``sync_beam_search_fusion``; ``frames`` stay in the original frame numbering, and an utterance
     whose frames are all dropped is an utterance of 0 frames.  ``ctc_rescore``: a weight ``>= 0`` - the ranked list
     then goes through ``ctc_rescore`` (the module-level function; on the unskipped encoder output) before it is
-    returned: ``ctc_logp`` filled, ``logp`` the combined score, ranked by it.  None: nothing of this runs."""
+    returned: ``ctc_logp`` filled, ``logp`` the combined score, ranked by it.  None: nothing of this runs.
+    ``ilm_weight``: internal-LM estimation, as in ``sync_beam_search_fusion``."""
     _check_sync_fusion(model, lm, lm_weight, bias)
+    _check_ilm_weight(ilm_weight)
     if skip_blank is not None:
         _check_skip(model, skip_blank)
     if ctc_rescore is not None:
@@ -771,24 +856,27 @@ def sync_beam_search_nbest(model, xs, xlen=None, W=10, *, lm=None, lm_weight=Non
         return _rescored(model, enc_out, lens,
                          sk.restore(sync_beam_search_nbest_enc(model, sk.enc_out, sk.lens, W, lm=lm,
                                                                lm_weight=lm_weight, length_bonus=length_bonus,
-                                                               lm_bos=lm_bos, bias=bias)), ctc_rescore)
+                                                               lm_bos=lm_bos, bias=bias, ilm_weight=ilm_weight)),
+                         ctc_rescore)
     return sync_beam_search_nbest_enc(model, enc_out, lens, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                      lm_bos=lm_bos, bias=bias, ctc_rescore=ctc_rescore)
+                                      lm_bos=lm_bos, bias=bias, ctc_rescore=ctc_rescore, ilm_weight=ilm_weight)
 
 
 def sync_beam_search_enc(model, enc_out, lens=None, W=10,
-                         *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+                         *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, ilm_weight=None):
     """``sync_beam_search`` over a given encoder output ``enc_out`` [B, T, P] (compute dtype) with ``lens`` (host int,
     encoder frames per utterance; None: all T)."""
-    return _best_of(sync_beam_search_nbest_enc(model, enc_out, lens, W,
-                                               lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
+    return _best_of(sync_beam_search_nbest_enc(model, enc_out, lens, W, lm=lm, lm_weight=lm_weight,
+                                               length_bonus=length_bonus, lm_bos=lm_bos, bias=bias,
+                                               ilm_weight=ilm_weight))
 
 
-def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10,
-                               *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, ctc_rescore=None):
+def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
+                               bias=None, ctc_rescore=None, ilm_weight=None):
     """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``.  ``ctc_rescore``: as there,
     the head scoring this ``enc_out``."""
     _check_sync_fusion(model, lm, lm_weight, bias)
+    _check_ilm_weight(ilm_weight)
     _check_sync_width(W)
     if ctc_rescore is not None:
         _check_rescore(model, ctc_rescore)
@@ -798,24 +886,26 @@ def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10,
     return _rescored(model, enc_out, lens,
                      sync_beam_search_nbest_rows(model, joint_rows(model, enc_out), B, T, P, lens, W, lm=lm,
                                                  lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos,
-                                                 bias=bias), ctc_rescore)
+                                                 bias=bias, ilm_weight=ilm_weight), ctc_rescore)
 
 
 def sync_beam_search_rows(model, E1, B, T, P, lens=None, W=10,
-                          *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+                          *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, ilm_weight=None):
     """``sync_beam_search_enc`` from the joint's encoder rows ``E1`` [B * T, J] (``joint_rows``) of an encoder output of
     width P."""
-    return _best_of(sync_beam_search_nbest_rows(model, E1, B, T, P, lens, W,
-                                                lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
+    return _best_of(sync_beam_search_nbest_rows(model, E1, B, T, P, lens, W, lm=lm, lm_weight=lm_weight,
+                                                length_bonus=length_bonus, lm_bos=lm_bos, bias=bias,
+                                                ilm_weight=ilm_weight))
 
 
 def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=None,
-                                *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+                                *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None, ilm_weight=None):
     """``sync_beam_search_nbest_enc`` from the joint's encoder rows, as ``sync_beam_search_rows``.  ``max_tokens``
     bounds a hypothesis' length (default T: one token per frame at most); a longer one raises, it is never cut."""
     from .bias import active
     from .lm import FusionLM
     _check_sync_fusion(model, lm, lm_weight, bias)
+    ilm = _check_ilm_weight(ilm_weight)
     _check_sync_width(W)
     _lib.require_cuda(E1)
     W = int(W)
@@ -834,9 +924,13 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     fused = flm is not None or bref is not None         # else: the plain entry points, untouched
     fargs = (flm.ref() if flm is not None else None, bref)
     dims = (dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W)
-    nbytes = (lib.edgedict_sync_beam_workspace_bytes_fusion(*dims, *fargs) if fused
-              else lib.edgedict_sync_beam_workspace_bytes(*dims))
-    if fused and nbytes == 0:
+    iarg = None if ilm is None else ctypes.byref(ilm)       # (None: the entry points of the call without ilm_weight)
+    if ilm is not None:
+        nbytes = lib.edgedict_sync_beam_workspace_bytes_ilme(*dims, *fargs, iarg)
+    else:
+        nbytes = (lib.edgedict_sync_beam_workspace_bytes_fusion(*dims, *fargs) if fused
+                  else lib.edgedict_sync_beam_workspace_bytes(*dims))
+    if (fused or ilm is not None) and nbytes == 0:
         raise ValueError("sync_beam_search: shapes out of range (the LM's hidden width must be a multiple of 4)")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     result = torch.empty(lib.edgedict_sync_beam_result_bytes(B, W, MT), dtype=torch.uint8, device=dev)
@@ -852,7 +946,9 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
             *net.args(P), int(model.blank), int(BOS), W, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp),
             vp(logp))
     tail = (_lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
-    if fused:
+    if ilm is not None:
+        rc = lib.edgedict_sync_beam_search_ilme(*args, *fargs, iarg, *tail)
+    elif fused:
         rc = lib.edgedict_sync_beam_search_fusion(*args, *fargs, *tail)
     else:
         rc = lib.edgedict_sync_beam_search(*args, *tail)
@@ -1240,9 +1336,11 @@ class StreamingSyncBeamSearch:
     def __init__(self, model, n_streams, W=10, node_capacity=None):
         self._setup(model, n_streams, W, node_capacity)
 
-    def _setup(self, model, n_streams, W, node_capacity, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None):
+    def _setup(self, model, n_streams, W, node_capacity, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None,
+               ilm_weight=None):
         from .bias import active
         _check_sync_fusion(model, lm, lm_weight, bias)
+        self._ilm = _check_ilm_weight(ilm_weight)       # None, or the weight as the c_double the advance points at
         _check_sync_width(W)
         if n_streams < 1:
             raise ValueError("n_streams must be >= 1")
@@ -1298,6 +1396,9 @@ class StreamingSyncBeamSearch:
         else:
             sbytes = lib.edgedict_sync_stream_state_bytes_fusion(*sdims, *fargs)
             wbytes = lib.edgedict_sync_stream_workspace_bytes_fusion(*wdims, *fargs)
+        if self._ilm is not None:       # (ILME has no part in the state)
+            wbytes = lib.edgedict_sync_stream_workspace_bytes_ilme(*wdims, *(fargs or (None, None)),
+                                                                   ctypes.byref(self._ilm))
         if sbytes == 0 or wbytes == 0:
             raise ValueError("StreamingSyncBeamSearch: shapes out of range (H and the LM's hidden width must be "
                              "multiples of 4)")
@@ -1413,7 +1514,10 @@ class StreamingSyncBeamSearch:
                 ctypes.byref(self._parity), vp(self._commit_buf), self.NC)
         tail = (_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
         flm, fargs = self._fusion()
-        if fargs is None:
+        if self._ilm is not None:
+            rc = _lib.load().edgedict_sync_stream_advance_ilme(*args, *(fargs or (None, None)), ctypes.byref(self._ilm),
+                                                               *tail)
+        elif fargs is None:
             rc = _lib.load().edgedict_sync_stream_advance(*args, *tail)
         else:
             rc = _lib.load().edgedict_sync_stream_advance_fusion(*args, *fargs, *tail)
@@ -1500,11 +1604,15 @@ class StreamingSyncFusionBeamSearch(StreamingSyncBeamSearch):
     cleared by ``reset`` and untouched by compaction; the LM's root token is ``lm_bos`` for the empty sequence only
     (``len`` counts committed tokens too).  The bias list is shared by all streams; ``set_bias`` swaps it between
     utterances.  Without an LM and without a list (or with an empty one) the plain kernels run until ``set_bias`` gives
-    the search a list.  With an LM a frame is ``6 + L + lm.nlayers + 1`` launches on the fused steps."""
+    the search a list.  With an LM a frame is ``6 + L + lm.nlayers + 1`` launches on the fused steps.
+
+    ``ilm_weight``: internal-LM estimation as in ``sync_beam_search_fusion``, with or without ``lm`` / ``bias``;
+    ``nbest()`` is then bit for bit ``sync_beam_search_nbest_rows(..., ilm_weight=)``.  It carries no per-row state: the
+    persistent state keeps its layout, and a frame its launch count on the fused step."""
 
     def __init__(self, model, n_streams, W=10, node_capacity=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                 lm_bos=1, bias=None):
-        self._setup(model, n_streams, W, node_capacity, lm, lm_weight, length_bonus, lm_bos, bias)
+                 lm_bos=1, bias=None, ilm_weight=None):
+        self._setup(model, n_streams, W, node_capacity, lm, lm_weight, length_bonus, lm_bos, bias, ilm_weight)
 
 
 def emission_times(frames, flags, time_reduction=2):

@@ -1423,52 +1423,75 @@ class Transducer(nn.Module):
         return greedy_decode_batch(self, xs, xlen)
 
     def beam_search(self, xs, xlen=None, W=10, prefix=False, max_expansions=None, *, lm=None, lm_weight=None,
-                    length_bonus=0.0, lm_bos=1, bias=None, skip_blank=None):
+                    length_bonus=0.0, lm_bos=1, bias=None, skip_blank=None, ilm_weight=None):
         """Beam search of the reference's legacy model (models.py:121-202), batched; see
         ``decode.beam_search_batch``.  ``prefix=True`` is its prefix-sum variant (:145-161).  ``lm`` (an
         ``edgedict_amd.lm.LMModel``) with ``lm_weight`` adds LM shallow fusion, ``bias`` (an
         ``edgedict_amd.bias.ContextGraph``) contextual biasing towards a phrase list (``decode`` module docstring).
         ``skip_blank`` (a threshold in (0, 1]; needs the CTC head, not with ``prefix=True``) searches only the frames
-        whose CTC blank posterior is at most the threshold (``decode.skip_blank_frames``)."""
-        from .decode import beam_search_batch
+        whose CTC blank posterior is at most the threshold (``decode.skip_blank_frames``).  ``ilm_weight`` raises
+        ``ValueError``: internal-LM estimation is the frame-synchronous search's (``sync_beam_search``)."""
+        from .decode import _no_ilm, beam_search_batch
+        _no_ilm(ilm_weight, "beam_search")
         return beam_search_batch(self, xs, xlen, W, max_expansions, prefix=prefix, lm=lm, lm_weight=lm_weight,
                                  length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, skip_blank=skip_blank)
 
     def beam_search_nbest(self, xs, xlen=None, W=10, max_expansions=None, *, lm=None, lm_weight=None, length_bonus=0.0,
-                          lm_bos=1, bias=None, skip_blank=None, ctc_rescore=None):
+                          lm_bos=1, bias=None, skip_blank=None, ctc_rescore=None, ilm_weight=None):
         """``beam_search`` (``prefix=False``) returning per utterance a ``decode.NBestResult``: the whole list B of the
         last frame in B's order, every hypothesis with its tokens, the encoder frame each token was emitted on, each
         token's score increment, and its log p; entry 0 is what ``beam_search`` returns.  ``skip_blank``: as in
         ``beam_search``, the frames reported in the original numbering.  ``ctc_rescore`` (a weight ``>= 0``; needs the
         CTC head): the list is rescored by the head - ``ctc_logp`` filled, ``logp = logp + weight * ctc_logp``, sorted
-        by it (``decode.ctc_rescore``).  See ``decode.beam_search_nbest``."""
-        from .decode import beam_search_nbest
+        by it (``decode.ctc_rescore``).  ``ilm_weight`` raises, as in ``beam_search``.  See
+        ``decode.beam_search_nbest``."""
+        from .decode import _no_ilm, beam_search_nbest
+        _no_ilm(ilm_weight, "beam_search_nbest")
         return beam_search_nbest(self, xs, xlen, W, max_expansions, lm=lm, lm_weight=lm_weight,
                                  length_bonus=length_bonus, lm_bos=lm_bos, bias=bias, skip_blank=skip_blank,
                                  ctc_rescore=ctc_rescore)
 
     @torch.no_grad()
     def sync_beam_search(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None,
-                         skip_blank=None):
+                         skip_blank=None, ilm_weight=None):
         """Frame-synchronous beam search (one symbol per frame at most, all B x W hypotheses in one step per frame,
         equal sequences merged by log-add; ``1 <= W <= 32``): a different algorithm from ``beam_search``, several times
         fewer launches.  ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` / ``bias``: LM shallow fusion and
-        contextual biasing, as ``beam_search`` takes them; ``skip_blank``: blank-frame skipping, as there.  Returns
-        ``(seqs, scores)`` in ``beam_search``'s types.  See ``decode.sync_beam_search_fusion``."""
+        contextual biasing, as ``beam_search`` takes them; ``skip_blank``: blank-frame skipping, as there.
+        ``ilm_weight`` (a finite number ``>= 0``): internal-LM estimation - the model's own prior over the non-blank
+        symbols (``ilm_score``) is subtracted with this weight.  Returns ``(seqs, scores)`` in ``beam_search``'s types.
+        See ``decode.sync_beam_search_fusion``."""
         from .decode import sync_beam_search_fusion
         return sync_beam_search_fusion(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                       lm_bos=lm_bos, bias=bias, skip_blank=skip_blank)
+                                       lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ilm_weight=ilm_weight)
 
     @torch.no_grad()
     def sync_beam_search_nbest(self, xs, xlen=None, W=10, *, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1,
-                               bias=None, skip_blank=None, ctc_rescore=None):
+                               bias=None, skip_blank=None, ctc_rescore=None, ilm_weight=None):
         """``sync_beam_search`` returning per utterance the final beam as a ranked ``decode.NBestResult``; entry 0 is
         what ``sync_beam_search`` returns.  ``ctc_rescore`` (a weight ``>= 0``; needs the CTC head): the list is
-        rescored by the head and ranked by ``logp + weight * ctc_logp`` (``decode.ctc_rescore``).  See
-        ``decode.sync_beam_search_nbest``."""
+        rescored by the head and ranked by ``logp + weight * ctc_logp`` (``decode.ctc_rescore``).  ``ilm_weight``: as in
+        ``sync_beam_search``.  See ``decode.sync_beam_search_nbest``."""
         from .decode import sync_beam_search_nbest
         return sync_beam_search_nbest(self, xs, xlen, W, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                                      lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ctc_rescore=ctc_rescore)
+                                      lm_bos=lm_bos, bias=bias, skip_blank=skip_blank, ctc_rescore=ctc_rescore,
+                                      ilm_weight=ilm_weight)
+
+    @torch.no_grad()
+    def ilm_logprobs(self, ys, ylen):
+        """The internal LM's per-token log-probabilities of label sequences: fp32 [B, U] on the device,
+        ``out[b, u] = log P_ILM(ys[b, u] | ys[b, :u])`` for ``u < ylen[b]`` and exactly 0 behind it.  The prediction
+        network is teacher-forced from BOS; the internal LM of a position is the joint on an all-zero encoder row,
+        normalised over the NON-BLANK symbols (what ``sync_beam_search(ilm_weight=)`` subtracts).  A blank label gives
+        ``-inf``, one outside the vocabulary NaN.  Nothing is read back to the host."""
+        from .decode import ilm_logprobs
+        return ilm_logprobs(self, ys, ylen)
+
+    @torch.no_grad()
+    def ilm_score(self, ys, ylen):
+        """Per utterance ``sum_u log P_ILM(y_u | y_<u)``: fp32 [B] on the device, no host sync.  The internal LM's
+        perplexity of a text is ``exp(-ilm_score.sum() / ylen.sum())``: the number to choose ``ilm_weight`` by."""
+        return self.ilm_logprobs(ys, ylen).sum(dim=1)
 
     EVALUATE_SEARCHES = ("greedy", "ctc_greedy", "beam", "sync_beam")
     last_error_rate = None       # the metrics.ErrorRateResult of the last evaluate_step

@@ -451,12 +451,14 @@ class BatchedStreamSyncFusionBeamDecoder(BatchedStreamSyncBeamDecoder):
     """``BatchedStreamSyncBeamDecoder`` with ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` (LM shallow fusion)
     and ``bias`` (a contextual-biasing list, ``edgedict_amd.bias.ContextGraph``), as in
     ``decode.StreamingSyncFusionBeamSearch``; ``self.search.set_bias`` swaps the list between utterances.  After any
-    chunk ``nbest()`` is what the offline fused search over the stream's audio so far returns."""
+    chunk ``nbest()`` is what the offline fused search over the stream's audio so far returns.  ``ilm_weight``:
+    internal-LM estimation, as in ``decode.sync_beam_search_fusion``."""
 
     def __init__(self, transducer, flags, n_streams, W=10, node_capacity=None, dither=None, *, lm=None, lm_weight=None,
-                 length_bonus=0.0, lm_bos=1, bias=None):
+                 length_bonus=0.0, lm_bos=1, bias=None, ilm_weight=None):
         self._setup(transducer, flags, n_streams, W, node_capacity, dither,
-                    dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias))
+                    dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias,
+                         ilm_weight=ilm_weight))
 
 
 class PytorchStreamDecoder(StreamTransducerDecoder):

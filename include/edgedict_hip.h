@@ -1530,6 +1530,66 @@ int edgedict_sync_stream_advance_fusion(int dtype, const void* E1, long long e_r
                                         int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
                                         void* state, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Internal-LM estimation (ILME) in the frame-synchronous search, offline and streaming, and the internal LM as a scorer.
+ * The *_ilme entry points take the *_fusion ones' arguments with `ilm_weight` (a HOST double, or null) behind `bias`;
+ * with ilm_weight null they ARE the *_fusion calls (same kernels, same layouts, same bits), and lm / bias may be null as
+ * there.  The *_fusion entry points call these with null.
+ *
+ * For a row whose prediction-network output after its last token is d [P2], the internal LM's logits are the step's
+ * joint on an all-zero encoder row, z_ilm = tanh(act(d W1d^T + b1)) W2^T + b2 (act: the rounding to the compute dtype),
+ * and lp_ilm[k] = (z_ilm[k] - m) - log(sum_{v != blank} exp(z_ilm[v] - m)), m = max_{v != blank} z_ilm[v], in fp32.
+ * A non-blank candidate's score is, in fp64 without contraction and in this order,
+ *   c = logp_i + (double)lp_i[k];  c = c + (weight * (double)lp_lm_i[k] + length_bonus);
+ *   c = c - ilm_weight * (double)lp_ilm_i[k];  c = c + (held[goto(s_i, k)] - pend[s_i])
+ * (a term is absent when its feature is); blank keeps logp_i + lp_i[blank]; token_logp stays lp_i[k].  ilm_weight = 0
+ * runs the ILME kernels and is bit-equal to the call without it.  ILME carries no per-row state: the persistent state
+ * of a stream, its reset and its read are the *_fusion forms'.  Launches per frame: on the fused step none more (one
+ * joint-hidden kernel writes both hidden vectors, the logits kernel runs on 2 B W rows); on the composed step two more.
+ *
+ *   sync_beam_workspace_bytes_ilme / sync_stream_workspace_bytes_ilme   the *_fusion size + ILME's buffers (hidden vectors
+ *                                        [2 rows, J], fp32 logits [2 rows, V], a zero encoder row)
+ * Checked before anything is launched (-1 and a message): ilm_weight finite and >= 0.  The size queries return 0 then.
+ *
+ *   ilm_workspace_bytes(dtype, R, J)     scratch of ilm_logits for R rows (0 for arguments out of range)
+ *   ilm_logits      logits fp32 [R, V] = z_ilm of R rows `dec` [R, P2] (compute dtype), by the kernels the search's step
+ *                   uses for a network of these widths (emb_dtype, E, H pick the route as they do there)
+ *   ilm_logprobs    out fp32 [B, U]: lp_ilm[b, u][targets[b, u]] from logits [B * U, V] for u < ylen[b], exactly 0
+ *                   behind it (targets int32 [B, U], ylen int32 [B], both on the device).  A blank target gives -inf, one
+ *                   outside the vocabulary NaN.  One wave per row, no atomics: the same bits every run.
+ */
+size_t edgedict_sync_beam_workspace_bytes_ilme(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2, int W,
+                                               const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                               const double* ilm_weight);
+int edgedict_sync_beam_search_ilme(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B,
+                                   int T, const int32_t* lens_host, int J, const void* W1d, long long ldw1,
+                                   const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
+                                   int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
+                                   const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
+                                   const float* bp, int blank, int bos, int W, int32_t* tokens_host,
+                                   int32_t* frames_host, double* token_logp_host, int max_tokens,
+                                   int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                   const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                   const double* ilm_weight, void* workspace, void* result, void* stream);
+size_t edgedict_sync_stream_workspace_bytes_ilme(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
+                                                 int node_capacity, const edgedict_beam_lm_t* lm,
+                                                 const edgedict_beam_bias_t* bias, const double* ilm_weight);
+int edgedict_sync_stream_advance_ilme(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride,
+                                      int S, int T, const int32_t* n_frames_host, int J, const void* W1d,
+                                      long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
+                                      const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
+                                      const void* const* w_hh, const float* const* b_ih, const float* const* b_hh,
+                                      int H, const void* Wp, const float* bp, int blank, int bos, int W,
+                                      int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+                                      int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                                      const double* ilm_weight, void* state, void* workspace, void* stream);
+size_t edgedict_ilm_workspace_bytes(int dtype, int R, int J);
+int edgedict_ilm_logits(int dtype, const void* dec, int R, int P2, int J, const void* W1d, long long ldw1,
+                        const float* b1, const void* W2, const float* b2, int V, int emb_dtype, int E, int H,
+                        float* logits, void* workspace, void* stream);
+int edgedict_ilm_logprobs(const float* logits, const int32_t* targets, const int32_t* ylen, int B, int U, int V,
+                          int blank, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
