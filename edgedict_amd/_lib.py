@@ -54,45 +54,9 @@ def load():
                 "(hipcc, gfx950). There is no CPU/PyTorch fallback for the hot path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         lib.edgedict_last_error.restype = ctypes.c_char_p
-        lib.edgedict_rnnt_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_rnnt_workspace_view.restype = ctypes.c_void_p
-        lib.edgedict_ctc_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_ctc_workspace_view.restype = ctypes.c_void_p
-        lib.edgedict_ctc_score_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_ctc_beam_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_greedy_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_state_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_lm_struct_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_workspace_bytes_lm.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_state_bytes_lm.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_workspace_bytes_lm.restype = ctypes.c_size_t
-        lib.edgedict_beam_bias_struct_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_workspace_bytes_bias.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_state_bytes_bias.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_workspace_bytes_bias.restype = ctypes.c_size_t
-        lib.edgedict_beam_detail_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_nbest_result_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_detail_state_bytes.restype = ctypes.c_size_t
-        lib.edgedict_beam_stream_detail_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_beam_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_beam_result_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_state_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_result_bytes.restype = ctypes.c_size_t
-        lib.edgedict_sync_beam_workspace_bytes_fusion.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_state_bytes_fusion.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_workspace_bytes_fusion.restype = ctypes.c_size_t
-        lib.edgedict_sync_beam_workspace_bytes_ilme.restype = ctypes.c_size_t
-        lib.edgedict_sync_stream_workspace_bytes_ilme.restype = ctypes.c_size_t
-        lib.edgedict_ilm_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_stream_encoder_workspace_bytes.restype = ctypes.c_size_t
         lib.edgedict_blaslt_calls.restype = ctypes.c_longlong
-        lib.edgedict_gelu_groupnorm_bwd_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_lstm_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_stack_workspace_bytes.restype = ctypes.c_size_t
-        lib.edgedict_stack_struct_bytes.restype = ctypes.c_size_t
         lib.edgedict_aux_stream.restype = ctypes.c_void_p
         lib.edgedict_stack_error_words.restype = ctypes.c_void_p
         # the one entry point with double arguments: declared, so that Python floats arrive as doubles
@@ -103,7 +67,9 @@ def load():
             if not hasattr(lib, name):
                 raise RuntimeError("edgedict_amd: %s lacks symbol %s declared in the header"
                                    % (LIB_PATH, name))
-        if lib.edgedict_abi_version() != 1:
+            if name.endswith("_bytes"):     # every size query returns size_t
+                getattr(lib, name).restype = ctypes.c_size_t
+        if lib.edgedict_abi_version() != 2:
             raise RuntimeError("edgedict_amd: ABI version mismatch")
         _lib = lib
     return _lib

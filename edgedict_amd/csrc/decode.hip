@@ -151,21 +151,7 @@ int composed_joint(const SearchNet& net, const char* e1t, const void* dec, const
     return edgedict_gemm(dtype, ED_F32, u.hid, J, 1, net.W2, J, 1, u.logits, net.V, B, net.V, J, net.b2, nullptr, 0, 1, s);
 }
 
-// The argument checks the searches share, in the order they have always run: dtype, shape, null pointers, and for the
-// beam searches blank / bos.  shape_ok / ptrs_ok carry the caller's own conditions, shape_note the tail of its message.
-int check_net(const SearchNet& n, const char* what, bool shape_ok, const char* shape_note, bool ptrs_ok, bool beam) {
-    const LstmNet& p = n.pred;
-    ED_CHECK_ARG(n.dtype == ED_F32 || n.dtype == ED_BF16, "%s: bad dtype", what);
-    ED_CHECK_ARG(shape_ok && n.B > 0 && n.J > 0 && n.V > 0 && p.L > 0 && p.H > 0 && n.P2 > 0 && p.E > 0, "%s: bad shape%s",
-                 what, shape_note);
-    ED_CHECK_ARG(ptrs_ok && n.W1d && n.b1 && n.W2 && n.b2 && p.emb && p.w_ih && p.w_hh && p.b_ih && p.b_hh && p.Wo && p.bo,
-                 "%s: null pointer", what);
-    ED_CHECK_ARG(!beam || (n.blank >= 0 && n.blank < n.V && n.bos >= 0 && n.bos < n.V),
-                 "%s: blank/bos outside the vocabulary", what);
-    return ED_OK;
-}
-
-// the shapes alone, for the size queries
+// the shapes alone, for the greedy search's size query
 SearchNet net_dims(int dtype, int B, int J, int V, int E, int L, int H, int P2) {
     SearchNet n{};
     n.dtype = dtype; n.esz = dtype == ED_F32 ? 4 : 2;
@@ -1485,40 +1471,42 @@ int ed_decode_bias_check(const edgedict_beam_bias_t* bias, int V, int prefix, co
 extern "C" size_t edgedict_beam_lm_struct_bytes(void) { return sizeof(edgedict_beam_lm_t); }
 extern "C" size_t edgedict_beam_bias_struct_bytes(void) { return sizeof(edgedict_beam_bias_t); }
 
-extern "C" size_t edgedict_beam_workspace_bytes_bias(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                     int W, int max_expansions, int prefix,
-                                                     const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias) {
-    if (B <= 0 || W <= 0 || max_expansions <= 0) return 0;
-    SearchNet n = net_dims(dtype, B, J, V, E, L, H, P2);
-    n.W = W;
-    n.EM = max_expansions;
-    const size_t base = beam_layout(n, (size_t)(T < 0 ? 0 : T) * n.EM + 1, prefix, false).total;
-    return ws_total(base, n, lm, bias, true);
-}
-
-extern "C" size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                   int W, int max_expansions, int prefix, const edgedict_beam_lm_t* lm) {
-    return edgedict_beam_workspace_bytes_bias(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, lm, nullptr);
-}
-
-extern "C" size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L,
-                                                int H, int P2, int W, int max_expansions, int prefix) {
-    return edgedict_beam_workspace_bytes_lm(dtype, B, T, J, V, E, L, H, P2, W, max_expansions, prefix, nullptr);
+extern "C" size_t edgedict_search_struct_bytes(int which) {
+    return which == 0 ? sizeof(edgedict_search_net_t) : which == 1 ? sizeof(edgedict_search_opts_t) : 0;
 }
 
 namespace {
-// Both offline searches.  nb == null: edgedict_beam_search[_lm], B[0] through tokens_host / ntokens_host / score_host;
+// internal-LM estimation is the frame-synchronous search's alone: the expansion searches refuse it, their size queries
+// return 0
+int no_ilm(const edgedict_search_opts_t& o, const char* what) {
+    ED_CHECK_ARG(!o.ilm_weight, "%s: ilm_weight is not supported (internal-LM estimation is in sync_beam_search)", what);
+    return ED_OK;
+}
+}  // namespace
+
+extern "C" size_t edgedict_beam_workspace_bytes(const edgedict_search_net_t* pn, int B, int T, int W, int max_expansions,
+                                                int prefix, const edgedict_search_opts_t* opts) {
+    if (!pn || !search_ptrs_ok(pn, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (o.ilm_weight || B <= 0 || W <= 0 || max_expansions <= 0) return 0;
+    const SearchNet n = search_net_of(*pn, nullptr, 0, 0, B, W, max_expansions, 0);
+    const size_t base = beam_layout(n, (size_t)(T < 0 ? 0 : T) * n.EM + 1, prefix, false).total;
+    return ws_total(base, n, o.lm, o.bias, true);
+}
+
+namespace {
+// Both offline searches.  nb == null: edgedict_beam_search, B[0] through tokens_host / ntokens_host / score_host;
 // else edgedict_beam_search_nbest: the detail is kept per node and the whole list B is read through nb.
-int beam_search_run(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-    void* workspace, const NBestOut* nb, void* stream_) {
+int beam_search_run(const edgedict_search_net_t* pn, const void* E1, long long e_row_stride, long long e_frame_stride,
+                    int B, int T, const int32_t* lens_host, int W, int max_expansions, int prefix, int32_t* tokens_host,
+                    int max_tokens, int32_t* ntokens_host, double* score_host, long long* expansions_host,
+                    const edgedict_search_opts_t* opts, void* workspace, const NBestOut* nb, void* stream_) {
     const int EM = max_expansions;
+    ED_CHECK_ARG(search_ptrs_ok(pn, opts), "%s: net / opts is not a pointer", nb ? "beam_search_nbest" : "beam_search");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
+    if (int rc = no_ilm(o, nb ? "beam_search_nbest" : "beam_search")) return rc;
     ED_CHECK_ARG(!nb || !prefix,
                  "beam_search_nbest: prefix = 1 is not supported (the prefix merge changes a hypothesis' score at frame "
                  "starts, so the per-token increments would no longer add up to it)");
@@ -1528,14 +1516,15 @@ int beam_search_run(
                      "beam_search_nbest: null pointer");
         tokens_host = o.tokens; ntokens_host = o.ntokens; score_host = o.logp;
     }
-    const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, B, J, W1d, ldw1, b1, P2, W2, b2, V,
-                        {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, T * EM + 1};
+    ED_CHECK_ARG(pn, "beam_search: null pointer");
+    const SearchNet net = search_net_of(*pn, E1, e_row_stride, e_frame_stride, B, W, EM, T * EM + 1);
+    const int L = net.pred.L, H = net.pred.H, V = net.V;
     if (int rc = check_net(net, "beam_search", T >= 0 && W > 0 && EM >= W && max_tokens >= 0,
                            " (max_expansions must be >= W)",
                            (T == 0 || E1) && lens_host && tokens_host && ntokens_host && score_host && workspace, true))
         return rc;
-    for (int b = 0; b < B; ++b)
-        ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "beam_search: lens[%d] = %d outside [0, %d]", b, lens_host[b], T);
+    int maxlen = 0;
+    if (int rc = check_lens(lens_host, B, T, "beam_search", &maxlen)) return rc;
     if (int rc = lm_check(lm, V, prefix, "beam_search")) return rc;
     if (int rc = bias_check(bias, V, prefix, "beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
@@ -1572,8 +1561,6 @@ int beam_search_run(
         ED_CHECK_HIP(hipMemsetAsync(q.lm_pred, 0, (size_t)B * 4, s));
     }
     hipLaunchKernelGGL(beam_init, dim3((B + 63) / 64), dim3(64), 0, s, q, B, W);
-    int maxlen = 0;
-    for (int b = 0; b < B; ++b) maxlen = lens_host[b] > maxlen ? lens_host[b] : maxlen;
     std::optional<PrefixMerge> merge;
     if (prefix) merge.emplace(net, bufs, p, w, lens_host, s);
     if (int rc = beam_frame_loop(net, bufs, maxlen, merge ? &*merge : nullptr, s)) return rc;
@@ -1612,35 +1599,6 @@ int beam_search_run(
 }
 }  // namespace
 
-extern "C" int edgedict_beam_search_lm(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, void* workspace, void* stream_) {
-    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
-                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
-                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, nullptr, workspace,
-                           nullptr, stream_);
-}
-
-extern "C" int edgedict_beam_search_bias(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-    void* workspace, void* stream_) {
-    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
-                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
-                           tokens_host, max_tokens, ntokens_host, score_host, expansions_host, lm, bias, workspace,
-                           nullptr, stream_);
-}
-
 extern "C" size_t edgedict_beam_detail_bytes(int B, int T, int max_expansions) {
     if (B <= 0 || max_expansions <= 0) return 0;
     return beam_detail_layout(B, (size_t)(T < 0 ? 0 : T) * max_expansions + 1).total;
@@ -1651,50 +1609,25 @@ extern "C" size_t edgedict_beam_nbest_result_bytes(int B, int W, int max_tokens)
     return nbest_result_layout(B, W, max_tokens).total;
 }
 
-extern "C" int edgedict_beam_search_nbest(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
-    int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host, long long* expansions_host,
-    const edgedict_beam_lm_t* lm, void* workspace, void* detail, void* result, void* stream_) {
-    return edgedict_beam_search_nbest_bias(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
-                                           W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
-                                           W, max_expansions, prefix, tokens_host, frames_host, token_logp_host,
-                                           max_tokens, ntokens_host, nhyp_host, logp_host, expansions_host, lm, nullptr,
-                                           workspace, detail, result, stream_);
-}
-
-extern "C" int edgedict_beam_search_nbest_bias(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
-    int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host, long long* expansions_host,
-    const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* workspace, void* detail, void* result,
-    void* stream_) {
+extern "C" int edgedict_beam_search_nbest(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                                          long long e_frame_stride, int B, int T, const int32_t* lens_host, int W,
+                                          int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host,
+                                          double* token_logp_host, int max_tokens, int32_t* ntokens_host,
+                                          int32_t* nhyp_host, double* logp_host, long long* expansions_host,
+                                          const edgedict_search_opts_t* opts, void* workspace, void* detail, void* result,
+                                          void* stream_) {
     const NBestOut nb{detail, result, {tokens_host, frames_host, token_logp_host, ntokens_host, nhyp_host, logp_host}};
-    return beam_search_run(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2, b2, V, emb,
-                           emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W, max_expansions, prefix,
-                           nullptr, max_tokens, nullptr, nullptr, expansions_host, lm, bias, workspace, &nb, stream_);
+    return beam_search_run(net, E1, e_row_stride, e_frame_stride, B, T, lens_host, W, max_expansions, prefix, nullptr,
+                           max_tokens, nullptr, nullptr, expansions_host, opts, workspace, &nb, stream_);
 }
 
-extern "C" int edgedict_beam_search(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
-    double* score_host, long long* expansions_host, void* workspace, void* stream_) {
-    return edgedict_beam_search_lm(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2, W2,
-                                   b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, prefix, tokens_host, max_tokens, ntokens_host, score_host,
-                                   expansions_host, nullptr, workspace, stream_);
+extern "C" int edgedict_beam_search(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                                    long long e_frame_stride, int B, int T, const int32_t* lens_host, int W,
+                                    int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
+                                    int32_t* ntokens_host, double* score_host, long long* expansions_host,
+                                    const edgedict_search_opts_t* opts, void* workspace, void* stream_) {
+    return beam_search_run(net, E1, e_row_stride, e_frame_stride, B, T, lens_host, W, max_expansions, prefix, tokens_host,
+                           max_tokens, ntokens_host, score_host, expansions_host, opts, workspace, nullptr, stream_);
 }
 
 
@@ -1939,56 +1872,34 @@ struct StreamDetailArgs {
 
 }  // namespace
 
-extern "C" size_t edgedict_beam_stream_state_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                        int W, int max_expansions, int node_capacity,
-                                                        const edgedict_beam_lm_t* lm,
-                                                        const edgedict_beam_bias_t* bias) {
-    (void)dtype; (void)J; (void)V; (void)E; (void)P2; (void)max_expansions;
-    if (S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
-    return beam_stream_state_layout(S, L, H, W, node_capacity, lm, bias).total;
+extern "C" size_t edgedict_beam_stream_state_bytes(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                                   int node_capacity) {
+    if (!search_ptrs_ok(nullptr, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (o.ilm_weight || S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
+    return beam_stream_state_layout(S, L, H, W, node_capacity, o.lm, o.bias).total;
 }
 
-extern "C" size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                      int W, int max_expansions, int node_capacity,
-                                                      const edgedict_beam_lm_t* lm) {
-    return edgedict_beam_stream_state_bytes_bias(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, lm,
-                                                 nullptr);
-}
-
-extern "C" size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
-                                                   int max_expansions, int node_capacity) {
-    return edgedict_beam_stream_state_bytes_lm(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, nullptr);
-}
-
-extern "C" size_t edgedict_beam_stream_workspace_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
-                                                            int P2, int W, int max_expansions, int node_capacity,
-                                                            const edgedict_beam_lm_t* lm,
-                                                            const edgedict_beam_bias_t* bias) {
-    if (S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
-    SearchNet n = net_dims(dtype, S, J, V, E, L, H, P2);
-    n.W = W;
-    n.EM = max_expansions;
+extern "C" size_t edgedict_beam_stream_workspace_bytes(const edgedict_search_net_t* pn, int S, int W, int max_expansions,
+                                                       int node_capacity, const edgedict_search_opts_t* opts) {
+    if (!pn || !search_ptrs_ok(pn, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (o.ilm_weight || S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
+    const SearchNet n = search_net_of(*pn, nullptr, 0, 0, S, W, max_expansions, 0);
     const size_t base = beam_layout(n, (size_t)node_capacity, 0, true).total;
-    return ws_total(base, n, lm, bias, false);
+    return ws_total(base, n, o.lm, o.bias, false);
 }
 
-extern "C" size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                          int W, int max_expansions, int node_capacity,
-                                                          const edgedict_beam_lm_t* lm) {
-    return edgedict_beam_stream_workspace_bytes_bias(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity, lm,
-                                                     nullptr);
-}
-
-extern "C" size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                       int W, int max_expansions, int node_capacity) {
-    return edgedict_beam_stream_workspace_bytes_lm(dtype, S, J, V, E, L, H, P2, W, max_expansions, node_capacity,
-                                                   nullptr);
-}
-
-namespace {
-// bias: only its presence matters here (the state then holds the survivors' automaton states; the root is state 0)
-int beam_stream_reset_run(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask, int mask_on_host,
-                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* stream_) {
+// opts->bias: only its presence matters here (the state then holds the survivors' automaton states; the root is state
+// 0).  detail_state non-null: the selected streams' frame count -> 0 as well.
+extern "C" int edgedict_beam_stream_reset(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                          int node_capacity, int bos, const int32_t* mask, int mask_on_host, void* state,
+                                          void* detail_state, void* stream_) {
+    ED_CHECK_ARG(search_ptrs_ok(nullptr, opts), "beam_stream_reset: opts is not a pointer");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
+    if (int rc = no_ilm(o, "beam_stream_reset")) return rc;
     ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0, "beam_stream_reset: bad shape");
     ED_CHECK_ARG(state, "beam_stream_reset: null state");
     ED_CHECK_ARG(!lm || (lm->L > 0 && lm->H > 0), "beam_stream_reset: bad LM shape");
@@ -2010,36 +1921,46 @@ int beam_stream_reset_run(int S, int L, int H, int W, int node_capacity, int bos
         }
     }
     ED_CHECK_LAUNCH("beam_stream_reset");
+    if (!detail_state) return ED_OK;
+    long long* fd = at<long long>((char*)detail_state, stream_detail_state_layout(S, node_capacity).frames_done);
+    if (!mask || !mask_on_host) {
+        hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((S + 63) / 64), dim3(64), 0, s, fd, mask, 0, S);
+    } else {
+        for (int b = 0; b < S;) {
+            if (!mask[b]) { ++b; continue; }
+            int e = b;
+            while (e < S && mask[e]) ++e;
+            hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((e - b + 63) / 64), dim3(64), 0, s, fd,
+                               (const int32_t*)nullptr, b, e - b);
+            b = e;
+        }
+    }
+    ED_CHECK_LAUNCH("beam_stream_reset_detail");
     return ED_OK;
 }
-}  // namespace
 
-extern "C" int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                             int mask_on_host, const edgedict_beam_lm_t* lm, void* state,
-                                             void* stream_) {
-    return beam_stream_reset_run(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, nullptr, state, stream_);
-}
-
-extern "C" int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                          int mask_on_host, void* state, void* stream_) {
-    return edgedict_beam_stream_reset_lm(S, L, H, W, node_capacity, bos, mask, mask_on_host, nullptr, state, stream_);
-}
-
-namespace {
-// Both advances.  dt == null: edgedict_beam_stream_advance[_lm]; else edgedict_beam_stream_advance_detail.
-int beam_stream_advance_run(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state,
-    void* workspace, const StreamDetailArgs* dt, void* stream_) {
+// The four detail arguments all null: the plain advance; all non-null: the detail is kept and committed too.
+extern "C" int edgedict_beam_stream_advance(const edgedict_search_net_t* pn, const void* E1, long long e_row_stride,
+                                            long long e_frame_stride, int S, const int32_t* n_frames_host, int W,
+                                            int max_expansions, int node_capacity, int32_t* commit_host,
+                                            int32_t* ncommit_host, long long* expansions_host,
+                                            const edgedict_search_opts_t* opts, void* state, void* workspace,
+                                            void* detail_state, void* detail_workspace, int32_t* commit_frame_host,
+                                            double* commit_logp_host, void* stream_) {
     const int EM = max_expansions, NC = node_capacity;
+    ED_CHECK_ARG(search_ptrs_ok(pn, opts), "beam_stream_advance: net / opts is not a pointer");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
+    if (int rc = no_ilm(o, "beam_stream_advance")) return rc;
+    const StreamDetailArgs detail{detail_state, detail_workspace, commit_frame_host, commit_logp_host};
+    const bool any_detail = detail_state || detail_workspace || commit_frame_host || commit_logp_host;
+    const StreamDetailArgs* dt = any_detail ? &detail : nullptr;
     ED_CHECK_ARG(!dt || (dt->dstate && dt->dws && dt->commit_frame_host && dt->commit_logp_host),
                  "beam_stream_advance_detail: null pointer");
-    const SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, S, J, W1d, ldw1, b1, P2, W2, b2, V,
-                        {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, EM, NC};
+    ED_CHECK_ARG(pn, "beam_stream_advance: null pointer");
+    const SearchNet net = search_net_of(*pn, E1, e_row_stride, e_frame_stride, S, W, EM, NC);
+    const int L = net.pred.L, H = net.pred.H, V = net.V;
     if (int rc = check_net(net, "beam_stream_advance", W > 0 && EM >= W && NC > 0, " (max_expansions must be >= W)",
                            n_frames_host && commit_host && ncommit_host && state && workspace, true))
         return rc;
@@ -2139,34 +2060,6 @@ int beam_stream_advance_run(
     }
     return ED_OK;
 }
-}  // namespace
-
-extern "C" int edgedict_beam_stream_advance_lm(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, const edgedict_beam_lm_t* lm, void* state, void* workspace, void* stream_) {
-    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
-                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, nullptr,
-                                   state, workspace, nullptr, stream_);
-}
-
-extern "C" int edgedict_beam_stream_advance_bias(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state,
-    void* workspace, void* stream_) {
-    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
-                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, bias,
-                                   state, workspace, nullptr, stream_);
-}
 
 extern "C" size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capacity) {
     if (S <= 0 || node_capacity <= 0) return 0;
@@ -2176,84 +2069,6 @@ extern "C" size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capaci
 extern "C" size_t edgedict_beam_stream_detail_workspace_bytes(int S, int node_capacity) {
     if (S <= 0 || node_capacity <= 0) return 0;
     return stream_detail_ws_layout(S, node_capacity).total;
-}
-
-extern "C" int edgedict_beam_stream_reset_detail(int S, int L, int H, int W, int node_capacity, int bos,
-                                                 const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
-                                                 void* state, void* detail_state, void* stream_) {
-    ED_CHECK_ARG(detail_state, "beam_stream_reset_detail: null detail state");
-    return edgedict_beam_stream_reset_bias(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, nullptr, state,
-                                           detail_state, stream_);
-}
-
-extern "C" int edgedict_beam_stream_reset_bias(int S, int L, int H, int W, int node_capacity, int bos,
-                                               const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
-                                               const edgedict_beam_bias_t* bias, void* state, void* detail_state,
-                                               void* stream_) {
-    if (int rc = beam_stream_reset_run(S, L, H, W, node_capacity, bos, mask, mask_on_host, lm, bias, state, stream_))
-        return rc;
-    if (!detail_state) return ED_OK;
-    hipStream_t s = (hipStream_t)stream_;
-    long long* fd = at<long long>((char*)detail_state, stream_detail_state_layout(S, node_capacity).frames_done);
-    if (!mask || !mask_on_host) {
-        hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((S + 63) / 64), dim3(64), 0, s, fd, mask, 0, S);
-    } else {
-        for (int b = 0; b < S;) {
-            if (!mask[b]) { ++b; continue; }
-            int e = b;
-            while (e < S && mask[e]) ++e;
-            hipLaunchKernelGGL(beam_detail_reset_kernel, dim3((e - b + 63) / 64), dim3(64), 0, s, fd,
-                               (const int32_t*)nullptr, b, e - b);
-            b = e;
-        }
-    }
-    ED_CHECK_LAUNCH("beam_stream_reset_detail");
-    return ED_OK;
-}
-
-extern "C" int edgedict_beam_stream_advance_detail(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* commit_frame_host,
-    double* commit_logp_host, int32_t* ncommit_host, long long* expansions_host, const edgedict_beam_lm_t* lm,
-    void* state, void* workspace, void* detail_state, void* detail_workspace, void* stream_) {
-    return edgedict_beam_stream_advance_detail_bias(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1,
-                                                    b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp,
-                                                    bp, blank, bos, W, max_expansions, node_capacity, commit_host,
-                                                    commit_frame_host, commit_logp_host, ncommit_host, expansions_host,
-                                                    lm, nullptr, state, workspace, detail_state, detail_workspace,
-                                                    stream_);
-}
-
-extern "C" int edgedict_beam_stream_advance_detail_bias(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* commit_frame_host,
-    double* commit_logp_host, int32_t* ncommit_host, long long* expansions_host, const edgedict_beam_lm_t* lm,
-    const edgedict_beam_bias_t* bias, void* state, void* workspace, void* detail_state, void* detail_workspace,
-    void* stream_) {
-    const StreamDetailArgs dt{detail_state, detail_workspace, commit_frame_host, commit_logp_host};
-    return beam_stream_advance_run(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1, P2, W2, b2,
-                                   V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos, W,
-                                   max_expansions, node_capacity, commit_host, ncommit_host, expansions_host, lm, bias,
-                                   state, workspace, &dt, stream_);
-}
-
-extern "C" int edgedict_beam_stream_advance(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, const int32_t* n_frames_host,
-    int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-    const void* emb, int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-    const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-    int W, int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-    long long* expansions_host, void* state, void* workspace, void* stream_) {
-    return edgedict_beam_stream_advance_lm(dtype, E1, e_row_stride, e_frame_stride, S, n_frames_host, J, W1d, ldw1, b1,
-                                           P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
-                                           blank, bos, W, max_expansions, node_capacity, commit_host, ncommit_host,
-                                           expansions_host, nullptr, state, workspace, stream_);
 }
 
 extern "C" int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, const void* state,

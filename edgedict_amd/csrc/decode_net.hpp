@@ -51,6 +51,50 @@ struct SearchNet {
     const char* frame(int t) const { return (const char*)E1 + (size_t)t * e_frame_stride * esz; }
 };
 
+// The public network (edgedict_search_net_t, non-null) as the SearchNet of a call over `rows` rows; a size query passes
+// no E1 and reads the shapes alone
+static inline SearchNet search_net_of(const edgedict_search_net_t& n, const void* E1, long long e_row_stride,
+                                      long long e_frame_stride, int rows, int W, int EM, int NODES) {
+    return SearchNet{n.dtype, n.dtype == ED_F32 ? 4 : 2, E1, e_row_stride, e_frame_stride, rows, n.J, n.W1d, n.ldw1, n.b1,
+                     n.P2, n.W2, n.b2, n.V,
+                     {n.emb, n.emb_dtype, n.V, n.E, n.L, n.w_ih, n.w_hh, n.b_ih, n.b_hh, n.H, n.Wp, n.bp, n.P2},
+                     n.blank, n.bos, W, EM, NODES};
+}
+// An address in the first page is no object: it is an integer that a caller written for ABI version 1 (positional
+// network arguments) left where `net` or `opts` now stand.  Such a call is refused, never dereferenced.
+static inline bool not_a_pointer(const void* p) { return p && (uintptr_t)p < 4096; }
+static inline bool search_ptrs_ok(const edgedict_search_net_t* n, const edgedict_search_opts_t* o) {
+    return !not_a_pointer(n) && !not_a_pointer(o);
+}
+// the optional features of a call: a null pointer is all members null
+static inline edgedict_search_opts_t search_opts_of(const edgedict_search_opts_t* o) {
+    return o ? *o : edgedict_search_opts_t{};
+}
+
+// The argument checks the searches share, in the order they have always run: dtype, shape, null pointers, and for the
+// beam searches blank / bos.  shape_ok / ptrs_ok carry the caller's own conditions, shape_note the tail of its message.
+static inline int check_net(const SearchNet& n, const char* what, bool shape_ok, const char* shape_note, bool ptrs_ok,
+                            bool beam) {
+    const LstmNet& p = n.pred;
+    ED_CHECK_ARG(n.dtype == ED_F32 || n.dtype == ED_BF16, "%s: bad dtype", what);
+    ED_CHECK_ARG(shape_ok && n.B > 0 && n.J > 0 && n.V > 0 && p.L > 0 && p.H > 0 && n.P2 > 0 && p.E > 0, "%s: bad shape%s",
+                 what, shape_note);
+    ED_CHECK_ARG(ptrs_ok && n.W1d && n.b1 && n.W2 && n.b2 && p.emb && p.w_ih && p.w_hh && p.b_ih && p.b_hh && p.Wo && p.bo,
+                 "%s: null pointer", what);
+    ED_CHECK_ARG(!beam || (n.blank >= 0 && n.blank < n.V && n.bos >= 0 && n.bos < n.V),
+                 "%s: blank/bos outside the vocabulary", what);
+    return ED_OK;
+}
+// every utterance's frame count inside [0, T]; *maxlen = the largest
+static inline int check_lens(const int32_t* lens_host, int B, int T, const char* what, int* maxlen) {
+    *maxlen = 0;
+    for (int b = 0; b < B; ++b) {
+        ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "%s: lens[%d] = %d outside [0, %d]", what, b, lens_host[b], T);
+        *maxlen = lens_host[b] > *maxlen ? lens_host[b] : *maxlen;
+    }
+    return ED_OK;
+}
+
 // Per-iteration buffers of the prediction-network step and the joint: offsets into a workspace ...
 struct Ws {
     size_t D1, hid, logits, pred, x, G, Hprev, Y0, Y1, Cst, h_new, c_new, dec_new, total;

@@ -21,13 +21,13 @@
 // logp = -inf, token BOS and a zero state; the rows of an utterance past its length keep its final beam and are left
 // alone by both kernels.  Rows flow through the step kernels either way and are row-independent there.
 //
-// LM shallow fusion and a bias list (the *_fusion entry points, the *_fused kernels): a row also carries the LM state
+// LM shallow fusion and a bias list (opts->lm / opts->bias, the *_fused kernels): a row also carries the LM state
 // from before its last token and the phrase automaton's state after its sequence; a frame gains the LM step on all
 // B * W rows (ed_decode_lm_step, behind the prediction-network step), and a non-blank candidate scores
 //   ((logp_i + (double) lp_i[k]) + (lm_w * (double) lp_lm_i[k] + lm_b)) + (held[goto(s_i, k)] - pend[s_i])
 // where a term is absent when its feature is.  Without either the plain kernels run, launch for launch.
 //
-// Internal-LM estimation (ILME; the *_ilme entry points, sync_row_topw_ilm): the prior the transducer learned from its
+// Internal-LM estimation (ILME; opts->ilm_weight, sync_row_topw_ilm): the prior the transducer learned from its
 // training transcripts is subtracted while an external LM is added.  The internal LM's logits of a row are the step's
 // joint on an all-zero encoder row, z_ilm = tanh(act(d W1d^T + b1)) W2^T + b2 for the row's prediction-network output d;
 // lp_ilm is their fp32 log-softmax over the NON-BLANK symbols, and a non-blank candidate's score gains
@@ -587,16 +587,13 @@ SyncRes sync_result_layout(size_t B, size_t W, size_t MT) {
 template <typename T>
 T* at(char* base, size_t off) { return (T*)(base + off); }
 
-SearchNet sync_dims(int dtype, int rows, int J, int V, int E, int L, int H, int P2) {
-    SearchNet n{};
-    n.dtype = dtype; n.esz = dtype == ED_F32 ? 4 : 2;
-    n.B = rows; n.J = J; n.V = V; n.P2 = P2;
-    n.pred.V = V; n.pred.E = E; n.pred.L = L; n.pred.H = H; n.pred.O = P2;
-    return n;
+bool sync_dims_ok(const edgedict_search_net_t& n, int B, int T, int W) {
+    return (n.dtype == ED_F32 || n.dtype == ED_BF16) && B > 0 && T > 0 && n.J > 0 && n.V > 0 && n.E > 0 && n.L > 0 &&
+           n.H > 0 && n.H % 4 == 0 && n.P2 > 0 && W >= 1 && W <= SB_MAXW && (long long)B * W <= 0x7fffffff / 256;
 }
-bool sync_dims_ok(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2, int W) {
-    return (dtype == ED_F32 || dtype == ED_BF16) && B > 0 && T > 0 && J > 0 && V > 0 && E > 0 && L > 0 && H > 0 &&
-           H % 4 == 0 && P2 > 0 && W >= 1 && W <= SB_MAXW && (long long)B * W <= 0x7fffffff / 256;
+// the step's network: B * W rows whose joint rows are gathered per frame, J apart (E1 is bound once the workspace is)
+SearchNet sync_net_of(const edgedict_search_net_t& n, int rows, int W, int NODES) {
+    return search_net_of(n, nullptr, (long long)n.J, 0, rows, W, 0, NODES);
 }
 
 // LM fusion / a bias list, host side.  Both parts are APPENDED behind a plain layout (offsets from `base`, a multiple of
@@ -650,6 +647,13 @@ int sync_fuse_check(const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bi
     if (int rc = ed_decode_lm_check(lm, V, 0, what)) return rc;
     ED_CHECK_ARG(!lm || lm->H % 4 == 0, "%s: the LM's hidden width H = %d must be a multiple of 4", what, lm->H);
     return ed_decode_bias_check(bias, V, 0, what);
+}
+// what check_net leaves to this search: every layer's pointers and the embedding table's dtype
+int sync_layers_check(const edgedict_search_net_t& n, const char* what) {
+    for (int k = 0; k < n.L; ++k)
+        ED_CHECK_ARG(n.w_ih[k] && n.w_hh[k] && n.b_ih[k] && n.b_hh[k], "%s: null pointer (layer %d)", what, k);
+    ED_CHECK_ARG(n.emb_dtype == ED_F32 || n.emb_dtype == ED_BF16, "%s: bad embedding dtype", what);
+    return ED_OK;
 }
 bool sync_fuse_dims_ok(const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, int V) {
     return (!lm || (lm->V == V && lm->L > 0 && lm->E > 0 && lm->H > 0 && lm->H % 4 == 0)) && (!bias || bias->S > 0);
@@ -817,27 +821,19 @@ void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u
 
 }  // namespace
 
-// ilm_weight null: the size of the _fusion form; else ILME's buffers behind it
-extern "C" size_t edgedict_sync_beam_workspace_bytes_ilme(int dtype, int B, int T, int J, int V, int E, int L, int H,
-                                                          int P2, int W, const edgedict_beam_lm_t* lm,
-                                                          const edgedict_beam_bias_t* bias, const double* ilm_weight) {
-    if (!sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W) || !sync_fuse_dims_ok(lm, bias, V) || !sync_ilm_ok(ilm_weight))
+// the plain size; an LM / a bias list append their parts behind it, ILME its buffers behind those
+extern "C" size_t edgedict_sync_beam_workspace_bytes(const edgedict_search_net_t* pn, int B, int T, int W,
+                                                     const edgedict_search_opts_t* opts) {
+    if (!pn || !search_ptrs_ok(pn, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (!sync_dims_ok(*pn, B, T, W) || !sync_fuse_dims_ok(o.lm, o.bias, pn->V) || !sync_ilm_ok(o.ilm_weight))
         return 0;
-    const size_t BW = (size_t)B * W, esz = dtype == ED_F32 ? 4 : 2;
-    const size_t plain = sync_layout(sync_dims(dtype, B * W, J, V, E, L, H, P2), B, W, T).total;
-    const size_t fuse = sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, esz, V, lm).total, BW, lm, bias).total;
-    return sync_ilm_layout(fuse, BW, esz, J, V, ilm_weight != nullptr).total;
-}
-
-extern "C" size_t edgedict_sync_beam_workspace_bytes_fusion(int dtype, int B, int T, int J, int V, int E, int L, int H,
-                                                            int P2, int W, const edgedict_beam_lm_t* lm,
-                                                            const edgedict_beam_bias_t* bias) {
-    return edgedict_sync_beam_workspace_bytes_ilme(dtype, B, T, J, V, E, L, H, P2, W, lm, bias, nullptr);
-}
-
-extern "C" size_t edgedict_sync_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                     int W) {
-    return edgedict_sync_beam_workspace_bytes_fusion(dtype, B, T, J, V, E, L, H, P2, W, nullptr, nullptr);
+    const SearchNet net = sync_net_of(*pn, B * W, W, T * W);
+    const size_t BW = (size_t)B * W, esz = net.esz;
+    const size_t plain = sync_layout(net, B, W, T).total;
+    const size_t fuse =
+        sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, esz, net.V, o.lm).total, BW, o.lm, o.bias).total;
+    return sync_ilm_layout(fuse, BW, esz, net.J, net.V, o.ilm_weight != nullptr).total;
 }
 
 extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) {
@@ -845,42 +841,37 @@ extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) 
     return sync_result_layout(B, W, max_tokens).total;
 }
 
-// lm / bias / ilm_weight null: the plain search, launch for launch;  ilm_weight null: the _fusion search, launch for launch
-extern "C" int edgedict_sync_beam_search_ilme(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
-    int32_t* nhyp_host, double* logp_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-    const double* ilm_weight, void* workspace, void* result, void* stream_) {
-    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_beam_search: bad dtype");
+// opts null or all its members null: the plain search, launch for launch;  ilm_weight null: the search without ILME
+extern "C" int edgedict_sync_beam_search(const edgedict_search_net_t* pn, const void* E1, long long e_row_stride,
+                                         long long e_frame_stride, int B, int T, const int32_t* lens_host, int W,
+                                         int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
+                                         int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                                         const edgedict_search_opts_t* opts, void* workspace, void* result,
+                                         void* stream_) {
+    ED_CHECK_ARG(search_ptrs_ok(pn, opts), "sync_beam_search: net / opts is not a pointer");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
+    const double* ilm_weight = o.ilm_weight;
+    ED_CHECK_ARG(pn, "sync_beam_search: null pointer");
+    const int BW = B * W, NODES = T * W;
+    SearchNet net = sync_net_of(*pn, BW, W, NODES);
+    const int dtype = net.dtype, J = net.J, V = net.V, L = net.pred.L, H = net.pred.H, blank = net.blank, bos = net.bos;
     ED_CHECK_ARG(W >= 1 && W <= SB_MAXW, "sync_beam_search: beam width W = %d outside [1, %d]", W, SB_MAXW);
     ED_CHECK_ARG(T > 0, "sync_beam_search: T = %d frames (must be > 0)", T);
-    ED_CHECK_ARG(sync_dims_ok(dtype, B, T, J, V, E, L, H, P2, W) && max_tokens >= 0, "sync_beam_search: bad shape (H must be a multiple of 4)");
-    ED_CHECK_ARG(E1 && lens_host && W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp && bp &&
-                     tokens_host && frames_host && token_logp_host && ntokens_host && nhyp_host && logp_host &&
-                     workspace && result,
-                 "sync_beam_search: null pointer");
-    for (int k = 0; k < L; ++k)
-        ED_CHECK_ARG(w_ih[k] && w_hh[k] && b_ih[k] && b_hh[k], "sync_beam_search: null pointer (layer %d)", k);
-    ED_CHECK_ARG(emb_dtype == ED_F32 || emb_dtype == ED_BF16, "sync_beam_search: bad embedding dtype");
-    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "sync_beam_search: blank/bos outside the vocabulary");
+    if (int rc = check_net(net, "sync_beam_search", sync_dims_ok(*pn, B, T, W) && max_tokens >= 0,
+                           " (H must be a multiple of 4)",
+                           E1 && lens_host && tokens_host && frames_host && token_logp_host && ntokens_host && nhyp_host &&
+                               logp_host && workspace && result,
+                           true))
+        return rc;
+    if (int rc = sync_layers_check(*pn, "sync_beam_search")) return rc;
     int maxlen = 0;
-    for (int b = 0; b < B; ++b) {
-        ED_CHECK_ARG(lens_host[b] >= 0 && lens_host[b] <= T, "sync_beam_search: lens[%d] = %d outside [0, %d]", b,
-                     lens_host[b], T);
-        maxlen = std::max(maxlen, lens_host[b]);
-    }
+    if (int rc = check_lens(lens_host, B, T, "sync_beam_search", &maxlen)) return rc;
     if (int rc = sync_fuse_check(lm, bias, V, "sync_beam_search")) return rc;
     if (int rc = sync_ilm_check(ilm_weight, "sync_beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    const int BW = B * W, NODES = T * W;
-    // the step's network: B * W rows whose joint rows are gathered per frame, J apart
     char* p = (char*)workspace;
-    SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, nullptr, (long long)J, 0, BW, J, W1d, ldw1, b1, P2, W2, b2, V,
-                  {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, 0, NODES};
     const SyncWs w = sync_layout(net, B, W, T);
     StepBufs u = bind(p + w.step_at, w.step);
     net.E1 = p + w.e1g;
@@ -925,7 +916,7 @@ extern "C" int edgedict_sync_beam_search_ilme(
         }
         hipLaunchKernelGGL(sync_init_fused, dim3((BW + 255) / 256), dim3(256), 0, s, fusion.f, BW);
     }
-    const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    const bool fused = ed_decode_fused_ok(dtype, net.pred.emb_dtype, J, V, net.pred.E, H, net.P2);
     SyncIlm ilm{};
     const SyncIlm* il = nullptr;
     if (ilm_weight) {
@@ -981,35 +972,6 @@ extern "C" int edgedict_sync_beam_search_ilme(
         ED_CHECK_HIP(hipStreamSynchronize(s));
     }
     return ED_OK;
-}
-
-extern "C" int edgedict_sync_beam_search_fusion(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
-    int32_t* nhyp_host, double* logp_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-    void* workspace, void* result, void* stream_) {
-    return edgedict_sync_beam_search_ilme(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
-                                          W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
-                                          W, tokens_host, frames_host, token_logp_host, max_tokens, ntokens_host,
-                                          nhyp_host, logp_host, lm, bias, nullptr, workspace, result, stream_);
-}
-
-extern "C" int edgedict_sync_beam_search(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-    const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-    const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-    const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-    const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos, int W,
-    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens, int32_t* ntokens_host,
-    int32_t* nhyp_host, double* logp_host, void* workspace, void* result, void* stream_) {
-    return edgedict_sync_beam_search_fusion(dtype, E1, e_row_stride, e_frame_stride, B, T, lens_host, J, W1d, ldw1, b1, P2,
-                                            W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, blank, bos,
-                                            W, tokens_host, frames_host, token_logp_host, max_tokens, ntokens_host,
-                                            nhyp_host, logp_host, nullptr, nullptr, workspace, result, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1250,38 +1212,29 @@ __global__ __launch_bounds__(64) void sync_stream_compact(SyncPtrs p, int32_t* _
 // The fused forms append the rows' LM (h, c) in both buffers, the LM's next symbols and the automaton states behind the
 // plain state, and the LM step's buffers behind the plain workspace: edgedict_sync_stream_read serves every form.
 // (V is not known to the state query: the LM's own V sizes nothing there.)
-extern "C" size_t edgedict_sync_stream_state_bytes_fusion(int S, int L, int H, int W, int node_capacity,
-                                                          const edgedict_beam_lm_t* lm,
-                                                          const edgedict_beam_bias_t* bias) {
-    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_fuse_dims_ok(lm, bias, lm ? lm->V : 0)) return 0;
-    return sync_fuse_rows_layout(sync_stream_state_layout(S, W, L, H, node_capacity).total, (size_t)S * W, lm, bias).total;
+extern "C" size_t edgedict_sync_stream_state_bytes(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                                   int node_capacity) {
+    if (!search_ptrs_ok(nullptr, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_fuse_dims_ok(o.lm, o.bias, o.lm ? o.lm->V : 0)) return 0;
+    return sync_fuse_rows_layout(sync_stream_state_layout(S, W, L, H, node_capacity).total, (size_t)S * W, o.lm, o.bias)
+        .total;
 }
 
-extern "C" size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, int node_capacity) {
-    return edgedict_sync_stream_state_bytes_fusion(S, L, H, W, node_capacity, nullptr, nullptr);
-}
-
-// ilm_weight null: the size of the _fusion form; else ILME's buffers behind it.  (The persistent state has no ILME part.)
-extern "C" size_t edgedict_sync_stream_workspace_bytes_ilme(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                            int W, int node_capacity, const edgedict_beam_lm_t* lm,
-                                                            const edgedict_beam_bias_t* bias, const double* ilm_weight) {
-    if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) ||
-        !sync_fuse_dims_ok(lm, bias, V) || !sync_ilm_ok(ilm_weight))
+// the plain size; an LM appends its step's buffers, ILME its own behind them.  (The persistent state has no ILME part.)
+extern "C" size_t edgedict_sync_stream_workspace_bytes(const edgedict_search_net_t* pn, int S, int W, int node_capacity,
+                                                       const edgedict_search_opts_t* opts) {
+    if (!pn || !search_ptrs_ok(pn, opts)) return 0;
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    if (!sync_stream_dims_ok(S, pn->L, pn->H, W, node_capacity) || !sync_dims_ok(*pn, S, 1, W) ||
+        !sync_fuse_dims_ok(o.lm, o.bias, pn->V) || !sync_ilm_ok(o.ilm_weight))
         return 0;
-    const size_t SW = (size_t)S * W, esz = dtype == ED_F32 ? 4 : 2;
-    const size_t plain = sync_stream_ws_layout(sync_dims(dtype, S * W, J, V, E, L, H, P2), S, W, node_capacity).total;
-    return sync_ilm_layout(sync_fuse_step_layout(plain, SW, esz, V, lm).total, SW, esz, J, V, ilm_weight != nullptr).total;
-}
-
-extern "C" size_t edgedict_sync_stream_workspace_bytes_fusion(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                              int W, int node_capacity, const edgedict_beam_lm_t* lm,
-                                                              const edgedict_beam_bias_t* bias) {
-    return edgedict_sync_stream_workspace_bytes_ilme(dtype, S, J, V, E, L, H, P2, W, node_capacity, lm, bias, nullptr);
-}
-
-extern "C" size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                                       int W, int node_capacity) {
-    return edgedict_sync_stream_workspace_bytes_fusion(dtype, S, J, V, E, L, H, P2, W, node_capacity, nullptr, nullptr);
+    const SearchNet net = sync_net_of(*pn, S * W, W, node_capacity);
+    const size_t SW = (size_t)S * W, esz = net.esz;
+    const size_t plain = sync_stream_ws_layout(net, S, W, node_capacity).total;
+    return sync_ilm_layout(sync_fuse_step_layout(plain, SW, esz, net.V, o.lm).total, SW, esz, net.J, net.V,
+                           o.ilm_weight != nullptr)
+        .total;
 }
 
 extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens) {
@@ -1298,10 +1251,15 @@ extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens
         ED_CHECK_ARG(sync_stream_dims_ok(S, L, H, W, NC), what ": bad shape (too many rows or nodes)");            \
     } while (0)
 
-// lm / bias null: the plain reset.  (The LM's and the list's vocabulary are the advance's to check: V is not known here.)
-extern "C" int edgedict_sync_stream_reset_fusion(int S, int L, int H, int W, int node_capacity, int bos,
-                                                 const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
-                                                 const edgedict_beam_bias_t* bias, void* state, void* stream_) {
+// opts->lm / bias null: the plain reset.  (The LM's and the list's vocabulary are the advance's to check: V is not known
+// here.  ILME carries no state: opts->ilm_weight is not read.)
+extern "C" int edgedict_sync_stream_reset(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                          int node_capacity, int bos, const int32_t* mask, int mask_on_host, void* state,
+                                          void* stream_) {
+    ED_CHECK_ARG(search_ptrs_ok(nullptr, opts), "sync_stream_reset: opts is not a pointer");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
     SYNC_STREAM_CHECK_SHAPE("sync_stream_reset", S, L, H, W, node_capacity);
     ED_CHECK_ARG(bos >= 0, "sync_stream_reset: bos = %d outside the vocabulary", bos);
     ED_CHECK_ARG(state, "sync_stream_reset: null pointer (state)");
@@ -1337,33 +1295,29 @@ extern "C" int edgedict_sync_stream_reset_fusion(int S, int L, int H, int W, int
     return ED_OK;
 }
 
-extern "C" int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                          int mask_on_host, void* state, void* stream_) {
-    return edgedict_sync_stream_reset_fusion(S, L, H, W, node_capacity, bos, mask, mask_on_host, nullptr, nullptr, state,
-                                             stream_);
-}
-
-// lm / bias / ilm_weight null: the plain advance, launch for launch;  ilm_weight null: the _fusion advance
-extern "C" int edgedict_sync_stream_advance_ilme(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
-    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
-    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
-    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, const double* ilm_weight, void* state,
-    void* workspace, void* stream_) {
+// opts null or all its members null: the plain advance, launch for launch;  ilm_weight null: the advance without ILME
+extern "C" int edgedict_sync_stream_advance(const edgedict_search_net_t* pn, const void* E1, long long e_row_stride,
+                                            long long e_frame_stride, int S, int T, const int32_t* n_frames_host, int W,
+                                            int node_capacity, int32_t* live_host, int32_t* parity_host,
+                                            void* commit_host, int max_commit, const edgedict_search_opts_t* opts,
+                                            void* state, void* workspace, void* stream_) {
     const int NC = node_capacity;
-    ED_CHECK_ARG(dtype == ED_F32 || dtype == ED_BF16, "sync_stream_advance: bad dtype");
+    ED_CHECK_ARG(search_ptrs_ok(pn, opts), "sync_stream_advance: net / opts is not a pointer");
+    const edgedict_search_opts_t o = search_opts_of(opts);
+    const edgedict_beam_lm_t* lm = o.lm;
+    const edgedict_beam_bias_t* bias = o.bias;
+    const double* ilm_weight = o.ilm_weight;
+    ED_CHECK_ARG(pn, "sync_stream_advance: null pointer");
+    const int SW = S * W;
+    SearchNet net = sync_net_of(*pn, SW, W, NC);
+    const int dtype = net.dtype, J = net.J, V = net.V, L = net.pred.L, H = net.pred.H, blank = net.blank, bos = net.bos;
     SYNC_STREAM_CHECK_SHAPE("sync_stream_advance", S, L, H, W, NC);
     ED_CHECK_ARG(T >= 0, "sync_stream_advance: T = %d frames (must be >= 0)", T);
-    ED_CHECK_ARG(sync_dims_ok(dtype, S, 1, J, V, E, L, H, P2, W) && max_commit >= 0, "sync_stream_advance: bad shape");
-    ED_CHECK_ARG((E1 || T == 0) && n_frames_host && W1d && b1 && W2 && b2 && emb && w_ih && w_hh && b_ih && b_hh && Wp &&
-                     bp && live_host && parity_host && commit_host && state && workspace,
-                 "sync_stream_advance: null pointer");
-    for (int k = 0; k < L; ++k)
-        ED_CHECK_ARG(w_ih[k] && w_hh[k] && b_ih[k] && b_hh[k], "sync_stream_advance: null pointer (layer %d)", k);
-    ED_CHECK_ARG(emb_dtype == ED_F32 || emb_dtype == ED_BF16, "sync_stream_advance: bad embedding dtype");
-    ED_CHECK_ARG(blank >= 0 && blank < V && bos >= 0 && bos < V, "sync_stream_advance: blank/bos outside the vocabulary");
+    if (int rc = check_net(net, "sync_stream_advance", sync_dims_ok(*pn, S, 1, W) && max_commit >= 0, "",
+                           (E1 || T == 0) && n_frames_host && live_host && parity_host && commit_host && state && workspace,
+                           true))
+        return rc;
+    if (int rc = sync_layers_check(*pn, "sync_stream_advance")) return rc;
     ED_CHECK_ARG(*parity_host == 0 || *parity_host == 1, "sync_stream_advance: parity = %d (0 or 1)", *parity_host);
     int maxlen = 0, cols = 0;
     for (int b = 0; b < S; ++b) {
@@ -1383,11 +1337,8 @@ extern "C" int edgedict_sync_stream_advance_ilme(
     if (int rc = sync_fuse_check(lm, bias, V, "sync_stream_advance")) return rc;
     if (int rc = sync_ilm_check(ilm_weight, "sync_stream_advance")) return rc;
     hipStream_t s = (hipStream_t)stream_;
-    const int SW = S * W;
     char* p = (char*)workspace;
     char* st = (char*)state;
-    SearchNet net{dtype, dtype == ED_F32 ? 4 : 2, nullptr, (long long)J, 0, SW, J, W1d, ldw1, b1, P2, W2, b2, V,
-                  {emb, emb_dtype, V, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp, P2}, blank, bos, W, 0, NC};
     const SyncStreamWs w = sync_stream_ws_layout(net, S, W, NC);
     const SyncStreamState a = sync_stream_state_layout(S, W, L, H, NC);
     StepBufs u = bind(p + w.step_at, w.step);
@@ -1408,7 +1359,7 @@ extern "C" int edgedict_sync_stream_advance_ilme(
     }
 
     ED_CHECK_HIP(hipMemcpyAsync(q.lens, n_frames_host, (size_t)S * 4, hipMemcpyHostToDevice, s));
-    const bool fused = ed_decode_fused_ok(dtype, emb_dtype, J, V, E, H, P2);
+    const bool fused = ed_decode_fused_ok(dtype, net.pred.emb_dtype, J, V, net.pred.E, H, net.P2);
     SyncIlm ilm{};
     const SyncIlm* il = nullptr;
     if (ilm_weight) {
@@ -1444,33 +1395,6 @@ extern "C" int edgedict_sync_stream_advance_ilme(
     const int32_t* rec = (const int32_t*)commit_host;
     for (int b = 0; b < S; ++b) live_host[b] = rec[(size_t)b * ((size_t)max_commit + 1) * 4 + 1];
     return ED_OK;
-}
-
-extern "C" int edgedict_sync_stream_advance_fusion(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
-    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
-    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
-    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-    int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* state, void* workspace,
-    void* stream_) {
-    return edgedict_sync_stream_advance_ilme(dtype, E1, e_row_stride, e_frame_stride, S, T, n_frames_host, J, W1d, ldw1,
-                                             b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
-                                             blank, bos, W, node_capacity, live_host, parity_host, commit_host,
-                                             max_commit, lm, bias, nullptr, state, workspace, stream_);
-}
-
-extern "C" int edgedict_sync_stream_advance(
-    int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S, int T,
-    const int32_t* n_frames_host, int J, const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
-    const float* b2, int V, const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-    const void* const* w_hh, const float* const* b_ih, const float* const* b_hh, int H, const void* Wp, const float* bp,
-    int blank, int bos, int W, int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-    int max_commit, void* state, void* workspace, void* stream_) {
-    return edgedict_sync_stream_advance_fusion(dtype, E1, e_row_stride, e_frame_stride, S, T, n_frames_host, J, W1d, ldw1,
-                                               b1, P2, W2, b2, V, emb, emb_dtype, E, L, w_ih, w_hh, b_ih, b_hh, H, Wp, bp,
-                                               blank, bos, W, node_capacity, live_host, parity_host, commit_host,
-                                               max_commit, nullptr, nullptr, state, workspace, stream_);
 }
 
 extern "C" int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, const void* state, void* result,

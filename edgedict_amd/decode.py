@@ -280,11 +280,28 @@ def beam_search_batch(model, xs, xlen=None, W=10, max_expansions=None, prefix=Fa
                            length_bonus=length_bonus, lm_bos=lm_bos, bias=bias)
 
 
+class SearchNetStruct(ctypes.Structure):
+    """ctypes mirror of ``edgedict_search_net_t`` (include/edgedict_hip.h)."""
+    _fields_ = [("dtype", ctypes.c_int), ("J", ctypes.c_int), ("W1d", ctypes.c_void_p), ("ldw1", ctypes.c_longlong),
+                ("b1", ctypes.c_void_p), ("P2", ctypes.c_int), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("V", ctypes.c_int), ("emb", ctypes.c_void_p), ("emb_dtype", ctypes.c_int), ("E", ctypes.c_int),
+                ("L", ctypes.c_int), ("w_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_ih", ctypes.c_void_p),
+                ("b_hh", ctypes.c_void_p), ("H", ctypes.c_int), ("Wp", ctypes.c_void_p), ("bp", ctypes.c_void_p),
+                ("blank", ctypes.c_int), ("bos", ctypes.c_int)]
+
+
+class SearchOpts(ctypes.Structure):
+    """ctypes mirror of ``edgedict_search_opts_t`` (include/edgedict_hip.h)."""
+    _fields_ = [("lm", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("ilm_weight", ctypes.c_void_p)]
+
+
 class _SearchNet:
     """The prediction network's and the joint's weights in the compute dtype ``cd`` (converted once through
     ``WEIGHTS``) with the shapes and ctypes arguments the native searches take."""
 
     def __init__(self, model, cd):
+        self.blank = int(model.blank)
+        self._refs = {}
         from .models import WEIGHTS
         dec = model.decoder
         l1, l2 = model.joint.joint[0], model.joint.joint[2]
@@ -308,8 +325,25 @@ class _SearchNet:
         B, T, P = enc_out.shape
         return ops.gemm(enc_out.reshape(B * T, P), self.w1c[:, :P]) if T > 0 else enc_out.new_empty(0, self.J)
 
+    def ref(self, P=0):
+        """``const edgedict_search_net_t*`` of the beam searches' native calls, for an encoder output of width P (cached
+        per P; the struct and the pointer arrays it names live as long as this object).  The size queries read the
+        shapes alone: any P serves them."""
+        if P not in self._refs:
+            from .tokenizer import BOS
+            arrays = [_ptr_array(t) for t in (self.w_ih, self.w_hh, self.b_ih, self.b_hh)]
+            vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
+            s = SearchNetStruct(
+                dtype=dtype_code(self.cd), J=self.J, W1d=_lib.ptr(self.w1c[:, P:]), ldw1=self.w1c.stride(0),
+                b1=_lib.ptr(self.b1), P2=self.P2, W2=_lib.ptr(self.w2c), b2=_lib.ptr(self.b2), V=self.V,
+                emb=_lib.ptr(self.emb), emb_dtype=dtype_code(self.emb.dtype), E=self.E, L=self.L, w_ih=vp(arrays[0]),
+                w_hh=vp(arrays[1]), b_ih=vp(arrays[2]), b_hh=vp(arrays[3]), H=self.H, Wp=_lib.ptr(self.wpc),
+                bp=_lib.ptr(self.bp), blank=self.blank, bos=int(BOS))
+            self._refs[P] = (s, arrays)
+        return ctypes.byref(self._refs[P][0])
+
     def args(self, P):
-        """(W1d ... bp) of the native calls, for an encoder output of width P."""
+        """(W1d ... bp) of ``edgedict_greedy_decode``, for an encoder output of width P."""
         w1d = self.w1c[:, P:]
         return (self.J, _lib.ptr(w1d), ctypes.c_longlong(self.w1c.stride(0)), _lib.ptr(self.b1), self.P2,
                 _lib.ptr(self.w2c), _lib.ptr(self.b2), self.V, _lib.ptr(self.emb), dtype_code(self.emb.dtype),
@@ -317,16 +351,17 @@ class _SearchNet:
                 _ptr_array(self.b_hh), self.H, _lib.ptr(self.wpc), _lib.ptr(self.bp))
 
 
-def _native(name, flm, *args, tail=(), bref=None):
-    """``edgedict_<name>(*args, *tail)``, or with a fusion LM ``edgedict_<name>_lm(*args, lm, *tail)``: the ``_lm`` entry
-    points take the plain ones' arguments with the LM in front of the trailing state / workspace / stream.  With a
-    bias list (``bref``, ``ContextGraph.ref``) ``edgedict_<name>_bias(*args, lm or NULL, bias, *tail)``."""
-    lib = _lib.load()
-    if bref is not None:
-        return getattr(lib, "edgedict_" + name + "_bias")(*args, flm.ref() if flm is not None else None, bref, *tail)
-    if flm is None:
-        return getattr(lib, "edgedict_" + name)(*args, *tail)
-    return getattr(lib, "edgedict_" + name + "_lm")(*args, flm.ref(), *tail)
+def _opts(flm=None, bref=None, ilm=None):
+    """``const edgedict_search_opts_t*`` of a native call: the fusion LM ``flm`` (``FusionLM``), the bias list ``bref``
+    (``ContextGraph.ref``), the ILME weight ``ilm`` (a ``c_double``).  None - a null pointer, the plain search - when
+    all three are absent.  The pointer keeps what it names alive."""
+    if flm is None and bref is None and ilm is None:
+        return None
+    o = SearchOpts(lm=None if flm is None else ctypes.addressof(flm.struct),
+                   bias=None if bref is None else ctypes.addressof(bref._obj),
+                   ilm_weight=None if ilm is None else ctypes.addressof(ilm))
+    o.keep = (flm, bref, ilm)
+    return ctypes.pointer(o)
 
 
 def joint_rows(model, enc_out):
@@ -368,20 +403,19 @@ def beam_search_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=None, p
     if active(bias) is not None:
         _lib.require_cuda(E1)
         bref = active(bias).ref(E1.device)
-    nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
-                     int(bool(prefix)), bref=bref)
+    lib, nref, opts = _lib.load(), net.ref(P), _opts(flm, bref)
+    nbytes = lib.edgedict_beam_workspace_bytes(nref, B, T, int(W), EM, int(bool(prefix)), opts)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=E1.device)
     max_tokens = T * EM + 1
     tokens = np.zeros((B, max_tokens), dtype=np.int32)
     ntok = np.zeros(B, dtype=np.int32)
     score = np.zeros(B, dtype=np.float64)
     nexp = ctypes.c_longlong(0)
-    from .tokenizer import BOS
-    args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T,
-            lens.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(model.blank), int(BOS), int(W), EM,
-            int(bool(prefix)), tokens.ctypes.data_as(ctypes.c_void_p), max_tokens, ntok.ctypes.data_as(ctypes.c_void_p),
-            score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-    rc = _native("beam_search", flm, *args, tail=(_lib.ptr(ws), _lib.stream_ptr()), bref=bref)
+    rc = lib.edgedict_beam_search(
+        nref, _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T,
+        lens.ctypes.data_as(ctypes.c_void_p), int(W), EM, int(bool(prefix)), tokens.ctypes.data_as(ctypes.c_void_p),
+        max_tokens, ntok.ctypes.data_as(ctypes.c_void_p), score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp), opts,
+        _lib.ptr(ws), _lib.stream_ptr())
     _lib.check(rc, "beam_search")
     beam_search_batch.last_expansions = int(nexp.value)
     seqs = [tokens[b, :ntok[b]].astype(np.int64) for b in range(B)]
@@ -649,8 +683,8 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
     if active(bias) is not None:
         _lib.require_cuda(E1)
         bref = active(bias).ref(E1.device)
-    nbytes = _native("beam_workspace_bytes", flm, dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W, EM,
-                     0, bref=bref)
+    nref, opts = net.ref(P), _opts(flm, bref)
+    nbytes = lib.edgedict_beam_workspace_bytes(nref, B, T, int(W), EM, 0, opts)
     MT = T * EM + 1 if max_tokens is None else int(max_tokens)
     dev = E1.device
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -664,15 +698,10 @@ def beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_expansions=N
     logp = np.zeros((B, W), dtype=np.float64)
     nexp = ctypes.c_longlong(0)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    from .tokenizer import BOS
-    nb_args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
-               *net.args(P), int(model.blank), int(BOS), int(W), EM, 0, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok),
-               vp(nhyp), vp(logp), ctypes.byref(nexp), flm.ref() if flm is not None else None)
-    nb_tail = (_lib.ptr(ws), _lib.ptr(detail), _lib.ptr(result), _lib.stream_ptr())
-    if bref is not None:
-        rc = lib.edgedict_beam_search_nbest_bias(*nb_args, bref, *nb_tail)
-    else:
-        rc = lib.edgedict_beam_search_nbest(*nb_args, *nb_tail)
+    rc = lib.edgedict_beam_search_nbest(
+        nref, _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens), int(W), EM, 0,
+        vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp), ctypes.byref(nexp), opts, _lib.ptr(ws),
+        _lib.ptr(detail), _lib.ptr(result), _lib.stream_ptr())
     _lib.check(rc, "beam_search_nbest")
     beam_search_batch.last_expansions = int(nexp.value)
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
@@ -921,16 +950,9 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     dev = E1.device
     flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
     bref = active(bias).ref(dev) if active(bias) is not None else None
-    fused = flm is not None or bref is not None         # else: the plain entry points, untouched
-    fargs = (flm.ref() if flm is not None else None, bref)
-    dims = (dtype_code(cd), B, T, net.J, net.V, net.E, net.L, net.H, net.P2, W)
-    iarg = None if ilm is None else ctypes.byref(ilm)       # (None: the entry points of the call without ilm_weight)
-    if ilm is not None:
-        nbytes = lib.edgedict_sync_beam_workspace_bytes_ilme(*dims, *fargs, iarg)
-    else:
-        nbytes = (lib.edgedict_sync_beam_workspace_bytes_fusion(*dims, *fargs) if fused
-                  else lib.edgedict_sync_beam_workspace_bytes(*dims))
-    if (fused or ilm is not None) and nbytes == 0:
+    nref, opts = net.ref(P), _opts(flm, bref, ilm)          # (no feature: a null opts, the plain search)
+    nbytes = lib.edgedict_sync_beam_workspace_bytes(nref, B, T, W, opts)
+    if opts is not None and nbytes == 0:
         raise ValueError("sync_beam_search: shapes out of range (the LM's hidden width must be a multiple of 4)")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     result = torch.empty(lib.edgedict_sync_beam_result_bytes(B, W, MT), dtype=torch.uint8, device=dev)
@@ -941,17 +963,9 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     nhyp = np.zeros(B, dtype=np.int32)
     logp = np.zeros((B, W), dtype=np.float64)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    from .tokenizer import BOS
-    args = (dtype_code(cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens),
-            *net.args(P), int(model.blank), int(BOS), W, vp(tokens), vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp),
-            vp(logp))
-    tail = (_lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
-    if ilm is not None:
-        rc = lib.edgedict_sync_beam_search_ilme(*args, *fargs, iarg, *tail)
-    elif fused:
-        rc = lib.edgedict_sync_beam_search_fusion(*args, *fargs, *tail)
-    else:
-        rc = lib.edgedict_sync_beam_search(*args, *tail)
+    rc = lib.edgedict_sync_beam_search(
+        nref, _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), B, T, vp(lens), W, vp(tokens),
+        vp(frames), vp(tlogp), MT, vp(ntok), vp(nhyp), vp(logp), opts, _lib.ptr(ws), _lib.ptr(result), _lib.stream_ptr())
     _lib.check(rc, "sync_beam_search")
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
 
@@ -1066,11 +1080,9 @@ class StreamingBeamSearch:
 
     def _alloc(self):
         """The persistent state and the workspace, sized for the current forms (LM, bias list)."""
-        net = self._weights()
-        flm = self._fusion()
-        dims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.EM, self.NC)
-        sbytes = _native("beam_stream_state_bytes", flm, *dims, bref=self._bref())
-        wbytes = _native("beam_stream_workspace_bytes", flm, *dims, bref=self._bref())
+        net, lib, opts = self._weights(), _lib.load(), self._opts()
+        sbytes = lib.edgedict_beam_stream_state_bytes(opts, self.S, net.L, net.H, self.W, self.NC)
+        wbytes = lib.edgedict_beam_stream_workspace_bytes(net.ref(), self.S, self.W, self.EM, self.NC, opts)
         self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
         self._ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
 
@@ -1114,9 +1126,9 @@ class StreamingBeamSearch:
         # converted once per parameter version by WEIGHTS (as run_search does); only the pointer bundle is rebuilt
         return _SearchNet(self.model, self.cd)
 
-    def _fusion(self):
+    def _opts(self):
         from .lm import FusionLM
-        return None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args)
+        return _opts(None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args), self._bref())
 
     def reset(self, mask=None):
         """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log."""
@@ -1130,19 +1142,9 @@ class StreamingBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
         mp = None if mh is None else mh.ctypes.data_as(ctypes.c_void_p)
-        if self.bias is not None:
-            flm = self._fusion()
-            rc = _lib.load().edgedict_beam_stream_reset_bias(
-                self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, flm.ref() if flm is not None else None,
-                self._bref(), _lib.ptr(self._state), _lib.ptr(self._dstate) if self.detail else None, _lib.stream_ptr())
-        elif self.detail:
-            flm = self._fusion()
-            rc = _lib.load().edgedict_beam_stream_reset_detail(
-                self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, flm.ref() if flm is not None else None,
-                _lib.ptr(self._state), _lib.ptr(self._dstate), _lib.stream_ptr())
-        else:
-            rc = _native("beam_stream_reset", self._fusion(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp,
-                         on_host, tail=(_lib.ptr(self._state), _lib.stream_ptr()))
+        rc = _lib.load().edgedict_beam_stream_reset(
+            self._opts(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host, _lib.ptr(self._state),
+            _lib.ptr(self._dstate) if self.detail else None, _lib.stream_ptr())
         _lib.check(rc, "beam_stream_reset")
         if not hasattr(self, "_committed"):
             self._committed = [[] for _ in range(self.S)]
@@ -1193,26 +1195,14 @@ class StreamingBeamSearch:
         self._advance(net, E1, T, P, nf)
 
     def _advance(self, net, E1, T, P, nf):
-        from .tokenizer import BOS
         nexp = ctypes.c_longlong(0)
-        args = (dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S,
-                nf.ctypes.data_as(ctypes.c_void_p), *net.args(P), int(self.model.blank), int(BOS), self.W, self.EM,
-                self.NC, self._commit_buf.ctypes.data_as(ctypes.c_void_p),
-                self._ncommit.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nexp))
-        if self.detail:
-            flm = self._fusion()
-            vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-            dargs = (*args[:-2], vp(self._commit_frame_buf), vp(self._commit_logp_buf), *args[-2:],
-                     flm.ref() if flm is not None else None)
-            dtail = (_lib.ptr(self._state), _lib.ptr(self._ws), _lib.ptr(self._dstate), _lib.ptr(self._dws),
-                     _lib.stream_ptr())
-            if self.bias is not None:
-                rc = _lib.load().edgedict_beam_stream_advance_detail_bias(*dargs, self._bref(), *dtail)
-            else:
-                rc = _lib.load().edgedict_beam_stream_advance_detail(*dargs, *dtail)
-        else:
-            rc = _native("beam_stream_advance", self._fusion(), *args,
-                         tail=(_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr()), bref=self._bref())
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        detail = ((_lib.ptr(self._dstate), _lib.ptr(self._dws), vp(self._commit_frame_buf), vp(self._commit_logp_buf))
+                  if self.detail else (None,) * 4)
+        rc = _lib.load().edgedict_beam_stream_advance(
+            net.ref(P), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, vp(nf), self.W,
+            self.EM, self.NC, vp(self._commit_buf), vp(self._ncommit), ctypes.byref(nexp), self._opts(),
+            _lib.ptr(self._state), _lib.ptr(self._ws), *detail, _lib.stream_ptr())
         _lib.check(rc, "beam_stream_advance")
         self._frames += nf
         self.last_expansions = int(nexp.value)
@@ -1374,31 +1364,17 @@ class StreamingSyncBeamSearch:
     def _weights(self):
         return _SearchNet(self.model, self.cd)
 
-    def _fusion(self):
-        """(FusionLM or None, (lm, bias) of the ``_fusion`` entry points, or None for the plain ones).  The FusionLM is
-        returned so that it outlives the call that reads its struct."""
+    def _opts(self):
+        """The ``opts`` of this search's native calls (None: the plain search)."""
         from .lm import FusionLM
-        flm = None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args)
-        bref = None if self.bias is None else self.bias.ref(self.device)
-        if flm is None and bref is None:
-            return None, None
-        return flm, (flm.ref() if flm is not None else None, bref)
+        return _opts(None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args),
+                     None if self.bias is None else self.bias.ref(self.device), self._ilm)
 
     def _alloc(self):
         """The persistent state and the workspace, sized for the current forms (LM, bias list)."""
-        net = self._weights()
-        lib = _lib.load()
-        flm, fargs = self._fusion()
-        sdims = (self.S, net.L, net.H, self.W, self.NC)
-        wdims = (dtype_code(self.cd), self.S, net.J, net.V, net.E, net.L, net.H, net.P2, self.W, self.NC)
-        if fargs is None:
-            sbytes, wbytes = lib.edgedict_sync_stream_state_bytes(*sdims), lib.edgedict_sync_stream_workspace_bytes(*wdims)
-        else:
-            sbytes = lib.edgedict_sync_stream_state_bytes_fusion(*sdims, *fargs)
-            wbytes = lib.edgedict_sync_stream_workspace_bytes_fusion(*wdims, *fargs)
-        if self._ilm is not None:       # (ILME has no part in the state)
-            wbytes = lib.edgedict_sync_stream_workspace_bytes_ilme(*wdims, *(fargs or (None, None)),
-                                                                   ctypes.byref(self._ilm))
+        net, lib, opts = self._weights(), _lib.load(), self._opts()
+        sbytes = lib.edgedict_sync_stream_state_bytes(opts, self.S, net.L, net.H, self.W, self.NC)  # (no ILME part)
+        wbytes = lib.edgedict_sync_stream_workspace_bytes(net.ref(), self.S, self.W, self.NC, opts)
         if sbytes == 0 or wbytes == 0:
             raise ValueError("StreamingSyncBeamSearch: shapes out of range (H and the LM's hidden width must be "
                              "multiples of 4)")
@@ -1449,13 +1425,8 @@ class StreamingSyncBeamSearch:
             sel = m.astype(bool).reshape(self.S)
             mh, on_host = np.ascontiguousarray(sel, dtype=np.int32), 1
             mp = mh.ctypes.data_as(ctypes.c_void_p)
-        flm, fargs = self._fusion()
-        if fargs is None:
-            rc = _lib.load().edgedict_sync_stream_reset(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp, on_host,
-                                                        _lib.ptr(self._state), _lib.stream_ptr())
-        else:
-            rc = _lib.load().edgedict_sync_stream_reset_fusion(self.S, net.L, net.H, self.W, self.NC, int(BOS), mp,
-                                                               on_host, *fargs, _lib.ptr(self._state), _lib.stream_ptr())
+        rc = _lib.load().edgedict_sync_stream_reset(self._opts(), self.S, net.L, net.H, self.W, self.NC, int(BOS), mp,
+                                                    on_host, _lib.ptr(self._state), _lib.stream_ptr())
         _lib.check(rc, "sync_stream_reset")
         self._frames[sel] = 0
         self._live[sel] = 0
@@ -1502,25 +1473,16 @@ class StreamingSyncBeamSearch:
         self._advance(net, E1, T, P, self._n_frames("advance_rows", n_frames, T))
 
     def _advance(self, net, E1, T, P, nf):
-        from .tokenizer import BOS
         need = self._live.astype(np.int64) + nf.astype(np.int64) * self.W
         if (need > self.NC).any():
             s = int(np.argmax(need > self.NC))
             raise RuntimeError("StreamingSyncBeamSearch: stream %d may need %d token-tree nodes (%d live + %d frames x "
                                "W = %d), node_capacity is %d" % (s, need[s], self._live[s], nf[s], self.W, self.NC))
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        args = (dtype_code(self.cd), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, T,
-                vp(nf), *net.args(P), int(self.model.blank), int(BOS), self.W, self.NC, vp(self._live),
-                ctypes.byref(self._parity), vp(self._commit_buf), self.NC)
-        tail = (_lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
-        flm, fargs = self._fusion()
-        if self._ilm is not None:
-            rc = _lib.load().edgedict_sync_stream_advance_ilme(*args, *(fargs or (None, None)), ctypes.byref(self._ilm),
-                                                               *tail)
-        elif fargs is None:
-            rc = _lib.load().edgedict_sync_stream_advance(*args, *tail)
-        else:
-            rc = _lib.load().edgedict_sync_stream_advance_fusion(*args, *fargs, *tail)
+        rc = _lib.load().edgedict_sync_stream_advance(
+            net.ref(P), _lib.ptr(E1), ctypes.c_longlong(T * net.J), ctypes.c_longlong(net.J), self.S, T, vp(nf), self.W,
+            self.NC, vp(self._live), ctypes.byref(self._parity), vp(self._commit_buf), self.NC, self._opts(),
+            _lib.ptr(self._state), _lib.ptr(self._ws), _lib.stream_ptr())
         _lib.check(rc, "sync_stream_advance")
         self._frames += nf
         ncommit = self._commit_buf[:, 0, 0]

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EDGEDICT_ABI_VERSION 1
+#define EDGEDICT_ABI_VERSION 2
 
 #define ED_OK 0
 #define ED_ERR_INVALID (-1) /* bad argument (shape / dtype / alignment) */
@@ -810,11 +810,56 @@ int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, int T, int 
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * What every search below takes: the transducer's search network, described once, and the optional features.
+ *   edgedict_search_net_t   the joint and the prediction network, operands as edgedict_greedy_decode's (w_ih / w_hh /
+ *                           b_ih / b_hh: HOST arrays [L] of DEVICE pointers), the compute dtype, blank, and bos = the token
+ *                           the empty hypothesis feeds first (BOS = 2, zero state).  The size queries read only the shape
+ *                           fields (dtype, J, P2, V, E, L, H) and return 0 for a null network
+ *   edgedict_search_opts_t  lm: LM shallow fusion, bias: contextual biasing, ilm_weight (a HOST double): internal-LM
+ *                           estimation - each specified in its own block below.  A null member switches its feature off,
+ *                           a null opts pointer is all members null: the plain search, launch for launch and bit for bit.
+ *                           The expansion searches (edgedict_beam_*) refuse ilm_weight before they touch the device
+ * A descriptor leads every argument list: net where the function needs the network (opts then stands in front of the
+ * trailing buffers), opts where it does not.  A non-null net / opts below address 4096 - the integer a caller written
+ * for ABI version 1 passes in that place - is an argument error (size queries: 0), never dereferenced.
+ * search_struct_bytes: sizeof(edgedict_search_net_t) (which = 0) / sizeof(edgedict_search_opts_t) (which = 1), for
+ * bindings that mirror them.
+ */
+struct edgedict_beam_lm_t;
+struct edgedict_beam_bias_t;
+typedef struct edgedict_search_net_t {
+    int dtype;
+    int J;
+    const void* W1d;
+    long long ldw1;
+    const float* b1;
+    int P2;
+    const void* W2;
+    const float* b2;
+    int V;
+    const void* emb;
+    int emb_dtype, E, L;
+    const void* const* w_ih;
+    const void* const* w_hh;
+    const float* const* b_ih;
+    const float* const* b_hh;
+    int H;
+    const void* Wp;
+    const float* bp;
+    int blank, bos;
+} edgedict_search_net_t;
+typedef struct edgedict_search_opts_t {
+    const struct edgedict_beam_lm_t* lm;
+    const struct edgedict_beam_bias_t* bias;
+    const double* ilm_weight;
+} edgedict_search_opts_t;
+size_t edgedict_search_struct_bytes(int which);
+
+/* ------------------------------------------------------------------------------------
  * Batched beam search: the reference's legacy Transducer.beam_search (models.py:121-202; Sequence
  * models.py:212-224) for B utterances in lockstep, over the maintained model's prediction network and
- * joint.  Operands as edgedict_greedy_decode, plus
+ * joint.  net / opts as above, E1 and its strides as edgedict_greedy_decode's, plus
  *   lens_host        HOST int32 [B]: encoder frames of each utterance (<= T)
- *   bos              the token the empty hypothesis feeds first (BOS = 2, zero state)
  *   W                beam width;  max_expansions >= W: cap on pops per utterance and frame
  *                    (exceeding it is an error, never a silent truncation)
  *   tokens_host      HOST int32 [B, max_tokens]: tokens of B[0] (no blanks, no BOS)
@@ -830,18 +875,12 @@ int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, int T, int 
  * Scores are accumulated in fp64 from fp32 log-softmax values, as the reference's Python floats
  * are.  The call synchronises the stream (the loop's stop test is data dependent).
  */
-size_t edgedict_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H,
-                                     int P2, int W, int max_expansions, int prefix);
-int edgedict_beam_search(int dtype, const void* E1, long long e_row_stride,
-                         long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
-                         const void* W1d, long long ldw1, const float* b1, int P2, const void* W2,
-                         const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-                         const void* const* w_ih, const void* const* w_hh,
-                         const float* const* b_ih, const float* const* b_hh, int H,
-                         const void* Wp, const float* bp, int blank, int bos, int W,
-                         int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
-                         int32_t* ntokens_host, double* score_host, long long* expansions_host,
-                         void* workspace, void* stream);
+size_t edgedict_beam_workspace_bytes(const edgedict_search_net_t* net, int B, int T, int W, int max_expansions,
+                                     int prefix, const edgedict_search_opts_t* opts);
+int edgedict_beam_search(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                         long long e_frame_stride, int B, int T, const int32_t* lens_host, int W, int max_expansions,
+                         int prefix, int32_t* tokens_host, int max_tokens, int32_t* ntokens_host, double* score_host,
+                         long long* expansions_host, const edgedict_search_opts_t* opts, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Streaming beam search: edgedict_beam_search (prefix = 0) with its frame-to-frame list B kept in a
@@ -872,24 +911,24 @@ int edgedict_beam_search(int dtype, const void* E1, long long e_row_stride,
  *                             its score -logp (fp64), the number of committed tokens before the tail
  *                             (ncommitted_host, nullable) and the expansions since the stream's reset
  *                             (expansions_host, nullable).  Synchronises the stream.
+ * The state's and the workspace's layout depend on opts (an LM and a bias list append their parts): size, reset and
+ * advance a state with the same features.  detail_state of reset and detail_state / detail_workspace /
+ * commit_frame_host / commit_logp_host of advance are the N-best detail (below): all null for none, partly null is an
+ * argument error.
  */
-size_t edgedict_beam_stream_state_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2,
-                                        int W, int max_expansions, int node_capacity);
-size_t edgedict_beam_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H,
-                                            int P2, int W, int max_expansions, int node_capacity);
-int edgedict_beam_stream_reset(int S, int L, int H, int W, int node_capacity, int bos,
-                               const int32_t* mask, int mask_on_host, void* state, void* stream);
-int edgedict_beam_stream_advance(int dtype, const void* E1, long long e_row_stride,
-                                 long long e_frame_stride, int S, const int32_t* n_frames_host, int J,
-                                 const void* W1d, long long ldw1, const float* b1, int P2,
-                                 const void* W2, const float* b2, int V, const void* emb,
-                                 int emb_dtype, int E, int L, const void* const* w_ih,
-                                 const void* const* w_hh, const float* const* b_ih,
-                                 const float* const* b_hh, int H, const void* Wp, const float* bp,
-                                 int blank, int bos, int W, int max_expansions, int node_capacity,
-                                 int32_t* commit_host, int32_t* ncommit_host,
-                                 long long* expansions_host, void* state, void* workspace,
-                                 void* stream);
+size_t edgedict_beam_stream_state_bytes(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                        int node_capacity);
+size_t edgedict_beam_stream_workspace_bytes(const edgedict_search_net_t* net, int S, int W, int max_expansions,
+                                            int node_capacity, const edgedict_search_opts_t* opts);
+int edgedict_beam_stream_reset(const edgedict_search_opts_t* opts, int S, int L, int H, int W, int node_capacity,
+                               int bos, const int32_t* mask, int mask_on_host, void* state, void* detail_state,
+                               void* stream);
+int edgedict_beam_stream_advance(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                                 long long e_frame_stride, int S, const int32_t* n_frames_host, int W,
+                                 int max_expansions, int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
+                                 long long* expansions_host, const edgedict_search_opts_t* opts, void* state,
+                                 void* workspace, void* detail_state, void* detail_workspace,
+                                 int32_t* commit_frame_host, double* commit_logp_host, void* stream);
 int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, const void* state,
                               int32_t* tokens_host, int max_tokens, int32_t* ntokens_host,
                               double* score_host, long long* ncommitted_host,
@@ -913,10 +952,10 @@ int edgedict_beam_stream_read(int S, int L, int H, int W, int node_capacity, con
  *   L, E, H, V   layers, embedding width, hidden width, ntoken (must equal the transducer's V)
  *   emb          [V, E] in emb_dtype;  w_ih / w_hh / b_ih / b_hh: HOST arrays [L] of DEVICE pointers
  *                ([4H, E or H], [4H, H] in the search's dtype; fp32 [4H]);  Wo [V, H] dtype, bo fp32 [V]
- * The *_lm entry points take the plain ones' arguments plus `lm` (null: exactly the plain call).
+ * The searches take the LM as opts->lm (null: exactly the plain call).
  * prefix = 1 with an LM is refused (it would need LM log-probs stored per token-tree node).  The
- * streaming state of the _lm form appends the survivors' LM (h, c) behind the plain layout, so
- * edgedict_beam_stream_read serves both; reset and advance of such a state must use the _lm forms.
+ * streaming state with an LM appends the survivors' LM (h, c) behind the plain layout, so
+ * edgedict_beam_stream_read serves both; reset and advance of such a state must be given the LM too.
  * beam_lm_struct_bytes: sizeof(edgedict_beam_lm_t), for bindings that mirror it.
  */
 typedef struct edgedict_beam_lm_t {
@@ -935,43 +974,10 @@ typedef struct edgedict_beam_lm_t {
 } edgedict_beam_lm_t;
 
 size_t edgedict_beam_lm_struct_bytes(void);
-size_t edgedict_beam_workspace_bytes_lm(int dtype, int B, int T, int J, int V, int E, int L, int H,
-                                        int P2, int W, int max_expansions, int prefix,
-                                        const edgedict_beam_lm_t* lm);
-int edgedict_beam_search_lm(int dtype, const void* E1, long long e_row_stride,
-                            long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
-                            const void* W1d, long long ldw1, const float* b1, int P2,
-                            const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
-                            int E, int L, const void* const* w_ih, const void* const* w_hh,
-                            const float* const* b_ih, const float* const* b_hh, int H,
-                            const void* Wp, const float* bp, int blank, int bos, int W,
-                            int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
-                            int32_t* ntokens_host, double* score_host, long long* expansions_host,
-                            const edgedict_beam_lm_t* lm, void* workspace, void* stream);
-size_t edgedict_beam_stream_state_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H,
-                                           int P2, int W, int max_expansions, int node_capacity,
-                                           const edgedict_beam_lm_t* lm);
-size_t edgedict_beam_stream_workspace_bytes_lm(int dtype, int S, int J, int V, int E, int L, int H,
-                                               int P2, int W, int max_expansions,
-                                               int node_capacity, const edgedict_beam_lm_t* lm);
-int edgedict_beam_stream_reset_lm(int S, int L, int H, int W, int node_capacity, int bos,
-                                  const int32_t* mask, int mask_on_host,
-                                  const edgedict_beam_lm_t* lm, void* state, void* stream);
-int edgedict_beam_stream_advance_lm(int dtype, const void* E1, long long e_row_stride,
-                                    long long e_frame_stride, int S, const int32_t* n_frames_host,
-                                    int J, const void* W1d, long long ldw1, const float* b1, int P2,
-                                    const void* W2, const float* b2, int V, const void* emb,
-                                    int emb_dtype, int E, int L, const void* const* w_ih,
-                                    const void* const* w_hh, const float* const* b_ih,
-                                    const float* const* b_hh, int H, const void* Wp,
-                                    const float* bp, int blank, int bos, int W, int max_expansions,
-                                    int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-                                    long long* expansions_host, const edgedict_beam_lm_t* lm,
-                                    void* state, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * N-best lists with token frames and log-probs from both beam searches.  The *_nbest / *_detail entry
- * points run the searches above (same frame loop, same pops, same scores) and keep, beside every
+ * N-best lists with token frames and log-probs from both beam searches.  edgedict_beam_search_nbest and
+ * the streaming calls with their detail pointers run the searches above (same frame loop, same pops, same scores) and keep, beside every
  * token-tree node, a DETAIL:
  *   frame   the encoder frame on which the expansion that produced the node's token ran (offline: the
  *           index into the utterance; streaming: counted since the stream's last reset)
@@ -989,8 +995,8 @@ int edgedict_beam_stream_advance_lm(int dtype, const void* E1, long long e_row_s
  *                                                      nodes' detail and the frames done per stream
  *   beam_stream_detail_workspace_bytes(S, node_capacity) per call, beside beam_stream_advance's
  *                                                      workspace (compaction moves the detail too)
- * beam_search_nbest            operands as edgedict_beam_search_lm (lm nullable; workspace sized by
- *                              edgedict_beam_workspace_bytes[_lm] with prefix = 0), with the outputs
+ * beam_search_nbest            operands as edgedict_beam_search (workspace sized by
+ *                              edgedict_beam_workspace_bytes with prefix = 0), with the outputs
  *                                tokens_host / frames_host  HOST int32 [B, W, max_tokens]
  *                                token_logp_host            HOST fp64  [B, W, max_tokens]
  *                                ntokens_host HOST int32 [B, W];  nhyp_host HOST int32 [B] (= n)
@@ -1000,49 +1006,26 @@ int edgedict_beam_stream_advance_lm(int dtype, const void* E1, long long e_row_s
  *                              is refused (-1) before anything runs: the prefix merge changes a score
  *                              at frame starts, so the increments would no longer add up to it.  A
  *                              hypothesis longer than max_tokens is an error, never a truncation.
- * beam_stream_reset_detail     edgedict_beam_stream_reset_lm, and the selected streams' frame count -> 0
- * beam_stream_advance_detail   edgedict_beam_stream_advance_lm; additionally commit_frame_host HOST int32
+ * beam_stream_reset, detail    the reset, and the selected streams' frame count -> 0
+ * beam_stream_advance, detail  the advance; additionally commit_frame_host HOST int32
  *                              / commit_logp_host HOST fp64 [S, node_capacity]: frames and increments of
  *                              the tokens committed by this advance, next to commit_host
  * beam_stream_read_nbest       per stream the uncommitted tails of every entry of B as above (the full
  *                              hypothesis is the committed log followed by the tail); ncommitted_host,
  *                              expansions_host as edgedict_beam_stream_read; frames_done_host HOST int64
  *                              [S], nullable: frames since the stream's reset.  Synchronises the stream.
- * A state advanced with the detail form must always be reset, advanced and read with it.
+ * A state advanced with the detail must always be reset, advanced and read with it.
  */
 size_t edgedict_beam_detail_bytes(int B, int T, int max_expansions);
 size_t edgedict_beam_nbest_result_bytes(int B, int W, int max_tokens);
-int edgedict_beam_search_nbest(int dtype, const void* E1, long long e_row_stride,
-                               long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
-                               const void* W1d, long long ldw1, const float* b1, int P2,
-                               const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
-                               int E, int L, const void* const* w_ih, const void* const* w_hh,
-                               const float* const* b_ih, const float* const* b_hh, int H,
-                               const void* Wp, const float* bp, int blank, int bos, int W,
-                               int max_expansions, int prefix, int32_t* tokens_host,
-                               int32_t* frames_host, double* token_logp_host, int max_tokens,
-                               int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
-                               long long* expansions_host, const edgedict_beam_lm_t* lm,
+int edgedict_beam_search_nbest(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                               long long e_frame_stride, int B, int T, const int32_t* lens_host, int W,
+                               int max_expansions, int prefix, int32_t* tokens_host, int32_t* frames_host,
+                               double* token_logp_host, int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host,
+                               double* logp_host, long long* expansions_host, const edgedict_search_opts_t* opts,
                                void* workspace, void* detail, void* result, void* stream);
 size_t edgedict_beam_stream_detail_state_bytes(int S, int node_capacity);
 size_t edgedict_beam_stream_detail_workspace_bytes(int S, int node_capacity);
-int edgedict_beam_stream_reset_detail(int S, int L, int H, int W, int node_capacity, int bos,
-                                      const int32_t* mask, int mask_on_host,
-                                      const edgedict_beam_lm_t* lm, void* state, void* detail_state,
-                                      void* stream);
-int edgedict_beam_stream_advance_detail(int dtype, const void* E1, long long e_row_stride,
-                                        long long e_frame_stride, int S, const int32_t* n_frames_host,
-                                        int J, const void* W1d, long long ldw1, const float* b1,
-                                        int P2, const void* W2, const float* b2, int V,
-                                        const void* emb, int emb_dtype, int E, int L,
-                                        const void* const* w_ih, const void* const* w_hh,
-                                        const float* const* b_ih, const float* const* b_hh, int H,
-                                        const void* Wp, const float* bp, int blank, int bos, int W,
-                                        int max_expansions, int node_capacity, int32_t* commit_host,
-                                        int32_t* commit_frame_host, double* commit_logp_host,
-                                        int32_t* ncommit_host, long long* expansions_host,
-                                        const edgedict_beam_lm_t* lm, void* state, void* workspace,
-                                        void* detail_state, void* detail_workspace, void* stream);
 int edgedict_beam_stream_read_nbest(int S, int L, int H, int W, int node_capacity, const void* state,
                                     const void* detail_state, void* result, int32_t* tokens_host,
                                     int32_t* frames_host, double* token_logp_host, int max_tokens,
@@ -1065,13 +1048,12 @@ int edgedict_beam_stream_read_nbest(int S, int L, int H, int W, int node_capacit
  *   row_ptr [S + 1] int32, exc_tok / exc_next [n_exc] int32: per state the EXCEPTIONS, the tokens (sorted)
  *                         where goto(s, k) != goto(0, k), and their targets; every other token takes root_next
  * All targets must lie in [0, S) and exc_tok in [0, V): the tables are trusted (ContextGraph writes them).
- * The *_bias entry points take the _lm ones' arguments with `bias` behind `lm`, both nullable: bias = null
- * is exactly the _lm call (same kernels, same layouts).  With a bias list the searches run the separately
+ * The searches take the list as opts->bias, with or without opts->lm: bias = null is exactly the call
+ * without it (same kernels, same layouts).  With a bias list the searches run the separately
  * compiled beam_pop[_detail]_bias / beam_expand[_lm]_bias kernels; prefix = 1 is refused.  The offline
  * workspace and the streams' state / workspace append the bias state arrays behind the LM's part, so
  * edgedict_beam_stream_read[_nbest] serve every form; a state sized with a bias list must be reset and
  * advanced with one (the list may change at a reset: the root state is 0 in every automaton).
- * beam_stream_reset_bias: detail_state nullable (non-null: as edgedict_beam_stream_reset_detail).
  * beam_bias_struct_bytes: sizeof(edgedict_beam_bias_t), for bindings that mirror it.
  */
 typedef struct edgedict_beam_bias_t {
@@ -1085,73 +1067,6 @@ typedef struct edgedict_beam_bias_t {
 } edgedict_beam_bias_t;
 
 size_t edgedict_beam_bias_struct_bytes(void);
-size_t edgedict_beam_workspace_bytes_bias(int dtype, int B, int T, int J, int V, int E, int L, int H,
-                                          int P2, int W, int max_expansions, int prefix,
-                                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias);
-int edgedict_beam_search_bias(int dtype, const void* E1, long long e_row_stride,
-                              long long e_frame_stride, int B, int T, const int32_t* lens_host, int J,
-                              const void* W1d, long long ldw1, const float* b1, int P2,
-                              const void* W2, const float* b2, int V, const void* emb, int emb_dtype,
-                              int E, int L, const void* const* w_ih, const void* const* w_hh,
-                              const float* const* b_ih, const float* const* b_hh, int H,
-                              const void* Wp, const float* bp, int blank, int bos, int W,
-                              int max_expansions, int prefix, int32_t* tokens_host, int max_tokens,
-                              int32_t* ntokens_host, double* score_host, long long* expansions_host,
-                              const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                              void* workspace, void* stream);
-int edgedict_beam_search_nbest_bias(int dtype, const void* E1, long long e_row_stride,
-                                    long long e_frame_stride, int B, int T, const int32_t* lens_host,
-                                    int J, const void* W1d, long long ldw1, const float* b1, int P2,
-                                    const void* W2, const float* b2, int V, const void* emb,
-                                    int emb_dtype, int E, int L, const void* const* w_ih,
-                                    const void* const* w_hh, const float* const* b_ih,
-                                    const float* const* b_hh, int H, const void* Wp, const float* bp,
-                                    int blank, int bos, int W, int max_expansions, int prefix,
-                                    int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
-                                    int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host,
-                                    double* logp_host, long long* expansions_host,
-                                    const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                    void* workspace, void* detail, void* result, void* stream);
-size_t edgedict_beam_stream_state_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
-                                             int P2, int W, int max_expansions, int node_capacity,
-                                             const edgedict_beam_lm_t* lm,
-                                             const edgedict_beam_bias_t* bias);
-size_t edgedict_beam_stream_workspace_bytes_bias(int dtype, int S, int J, int V, int E, int L, int H,
-                                                 int P2, int W, int max_expansions, int node_capacity,
-                                                 const edgedict_beam_lm_t* lm,
-                                                 const edgedict_beam_bias_t* bias);
-int edgedict_beam_stream_reset_bias(int S, int L, int H, int W, int node_capacity, int bos,
-                                    const int32_t* mask, int mask_on_host, const edgedict_beam_lm_t* lm,
-                                    const edgedict_beam_bias_t* bias, void* state, void* detail_state,
-                                    void* stream);
-int edgedict_beam_stream_advance_bias(int dtype, const void* E1, long long e_row_stride,
-                                      long long e_frame_stride, int S, const int32_t* n_frames_host,
-                                      int J, const void* W1d, long long ldw1, const float* b1, int P2,
-                                      const void* W2, const float* b2, int V, const void* emb,
-                                      int emb_dtype, int E, int L, const void* const* w_ih,
-                                      const void* const* w_hh, const float* const* b_ih,
-                                      const float* const* b_hh, int H, const void* Wp,
-                                      const float* bp, int blank, int bos, int W, int max_expansions,
-                                      int node_capacity, int32_t* commit_host, int32_t* ncommit_host,
-                                      long long* expansions_host, const edgedict_beam_lm_t* lm,
-                                      const edgedict_beam_bias_t* bias, void* state, void* workspace,
-                                      void* stream);
-int edgedict_beam_stream_advance_detail_bias(int dtype, const void* E1, long long e_row_stride,
-                                             long long e_frame_stride, int S,
-                                             const int32_t* n_frames_host, int J, const void* W1d,
-                                             long long ldw1, const float* b1, int P2, const void* W2,
-                                             const float* b2, int V, const void* emb, int emb_dtype,
-                                             int E, int L, const void* const* w_ih,
-                                             const void* const* w_hh, const float* const* b_ih,
-                                             const float* const* b_hh, int H, const void* Wp,
-                                             const float* bp, int blank, int bos, int W,
-                                             int max_expansions, int node_capacity, int32_t* commit_host,
-                                             int32_t* commit_frame_host, double* commit_logp_host,
-                                             int32_t* ncommit_host, long long* expansions_host,
-                                             const edgedict_beam_lm_t* lm,
-                                             const edgedict_beam_bias_t* bias, void* state,
-                                             void* workspace, void* detail_state,
-                                             void* detail_workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Row log-softmax (LMModel.forward's F.log_softmax(decoded, dim=-1), models.py:251):
@@ -1379,7 +1294,7 @@ int edgedict_frame_skip_gather(const void* enc_out, int dtype, const int32_t* fr
  * do not return the same hypotheses.  A fixed list of launches per frame, no host synchronisation inside the frame
  * loop, no atomics; results are bit-identical from run to run.
  *
- *   operands   as edgedict_beam_search_nbest without max_expansions, prefix, expansions_host, lm and detail
+ *   operands   as edgedict_beam_search_nbest without max_expansions, prefix, expansions_host and detail
  *   W          beam width, 1 .. 32;  T > 0;  lens_host[b] in [0, T];  H a multiple of 4 (the LSTM kernels ask for 8)
  *   tokens_host / frames_host  HOST int32 [B, W, max_tokens]: hypothesis h's tokens root to leaf and the frame each
  *              token's node was created on;  token_logp_host HOST fp64 [B, W, max_tokens]: the token's log-softmax
@@ -1393,16 +1308,14 @@ int edgedict_frame_skip_gather(const void* enc_out, int dtype, const int32_t* fr
  * Arguments are checked before anything is launched: a bad W, T <= 0, a null pointer give -1 and a message.
  * Synchronises the stream once, at the end.
  */
-size_t edgedict_sync_beam_workspace_bytes(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2, int W);
+size_t edgedict_sync_beam_workspace_bytes(const edgedict_search_net_t* net, int B, int T, int W,
+                                          const edgedict_search_opts_t* opts);
 size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens);
-int edgedict_sync_beam_search(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B, int T,
-                              const int32_t* lens_host, int J, const void* W1d, long long ldw1, const float* b1, int P2,
-                              const void* W2, const float* b2, int V, const void* emb, int emb_dtype, int E, int L,
-                              const void* const* w_ih, const void* const* w_hh, const float* const* b_ih,
-                              const float* const* b_hh, int H, const void* Wp, const float* bp, int blank, int bos,
-                              int W, int32_t* tokens_host, int32_t* frames_host, double* token_logp_host,
-                              int max_tokens, int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
-                              void* workspace, void* result, void* stream);
+int edgedict_sync_beam_search(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                              long long e_frame_stride, int B, int T, const int32_t* lens_host, int W,
+                              int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
+                              int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
+                              const edgedict_search_opts_t* opts, void* workspace, void* result, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Streaming form of the frame-synchronous search: the beams of S streams live in a persistent device STATE, so that
@@ -1448,29 +1361,27 @@ int edgedict_sync_beam_search(int dtype, const void* E1, long long e_row_stride,
  * Every entry point checks its arguments before any launch (W outside [1, 32], S <= 0, node_capacity < W, null
  * pointers, dtypes, blank / bos, n_frames, H % 4) and returns -1 with a message.
  */
-size_t edgedict_sync_stream_state_bytes(int S, int L, int H, int W, int node_capacity);
-size_t edgedict_sync_stream_workspace_bytes(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
-                                            int node_capacity);
+size_t edgedict_sync_stream_state_bytes(const edgedict_search_opts_t* opts, int S, int L, int H, int W,
+                                        int node_capacity);
+size_t edgedict_sync_stream_workspace_bytes(const edgedict_search_net_t* net, int S, int W, int node_capacity,
+                                            const edgedict_search_opts_t* opts);
 size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens);
-int edgedict_sync_stream_reset(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                               int mask_on_host, void* state, void* stream);
-int edgedict_sync_stream_advance(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int S,
-                                 int T, const int32_t* n_frames_host, int J, const void* W1d, long long ldw1,
-                                 const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
-                                 int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-                                 const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
-                                 const float* bp, int blank, int bos, int W, int node_capacity, int32_t* live_host,
-                                 int32_t* parity_host, void* commit_host, int max_commit, void* state,
-                                 void* workspace, void* stream);
+int edgedict_sync_stream_reset(const edgedict_search_opts_t* opts, int S, int L, int H, int W, int node_capacity,
+                               int bos, const int32_t* mask, int mask_on_host, void* state, void* stream);
+int edgedict_sync_stream_advance(const edgedict_search_net_t* net, const void* E1, long long e_row_stride,
+                                 long long e_frame_stride, int S, int T, const int32_t* n_frames_host, int W,
+                                 int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
+                                 int max_commit, const edgedict_search_opts_t* opts, void* state, void* workspace,
+                                 void* stream);
 int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, const void* state, void* result,
                               int32_t* tokens_host, int32_t* frames_host, double* token_logp_host, int max_tokens,
                               int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
                               long long* ncommitted_host, long long* nframes_host, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * LM shallow fusion and contextual biasing in the frame-synchronous search, offline and streaming.  The *_fusion entry
- * points take the plain ones' arguments with `lm` and `bias` in front of the trailing state / workspace / result /
- * stream; either may be null, and with both null they ARE the plain calls (same kernels, same layouts, same bits).
+ * LM shallow fusion and contextual biasing in the frame-synchronous search, offline and streaming: opts->lm and
+ * opts->bias of the edgedict_sync_* entry points.  Either may be null, and with both null the calls ARE the plain ones
+ * (same kernels, same layouts, same bits).
  *
  * Every row carries, beside its prediction-network state, the LM state from BEFORE its last token and the phrase
  * automaton's state s after its sequence (root: 0).  Per frame every row steps the LM on its last token - a row with
@@ -1486,55 +1397,24 @@ int edgedict_sync_stream_read(int S, int L, int H, int W, int node_capacity, con
  * bit-equal to the plain search.  A frame is the plain search's launches plus the LM step on all B * W rows
  * (lm->L + 1 launches on the fused step); a bias list adds none.
  *
- *   sync_beam_workspace_bytes_fusion     the plain workspace + the LM step's buffers + the rows' LM (h, c) [lm->L][B*W][lm->H]
+ *   sync_beam_workspace_bytes            the plain workspace + the LM step's buffers + the rows' LM (h, c) [lm->L][B*W][lm->H]
  *                                        in two buffers, the LM's next symbols and the automaton states
- *   sync_stream_state_bytes_fusion       the plain state with the rows' LM (h, c) in both buffers, the LM's next symbols
+ *   sync_stream_state_bytes              the plain state with the rows' LM (h, c) in both buffers, the LM's next symbols
  *                                        and the automaton states APPENDED: edgedict_sync_stream_read serves every form.
  *                                        A state sized with an LM / a list must be reset and advanced with one
- *   sync_stream_workspace_bytes_fusion   the plain workspace + the LM step's buffers
- *   sync_stream_reset_fusion             the plain reset; the selected streams' LM states are zeroed, their automaton
+ *   sync_stream_workspace_bytes          the plain workspace + the LM step's buffers
+ *   sync_stream_reset                    the plain reset; the selected streams' LM states are zeroed, their automaton
  *                                        states set to the root (the list may change at a reset)
- *   sync_stream_advance_fusion           the plain advance on the fused scores; compaction is unchanged
+ *   sync_stream_advance                  the plain advance on the fused scores; compaction is unchanged
  * Checked before anything is launched (-1 and a message): the LM's ntoken and the list's vocabulary equal V, lm->H a
  * multiple of 4, lm->bos inside the vocabulary, finite weight / length_bonus, non-null weights and tables, bias->S > 0.
  * The size queries return 0 for arguments out of range.
  */
-size_t edgedict_sync_beam_workspace_bytes_fusion(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2,
-                                                 int W, const edgedict_beam_lm_t* lm,
-                                                 const edgedict_beam_bias_t* bias);
-int edgedict_sync_beam_search_fusion(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B,
-                                     int T, const int32_t* lens_host, int J, const void* W1d, long long ldw1,
-                                     const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
-                                     int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-                                     const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
-                                     const float* bp, int blank, int bos, int W, int32_t* tokens_host,
-                                     int32_t* frames_host, double* token_logp_host, int max_tokens,
-                                     int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
-                                     const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, void* workspace,
-                                     void* result, void* stream);
-size_t edgedict_sync_stream_state_bytes_fusion(int S, int L, int H, int W, int node_capacity,
-                                               const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias);
-size_t edgedict_sync_stream_workspace_bytes_fusion(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
-                                                   int node_capacity, const edgedict_beam_lm_t* lm,
-                                                   const edgedict_beam_bias_t* bias);
-int edgedict_sync_stream_reset_fusion(int S, int L, int H, int W, int node_capacity, int bos, const int32_t* mask,
-                                      int mask_on_host, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                      void* state, void* stream);
-int edgedict_sync_stream_advance_fusion(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride,
-                                        int S, int T, const int32_t* n_frames_host, int J, const void* W1d,
-                                        long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                                        const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                                        const void* const* w_hh, const float* const* b_ih, const float* const* b_hh,
-                                        int H, const void* Wp, const float* bp, int blank, int bos, int W,
-                                        int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-                                        int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                        void* state, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Internal-LM estimation (ILME) in the frame-synchronous search, offline and streaming, and the internal LM as a scorer.
- * The *_ilme entry points take the *_fusion ones' arguments with `ilm_weight` (a HOST double, or null) behind `bias`;
- * with ilm_weight null they ARE the *_fusion calls (same kernels, same layouts, same bits), and lm / bias may be null as
- * there.  The *_fusion entry points call these with null.
+ * opts->ilm_weight (a HOST double, or null) of the edgedict_sync_* entry points switches it on; with ilm_weight null the
+ * calls ARE the ones without it (same kernels, same layouts, same bits), and lm / bias may be null as there.
  *
  * For a row whose prediction-network output after its last token is d [P2], the internal LM's logits are the step's
  * joint on an all-zero encoder row, z_ilm = tanh(act(d W1d^T + b1)) W2^T + b2 (act: the rounding to the compute dtype),
@@ -1544,10 +1424,10 @@ int edgedict_sync_stream_advance_fusion(int dtype, const void* E1, long long e_r
  *   c = c - ilm_weight * (double)lp_ilm_i[k];  c = c + (held[goto(s_i, k)] - pend[s_i])
  * (a term is absent when its feature is); blank keeps logp_i + lp_i[blank]; token_logp stays lp_i[k].  ilm_weight = 0
  * runs the ILME kernels and is bit-equal to the call without it.  ILME carries no per-row state: the persistent state
- * of a stream, its reset and its read are the *_fusion forms'.  Launches per frame: on the fused step none more (one
+ * of a stream, its reset and its read take no part in it.  Launches per frame: on the fused step none more (one
  * joint-hidden kernel writes both hidden vectors, the logits kernel runs on 2 B W rows); on the composed step two more.
  *
- *   sync_beam_workspace_bytes_ilme / sync_stream_workspace_bytes_ilme   the *_fusion size + ILME's buffers (hidden vectors
+ *   sync_beam_workspace_bytes / sync_stream_workspace_bytes   the size without it + ILME's buffers (hidden vectors
  *                                        [2 rows, J], fp32 logits [2 rows, V], a zero encoder row)
  * Checked before anything is launched (-1 and a message): ilm_weight finite and >= 0.  The size queries return 0 then.
  *
@@ -1558,31 +1438,6 @@ int edgedict_sync_stream_advance_fusion(int dtype, const void* E1, long long e_r
  *                   behind it (targets int32 [B, U], ylen int32 [B], both on the device).  A blank target gives -inf, one
  *                   outside the vocabulary NaN.  One wave per row, no atomics: the same bits every run.
  */
-size_t edgedict_sync_beam_workspace_bytes_ilme(int dtype, int B, int T, int J, int V, int E, int L, int H, int P2, int W,
-                                               const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                               const double* ilm_weight);
-int edgedict_sync_beam_search_ilme(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride, int B,
-                                   int T, const int32_t* lens_host, int J, const void* W1d, long long ldw1,
-                                   const float* b1, int P2, const void* W2, const float* b2, int V, const void* emb,
-                                   int emb_dtype, int E, int L, const void* const* w_ih, const void* const* w_hh,
-                                   const float* const* b_ih, const float* const* b_hh, int H, const void* Wp,
-                                   const float* bp, int blank, int bos, int W, int32_t* tokens_host,
-                                   int32_t* frames_host, double* token_logp_host, int max_tokens,
-                                   int32_t* ntokens_host, int32_t* nhyp_host, double* logp_host,
-                                   const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                   const double* ilm_weight, void* workspace, void* result, void* stream);
-size_t edgedict_sync_stream_workspace_bytes_ilme(int dtype, int S, int J, int V, int E, int L, int H, int P2, int W,
-                                                 int node_capacity, const edgedict_beam_lm_t* lm,
-                                                 const edgedict_beam_bias_t* bias, const double* ilm_weight);
-int edgedict_sync_stream_advance_ilme(int dtype, const void* E1, long long e_row_stride, long long e_frame_stride,
-                                      int S, int T, const int32_t* n_frames_host, int J, const void* W1d,
-                                      long long ldw1, const float* b1, int P2, const void* W2, const float* b2, int V,
-                                      const void* emb, int emb_dtype, int E, int L, const void* const* w_ih,
-                                      const void* const* w_hh, const float* const* b_ih, const float* const* b_hh,
-                                      int H, const void* Wp, const float* bp, int blank, int bos, int W,
-                                      int node_capacity, int32_t* live_host, int32_t* parity_host, void* commit_host,
-                                      int max_commit, const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
-                                      const double* ilm_weight, void* state, void* workspace, void* stream);
 size_t edgedict_ilm_workspace_bytes(int dtype, int R, int J);
 int edgedict_ilm_logits(int dtype, const void* dec, int R, int P2, int J, const void* W1d, long long ldw1,
                         const float* b1, const void* W2, const float* b2, int V, int emb_dtype, int E, int H,

@@ -175,4 +175,4 @@ def test_new_symbols_are_declared_and_exported(hip_lib):
     assert want <= set(_lib.declared_symbols())
     for name in want:
         assert hasattr(hip_lib, name), name
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2

@@ -215,14 +215,16 @@ def test_ctypes_mirrors_have_the_header_struct_sizes(hip_lib):
 
 
 def test_native_bias_errors_are_status_codes_and_sizes_grow(hip_lib):
-    """edgedict_beam_search_bias validates the list before it touches the device (the device pointers below are never
-    dereferenced); without a list the size queries equal the _lm ones."""
+    """edgedict_beam_search validates opts->bias before it touches the device (the device pointers below are never
+    dereferenced); without a list the size queries equal the plain ones."""
     from edgedict_amd.bias import BeamBias
+    from search_abi import make_net, make_opts
     fake = ctypes.c_void_p(256)
     arr = (ctypes.c_void_p * 1)(256)
     bias = BeamBias()
     bias.S, bias.V, bias.n_exc = 3, 41, 0
     bias.root_next = bias.held = bias.pend = bias.row_ptr = bias.exc_tok = bias.exc_next = 256
+    opts = ctypes.byref(make_opts(bias=bias))
     lens = np.array([3], dtype=np.int32)
     toks = np.zeros(64, dtype=np.int32)
     ntok = np.zeros(1, dtype=np.int32)
@@ -230,10 +232,10 @@ def test_native_bias_errors_are_status_codes_and_sizes_grow(hip_lib):
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
     def call(V, prefix):
-        return hip_lib.edgedict_beam_search_bias(
-            0, fake, ctypes.c_longlong(96), ctypes.c_longlong(32), 1, 3, vp(lens), 32, fake, ctypes.c_longlong(56), fake,
-            24, fake, fake, V, fake, 0, 16, 1, arr, arr, arr, arr, 32, fake, fake, 0, 2, 2, 16, prefix, vp(toks), 64,
-            vp(ntok), vp(score), None, None, ctypes.byref(bias), fake, None)
+        net = make_net(fake, V=V, L=1, w_ih=arr, w_hh=arr, b_ih=arr, b_hh=arr)
+        return hip_lib.edgedict_beam_search(
+            ctypes.byref(net), fake, ctypes.c_longlong(96), ctypes.c_longlong(32), 1, 3, vp(lens), 2, 16, prefix,
+            vp(toks), 64, vp(ntok), vp(score), None, opts, fake, None)
 
     assert call(40, 0) == -1
     assert b"vocabulary" in hip_lib.edgedict_last_error()
@@ -242,14 +244,13 @@ def test_native_bias_errors_are_status_codes_and_sizes_grow(hip_lib):
     bias.held = 0
     assert call(41, 0) == -1
     assert b"null bias" in hip_lib.edgedict_last_error()
-    dims = (1, 4, 10, 32, 40, 16, 2, 32, 24, 4, 32, 0)
-    plain = hip_lib.edgedict_beam_workspace_bytes(*dims)
-    assert hip_lib.edgedict_beam_workspace_bytes_bias(*dims, None, None) == plain
-    assert hip_lib.edgedict_beam_workspace_bytes_bias(*dims, None, ctypes.byref(bias)) > plain
-    sdims = (1, 4, 32, 40, 16, 2, 32, 24, 4, 32, 256)
-    st = hip_lib.edgedict_beam_stream_state_bytes(*sdims)
-    ws = hip_lib.edgedict_beam_stream_workspace_bytes(*sdims)
-    assert hip_lib.edgedict_beam_stream_state_bytes_bias(*sdims, None, None) == st
-    assert hip_lib.edgedict_beam_stream_state_bytes_bias(*sdims, None, ctypes.byref(bias)) > st
-    assert hip_lib.edgedict_beam_stream_workspace_bytes_bias(*sdims, None, None) == ws
-    assert hip_lib.edgedict_beam_stream_workspace_bytes_bias(*sdims, None, ctypes.byref(bias)) > ws
+    net, empty = ctypes.byref(make_net(dtype=1)), ctypes.byref(make_opts())
+    plain = hip_lib.edgedict_beam_workspace_bytes(net, 4, 10, 4, 32, 0, None)
+    assert hip_lib.edgedict_beam_workspace_bytes(net, 4, 10, 4, 32, 0, empty) == plain > 0
+    assert hip_lib.edgedict_beam_workspace_bytes(net, 4, 10, 4, 32, 0, opts) > plain
+    st = hip_lib.edgedict_beam_stream_state_bytes(None, 4, 2, 32, 4, 256)
+    ws = hip_lib.edgedict_beam_stream_workspace_bytes(net, 4, 4, 32, 256, None)
+    assert hip_lib.edgedict_beam_stream_state_bytes(empty, 4, 2, 32, 4, 256) == st > 0
+    assert hip_lib.edgedict_beam_stream_state_bytes(opts, 4, 2, 32, 4, 256) > st
+    assert hip_lib.edgedict_beam_stream_workspace_bytes(net, 4, 4, 32, 256, empty) == ws > 0
+    assert hip_lib.edgedict_beam_stream_workspace_bytes(net, 4, 4, 32, 256, opts) > ws

@@ -107,7 +107,7 @@ def test_new_symbol_is_declared_and_exported(hip_lib):
     from edgedict_amd import _lib
     assert "edgedict_ctc_align" in _lib.declared_symbols()
     assert hasattr(hip_lib, "edgedict_ctc_align")
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
 
 
 def test_argument_errors_are_raised_before_any_launch(hip_lib):

@@ -100,7 +100,7 @@ def test_new_symbols_are_declared_and_exported(hip_lib):
     assert want <= set(_lib.declared_symbols())
     for name in want:
         assert hasattr(hip_lib, name), name
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
     f = hip_lib.edgedict_ctc_beam_workspace_bytes
     assert f.restype is ctypes.c_size_t
     assert f(0, 5, 4, 8) == 0 and f(2, 0, 4, 8) == 0

@@ -119,7 +119,7 @@ def test_new_symbols_are_declared_and_exported(hip_lib):
     assert want <= set(_lib.declared_symbols())
     for name in want:
         assert hasattr(hip_lib, name), name
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
     assert hip_lib.edgedict_ctc_workspace_bytes(0, 5, 3) == 0
     n = hip_lib.edgedict_ctc_workspace_bytes(2, 5, 3)
     assert n >= 2 * 2 * 5 * 7 * 8 and n % 256 == 0

@@ -182,7 +182,7 @@ def test_new_symbols_are_declared_and_exported(hip_lib):
     for name in ("edgedict_ctc_score_workspace_bytes", "edgedict_ctc_score_nbest"):
         assert name in _lib.declared_symbols()
         assert hasattr(hip_lib, name)
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
 
 
 def test_workspace_holds_the_two_row_arrays_only(hip_lib):

@@ -118,4 +118,4 @@ def test_new_symbols_are_declared_and_exported(hip_lib):
             "edgedict_rnnt_loss_backward_packed_colsum_fe", "edgedict_rnnt_loss_backward_packed_range_fe",
             "edgedict_rnnt_align", "edgedict_rnnt_align_packed", "edgedict_rnnt_align_packed_parts"}
     assert want <= set(_lib.declared_symbols())
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2

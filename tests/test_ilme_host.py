@@ -140,45 +140,51 @@ def test_python_entry_points_check_ilm_weight_first():
 
 
 # ------------------------------------------------------------------------------------------- the native entry points
-NAMES = {"edgedict_sync_beam_workspace_bytes_ilme", "edgedict_sync_beam_search_ilme",
-         "edgedict_sync_stream_workspace_bytes_ilme", "edgedict_sync_stream_advance_ilme", "edgedict_ilm_workspace_bytes",
-         "edgedict_ilm_logits", "edgedict_ilm_logprobs"}
+NAMES = {"edgedict_sync_beam_workspace_bytes", "edgedict_sync_beam_search", "edgedict_sync_stream_workspace_bytes",
+         "edgedict_sync_stream_advance"}
+ILM_NAMES = {"edgedict_ilm_workspace_bytes", "edgedict_ilm_logits", "edgedict_ilm_logprobs"}
 
 
 def test_ilme_symbols_are_declared_exported_and_sized(hip_lib):
     from edgedict_amd import _lib
     from edgedict_amd.lm import BeamLM
-    assert NAMES <= set(_lib.declared_symbols())
-    for name in NAMES:
+    from search_abi import assert_search_surface, make_net, make_opts
+    assert_search_surface(hip_lib, NAMES)
+    assert ILM_NAMES <= set(_lib.declared_symbols())
+    for name in ILM_NAMES:
         assert hasattr(hip_lib, name), name
     assert hip_lib.edgedict_beam_lm_struct_bytes() == ctypes.sizeof(BeamLM)         # the mirrored struct kept its size
     buf, fake = _fake()
     keep, lm, bias = _structs(fake)
-    rl, rb = ctypes.byref(lm), ctypes.byref(bias)
-    w = ctypes.byref(ctypes.c_double(0.3))
-    f, g = hip_lib.edgedict_sync_beam_workspace_bytes_ilme, hip_lib.edgedict_sync_beam_workspace_bytes_fusion
+    w = ctypes.c_double(0.3)
+    opts = lambda lm=None, bias=None, w=None: ctypes.byref(make_opts(lm, bias, w))
+    f = hip_lib.edgedict_sync_beam_workspace_bytes
     assert f.restype is ctypes.c_size_t
-    dims = (0, 2, 9, 32, V, 16, 2, 32, 24, 4)          # dtype, B, T, J, V, E, L, H, P2, W
+    net = ctypes.byref(make_net(V=V))                  # fp32, J 32, E 16, L 2, H 32, P2 24
+    dims = (net, 2, 9, 4)                              # B, T, W
     rows, J = 2 * 4, 32
-    for fa in ((None, None), (rl, None), (None, rb), (rl, rb)):
-        assert f(*dims, *fa, None) == g(*dims, *fa)
+    assert f(*dims, opts()) == f(*dims, None) > 0
+    for fa in ((None, None), (lm, None), (None, bias), (lm, bias)):
         # ILME adds hidden vectors and fp32 logits for twice the rows, and a zero encoder row
-        extra = f(*dims, *fa, w) - g(*dims, *fa)
+        extra = f(*dims, opts(*fa, w)) - f(*dims, opts(*fa))
         assert 2 * rows * (J + V) * 4 + J * 4 <= extra <= 2 * rows * (J + V) * 4 + J * 4 + 3 * 255
-        assert f(*dims, *fa, w) % 256 == 0
+        assert f(*dims, opts(*fa, w)) % 256 == 0
     for bad in (-0.5, float("nan"), float("inf")):
-        assert f(*dims, None, None, ctypes.byref(ctypes.c_double(bad))) == 0
-    assert f(0, 2, 9, 32, V, 16, 2, 30, 24, 4, None, None, w) == 0             # H no multiple of 4
-    assert f(0, 2, 9, 32, V, 16, 2, 32, 24, 33, None, None, w) == 0            # W = 33
+        assert f(*dims, opts(w=ctypes.c_double(bad))) == 0
+    assert f(ctypes.byref(make_net(V=V, H=30)), 2, 9, 4, opts(w=w)) == 0       # H no multiple of 4
+    assert f(net, 2, 9, 33, opts(w=w)) == 0                                    # W = 33
     _, lm_bad, _ = _structs(fake, lm_V=V + 1)
-    assert f(*dims, ctypes.byref(lm_bad), None, w) == 0
-    fs, gs = hip_lib.edgedict_sync_stream_workspace_bytes_ilme, hip_lib.edgedict_sync_stream_workspace_bytes_fusion
+    assert f(*dims, opts(lm_bad, None, w)) == 0
+    fs = hip_lib.edgedict_sync_stream_workspace_bytes
     assert fs.restype is ctypes.c_size_t
-    wdims = (0, 3, 32, V, 16, 2, 32, 24, 4, 64)
-    assert fs(*wdims, rl, rb, None) == gs(*wdims, rl, rb) and fs(*wdims, None, None, None) == gs(*wdims, None, None)
-    assert fs(*wdims, rl, rb, w) > gs(*wdims, rl, rb) and fs(*wdims, None, None, w) > gs(*wdims, None, None)
-    assert fs(*wdims, None, None, ctypes.byref(ctypes.c_double(-1.0))) == 0
-    assert fs(0, 3, 32, V, 16, 2, 32, 24, 4, 2, None, None, w) == 0            # node_capacity < W
+    wdims = (net, 3, 4, 64)                            # S, W, NC
+    assert fs(*wdims, opts()) == fs(*wdims, None) > 0
+    assert fs(*wdims, opts(lm, bias, w)) > fs(*wdims, opts(lm, bias)) and fs(*wdims, opts(w=w)) > fs(*wdims, None)
+    assert fs(*wdims, opts(w=ctypes.c_double(-1.0))) == 0
+    assert fs(net, 3, 4, 2, opts(w=w)) == 0                                    # node_capacity < W
+    # ILME carries no per-row state: the state's size does not see the weight
+    g = hip_lib.edgedict_sync_stream_state_bytes
+    assert g(opts(w=w), 3, 2, 32, 4, 64) == g(None, 3, 2, 32, 4, 64) > 0
     q = hip_lib.edgedict_ilm_workspace_bytes
     assert q.restype is ctypes.c_size_t
     assert q(0, 10, 32) >= 2 * 10 * 32 * 4 + 32 * 4 and q(1, 10, 32) < q(0, 10, 32)
@@ -190,30 +196,31 @@ def test_native_ilme_argument_errors_come_before_any_launch(hip_lib):
     layers = (ctypes.c_void_p * 2)(fake.value, fake.value)
     lens = (ctypes.c_int32 * 2)(5, 3)
 
+    from search_abi import make_net, make_opts
+    net = ctypes.byref(make_net(fake, V=V, w_ih=layers, w_hh=layers, b_ih=layers, b_hh=layers))
+
     def offline(lm, bias, w, W=4):
-        return hip_lib.edgedict_sync_beam_search_ilme(
-            0, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, lens, 32, fake, ctypes.c_longlong(56), fake,
-            24, fake, fake, V, fake, 0, 16, 2, layers, layers, layers, layers, 32, fake, fake, 0, 2, W, fake, fake, fake, 5,
-            fake, fake, fake, lm, bias, w, fake, fake, None)
+        return hip_lib.edgedict_sync_beam_search(
+            net, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, lens, W, fake, fake, fake, 5, fake, fake,
+            fake, ctypes.byref(make_opts(lm, bias, w)), fake, fake, None)
 
     def advance(lm, bias, w, W=4):
         nf, live = (ctypes.c_int32 * 2)(5, 3), (ctypes.c_int32 * 2)(0, 0)
-        return hip_lib.edgedict_sync_stream_advance_ilme(
-            0, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, nf, 32, fake, ctypes.c_longlong(56), fake, 24,
-            fake, fake, V, fake, 0, 16, 2, layers, layers, layers, layers, 32, fake, fake, 0, 2, W, 64, live,
-            ctypes.pointer(ctypes.c_int32(0)), fake, 64, lm, bias, w, fake, fake, None)
+        return hip_lib.edgedict_sync_stream_advance(
+            net, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, nf, W, 64, live,
+            ctypes.pointer(ctypes.c_int32(0)), fake, 64, ctypes.byref(make_opts(lm, bias, w)), fake, fake, None)
 
     keep, lm, bias = _structs(fake)
-    good = ctypes.byref(ctypes.c_double(0.3))
+    good = ctypes.c_double(0.3)
     for call, what in ((offline, b"sync_beam_search"), (advance, b"sync_stream_advance")):
         for bad in (-0.25, float("nan"), float("inf"), float("-inf")):
-            for fa in ((None, None), (ctypes.byref(lm), ctypes.byref(bias))):
-                assert call(*fa, ctypes.byref(ctypes.c_double(bad))) == -1
+            for fa in ((None, None), (lm, bias)):
+                assert call(*fa, ctypes.c_double(bad)) == -1
                 msg = hip_lib.edgedict_last_error()
                 assert msg.startswith(what) and b"ilm_weight" in msg, msg
         # the fusion checks still come, with a good weight
         _, lm_bad, _ = _structs(fake, lm_V=V + 1)
-        assert call(ctypes.byref(lm_bad), None, good) == -1 and b"ntoken = 41" in hip_lib.edgedict_last_error()
+        assert call(lm_bad, None, good) == -1 and b"ntoken = 41" in hip_lib.edgedict_last_error()
         assert call(None, None, good, W=33) == -1 and b"W = 33" in hip_lib.edgedict_last_error()
     # the scorer
     assert hip_lib.edgedict_ilm_logits(0, None, 4, 24, 32, fake, ctypes.c_longlong(56), fake, fake, fake, V, 0, 16, 32,

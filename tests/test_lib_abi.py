@@ -11,7 +11,7 @@ def test_library_exports_every_declared_symbol(hip_lib):
 
 
 def test_abi_version_and_workspace_query(hip_lib):
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
     n = hip_lib.edgedict_rnnt_workspace_bytes(64, 201, 65)
     assert n >= 7 * 64 * 201 * 65 * 4
     assert hip_lib.edgedict_rnnt_workspace_bytes(0, 1, 1) == 0

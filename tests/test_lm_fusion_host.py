@@ -96,9 +96,10 @@ def test_python_argument_errors_come_before_any_launch():
 
 
 def test_native_lm_errors_are_status_codes(hip_lib):
-    """edgedict_beam_search_lm validates the LM before it touches the device: a vocabulary mismatch and prefix = 1 are
+    """edgedict_beam_search validates opts->lm before it touches the device: a vocabulary mismatch and prefix = 1 are
     ED_ERR_INVALID with a message (the device pointers below are never dereferenced)."""
     from edgedict_amd.lm import BeamLM
+    from search_abi import make_net, make_opts
     fake = ctypes.c_void_p(256)
     arr = (ctypes.c_void_p * 1)(256)
     lm = BeamLM()
@@ -106,34 +107,39 @@ def test_native_lm_errors_are_status_codes(hip_lib):
     lm.emb, lm.emb_dtype = 256, 0
     lm.w_ih = lm.w_hh = lm.b_ih = lm.b_hh = ctypes.cast(arr, ctypes.c_void_p).value
     lm.Wo, lm.bo, lm.bos, lm.weight, lm.length_bonus = 256, 256, 1, 0.5, 0.0
+    opts = ctypes.byref(make_opts(lm=lm))
     lens = np.array([3], dtype=np.int32)
     toks = np.zeros(64, dtype=np.int32)
     ntok = np.zeros(1, dtype=np.int32)
     score = np.zeros(1, dtype=np.float64)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
+    def net(V, dtype=0, L=1):
+        return ctypes.byref(make_net(fake, dtype=dtype, V=V, L=L, w_ih=arr, w_hh=arr, b_ih=arr, b_hh=arr))
+
     def call(V, prefix):
-        return hip_lib.edgedict_beam_search_lm(
-            0, fake, ctypes.c_longlong(96), ctypes.c_longlong(32), 1, 3, vp(lens), 32, fake, ctypes.c_longlong(56), fake,
-            24, fake, fake, V, fake, 0, 16, 1, arr, arr, arr, arr, 32, fake, fake, 0, 2, 2, 16, prefix, vp(toks), 64,
-            vp(ntok), vp(score), None, ctypes.byref(lm), fake, None)
+        return hip_lib.edgedict_beam_search(
+            net(V), fake, ctypes.c_longlong(96), ctypes.c_longlong(32), 1, 3, vp(lens), 2, 16, prefix, vp(toks), 64,
+            vp(ntok), vp(score), None, opts, fake, None)
 
     assert call(40, 0) == -1
     assert b"ntoken" in hip_lib.edgedict_last_error()
     assert call(41, 1) == -1
     assert b"prefix" in hip_lib.edgedict_last_error()
-    sb = hip_lib.edgedict_beam_stream_advance_lm
     nf = np.array([2], dtype=np.int32)
     commit = np.zeros(64, dtype=np.int32)
-    rc = sb(0, fake, ctypes.c_longlong(64), ctypes.c_longlong(32), 1, vp(nf), 32, fake, ctypes.c_longlong(56), fake, 24,
-            fake, fake, 40, fake, 0, 16, 1, arr, arr, arr, arr, 32, fake, fake, 0, 2, 2, 16, 64, vp(commit), vp(ntok),
-            None, ctypes.byref(lm), fake, fake, None)
+    rc = hip_lib.edgedict_beam_stream_advance(
+        net(40), fake, ctypes.c_longlong(64), ctypes.c_longlong(32), 1, vp(nf), 2, 16, 64, vp(commit), vp(ntok), None,
+        opts, fake, fake, None, None, None, None, None)
     assert rc == -1
     assert b"ntoken" in hip_lib.edgedict_last_error()
     # the size queries grow by the LM's state and buffers, and without an LM equal the plain ones
-    plain = hip_lib.edgedict_beam_workspace_bytes(1, 4, 10, 32, 40, 16, 2, 32, 24, 4, 32, 0)
-    assert hip_lib.edgedict_beam_workspace_bytes_lm(1, 4, 10, 32, 40, 16, 2, 32, 24, 4, 32, 0, None) == plain
-    assert hip_lib.edgedict_beam_workspace_bytes_lm(1, 4, 10, 32, 40, 16, 2, 32, 24, 4, 32, 0, ctypes.byref(lm)) > plain
-    st = hip_lib.edgedict_beam_stream_state_bytes(1, 4, 32, 40, 16, 2, 32, 24, 4, 32, 256)
-    assert hip_lib.edgedict_beam_stream_state_bytes_lm(1, 4, 32, 40, 16, 2, 32, 24, 4, 32, 256, None) == st
-    assert hip_lib.edgedict_beam_stream_state_bytes_lm(1, 4, 32, 40, 16, 2, 32, 24, 4, 32, 256, ctypes.byref(lm)) > st
+    empty = ctypes.byref(make_opts())
+    f = hip_lib.edgedict_beam_workspace_bytes
+    plain = f(net(40, 1, 2), 4, 10, 4, 32, 0, None)
+    assert f(net(40, 1, 2), 4, 10, 4, 32, 0, empty) == plain > 0
+    assert f(net(40, 1, 2), 4, 10, 4, 32, 0, opts) > plain
+    g = hip_lib.edgedict_beam_stream_state_bytes
+    st = g(None, 4, 2, 32, 4, 256)
+    assert g(empty, 4, 2, 32, 4, 256) == st > 0
+    assert g(opts, 4, 2, 32, 4, 256) > st

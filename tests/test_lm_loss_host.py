@@ -151,4 +151,4 @@ def test_native_argument_errors_are_status_codes(hip_lib):
     assert b"mean" in hip_lib.edgedict_last_error()
     assert bwd(1, fake, ll(8), fake, 0, 8, 0, fake, fake, 0, fake, 1, None) == 0      # no rows: nothing to launch
     assert hip_lib.edgedict_log_softmax_rows_bwd(fake, fake, ll(4), 0, fake, 2, 8, None) == -1
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2

@@ -260,7 +260,7 @@ def test_new_symbol_is_declared_and_exported(hip_lib):
     from edgedict_amd.trainer import TrainEngine
     assert "edgedict_mwer_risk" in _lib.declared_symbols()
     assert hasattr(hip_lib, "edgedict_mwer_risk")
-    assert hip_lib.edgedict_abi_version() == 1
+    assert hip_lib.edgedict_abi_version() == 2
     for name in ("mwer_risk", "MWERLoss", "mwer_rows", "MWERRows", "MWER_MAX_N"):
         assert hasattr(loss, name), name
     assert loss.MWER_MAX_N == 32

@@ -354,7 +354,7 @@ def test_prefix_with_detail_is_refused(hip_lib):
     with pytest.raises(ValueError, match="prefix"):
         decode.StreamingBeamSearch(m, 2, W=4, prefix=True, detail=True)
     # ... and by the native call itself, with a status code, before it looks at anything else
-    rc = hip_lib.edgedict_beam_search_nbest(*([0, None, ctypes.c_longlong(0), ctypes.c_longlong(0), 1, 1] + [None] * 24
+    rc = hip_lib.edgedict_beam_search_nbest(*([None, None, ctypes.c_longlong(0), ctypes.c_longlong(0), 1, 1, None, 0, 0]
                                               + [1] + [None] * 13))
     assert rc == -1 and b"prefix" in hip_lib.edgedict_last_error()
 

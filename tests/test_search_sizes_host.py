@@ -29,23 +29,25 @@ def _lm(V, shape):
 
 def _rows(lib):
     """[(key, bytes)] over both dtypes x both shapes x (prefix 0/1 where it applies) x (without / with an LM)."""
+    from search_abi import make_net, make_opts
     out = []
     for dt, (name, sh) in itertools.product((0, 1), SHAPES.items()):
         J, V, E, L, H, P2 = sh["net"]
         B, T, W, EM, NC = sh["B"], sh["T"], sh["W"], sh["EM"], sh["NC"]
         out.append(("greedy_workspace dtype=%d %s" % (dt, name),
                     lib.edgedict_greedy_workspace_bytes(dt, B, J, V, E, L, H, P2)))
-        for with_lm in (0, 1):
-            lm = (ctypes.byref(_lm(V, sh["lm"])),) if with_lm else ()
+        net = ctypes.byref(make_net(dtype=dt, J=J, V=V, E=E, L=L, H=H, P2=P2))
+        for with_lm in (0, 1):         # (the keys keep the names the record was made under: _lm = with an LM in opts)
+            lm = _lm(V, sh["lm"])
+            opts = ctypes.byref(make_opts(lm=lm)) if with_lm else None
             sfx = "_lm" if with_lm else ""
             for prefix in (0, 1):
-                fn = getattr(lib, "edgedict_beam_workspace_bytes" + sfx)
                 out.append(("beam_workspace%s dtype=%d %s prefix=%d" % (sfx, dt, name, prefix),
-                            fn(dt, B, T, J, V, E, L, H, P2, W, EM, prefix, *lm)))
-            for what in ("state", "workspace"):
-                fn = getattr(lib, "edgedict_beam_stream_%s_bytes%s" % (what, sfx))
-                out.append(("beam_stream_%s%s dtype=%d %s" % (what, sfx, dt, name),
-                            fn(dt, B, J, V, E, L, H, P2, W, EM, NC, *lm)))
+                            lib.edgedict_beam_workspace_bytes(net, B, T, W, EM, prefix, opts)))
+            out.append(("beam_stream_state%s dtype=%d %s" % (sfx, dt, name),
+                        lib.edgedict_beam_stream_state_bytes(opts, B, L, H, W, NC)))
+            out.append(("beam_stream_workspace%s dtype=%d %s" % (sfx, dt, name),
+                        lib.edgedict_beam_stream_workspace_bytes(net, B, W, EM, NC, opts)))
     return out
 
 
@@ -59,16 +61,23 @@ def test_size_queries_return_the_recorded_bytes(hip_lib):
 
 
 def test_lm_forms_without_an_lm_equal_the_plain_queries(hip_lib):
+    """opts with three null members is the null opts; ILME, which these searches do not have, sizes nothing."""
+    from search_abi import make_net, make_opts
+    empty, ilm = ctypes.byref(make_opts()), ctypes.c_double(0.5)
     for dt, sh in itertools.product((0, 1), SHAPES.values()):
         J, V, E, L, H, P2 = sh["net"]
         B, T, W, EM, NC = sh["B"], sh["T"], sh["W"], sh["EM"], sh["NC"]
+        net = ctypes.byref(make_net(dtype=dt, J=J, V=V, E=E, L=L, H=H, P2=P2))
         for prefix in (0, 1):
-            a = (dt, B, T, J, V, E, L, H, P2, W, EM, prefix)
-            assert hip_lib.edgedict_beam_workspace_bytes_lm(*a, None) == hip_lib.edgedict_beam_workspace_bytes(*a)
-        a = (dt, B, J, V, E, L, H, P2, W, EM, NC)
-        for what in ("state", "workspace"):
-            plain = getattr(hip_lib, "edgedict_beam_stream_%s_bytes" % what)
-            assert getattr(hip_lib, "edgedict_beam_stream_%s_bytes_lm" % what)(*a, None) == plain(*a)
+            a = (net, B, T, W, EM, prefix)
+            assert hip_lib.edgedict_beam_workspace_bytes(*a, empty) == hip_lib.edgedict_beam_workspace_bytes(*a, None) > 0
+        f, g = hip_lib.edgedict_beam_stream_state_bytes, hip_lib.edgedict_beam_stream_workspace_bytes
+        assert f(empty, B, L, H, W, NC) == f(None, B, L, H, W, NC) > 0
+        assert g(net, B, W, EM, NC, empty) == g(net, B, W, EM, NC, None) > 0
+        with_ilm = ctypes.byref(make_opts(ilm_weight=ilm))
+        assert hip_lib.edgedict_beam_workspace_bytes(net, B, T, W, EM, 0, with_ilm) == 0
+        assert f(with_ilm, B, L, H, W, NC) == 0 and g(net, B, W, EM, NC, with_ilm) == 0
+        assert hip_lib.edgedict_beam_workspace_bytes(None, B, T, W, EM, 0, None) == 0 and g(None, B, W, EM, NC, None) == 0
 
 
 if __name__ == "__main__":

@@ -85,19 +85,19 @@ def test_width_one_is_the_greedy_search_without_its_blanks():
 
 
 def test_new_symbols_are_declared_and_exported(hip_lib):
-    from edgedict_amd import _lib
-    want = {"edgedict_sync_beam_workspace_bytes", "edgedict_sync_beam_result_bytes", "edgedict_sync_beam_search"}
-    assert want <= set(_lib.declared_symbols())
-    for name in want:
-        assert hasattr(hip_lib, name), name
+    from search_abi import assert_search_surface, make_net, make_opts
+    assert_search_surface(hip_lib, {"edgedict_sync_beam_workspace_bytes", "edgedict_sync_beam_result_bytes",
+                                    "edgedict_sync_beam_search"})
     f = hip_lib.edgedict_sync_beam_workspace_bytes
     assert f.restype is ctypes.c_size_t
-    dims = (0, 2, 9, 32, 40, 16, 2, 32, 24)         # dtype, B, T, J, V, E, L, H, P2
-    assert f(*dims, 0) == 0 and f(*dims, 33) == 0 and f(0, 2, 0, 32, 40, 16, 2, 32, 24, 4) == 0
-    n = f(*dims, 4)
+    net = ctypes.byref(make_net())                  # fp32, J 32, V 40, E 16, L 2, H 32, P2 24
+    assert f(net, 2, 9, 0, None) == 0 and f(net, 2, 9, 33, None) == 0 and f(net, 2, 0, 4, None) == 0
+    assert f(None, 2, 9, 4, None) == 0
+    n = f(net, 2, 9, 4, None)
+    assert f(net, 2, 9, 4, ctypes.byref(make_opts())) == n
     # both state buffers of B W rows, and T W tree nodes of 16 bytes per utterance
     assert n >= 4 * (2 * 4) * 2 * 32 * 4 + 2 * (9 * 4) * 16 and n % 256 == 0
-    assert f(*dims, 10) > n
+    assert f(net, 2, 9, 10, None) > n
     g = hip_lib.edgedict_sync_beam_result_bytes
     assert g.restype is ctypes.c_size_t
     assert g(0, 4, 9) == 0 and g(2, 0, 9) == 0 and g(2, 4, 9) >= 2 * 4 * 9 * 16
@@ -110,18 +110,17 @@ def test_native_argument_errors_come_before_any_launch(hip_lib):
     fake = ctypes.cast(buf, ctypes.c_void_p)
     lens = (ctypes.c_int32 * 2)(5, 3)
     layers = (ctypes.c_void_p * 2)(fake.value, fake.value)
-    names = ("E1", "lens", "W1d", "b1", "W2", "b2", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "Wp", "bp", "tokens", "frames",
-             "tlp", "ntok", "nhyp", "logp", "ws", "result")
+    from search_abi import NET_POINTERS, make_net
+    names = ("net", "E1", "lens") + NET_POINTERS + ("tokens", "frames", "tlp", "ntok", "nhyp", "logp", "ws", "result")
 
     def run(dtype=0, T=5, W=4, blank=0, bos=2, **kw):
         a = {n: fake for n in names}
         a.update(lens=lens, w_ih=layers, w_hh=layers, b_ih=layers, b_hh=layers)
         a.update(kw)
+        net = make_net(dtype=dtype, blank=blank, bos=bos, **{n: a[n] for n in NET_POINTERS})
         return hip_lib.edgedict_sync_beam_search(
-            dtype, a["E1"], ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, T, a["lens"], 32, a["W1d"],
-            ctypes.c_longlong(56), a["b1"], 24, a["W2"], a["b2"], 40, a["emb"], 0, 16, 2, a["w_ih"], a["w_hh"],
-            a["b_ih"], a["b_hh"], 32, a["Wp"], a["bp"], blank, bos, W, a["tokens"], a["frames"], a["tlp"], 5, a["ntok"],
-            a["nhyp"], a["logp"], a["ws"], a["result"], None)
+            a["net"] and ctypes.byref(net), a["E1"], ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, T, a["lens"], W,
+            a["tokens"], a["frames"], a["tlp"], 5, a["ntok"], a["nhyp"], a["logp"], None, a["ws"], a["result"], None)
 
     for name in names:
         assert run(**{name: None}) == -1, name

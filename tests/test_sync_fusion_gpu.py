@@ -221,8 +221,9 @@ def test_fusion_argument_errors_launch_nothing(hip_lib):
     # null tables through the C ABI: a status and a message
     buf, fake = _fake()
     keep, lm, bias = _structs(fake, null_bias="held")
-    assert hip_lib.edgedict_sync_stream_reset_fusion(2, 2, 32, 4, 64, 2, None, 0, None, ctypes.byref(bias), fake,
-                                                     None) == -1
+    from search_abi import make_opts
+    assert hip_lib.edgedict_sync_stream_reset(ctypes.byref(make_opts(bias=bias)), 2, 2, 32, 4, 64, 2, None, 0, fake,
+                                              None) == -1
     assert b"null bias table pointer" in hip_lib.edgedict_last_error()
     # the search still runs after the refusals
     assert len(m.sync_beam_search_nbest(x, xlen, W=4, lm=lm40, lm_weight=0.5)) == xs.shape[0]

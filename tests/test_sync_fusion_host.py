@@ -99,9 +99,8 @@ def test_chunked_oracle_equals_the_offline_oracle(W, seed):
 
 
 # ------------------------------------------------------------------------------------------- the native entry points
-NAMES = {"edgedict_sync_beam_workspace_bytes_fusion", "edgedict_sync_beam_search_fusion",
-         "edgedict_sync_stream_state_bytes_fusion", "edgedict_sync_stream_workspace_bytes_fusion",
-         "edgedict_sync_stream_reset_fusion", "edgedict_sync_stream_advance_fusion"}
+NAMES = {"edgedict_sync_beam_workspace_bytes", "edgedict_sync_beam_search", "edgedict_sync_stream_state_bytes",
+         "edgedict_sync_stream_workspace_bytes", "edgedict_sync_stream_reset", "edgedict_sync_stream_advance"}
 
 
 def _fake():
@@ -132,61 +131,61 @@ def _structs(fake, lm_V=V, lm_H=32, bias_V=V, weight=0.5, null_lm=None, null_bia
 
 
 def test_fusion_symbols_are_declared_exported_and_sized(hip_lib):
-    from edgedict_amd import _lib
-    assert NAMES <= set(_lib.declared_symbols())
-    for name in NAMES:
-        assert hasattr(hip_lib, name), name
+    from search_abi import assert_search_surface, make_net, make_opts
+    assert_search_surface(hip_lib, NAMES)
     buf, fake = _fake()
     keep, lm, bias = _structs(fake)
-    rl, rb = ctypes.byref(lm), ctypes.byref(bias)
-    f = hip_lib.edgedict_sync_beam_workspace_bytes_fusion
+    none, empty = None, ctypes.byref(make_opts())
+    rl, rb, rlb = (ctypes.byref(make_opts(**kw)) for kw in (dict(lm=lm), dict(bias=bias), dict(lm=lm, bias=bias)))
+    net = ctypes.byref(make_net())                      # J 32, V 40, E 16, L 2, H 32, P2 24, fp32
+    f = hip_lib.edgedict_sync_beam_workspace_bytes
     assert f.restype is ctypes.c_size_t
-    dims = (0, 2, 9, 32, V, 16, 2, 32, 24, 4)          # dtype, B, T, J, V, E, L, H, P2, W
-    plain = hip_lib.edgedict_sync_beam_workspace_bytes(*dims)
-    assert f(*dims, None, None) == plain
+    dims = (net, 2, 9, 4)                               # B, T, W
+    plain = f(*dims, none)
+    assert f(*dims, empty) == plain > 0
     rows = 2 * 4
     # a list adds the rows' automaton states, an LM at least both (h, c) buffers and the LM's logits
-    assert plain < f(*dims, None, rb) <= plain + 256 * ((rows * 4 + 255) // 256)
-    assert f(*dims, rl, None) >= plain + 4 * rows * 2 * 32 * 4 + rows * V * 4
-    assert f(*dims, rl, rb) > f(*dims, rl, None) and f(*dims, rl, rb) % 256 == 0
+    assert plain < f(*dims, rb) <= plain + 256 * ((rows * 4 + 255) // 256)
+    assert f(*dims, rl) >= plain + 4 * rows * 2 * 32 * 4 + rows * V * 4
+    assert f(*dims, rlb) > f(*dims, rl) and f(*dims, rlb) % 256 == 0
     _, lm_bad, _ = _structs(fake, lm_V=V + 1)
-    assert f(*dims, ctypes.byref(lm_bad), None) == 0
-    g = hip_lib.edgedict_sync_stream_state_bytes_fusion
+    assert f(*dims, ctypes.byref(make_opts(lm=lm_bad))) == 0
+    g = hip_lib.edgedict_sync_stream_state_bytes
     assert g.restype is ctypes.c_size_t
-    sdims = (3, 2, 32, 4, 64)                           # S, L, H, W, NC
-    splain = hip_lib.edgedict_sync_stream_state_bytes(*sdims)
-    assert g(*sdims, None, None) == splain
-    assert g(*sdims, rl, None) >= splain + 4 * (3 * 4) * 2 * 32 * 4 and splain < g(*sdims, None, rb) < g(*sdims, rl, rb)
-    assert g(3, 2, 32, 33, 64, rl, rb) == 0
-    w = hip_lib.edgedict_sync_stream_workspace_bytes_fusion
+    sdims = (3, 2, 32, 4, 64)                           # S, L, H, W, NC (behind opts)
+    splain = g(none, *sdims)
+    assert g(empty, *sdims) == splain > 0
+    assert g(rl, *sdims) >= splain + 4 * (3 * 4) * 2 * 32 * 4 and splain < g(rb, *sdims) < g(rlb, *sdims)
+    assert g(rlb, 3, 2, 32, 33, 64) == 0
+    w = hip_lib.edgedict_sync_stream_workspace_bytes
     assert w.restype is ctypes.c_size_t
-    wdims = (0, 3, 32, V, 16, 2, 32, 24, 4, 64)
-    wplain = hip_lib.edgedict_sync_stream_workspace_bytes(*wdims)
-    assert w(*wdims, None, None) == wplain == w(*wdims, None, rb) and w(*wdims, rl, rb) > wplain
+    wdims = (net, 3, 4, 64)                             # S, W, NC
+    wplain = w(*wdims, none)
+    assert w(*wdims, empty) == wplain == w(*wdims, rb) > 0 and w(*wdims, rlb) > wplain
 
 
 def test_native_fusion_argument_errors_come_before_any_launch(hip_lib):
     """An LM or a list of another vocabulary, null tables, a weight that is not finite, W = 33: -1 with a message from
     the offline search, the streaming advance and the streaming reset, and no device needed to get it."""
+    from search_abi import make_net, make_opts
     buf, fake = _fake()
     layers = (ctypes.c_void_p * 2)(fake.value, fake.value)
     lens = (ctypes.c_int32 * 2)(5, 3)
+    net = ctypes.byref(make_net(fake, w_ih=layers, w_hh=layers, b_ih=layers, b_hh=layers))
 
     def offline(lm, bias, W=4):
-        return hip_lib.edgedict_sync_beam_search_fusion(
-            0, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, lens, 32, fake, ctypes.c_longlong(56), fake,
-            24, fake, fake, V, fake, 0, 16, 2, layers, layers, layers, layers, 32, fake, fake, 0, 2, W, fake, fake, fake, 5,
-            fake, fake, fake, lm, bias, fake, fake, None)
+        return hip_lib.edgedict_sync_beam_search(
+            net, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, lens, W, fake, fake, fake, 5, fake, fake,
+            fake, ctypes.byref(make_opts(lm, bias)), fake, fake, None)
 
     def advance(lm, bias, W=4):
         nf, live = (ctypes.c_int32 * 2)(5, 3), (ctypes.c_int32 * 2)(0, 0)
-        return hip_lib.edgedict_sync_stream_advance_fusion(
-            0, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, nf, 32, fake, ctypes.c_longlong(56), fake, 24,
-            fake, fake, V, fake, 0, 16, 2, layers, layers, layers, layers, 32, fake, fake, 0, 2, W, 64, live,
-            ctypes.pointer(ctypes.c_int32(0)), fake, 64, lm, bias, fake, fake, None)
+        return hip_lib.edgedict_sync_stream_advance(
+            net, fake, ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), 2, 5, nf, W, 64, live,
+            ctypes.pointer(ctypes.c_int32(0)), fake, 64, ctypes.byref(make_opts(lm, bias)), fake, fake, None)
 
     def reset(lm, bias, W=4):
-        return hip_lib.edgedict_sync_stream_reset_fusion(2, 2, 32, W, 64, 2, None, 0, lm, bias, fake, None)
+        return hip_lib.edgedict_sync_stream_reset(ctypes.byref(make_opts(lm, bias)), 2, 2, 32, W, 64, 2, None, 0, fake, None)
 
     cases = [(dict(lm_V=V + 1), "lm", b"ntoken = 41"), (dict(bias_V=V + 2), "bias", b"vocabulary = 42"),
              (dict(weight=float("nan")), "lm", b"not finite"), (dict(lm_H=30), "lm", b"multiple of 4"),
@@ -198,13 +197,12 @@ def test_native_fusion_argument_errors_come_before_any_launch(hip_lib):
             if call is reset and (b"ntoken" in word or b"vocabulary" in word):
                 continue            # (the reset does not know V: the advance checks the vocabularies)
             keep, lm, bias = _structs(fake, **kw)
-            for args in (((ctypes.byref(lm), None) if which == "lm" else (None, ctypes.byref(bias))),
-                         (ctypes.byref(lm), ctypes.byref(bias))):
+            for args in (((lm, None) if which == "lm" else (None, bias)), (lm, bias)):
                 assert call(*args) == -1, (what, kw)
                 msg = hip_lib.edgedict_last_error()
                 assert word in msg and msg.startswith(what), (what, kw, msg)
         keep, lm, bias = _structs(fake)
-        assert call(ctypes.byref(lm), ctypes.byref(bias), W=33) == -1
+        assert call(lm, bias, W=33) == -1
         assert b"W = 33" in hip_lib.edgedict_last_error()
 
 

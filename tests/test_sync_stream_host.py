@@ -106,28 +106,29 @@ NAMES = {"edgedict_sync_stream_state_bytes", "edgedict_sync_stream_workspace_byt
 
 
 def test_new_symbols_are_declared_and_exported(hip_lib):
-    from edgedict_amd import _lib
-    assert NAMES <= set(_lib.declared_symbols())
-    for name in NAMES:
-        assert hasattr(hip_lib, name), name
-    assert hip_lib.edgedict_abi_version() == 1
-    f = hip_lib.edgedict_sync_stream_state_bytes             # S, L, H, W, NC
+    from search_abi import assert_search_surface, make_net, make_opts
+    assert_search_surface(hip_lib, NAMES)
+    assert hip_lib.edgedict_abi_version() == 2
+    empty = ctypes.byref(make_opts())
+    f = hip_lib.edgedict_sync_stream_state_bytes             # opts, S, L, H, W, NC
     assert f.restype is ctypes.c_size_t
-    n = f(3, 2, 32, 4, 64)
+    n = f(None, 3, 2, 32, 4, 64)
+    assert f(empty, 3, 2, 32, 4, 64) == n
     # both state buffers of S W rows (h and c), and NC nodes of 16 bytes per stream
     assert n >= 4 * (3 * 4) * 2 * 32 * 4 + 3 * 64 * 16 and n % 256 == 0
-    assert f(3, 2, 32, 10, 64) > n and f(5, 2, 32, 4, 64) > n and f(3, 2, 32, 4, 640) > n
+    assert f(None, 3, 2, 32, 10, 64) > n and f(None, 5, 2, 32, 4, 64) > n and f(None, 3, 2, 32, 4, 640) > n
     for bad in ((0, 2, 32, 4, 64), (3, 2, 32, 0, 64), (3, 2, 32, 33, 64), (3, 2, 30, 4, 64), (3, 2, 32, 4, 3),
                 (3, 0, 32, 4, 64)):
-        assert f(*bad) == 0, bad
-    g = hip_lib.edgedict_sync_stream_workspace_bytes         # dtype, S, J, V, E, L, H, P2, W, NC
+        assert f(None, *bad) == 0, bad
+    g = hip_lib.edgedict_sync_stream_workspace_bytes         # net, S, W, NC, opts
     assert g.restype is ctypes.c_size_t
-    dims = (0, 3, 32, 40, 16, 2, 32, 24)
-    m = g(*dims, 4, 64)
-    assert m > 0 and m % 256 == 0
-    assert g(*dims, 10, 64) > m and g(*dims, 4, 640) > m and g(0, 5, 32, 40, 16, 2, 32, 24, 4, 64) > m
-    assert g(*dims, 0, 64) == 0 and g(*dims, 33, 64) == 0 and g(*dims, 4, 3) == 0 and g(7, *dims[1:], 4, 64) == 0
-    assert g(0, 0, 32, 40, 16, 2, 32, 24, 4, 64) == 0
+    net = ctypes.byref(make_net())                           # fp32, J 32, V 40, E 16, L 2, H 32, P2 24
+    m = g(net, 3, 4, 64, None)
+    assert m > 0 and m % 256 == 0 and g(net, 3, 4, 64, empty) == m
+    assert g(net, 3, 10, 64, None) > m and g(net, 3, 4, 640, None) > m and g(net, 5, 4, 64, None) > m
+    assert g(net, 3, 0, 64, None) == 0 and g(net, 3, 33, 64, None) == 0 and g(net, 3, 4, 3, None) == 0
+    assert g(ctypes.byref(make_net(dtype=7)), 3, 4, 64, None) == 0
+    assert g(net, 0, 4, 64, None) == 0 and g(None, 3, 4, 64, None) == 0
     r = hip_lib.edgedict_sync_stream_result_bytes
     assert r.restype is ctypes.c_size_t
     assert r(0, 4, 9) == 0 and r(2, 0, 9) == 0 and r(2, 33, 9) == 0 and r(2, 4, -1) == 0
@@ -142,8 +143,8 @@ def _fake():
 def test_native_advance_argument_errors_come_before_any_launch(hip_lib):
     buf, fake = _fake()
     layers = (ctypes.c_void_p * 2)(fake.value, fake.value)
-    names = ("E1", "nf", "W1d", "b1", "W2", "b2", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "Wp", "bp", "live", "parity",
-             "commit", "state", "ws")
+    from search_abi import NET_POINTERS, make_net
+    names = ("net", "E1", "nf") + NET_POINTERS + ("live", "parity", "commit", "state", "ws")
 
     def run(dtype=0, S=2, T=5, W=4, NC=64, H=32, blank=0, bos=2, emb_dtype=0, live_v=(0, 0), nf_v=(5, 3), parity_v=0,
             max_commit=64, **kw):
@@ -152,11 +153,10 @@ def test_native_advance_argument_errors_come_before_any_launch(hip_lib):
                  parity=ctypes.pointer(ctypes.c_int32(parity_v)),
                  w_ih=layers, w_hh=layers, b_ih=layers, b_hh=layers)
         a.update(kw)
+        net = make_net(dtype=dtype, H=H, blank=blank, bos=bos, emb_dtype=emb_dtype, **{n: a[n] for n in NET_POINTERS})
         return hip_lib.edgedict_sync_stream_advance(
-            dtype, a["E1"], ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), S, T, a["nf"], 32, a["W1d"],
-            ctypes.c_longlong(56), a["b1"], 24, a["W2"], a["b2"], 40, a["emb"], emb_dtype, 16, 2, a["w_ih"], a["w_hh"],
-            a["b_ih"], a["b_hh"], H, a["Wp"], a["bp"], blank, bos, W, NC, a["live"], a["parity"], a["commit"],
-            max_commit, a["state"], a["ws"], None)
+            a["net"] and ctypes.byref(net), a["E1"], ctypes.c_longlong(5 * 32), ctypes.c_longlong(32), S, T, a["nf"], W,
+            NC, a["live"], a["parity"], a["commit"], max_commit, None, a["state"], a["ws"], None)
 
     for name in names:
         assert run(**{name: None}) == -1, name
@@ -179,7 +179,7 @@ def test_native_reset_and_read_argument_errors_come_before_any_launch(hip_lib):
     buf, fake = _fake()
 
     def reset(S=2, L=2, H=32, W=4, NC=64, bos=2, state=fake):
-        return hip_lib.edgedict_sync_stream_reset(S, L, H, W, NC, bos, None, 0, state, None)
+        return hip_lib.edgedict_sync_stream_reset(None, S, L, H, W, NC, bos, None, 0, state, None)
 
     names = ("state", "result", "tokens", "ntok", "nhyp", "logp")        # (frames and token_logp are nullable)
 
