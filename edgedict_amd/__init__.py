@@ -11,3 +11,11 @@ _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 # imported - and torch's factory functions only wrapped - when the switch is on
 if _os.environ.get("EDGEDICT_POISON", "0") == "1":
     from . import _poison as _poison  # noqa: E402,F401
+
+
+def __getattr__(name):
+    # the host-side classes a user builds before any search (imported on first use: they pull in nothing native)
+    if name == "NGramLM":
+        from .ngram import NGramLM
+        return NGramLM
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

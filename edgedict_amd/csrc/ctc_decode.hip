@@ -16,6 +16,10 @@
 // After the last frame the beam is the N-best list.  BIAS: a node carries the phrase automaton's state after its token,
 // s = goto(s(parent), token), and Bn = Bn(parent) + D(s(parent), token), D(s, k) = held[goto(s, k)] - pend[s]; Bn enters
 // the ranking and the reported logp only, pb / pnb stay pure CTC.  Pruning to C_t happens BEFORE the bias is seen.
+// LM (a back-off n-gram, ngram_tables.hpp): a node carries the LM state after its token and the total
+// Ln = Ln(parent) + (weight * step(s_lm(parent), token) + length_bonus); the root has the LM's start state and 0.  A new
+// candidate ranks by (p + Bn) + Ln, a stay by (logadd(pb', pnb') + Bn) + Ln, the reported logp is (tot + Bn) + Ln; an
+// extension that merges into an existing entry adds no LM term, and the candidate cut stays ahead of both terms.
 //
 // Kernels (no atomics, results bit-identical from run to run):
 //   ctc_beam_rows    : one wave64 per row (b, t < T_b), as ctc_lse_gather: the row's log-sum-exp (16-byte loads when
@@ -34,6 +38,7 @@
 #include "bias_tables.hpp"
 #include "common.hpp"
 #include "ctc_rows.hpp"
+#include "ngram_tables.hpp"
 
 namespace {
 
@@ -210,14 +215,17 @@ __global__ __launch_bounds__(256) void ctc_beam_rows(const T* __restrict__ logit
 //   E  lane r builds entry r of the new beam; new nodes take consecutive ids in ranked order (ballot + prefix count) and
 //      are written with one 16-byte store; the gather for the next frame is requested.
 // The ring q* holds lse, lp[blank] and lane l's candidate l of the D frames ahead (static slots, as ctc_alpha_beta).
-template <typename T, bool BIAS>
+// LM: step C makes one n-gram lookup per live item (a binary search per back-off level: dependent reads of tables that
+// stay in the caches), step E one more per selected new node to keep its state; the LM = false instantiations are the
+// kernels without any of it.
+template <typename T, bool BIAS, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits, const int32_t* __restrict__ act_lens,
                                                     int Tm, int V, int W, int K, int cand,
                                                     const float* __restrict__ lse, const float* __restrict__ lpb,
                                                     const int32_t* __restrict__ ctok, const float* __restrict__ clp,
                                                     int4* __restrict__ nodes, int NC, int32_t* __restrict__ fnode,
                                                     int32_t* __restrict__ fdepth, int32_t* __restrict__ n_hyp,
-                                                    double* __restrict__ logp, CbBias bt) {
+                                                    double* __restrict__ logp, CbBias bt, NgramTables lt) {
     constexpr int D = 4, R = 8;
     __shared__ double s_sc[CB_MAXW * (CB_MAXC + 1)];
     __shared__ double s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW], s_tot[2][CB_MAXW], s_bn[2][CB_MAXW];
@@ -225,6 +233,8 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
     __shared__ int s_node[2][CB_MAXW], s_tok[2][CB_MAXW], s_par[2][CB_MAXW], s_dep[2][CB_MAXW], s_st[2][CB_MAXW];
     __shared__ int s_ctok[CB_MAXC];
     __shared__ float s_clp[CB_MAXC];
+    __shared__ double s_ln[2][LM ? CB_MAXW : 1];
+    __shared__ int s_lm[2][LM ? CB_MAXW : 1];
 
     const int b = blockIdx.x, lane = threadIdx.x;
     const int Tb = max(0, min(act_lens[b], Tm));
@@ -239,6 +249,7 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
         s_pb[0][0] = 0.0; s_pnb[0][0] = NEG; s_tot[0][0] = 0.0; s_bn[0][0] = 0.0;
         s_node[0][0] = 0; s_tok[0][0] = -1; s_par[0][0] = -1; s_dep[0][0] = 0; s_st[0][0] = 0;
         nd[0] = make_int4(-1, -1, -1, 0);
+        if (LM) { s_ln[0][0] = 0.0; s_lm[0][0] = lt.lm_start; }
     }
     float ge = 0.f;                                   // lp[e_lane] of the coming frame
     float qlse[D], qlpb[D], qlp[D];
@@ -283,10 +294,16 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
                     if (c >= K) continue;
                     double p = (tk == s_tok[cur][i] ? s_pb[cur][i] : s_tot[cur][i]) + lpc;
                     if (tk < 0) p = NEG;
-                    if (BIAS && p > NEG) {
+                    const bool real = p > NEG;
+                    if (BIAS && real) {
                         const int s = bias_state(bt, s_st[cur][i]);
                         const int n = bias_goto(bt, s, tk);
                         p += s_bn[cur][i] + (bt.bias_held[n] - bt.bias_pend[s]);
+                    }
+                    if (LM && real) {
+                        int nx;
+                        const double l = ngram_step(lt, s_lm[cur][i], tk, &nx);
+                        p += s_ln[cur][i] + ngram_term(lt.lm_weight, l, lt.lm_bonus);
                     }
                     s_sc[nb + i * K + c] = p;
                 }
@@ -319,6 +336,7 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
                 s_pnbn[lane] = pnbn;
                 double rk = log_add64(pbn, pnbn);
                 if (BIAS) rk += s_bn[cur][lane];
+                if (LM) rk += s_ln[cur][lane];
                 s_sc[lane] = rk;
             }
             __syncthreads();
@@ -374,9 +392,10 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
             const bool have = lane < nsel, fresh = have && mysel >= nb;
             const unsigned long long mask = __ballot(fresh);
             if (have) {
-                int node, tok, par, dep, st = 0;
-                double pb, pnb, bn = 0.0;
+                int node, tok, par, dep, st = 0, slm = 0;
+                double pb, pnb, bn = 0.0, ln = 0.0;
                 if (!fresh) {
+                    if (LM) { slm = s_lm[cur][mysel]; ln = s_ln[cur][mysel]; }
                     node = s_node[cur][mysel]; tok = s_tok[cur][mysel]; par = s_par[cur][mysel];
                     dep = s_dep[cur][mysel]; st = s_st[cur][mysel]; bn = s_bn[cur][mysel];
                     pb = s_pbn[mysel]; pnb = s_pnbn[mysel];
@@ -393,10 +412,15 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
                         st = bias_goto(bt, s, tok);
                         bn = s_bn[cur][i] + (bt.bias_held[st] - bt.bias_pend[s]);
                     }
+                    if (LM) {
+                        const double l = ngram_step(lt, s_lm[cur][i], tok, &slm);
+                        ln = s_ln[cur][i] + ngram_term(lt.lm_weight, l, lt.lm_bonus);
+                    }
                     if (node < NC) nd[node] = make_int4(par, tok, r, __float_as_int(s_clp[c]));
                 }
                 s_node[nxt][lane] = node; s_tok[nxt][lane] = tok; s_par[nxt][lane] = par; s_dep[nxt][lane] = dep;
                 s_st[nxt][lane] = st; s_bn[nxt][lane] = bn;
+                if (LM) { s_lm[nxt][lane] = slm; s_ln[nxt][lane] = ln; }
                 s_pb[nxt][lane] = pb; s_pnb[nxt][lane] = pnb; s_tot[nxt][lane] = log_add64(pb, pnb);
                 if (r + 1 < Tb && tok >= 0 && tok < V)
                     ge = ElemIO<T>::load(logits + (row0 + r + 1) * (long long)V + tok) - lse_next;
@@ -411,7 +435,9 @@ __global__ __launch_bounds__(64) void ctc_beam_walk(const T* __restrict__ logits
         const bool live = lane < nb;
         fnode[b * W + lane] = live ? s_node[cur][lane] : -1;
         fdepth[b * W + lane] = live ? s_dep[cur][lane] : 0;
-        logp[b * W + lane] = live ? s_tot[cur][lane] + (BIAS ? s_bn[cur][lane] : 0.0) : NEG;
+        double lp = live ? s_tot[cur][lane] + (BIAS ? s_bn[cur][lane] : 0.0) : NEG;
+        if (LM && live) lp += s_ln[cur][lane];
+        logp[b * W + lane] = lp;
     }
     if (lane == 0) n_hyp[b] = nb;
 }
@@ -454,10 +480,13 @@ extern "C" size_t edgedict_ctc_beam_workspace_bytes(int B, int T, int W, int can
     return cb_ws(B, T, W, cand).total;
 }
 
-extern "C" int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V,
-                                        int blank, int W, int cand, const edgedict_beam_bias_t* bias, int32_t* tokens,
-                                        int32_t* frames, float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp,
-                                        void* workspace, void* stream_) {
+extern "C" int edgedict_ctc_beam_search_fused(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V,
+                                              int blank, int W, int cand, const edgedict_ctc_beam_opts_t* opts,
+                                              int32_t* tokens, int32_t* frames, float* token_lp, int32_t* ntok,
+                                              int32_t* n_hyp, double* logp, void* workspace, void* stream_) {
+    ED_CHECK_ARG(!opts || (uintptr_t)opts >= 4096, "ctc_beam_search: opts is not a pointer");
+    const edgedict_beam_bias_t* bias = opts ? opts->bias : nullptr;
+    const edgedict_ngram_lm_t* lm = opts ? opts->ngram : nullptr;
     ED_CHECK_ARG(B > 0 && T > 0, "ctc_beam_search: B, T must be positive (got %d, %d)", B, T);
     ED_CHECK_ARG(V >= 2, "ctc_beam_search: V = %d, need at least the blank and one symbol", V);
     ED_CHECK_ARG(blank >= 0 && blank < V, "ctc_beam_search: blank %d outside [0,%d)", blank, V);
@@ -478,6 +507,17 @@ extern "C" int edgedict_ctc_beam_search(const void* logits, int dtype, const int
         ED_CHECK_ARG(bias->root_next && bias->held && bias->pend && bias->row_ptr && bias->exc_tok && bias->exc_next,
                      "ctc_beam_search: null bias table pointer");
         bt = CbBias{bias->root_next, bias->held, bias->pend, bias->row_ptr, bias->exc_tok, bias->exc_next, bias->S};
+    }
+    NgramTables lt{};
+    if (lm) {
+        if (int rc = ed_ngram_check(lm, "ctc_beam_search")) return rc;
+        ED_CHECK_ARG(lm->V == V, "ctc_beam_search: the n-gram's vocabulary = %d differs from the head's V = %d", lm->V, V);
+        ED_CHECK_ARG(lm->blank == blank, "ctc_beam_search: the n-gram's blank = %d differs from the search's %d",
+                     lm->blank, blank);
+        ED_CHECK_ARG(isfinite(lm->weight) && lm->weight >= 0.0 && isfinite(lm->length_bonus),
+                     "ctc_beam_search: lm weight %g must be finite and >= 0, length_bonus %g finite", lm->weight,
+                     lm->length_bonus);
+        lt = ed_ngram_tables(lm);
     }
     hipStream_t stream = (hipStream_t)stream_;
     const CbWs w = cb_ws(B, T, W, cand);
@@ -502,18 +542,29 @@ extern "C" int edgedict_ctc_beam_search(const void* logits, int dtype, const int
         hipLaunchKernelGGL(ctc_beam_rows<bf16_t>, grid1, dim3(256), 0, stream, (const bf16_t*)logits, act_lens, T, V,
                            blank, K, cand, lse, lpb, ctok, clp, vec_ok);
     ED_CHECK_LAUNCH("ctc_beam_rows");
-#define ED_CB_WALK(TT, BB)                                                                                            \
-    hipLaunchKernelGGL((ctc_beam_walk<TT, BB>), dim3(B), dim3(64), 0, stream, (const TT*)logits, act_lens, T, V, W, K, \
-                       cand, lse, lpb, ctok, clp, nodes, NC, fnode, fdepth, n_hyp, logp, bt)
-    if (dtype == ED_F32) {
-        if (bias) ED_CB_WALK(float, true); else ED_CB_WALK(float, false);
-    } else {
-        if (bias) ED_CB_WALK(bf16_t, true); else ED_CB_WALK(bf16_t, false);
-    }
+#define ED_CB_WALK(TT, BB, LL)                                                                                  \
+    hipLaunchKernelGGL((ctc_beam_walk<TT, BB, LL>), dim3(B), dim3(64), 0, stream, (const TT*)logits, act_lens, T, V, \
+                       W, K, cand, lse, lpb, ctok, clp, nodes, NC, fnode, fdepth, n_hyp, logp, bt, lt)
+#define ED_CB_WALK_T(TT)                                                                  \
+    do {                                                                                  \
+        if (lm) { if (bias) ED_CB_WALK(TT, true, true); else ED_CB_WALK(TT, false, true); } \
+        else { if (bias) ED_CB_WALK(TT, true, false); else ED_CB_WALK(TT, false, false); }  \
+    } while (0)
+    if (dtype == ED_F32) ED_CB_WALK_T(float); else ED_CB_WALK_T(bf16_t);
+#undef ED_CB_WALK_T
 #undef ED_CB_WALK
     ED_CHECK_LAUNCH("ctc_beam_walk");
     hipLaunchKernelGGL(ctc_beam_readout, dim3(B * W), dim3(64), 0, stream, (const int4*)nodes, NC, fnode, fdepth, T,
                        tokens, frames, token_lp, ntok, W);
     ED_CHECK_LAUNCH("ctc_beam_readout");
     return ED_OK;
+}
+
+extern "C" int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V,
+                                        int blank, int W, int cand, const edgedict_beam_bias_t* bias, int32_t* tokens,
+                                        int32_t* frames, float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp,
+                                        void* workspace, void* stream) {
+    const edgedict_ctc_beam_opts_t opts{bias, nullptr};
+    return edgedict_ctc_beam_search_fused(logits, dtype, act_lens, B, T, V, blank, W, cand, &opts, tokens, frames,
+                                          token_lp, ntok, n_hyp, logp, workspace, stream);
 }

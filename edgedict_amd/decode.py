@@ -40,7 +40,9 @@ plain kernels).  See ``edgedict_amd.bias``.
 
 ``ctc_beam_search`` is the first pass from the encoder alone: a CTC prefix beam search on the CTC head's logits
 (``Transducer(ctc_weight > 0)``; csrc/ctc_decode.hip), all frames inside one launch, returning ranked ``NBestResult``
-lists; it takes ``bias=`` too.
+lists; it takes ``bias=`` too, and ``lm=`` - there an ``edgedict_amd.ngram.NGramLM``, a back-off n-gram in device
+tables read inside the walk (``lm_weight``, ``length_bonus``), not an ``LMModel``.  ``lm_rescore`` re-ranks any
+search's ``NBestResult`` lists with such an n-gram (``NBestResult.lm_logp``; csrc/ngram.hip).
 
 ``sync_beam_search`` (``_nbest``, ``_enc``, ``_rows``) is a SECOND RNN-T beam search, frame-synchronous (at most one
 symbol per frame and hypothesis, all B x W hypotheses in one step per frame, equal sequences merged by log-add;
@@ -440,9 +442,11 @@ class NBestResult:
                        after ``ctc_rescore`` the combined score ``logp + weight * ctc_logp``
     ``ctc_logp``       None, or float64 [n]: the CTC head's log-likelihood of each hypothesis' tokens (``ctc_rescore``
                        fills it; -inf: the head has no path for them)
+    ``lm_logp``        None, or float64 [n]: an n-gram LM's log-probability of each hypothesis' tokens (``lm_rescore``
+                       fills it)
     """
 
-    def __init__(self, tokens, frames, token_logp, logp, ctc_logp=None):
+    def __init__(self, tokens, frames, token_logp, logp, ctc_logp=None, lm_logp=None):
         self.tokens = list(tokens)
         self.frames = list(frames)
         self.token_logp = list(token_logp)
@@ -452,6 +456,9 @@ class NBestResult:
             raise ValueError("NBestResult: fields of different lengths")
         if self.ctc_logp is not None and self.ctc_logp.shape != self.logp.shape:
             raise ValueError("NBestResult: ctc_logp must have one value per hypothesis")
+        self.lm_logp = None if lm_logp is None else np.asarray(lm_logp, dtype=np.float64)
+        if self.lm_logp is not None and self.lm_logp.shape != self.logp.shape:
+            raise ValueError("NBestResult: lm_logp must have one value per hypothesis")
 
     def __len__(self):
         return len(self.tokens)
@@ -462,7 +469,7 @@ class NBestResult:
         sequence can be in B twice, reached with different emission frames); the folded entry keeps the frames and
         increments of its most probable member (the first one on ties) and stands at that member's place in B.
         ``ctc_logp`` is carried along; a folded entry keeps its kept member's value (equal token sequences have equal
-        CTC scores, so the log-add of combined scores is the combined score of the log-add)."""
+        CTC scores, so the log-add of combined scores is the combined score of the log-add); ``lm_logp`` likewise."""
         idx = list(range(len(self)))
         logp = self.logp.copy()
         if merge:
@@ -480,7 +487,8 @@ class NBestResult:
         order = sorted(idx, key=lambda i: -logp[i])          # sorted() is stable
         return NBestResult([self.tokens[i] for i in order], [self.frames[i] for i in order],
                            [self.token_logp[i] for i in order], logp[order] if order else np.zeros(0),
-                           None if self.ctc_logp is None else (self.ctc_logp[order] if order else np.zeros(0)))
+                           None if self.ctc_logp is None else (self.ctc_logp[order] if order else np.zeros(0)),
+                           None if self.lm_logp is None else (self.lm_logp[order] if order else np.zeros(0)))
 
 
 def _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp, prefix=None):
@@ -592,6 +600,35 @@ def ctc_rescore(model, enc_out, lens, results, weight):
         combined, order = combine_ctc(r.logp, ctc, w)
         out.append(NBestResult([r.tokens[i] for i in order], [r.frames[i] for i in order],
                                [r.token_logp[i] for i in order], combined[order], ctc[order]))
+    return out
+
+
+def lm_rescore(results, lm, weight, length_bonus=0.0, eos=False):
+    """Rescore N-best lists with an n-gram LM (``ngram.NGramLM``): all hypotheses of ``results`` (one ``NBestResult``
+    per utterance, from any search) are scored by ``lm.score_lists`` - one upload, one ``ngram_score`` launch, one read.
+    Returns new ``NBestResult`` objects: ``lm_logp`` is the LM's log-probability of each hypothesis' tokens (from
+    ``<s>``, with the end-of-sentence step for ``eos=True``), ``logp`` the combined score
+    ``logp + (weight * lm_logp + length_bonus * ntok)`` (float64 on the host, exactly that expression), the entries
+    sorted by it descending, stably; ``ctc_logp`` is carried along.  For ``weight == 0`` the LM term is left out (no
+    ``0 * -inf``) and ``lm_logp`` is still filled.  ``weight`` must be finite and ``>= 0``,
+    ``length_bonus`` finite (``ValueError``)."""
+    from .ngram import NGramLM
+    if not isinstance(lm, NGramLM):
+        raise TypeError("lm_rescore: lm must be an edgedict_amd.ngram.NGramLM (got %s)" % type(lm).__name__)
+    w, lb = float(weight), float(length_bonus)
+    if not (np.isfinite(w) and w >= 0.0) or not np.isfinite(lb):
+        raise ValueError("lm_rescore: weight must be finite and >= 0, length_bonus finite (got %r, %r)"
+                         % (weight, length_bonus))
+    results = list(results)
+    scores = lm.score_lists([r.tokens for r in results], bos=True, eos=eos) if results else []
+    out = []
+    for r, lp in zip(results, scores):
+        ntok = np.array([len(t) for t in r.tokens], dtype=np.float64)
+        combined = r.logp + (w * lp + lb * ntok) if w > 0 else r.logp + lb * ntok      # (no 0 * -inf)
+        order = np.argsort(-combined, kind="stable")
+        out.append(NBestResult([r.tokens[i] for i in order], [r.frames[i] for i in order],
+                               [r.token_logp[i] for i in order], combined[order],
+                               None if r.ctc_logp is None else r.ctc_logp[order], lp[order]))
     return out
 
 
@@ -970,7 +1007,7 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     return _nbest_results(tokens, frames, tlogp, ntok, nhyp, logp)
 
 
-def ctc_beam_search(model, xs, xlen, W=10, cand=None, bias=None):
+def ctc_beam_search(model, xs, xlen, W=10, cand=None, bias=None, *, lm=None, lm_weight=None, length_bonus=0.0):
     """First-pass N-best from the encoder alone: encoder, CTC head, ``loss.ctc_prefix_beam`` (the CTC prefix beam search
     of csrc/ctc_decode.hip), then ONE read to the host - neither the prediction network nor the joint runs.  Returns a
     list of ``NBestResult``, one per utterance, already ranked: ``logp`` is descending and entry 0 is the answer.
@@ -981,8 +1018,12 @@ def ctc_beam_search(model, xs, xlen, W=10, cand=None, bias=None):
     paths of a prefix, so ``logp[i]`` is not the sum of per-token terms.  With ``bias`` (an
     ``edgedict_amd.bias.ContextGraph``) ``logp`` includes the prefix' bias total ``bias.score(tokens)``; a frame's
     candidate list (``cand``, default ``min(V - 1, 32)``) is cut before the bias is seen, so a boosted token outside it
-    is not rescued.  Raises ``RuntimeError`` on a model built without ``ctc_weight > 0``, as ``ctc_greedy_decode``."""
+    is not rescued.  ``lm`` / ``lm_weight`` / ``length_bonus``: an ``edgedict_amd.ngram.NGramLM`` fused into the search
+    (``loss.ctc_prefix_beam``); ``logp`` then includes the prefix' LM total as well.  Raises ``RuntimeError`` on a model
+    built without ``ctc_weight > 0``, as ``ctc_greedy_decode``."""
     from .loss import ctc_prefix_beam
+    from .ngram import check_ngram_args
+    check_ngram_args(lm, lm_weight, length_bonus)
     if getattr(model, "ctc_head", None) is None:
         raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
     _lib.require_cuda(xs)
@@ -990,7 +1031,8 @@ def ctc_beam_search(model, xs, xlen, W=10, cand=None, bias=None):
         xs = xs[:, :xlen.max()].contiguous()
         h_enc, _ = model.encoder(xs)
         act = model.scale_length(h_enc, xlen).to(device=h_enc.device, dtype=torch.int32).contiguous()
-        out = ctc_prefix_beam(model._ctc_logits(h_enc).contiguous(), act, W, model.blank, cand, bias)
+        out = ctc_prefix_beam(model._ctc_logits(h_enc).contiguous(), act, W, model.blank, cand, bias, lm=lm,
+                              lm_weight=lm_weight, length_bonus=length_bonus)
         B, Wn, T = out[0].shape
         # one read: the int32 fields and token_lp as raw bits in one buffer, logp beside them
         packed = torch.cat([out[0].reshape(B, -1), out[1].reshape(B, -1), out[2].view(torch.int32).reshape(B, -1),

@@ -552,7 +552,8 @@ CTC_BEAM_MAX_CAND = 64
 
 
 @torch.no_grad()
-def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
+def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None, *, lm=None, lm_weight=None,
+                    length_bonus=0.0):
     """CTC prefix beam search of head logits ``[B, T, V]`` (float32 / bfloat16, contiguous, device), the counterpart of
     ``ctc_greedy`` with a beam (csrc/ctc_decode.hip states the search): per frame ``t < act_lens[b]`` every prefix of
     the beam stays or is extended with one of the ``min(cand, V - 1)`` most probable non-blank tokens of the frame, a
@@ -563,6 +564,13 @@ def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
     automaton's state and its total bias ``graph.score(tokens)``, which enters the ranking and ``logp`` only.  The
     candidate list is cut BEFORE the bias is seen: a boosted token outside a frame's top ``cand`` is not rescued.
     ``bias=None`` and an empty graph run the plain kernel.
+
+    ``lm``: an ``edgedict_amd.ngram.NGramLM`` (a back-off n-gram in device tables; an LSTM ``LMModel`` raises
+    ``TypeError``: its step cannot run inside the walk), with ``lm_weight`` (required, finite, ``>= 0``) and
+    ``length_bonus`` (per token).  Every prefix then carries one LM state and the total
+    ``Ln = sum (lm_weight * lm.step(...) + length_bonus)`` over its tokens, which enters the ranking and ``logp``
+    beside the bias total: ``logp = (logadd(pb, pnb) + bias total) + Ln``.  No end-of-sentence term.  The candidate
+    list is cut before the LM is seen as well.  ``lm=None`` calls exactly what is called without the keyword.
 
     Returns device tensors ``(tokens, frames, token_lp, ntok, n_hyp, logp)``: ``tokens`` / ``frames`` int32
     ``[B, W, T]`` (hypothesis h's tokens and the frame each token's node was created on; -1 behind ``ntok[b, h]``),
@@ -596,6 +604,8 @@ def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
     if not 1 <= cand <= CTC_BEAM_MAX_CAND:
         raise ValueError("cand = %d outside [1, %d]" % (cand, CTC_BEAM_MAX_CAND))
     check_bias_args(bias, V, False)
+    from .ngram import CtcBeamOpts, check_ngram_args
+    check_ngram_args(lm, lm_weight, length_bonus, V, blank)
     _lib.require_cuda(logits, act_lens)
     dev = logits.device
     graph = active(bias)
@@ -608,8 +618,16 @@ def ctc_prefix_beam(logits, act_lens, W=10, blank=0, cand=None, bias=None):
     n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
     logp = torch.empty(B, W, dtype=torch.float64, device=dev)
     ws = torch.empty(lib.edgedict_ctc_beam_workspace_bytes(B, T, W, cand), dtype=torch.uint8, device=dev)
-    _lib.call("ctc_beam_search", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, W, cand, bref,
-              tokens, frames, token_lp, ntok, n_hyp, logp, ws)
+    if lm is None:
+        _lib.call("ctc_beam_search", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, W, cand,
+                  bref, tokens, frames, token_lp, ntok, n_hyp, logp, ws)
+        return tokens, frames, token_lp, ntok, n_hyp, logp
+    lms = lm.struct(dev, lm_weight, length_bonus)
+    opts = CtcBeamOpts()
+    opts.bias = ctypes.addressof(graph.tables(dev)["struct"]) if graph is not None else None
+    opts.ngram = ctypes.addressof(lms)
+    _lib.call("ctc_beam_search_fused", logits.detach(), _lib.dtype_code(logits.dtype), act_lens, B, T, V, blank, W, cand,
+              ctypes.byref(opts), tokens, frames, token_lp, ntok, n_hyp, logp, ws)
     return tokens, frames, token_lp, ntok, n_hyp, logp
 
 

@@ -1208,13 +1208,14 @@ class Transducer(nn.Module):
         lab = torch.where(scores == float("-inf"), torch.zeros_like(lab), lab)
         return alignment_windows(frames, act, lab, left, right)
 
-    def ctc_beam_search(self, xs, xlen, W=10, cand=None, bias=None):
+    def ctc_beam_search(self, xs, xlen, W=10, cand=None, bias=None, *, lm=None, lm_weight=None, length_bonus=0.0):
         """First-pass N-best from the encoder alone: encoder, CTC head, the CTC prefix beam search
         (``loss.ctc_prefix_beam``), one read to the host.  Returns a list of ``decode.NBestResult``, one per utterance,
         ranked (``logp`` descending, entry 0 the answer); ``bias`` (an ``edgedict_amd.bias.ContextGraph``) boosts a
-        phrase list.  See ``decode.ctc_beam_search``.  Raises RuntimeError on a model built without ``ctc_weight > 0``."""
+        phrase list, ``lm`` (an ``edgedict_amd.ngram.NGramLM``, with ``lm_weight`` and ``length_bonus``) fuses a
+        back-off n-gram into the search.  See ``decode.ctc_beam_search``.  Raises RuntimeError on a model built without ``ctc_weight > 0``."""
         from .decode import ctc_beam_search
-        return ctc_beam_search(self, xs, xlen, W, cand, bias)
+        return ctc_beam_search(self, xs, xlen, W, cand, bias, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)
 
     def _ctc_encode(self, xs, xlen):
         """The encoder as the N-best searches run it: (enc_out contiguous, host int32 frame counts or None)."""

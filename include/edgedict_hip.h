@@ -1263,6 +1263,66 @@ int edgedict_ctc_beam_search(const void* logits, int dtype, const int32_t* act_l
                              void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Back-off n-gram language model in device tables (csrc/ngram_tables.hpp, csrc/ngram.hip; edgedict_amd/ngram.py
+ * writes the tables).  Symbols are the ids 0 .. V-1 plus eos = V (tables only); <s> is the BOS id inside contexts; the
+ * blank is no symbol.  A state is a context of 0 .. order-1 tokens, state 0 the empty one, `start` the state of (BOS).
+ *   uni_lp, uni_next  [V + 1]  fp64 natural-log unigrams (blank: 0, never read) and the state after them
+ *   row_ptr           [S + 1]  per state a row of arcs sorted by token; state 0's row is empty
+ *   fail, backoff     [S]      the state of the context without its oldest token; the back-off weight (fp64)
+ *   arc_tok, arc_lp, arc_next [n_arcs]
+ * step(s, k), in exactly this order of fp64 additions:
+ *   acc = 0;  repeat: s == 0: return acc + uni_lp[k], uni_next[k];  k in row(s): return acc + arc_lp, arc_next;
+ *                     acc = acc + backoff[s]; s = fail[s]
+ * The kernels clamp every state into [0, S), every row bound into [0, n_arcs], and leave the back-off loop after
+ * `order` rounds: a corrupt table gives a wrong score, never a hang or an out-of-range read.  The pointers must not be
+ * null (an empty table is a pointer to one element).  weight / length_bonus are read by the fused search only.
+ * ngram_lm_struct_bytes: sizeof(edgedict_ngram_lm_t), for bindings that mirror it.
+ */
+typedef struct edgedict_ngram_lm_t {
+    int V, order, S, n_arcs, start, blank;
+    const double* uni_lp;
+    const int32_t* uni_next;
+    const int32_t* row_ptr;
+    const int32_t* fail;
+    const double* backoff;
+    const int32_t* arc_tok;
+    const double* arc_lp;
+    const int32_t* arc_next;
+    double weight, length_bonus;
+} edgedict_ngram_lm_t;
+
+size_t edgedict_ngram_lm_struct_bytes(void);
+/* Dense rows: lp [R, V] fp32, lp[r][k] = (float)step(states[r], k), 0 in the blank column - the lp_lm row format of the
+ * RNN-T searches; next [R, V] int32 (nullable): the state after k (blank column: the clamped state itself).
+ * states [R] int32.  One wave per row; no atomics, results bit-identical from run to run. */
+int edgedict_ngram_logprobs(const edgedict_ngram_lm_t* lm, const int32_t* states, int R, float* lp, int32_t* next,
+                            void* stream);
+/* Sentence scores in the N-best layout of edgedict_ctc_score_nbest: hyps [B, N, U] int32 (nullable when U == 0),
+ * hyp_lens [B, N], n_hyp [B] (nullable: all N slots live).  total [B, N] fp64 = the sum of the steps in token order from
+ * `start` (bos != 0) or state 0, then the eos step (eos != 0); -inf for a token outside [0, V) or the blank, and for the
+ * slots behind n_hyp[b].  token_lp [B, N, U] fp32 (nullable): every step's value, 0 behind the hypothesis.  One wave per
+ * hypothesis; a row is searched 64 arcs per load. */
+int edgedict_ngram_score(const edgedict_ngram_lm_t* lm, const int32_t* hyps, const int32_t* hyp_lens,
+                         const int32_t* n_hyp, int B, int N, int U, int bos, int eos, double* total, float* token_lp,
+                         void* stream);
+
+/* edgedict_ctc_beam_search with its options as a struct: the phrase automaton and / or an n-gram LM (both nullable, and
+ * opts itself: null is {null, null}).  With an n-gram a prefix carries one LM state and the total
+ * Ln = sum (weight * step + length_bonus) over its tokens; a new candidate ranks by (p + Bn) + Ln, a stay by
+ * (logadd(pb, pnb) + Bn) + Ln, and logp is (tot + Bn) + Ln; pb / pnb stay pure CTC, the candidate cut stays ahead of
+ * both terms, an extension that merges into an existing entry adds nothing.  ngram->V == V, ngram->blank == blank,
+ * 1 <= order <= 6, S > 0, non-null tables, finite weight >= 0 and finite bonus, else ED_ERR_INVALID before any launch.
+ * ngram = null launches the kernels of edgedict_ctc_beam_search; the workspace is the same. */
+typedef struct edgedict_ctc_beam_opts_t {
+    const edgedict_beam_bias_t* bias;
+    const edgedict_ngram_lm_t* ngram;
+} edgedict_ctc_beam_opts_t;
+int edgedict_ctc_beam_search_fused(const void* logits, int dtype, const int32_t* act_lens, int B, int T, int V,
+                                   int blank, int W, int cand, const edgedict_ctc_beam_opts_t* opts, int32_t* tokens,
+                                   int32_t* frames, float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp,
+                                   void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Blank-frame skipping ahead of the RNN-T beam searches (csrc/frame_skip.hip): the CTC head's blank posterior decides
  * which encoder frames a search sees.  No host sync inside either call, no atomics; results bit-identical from run to
  * run.
