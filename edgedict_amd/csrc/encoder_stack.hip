@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -319,7 +320,7 @@ struct WsLayout {
     std::vector<size_t> gimg;                       // per layer: one dG fragment image per frame (launch-persistent BPTT)
     size_t gimg_stride = 0;
     std::vector<size_t> skpart;                     // per layer: partial sums of the split-K BPTT [2][H/64][4][64][64] f32
-    size_t tmpW = 0, tmpB = 0, dX0 = 0, wsr_sync = 0, total = 0;
+    size_t tmpW = 0, tmpB = 0, tmpB2 = 0, dX0 = 0, wsr_sync = 0, total = 0;
 };
 // sync region of the workspace, in 4-byte words: chunk flags of the forward / backward pass [8 layers][512 chunks] each,
 // arrival counters of the launch-persistent forward and of the split-K BPTT's layer-wide fallback [8 layers] lines of 256
@@ -362,6 +363,7 @@ WsLayout ws_layout(const edgedict_stack_desc_t* d) {
     }
     w.tmpW = off; off += align256((size_t)8 * 4 * d->H * maxK * sizeof(float));   // up to 8 K slices
     w.tmpB = off; off += align256((size_t)4 * d->H * sizeof(float));
+    w.tmpB2 = off; off += align256((size_t)4 * d->H * sizeof(float));   // bias column sums that run on the side stream
     w.dX0 = off; off += align256((size_t)d->T0 * d->B * d->I0 * sizeof(bf16_t));
     w.wsr_sync = off; off += WSR_SYNC_BYTES;
     // one h image per frame and layer (stack_kernels.hpp EdLpwSlot::img): (T + 1) x B16 x H bf16 - 51 MB for an
@@ -468,8 +470,33 @@ struct ScheduleTrace {
                                          // product was enqueued (-1: available from the start)
     std::vector<int> toff, coff;
     int launches = 0, max_slots = 0;
+    std::vector<int32_t>* events = nullptr;   // backward pass: (kind, layer, arg, stream) in enqueue order (EdStackEvent)
 };
 thread_local ScheduleTrace* g_trace = nullptr;
+// what the backward pass enqueues, as the dry run reports it (edgedict_stack_schedule_events; include/edgedict_hip.h)
+enum EdStackEvent { EV_LAUNCH = 1, EV_LN_BWD = 2, EV_LN_SUM = 3, EV_DW = 4, EV_BIAS = 5, EV_GRADS_FINAL = 6, EV_DX0 = 7,
+                    EV_IN_NORM = 8, EV_END = 9 };
+enum { EVS_R = 0, EVS_SIDE = 1, EVS_W = 2 };
+inline void trace_event(int kind, int layer, int arg, int stream) {
+    if (g_trace && g_trace->events) g_trace->events->insert(g_trace->events->end(), {kind, layer, arg, stream});
+}
+
+// ---- EDGEDICT_STACK_TAIL: what the backward pass enqueues behind its last BPTT launches, where the weight-gradient stream's
+// serial chain is what the caller waits for (on / off, read once; default on, 0 = everything where it was before).  On:
+// the bias column sums of the two layers that finish last (1 and 0: their products run after the last launches, on a
+// chip the BPTT no longer uses) run on the side stream beside the products, not behind them - for a layer whose weight
+// gradients are issued in ONE call; a layer issued in segments (EDGEDICT_STACK_DW_SEG, _TAIL_SPLIT) keeps every bias
+// update on the weight-gradient stream, in order.  Same kernels, same inputs, same order of the updates of a gradient:
+// only the stream a kernel is enqueued on changes.  (What else was tried in the tail: DESIGN_APPENDIX.md O)
+std::atomic<int> g_tail_override{-1};    // edgedict_stack_tail_mode: tests and tools compare both settings in one process
+bool stack_tail_on() {
+    static const bool env = [] {
+        const char* e = getenv("EDGEDICT_STACK_TAIL");
+        return e ? atoi(e) != 0 : true;
+    }();
+    const int o = g_tail_override.load(std::memory_order_relaxed);
+    return o >= 0 ? o != 0 : env;
+}
 #define ED_DEV(expr)                      \
     do {                                  \
         if (!g_trace) ED_TRY(expr);       \
@@ -1234,6 +1261,42 @@ extern "C" int edgedict_stack_schedule(const edgedict_stack_desc_t* d, int backw
     return rc;
 }
 
+extern "C" int edgedict_stack_schedule_events(const edgedict_stack_desc_t* d, int32_t* events, int capacity,
+                                              int32_t* n_events) {
+    ED_CHECK_ARG(d && n_events && capacity >= 0 && (events || capacity == 0), "stack_schedule_events: bad arguments");
+    std::vector<int32_t> ev, steps, chunks;
+    ScheduleTrace tr;
+    {
+        std::vector<Geom> g;
+        ED_TRY(validate(d, g, true));
+        int to = 0, co = 0;
+        for (int l = 0; l < d->L; ++l) {
+            tr.toff.push_back(to);
+            tr.coff.push_back(co);
+            to += g[l].T;
+            co += g[l].nchunks;
+        }
+        steps.assign(to, -1);
+        chunks.assign(co, -1);
+    }
+    tr.step_launch = steps.data();
+    tr.chunk_enqueued = chunks.data();
+    tr.events = &ev;
+    g_trace = &tr;
+    const int rc = edgedict_stack_backward(d, nullptr);
+    g_trace = nullptr;
+    ED_TRY(rc);
+    *n_events = (int32_t)(ev.size() / 4);
+    for (size_t i = 0; i < ev.size() && i < (size_t)capacity * 4; ++i) events[i] = ev[i];
+    return ED_OK;
+}
+
+extern "C" int edgedict_stack_tail_mode(int bits) {
+    if (bits >= 0) g_tail_override = bits != 0 ? 1 : 0;
+    else if (bits == -1) g_tail_override = -1;
+    return stack_tail_on() ? 1 : 0;
+}
+
 extern "C" int edgedict_stack_last_timing(int backward, float* ms, int* launches) {
     ED_CHECK_ARG(ms && launches, "stack_last_timing: null pointer");
     Runtime* r = runtime_for_current_device();
@@ -1362,6 +1425,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
         Eb[l].assign(g[l].nchunks, nullptr);
         queued[l].assign(g[l].nchunks, l == L - 1 ? 1 : 0);
     }
+    const bool tail_on = stack_tail_on();
     // ---- LayerNorm backward of the TOP layer, chunk by chunk on the side stream, last chunk first: the
     // BPTT starts after ONE chunk's kernel (~10 us) instead of after all frames' (150 us on the caller's
     // stream, with nothing beside it)
@@ -1377,6 +1441,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
                                    t0, t1, y.reduce, S, dcT.thresh, dcT.seed, dcT.scale, dcT.T_out));
             if (soft) ED_DEV(ed_stack_set_flag(bflag + (L - 1) * 512 + k, S));
             else ED_TRY(st.record(Eb[L - 1][k], S));
+            trace_event(EV_LN_BWD, L - 1, k, EVS_SIDE);
         }
     }
     std::vector<int> deferred;   // layers whose weight gradients run after the BPTT (DW_AT_END)
@@ -1387,46 +1452,70 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
     // the products are spread under the whole recurrence instead of piling up behind the last
     // layers (the BPTT launches next to a busy W stream take 27 us instead of 16).
     auto weight_grads = [&](int l, int t0, int t1, bool first, bool last_of_all) -> int {
-        if (g_trace) {
-            // dry run: no product, but the host callback fires at the same point of the schedule - a data-parallel
-            // host can be tested for WHEN each layer's bucket may leave (tests/test_dp_gloo.py: ranks whose batches
-            // differ in length run different launch counts and must still issue the same collectives in the same order)
-            if (t0 == 0 && d->grads_final) d->grads_final(l, d->grads_final_user);
-            return ED_OK;
-        }
+        // (dry run: no product, but the events are recorded and the host callback fires at the same point of the
+        // schedule - a data-parallel host can be tested for WHEN each layer's bucket may leave (tests/test_dp_gloo.py:
+        // ranks whose batches differ in length run different launch counts and must still issue the same collectives
+        // in the same order))
         const edgedict_stack_layer_t& y = d->layers[l];
         const int M = (t1 - t0) * B;
         const long long r0 = (long long)t0 * B;
         float* tmpW = (float*)(ws + wl.tmpW);
-        float* tmpB = (float*)(ws + wl.tmpB);
         // the very last product has nothing left to disturb: it may take the whole chip
         const int sk = d->split_k > 0 ? d->split_k : (last_of_all ? 8 : 2);
         const int cap = last_of_all ? 4 : 2;
         const int acc = (acc_grads || !first) ? 1 : 0;
         int S = 1;
+        // the bias gradient: column sum of dG (it reads the products' 4H-wide operand once more: bandwidth-bound),
+        // then the un-permute into both bias gradients.  Behind the products on the weight-gradient stream - except for
+        // the two layers whose products run after the last BPTT launches (EDGEDICT_STACK_TAIL): there the column sums were
+        // a sixth of that stream's serial chain while the side stream had long finished, so they run beside the
+        // matrix-bound products, with a scratch row of their own, and the weight-gradient stream joins them at the end.
+        // Only when this call covers the whole layer (first && t0 == 0): the segments of a split layer update db one
+        // after the other (store, then read-modify-write) and stay in order on the weight-gradient stream
+        const bool bias_on_side = tail_on && l <= 1 && first && t0 == 0;
+        hipStream_t sb = bias_on_side ? st.S[0] : st.W;
+        float* tmpB = (float*)(ws + (bias_on_side ? wl.tmpB2 : wl.tmpB));
+        auto bias_grad = [&]() -> int {
+            ED_DEV(ed_stack_zero(tmpB, (size_t)4 * H * sizeof(float), sb));
+            ED_DEV(edgedict_colsum(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, tmpB, M, 4 * H, sb));
+            if (!g_trace) {
+                hipLaunchKernelGGL(unpermute_rows_kernel, dim3(ed_grid_for(4ll * H, 256, 4096)), dim3(256),
+                                   0, sb, tmpB, 0, 1, y.db, y.db_hh, H, 1, acc);
+                ED_CHECK_LAUNCH("unpermute_rows_kernel");
+            }
+            trace_event(EV_BIAS, l, 0, bias_on_side ? EVS_SIDE : EVS_W);
+            return ED_OK;
+        };
+        if (bias_on_side) {
+            ED_TRY(st.chain(st.RS(l), sb));
+            ED_TRY(bias_grad());
+        }
         // QUIET products (K slices written once, no atomics: a concurrent kernel with dirty lines
         // makes every BPTT launch boundary 3-10x dearer); rows come out in interleaved gate order
         // and are summed + un-permuted in one pass
-        ED_TRY(ed_gemm_quiet_partials(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, 0, bptr(y.X) + r0 * y.I, y.I, 0,
+        ED_DEV(ed_gemm_quiet_partials(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, 0, bptr(y.X) + r0 * y.I, y.I, 0,
                                       4 * H, y.I, M, sk, cap, tmpW, &S, st.W));
-        ED_TRY(unpermute_rows(tmpW, 4ll * H * y.I, S, y.dW_ih, nullptr, H, y.I, acc, st.W));
-        ED_TRY(ed_gemm_quiet_partials(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, 0, bptr(y.Yx) + r0 * H, H, 0,
+        ED_DEV(unpermute_rows(tmpW, 4ll * H * y.I, S, y.dW_ih, nullptr, H, y.I, acc, st.W));
+        trace_event(EV_DW, l, 0, EVS_W);
+        ED_DEV(ed_gemm_quiet_partials(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, 0, bptr(y.Yx) + r0 * H, H, 0,
                                       4 * H, H, M, sk, cap, tmpW, &S, st.W));
-        ED_TRY(unpermute_rows(tmpW, 4ll * H * H, S, y.dW_hh, nullptr, H, H, acc, st.W));
-        ED_TRY(ed_stack_zero(tmpB, (size_t)4 * H * sizeof(float), st.W));
-        ED_TRY(edgedict_colsum(ED_BF16, bptr(y.G) + r0 * 4 * H, 4ll * H, tmpB, M, 4 * H, st.W));
-        hipLaunchKernelGGL(unpermute_rows_kernel, dim3(ed_grid_for(4ll * H, 256, 4096)), dim3(256),
-                           0, st.W, tmpB, 0, 1, y.db, y.db_hh, H, 1, acc);
-        ED_CHECK_LAUNCH("unpermute_rows_kernel");
+        ED_DEV(unpermute_rows(tmpW, 4ll * H * H, S, y.dW_hh, nullptr, H, H, acc, st.W));
+        trace_event(EV_DW, l, 1, EVS_W);
+        if (bias_on_side) ED_TRY(st.chain(sb, st.W));
+        else ED_TRY(bias_grad());
         // frames [0, t1) were the last ones of this layer: its weight gradients are final once the
         // auxiliary stream reaches this point
-        if (t0 == 0 && d->grads_final) d->grads_final(l, d->grads_final_user);
+        if (t0 == 0) {
+            if (d->grads_final) d->grads_final(l, d->grads_final_user);
+            trace_event(EV_GRADS_FINAL, l, 0, EVS_W);
+        }
         return ED_OK;
     };
     int dw_seg = 1 << 20;   // measured: 8 / 4 / 2 / 1 chunks per segment cost +0.3 / +0.6 / +1.6 / +5.3 ms per step
     if (const char* e = getenv("EDGEDICT_STACK_DW_SEG")) dw_seg = max(1, atoi(e));
     if (d->flags & EDGEDICT_STACK_DW_AT_END) dw_seg = 1 << 20;
-    int tail_split = 0;   // measured: 4 -> +0.2..0.7 ms per step (BPTT period 23.6 -> 24.8 us outweighs the shorter tail)
+    int tail_split = 0;   // measured with the split-K BPTT: 2 / 3 -> +0.14 / +0.18 ms per step (profiles/r6_sweep.txt: the
+                          // pass is 0.14 ms longer though the launch period does not grow; the tail is no shorter)
     if (const char* e = getenv("EDGEDICT_STACK_TAIL_SPLIT")) tail_split = atoi(e);
 
     int margin = margin_launches(d, g, true);
@@ -1460,6 +1549,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
                                        drop_of(z).scale, drop_of(z).T_out));
                 if (soft) ED_DEV(ed_stack_set_flag(bflag + (l - 1) * 512 + k, S));
                 else ED_TRY(st.record(Eb[l - 1][k], S));
+                trace_event(EV_LN_BWD, l - 1, k, EVS_SIDE);
                 queued[l - 1][k] = 1;
                 ready_w[l - 1][k] = w + margin;
                 if (g_trace) g_trace->chunk_enqueued[g_trace->coff[l - 1] + k] = g_trace->launches;
@@ -1575,6 +1665,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
             ED_DEV(ed_stack_launch_bwd_sk(Ls, st.R));
             if (g_trace) {
                 g_trace->max_slots = max(g_trace->max_slots, Ls.nslot);
+                trace_event(EV_LAUNCH, -1, g_trace->launches, EVS_R);
                 ++g_trace->launches;
             }
             if (ndone > 1) ED_TRY(st.share(st.R));
@@ -1638,6 +1729,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
         if (st.R2 != st.R) ED_DEV(ed_stack_launch_bwd(Lcs[1], st.R2));
         if (g_trace) {
             g_trace->max_slots = max(g_trace->max_slots, Lcs[0].nstep + Lcs[1].nstep);
+            trace_event(EV_LAUNCH, -1, g_trace->launches, EVS_R);
             ++g_trace->launches;
         }
         for (int i = 0; i < ndone; ++i) ED_TRY(chunk_done(done[i].l, done[i].k, w));
@@ -1655,14 +1747,17 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
         ED_DEV(edgedict_gemm(ED_BF16, ED_BF16, y.G, 4ll * H, 1, y.wih_t ? y.wih_t : y.wih_p,
                              y.wih_t ? 4ll * H : y.I, y.wih_t ? 1 : 0, dX0, y.I, y.T * B, y.I, 4 * H,
                              nullptr, nullptr, 0, 1, st.S[0]));
+        trace_event(EV_DX0, 0, 0, EVS_SIDE);
         ED_DEV(ed_stack_input_norm_bwd(d->x_dtype, d->x, dX0, d->in_mean, d->in_rstd, d->d_in_gamma,
                                        d->d_in_beta, B, d->T0, d->I0, st.S[0]));
+        trace_event(EV_IN_NORM, 0, 0, EVS_SIDE);
         // LayerNorm parameter gradients: sum the per-workgroup partial rows of every launch
         for (int l = 1; l < L; ++l) ED_TRY(st.chain(st.S[l], st.S[0]));
         for (int l = 0; l < L; ++l) {
             const edgedict_stack_layer_t& z = d->layers[l];
             const float* part = (const float*)(ws + wl.lnpart[l]);
             ED_DEV(ed_stack_sum_parts(part, g[l].nchunks * LNB_GRID, H, z.dgamma, z.dbeta, st.S[0]));
+            trace_event(EV_LN_SUM, l, 0, EVS_SIDE);
         }
     }
     if (!deferred.empty()) {
@@ -1670,6 +1765,7 @@ extern "C" int edgedict_stack_backward(const edgedict_stack_desc_t* d, void* str
         if (st.R2 != st.R) ED_TRY(st.chain(st.R2, st.W));
         for (int l : deferred) ED_TRY(weight_grads(l, 0, d->layers[l].T, true, false));
     }
+    trace_event(EV_END, -1, 0, EVS_R);
     ED_TRY(st.chain(st.R, st.C));
     if (st.R2 != st.R) ED_TRY(st.chain(st.R2, st.C));
     for (int l = 0; l < L; ++l) ED_TRY(st.chain(st.S[l], st.C));

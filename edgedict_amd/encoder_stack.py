@@ -397,15 +397,9 @@ class EncoderStackFn(torch.autograd.Function):
         return tuple(out)
 
 
-def schedule(T0, I0, H, reductions, B=64, chunk=None, backward=False, lag=0, flags=0, grads_final=None):
-    """Dry run of the native scheduler (no device): returns ``(step_launch, chunk_enqueued,
-    n_launches, max_slots)`` where ``step_launch[l][t]`` is the launch index that carries step t of
-    layer l and ``chunk_enqueued[l][k]`` the number of launches issued when chunk k's side-stream
-    product was enqueued (-1 = available from the start).  Used by tests/test_stack_schedule.py.
-    ``grads_final(layer)`` (backward only) is called where the real pass reports a layer's weight gradients final
-    (``edgedict_stack_desc_t.grads_final``): tests/test_dp_gloo.py drives the gradient exchange with it."""
-    import numpy as np
-    lib = _lib.load()
+def _dry_desc(T0, I0, H, reductions, B, chunk, lag, flags, grads_final):
+    """A descriptor for the dry-run entry points (pointers that are never dereferenced): (desc, keep-alive objects,
+    frames per layer, chunks per layer)."""
     L = len(reductions)
     chunk = chunk or CHUNK
     layers = (StackLayer * L)()
@@ -444,6 +438,20 @@ def schedule(T0, I0, H, reductions, B=64, chunk=None, backward=False, lag=0, fla
         fl.append(f)
         f //= reductions[l]
     nch = [(Ts[l] + chunk * fl[l] - 1) // (chunk * fl[l]) for l in range(L)]
+    return d, (layers, cb), Ts, nch
+
+
+def schedule(T0, I0, H, reductions, B=64, chunk=None, backward=False, lag=0, flags=0, grads_final=None):
+    """Dry run of the native scheduler (no device): returns ``(step_launch, chunk_enqueued,
+    n_launches, max_slots)`` where ``step_launch[l][t]`` is the launch index that carries step t of
+    layer l and ``chunk_enqueued[l][k]`` the number of launches issued when chunk k's side-stream
+    product was enqueued (-1 = available from the start).  Used by tests/test_stack_schedule.py.
+    ``grads_final(layer)`` (backward only) is called where the real pass reports a layer's weight gradients final
+    (``edgedict_stack_desc_t.grads_final``): tests/test_dp_gloo.py drives the gradient exchange with it."""
+    import numpy as np
+    lib = _lib.load()
+    L = len(reductions)
+    d, _keep, Ts, nch = _dry_desc(T0, I0, H, reductions, B, chunk, lag, flags, grads_final)
     steps = np.full(sum(Ts), -2, dtype=np.int32)
     enq = np.full(sum(nch), -2, dtype=np.int32)
     nl, ms = ctypes.c_int32(0), ctypes.c_int32(0)
@@ -455,3 +463,29 @@ def schedule(T0, I0, H, reductions, B=64, chunk=None, backward=False, lag=0, fla
     co = np.cumsum([0] + nch)
     return ([steps[so[l]:so[l + 1]] for l in range(L)], [enq[co[l]:co[l + 1]] for l in range(L)],
             int(nl.value), int(ms.value))
+
+
+# kinds and streams of edgedict_stack_schedule_events (include/edgedict_hip.h)
+EV_LAUNCH, EV_LN_BWD, EV_LN_SUM, EV_DW, EV_BIAS, EV_GRADS_FINAL, EV_DX0, EV_IN_NORM, EV_END = range(1, 10)
+EVS_R, EVS_SIDE, EVS_W = 0, 1, 2
+
+
+def schedule_events(T0, I0, H, reductions, B=64, chunk=None, lag=0, flags=0, grads_final=None):
+    """Dry run of the backward pass (no device): what it enqueues, in enqueue order, as a list of
+    ``(kind, layer, arg, stream)`` tuples (``EV_*`` / ``EVS_*`` above).  Used by tests/test_stack_tail_schedule.py."""
+    import numpy as np
+    lib = _lib.load()
+    d, _keep, _Ts, _nch = _dry_desc(T0, I0, H, reductions, B, chunk, lag, flags, grads_final)
+    n = ctypes.c_int32(0)
+    _lib.check(lib.edgedict_stack_schedule_events(ctypes.byref(d), None, 0, ctypes.byref(n)), "stack_schedule_events")
+    ev = np.zeros((max(1, n.value), 4), dtype=np.int32)
+    d.grads_final = None          # the callback fired in the counting call
+    _lib.check(lib.edgedict_stack_schedule_events(ctypes.byref(d), ev.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                  ctypes.byref(n)), "stack_schedule_events")
+    return [tuple(int(x) for x in row) for row in ev[:n.value]]
+
+
+def tail_mode(on=-2):
+    """``EDGEDICT_STACK_TAIL`` for this process: ``on >= 0`` overrides the environment (0 off, else on), ``-1`` drops the
+    override, the default only queries.  Returns 1 or 0, the setting in effect (``edgedict_stack_tail_mode``)."""
+    return int(_lib.load().edgedict_stack_tail_mode(int(on)))

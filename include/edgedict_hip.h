@@ -582,6 +582,24 @@ int edgedict_stack_launch_stamps(int backward, unsigned long long* out, int max_
  *   n_launches, max_slots  HOST int32: launches of the step kernel, most layer-steps in one launch */
 int edgedict_stack_schedule(const edgedict_stack_desc_t* d, int backward, int32_t* step_launch,
                             int32_t* chunk_enqueued, int32_t* n_launches, int32_t* max_slots);
+/* dry run of the backward pass that reports WHAT is enqueued, in enqueue order: quadruples (kind, layer, arg, stream) of
+ * HOST int32, the first `capacity` of them written to `events`, their number to *n_events.  kind: 1 a BPTT launch (arg =
+ * its index), 2 a LayerNorm-backward chunk that writes layer `layer`'s partial rows (arg = chunk), 3 layer's LayerNorm
+ * parameter sum, 4 a weight-gradient product with its un-permute (arg 0 = dW_ih, 1 = dW_hh), 5 layer's bias gradient
+ * (column sum + un-permute), 6 the grads_final callback of the layer, 7 the layer-0 dX product, 8 the input norm's
+ * parameter gradient, 9 the end of the pass.  stream: 0 recurrence, 1 side, 2 weight-gradient stream.  layer = -1 where
+ * none applies.  d->grads_final is called as in edgedict_stack_schedule. */
+int edgedict_stack_schedule_events(const edgedict_stack_desc_t* d, int32_t* events, int capacity, int32_t* n_events);
+/* EDGEDICT_STACK_TAIL (read once from the environment; on unless it is 0): on, the bias column sums of layers 1 and 0 run
+ * on the side stream beside those layers' weight-gradient products, not behind them in the serial chain the caller waits
+ * for after the last BPTT launch (the weight-gradient stream joins them before grads_final fires) - for a layer whose
+ * weight gradients are issued in one call; a layer issued in segments keeps its bias updates in order on the
+ * weight-gradient stream.  0 enqueues everything where it was before.  No kernel, no input and the order of no gradient's
+ * updates changes.
+ * edgedict_stack_tail_mode(on >= 0) overrides the environment for the process (0 off, else on: tests and tools compare
+ * both settings in one process), (-1) drops the override, any other value only queries; returns 1 or 0, the setting in
+ * effect.  A backward call reads the setting once, when it starts. */
+int edgedict_stack_tail_mode(int bits);
 int edgedict_stack_backward(const edgedict_stack_desc_t* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
