@@ -176,8 +176,9 @@ def is_gru(sd):
     return w.shape[0] == 3 * w.shape[1]
 
 
-def encoder_forward_gru(sd, xs, hiddens=None, time_reductions=(1,)):
-    """rnnt/models.py:131-136 + :99-116 (ResLayerNormGRU).  Returns (ys [B,T',P], hs [L,B,H])."""
+def encoder_forward_gru(sd, xs, hiddens=None, time_reductions=(1,), after_layer=None):
+    """rnnt/models.py:131-136 + :99-116 (ResLayerNormGRU).  Returns (ys [B,T',P], hs [L,B,H]).
+    ``after_layer``: see ``encoder_forward``."""
     x = layer_norm(xs, sd["encoder.norm.weight"], sd["encoder.norm.bias"])
     hs = []
     for i in range(n_enc_layers(sd)):
@@ -189,6 +190,8 @@ def encoder_forward_gru(sd, xs, hiddens=None, time_reductions=(1,)):
                        sd["encoder.lstm.projs.%d.0.bias" % i])
         if i in time_reductions:
             x = time_reduction(x)
+        if after_layer is not None:
+            x = after_layer(i, x)
         hs.append(h)
     y = x @ sd["encoder.proj.weight"].t() + sd["encoder.proj.bias"]
     return y, torch.stack(hs)
@@ -208,11 +211,13 @@ def n_dec_layers(sd):
     return n
 
 
-def encoder_forward(sd, xs, hiddens=None, time_reductions=(1,), explicit=False):
+def encoder_forward(sd, xs, hiddens=None, time_reductions=(1,), explicit=False, after_layer=None):
     """rnnt/models.py:131-136 + :55-75.  Returns (ys [B,T',P], (hs, cs) [L,B,H]); for a GRU
-    state dict (module_type='GRU') the second item is hs alone, as in the reference."""
+    state dict (module_type='GRU') the second item is hs alone, as in the reference.
+    ``after_layer`` (None, or callable(layer_index, tensor) -> tensor): applied to every layer's output behind its
+    LayerNorm (+ TimeReduction), where the reference's training-mode nn.Dropout sits (rnnt/models.py:47-53)."""
     if is_gru(sd):
-        return encoder_forward_gru(sd, xs, hiddens, time_reductions)
+        return encoder_forward_gru(sd, xs, hiddens, time_reductions, after_layer)
     x = layer_norm(xs, sd["encoder.norm.weight"], sd["encoder.norm.bias"])
     hs, cs = [], []
     for i in range(n_enc_layers(sd)):
@@ -227,14 +232,18 @@ def encoder_forward(sd, xs, hiddens=None, time_reductions=(1,), explicit=False):
                        sd["encoder.lstm.projs.%d.0.bias" % i])
         if i in time_reductions:
             x = time_reduction(x)
+        if after_layer is not None:
+            x = after_layer(i, x)
         hs.append(h)
         cs.append(c)
     y = x @ sd["encoder.proj.weight"].t() + sd["encoder.proj.bias"]
     return y, (torch.stack(hs), torch.stack(cs))
 
 
-def decoder_forward(sd, ys, hidden=None, explicit=False):
-    """rnnt/models.py:150-157.  ``hidden is None`` => training mode: BOS is left-padded."""
+def decoder_forward(sd, ys, hidden=None, explicit=False, after_layer=None):
+    """rnnt/models.py:150-157.  ``hidden is None`` => training mode: BOS is left-padded.
+    ``after_layer`` (None, or callable(layer_index, tensor) -> tensor): applied to every LSTM layer's output (the caller
+    decides where nn.LSTM(dropout=p) acts: behind every layer but the last)."""
     ys = ys.long()
     if hidden is None:
         ys = torch.cat([torch.full((ys.shape[0], 1), BOS, dtype=torch.long), ys], dim=1)
@@ -248,6 +257,8 @@ def decoder_forward(sd, ys, hidden=None, explicit=False):
                              sd["decoder.lstm.weight_hh_l%d" % k],
                              sd["decoder.lstm.bias_ih_l%d" % k],
                              sd["decoder.lstm.bias_hh_l%d" % k], h0, c0, explicit)
+        if after_layer is not None:
+            x = after_layer(k, x)
         hs.append(h)
         cs.append(c)
     y = x @ sd["decoder.proj.weight"].t() + sd["decoder.proj.bias"]

@@ -12,11 +12,16 @@ every layer's pre-activation gradient dG_l from autograd.  ``layer_forward64`` i
 given input (the forward buffers through ``lstm_ref.lstm_steps64``): on a kernel's own stored X_l it says what that layer
 should have made of it, whatever happened below.  ``weight_grads_from_buffers`` are the three weight-gradient products
 of a layer from given dG, X and h_{t-1} buffers, with the magnitude sums an fp32 error bound needs.
+
+Dropout (``drop=``, default None: none): mask * scale behind every layer's norm role, the mask restated by
+tests/dropout_ref.py over the layer's REDUCED batch-first output, element index (b T_out + tau) H + j.
 """
 import collections
 
+import numpy as np
 import torch
 
+import dropout_ref as D
 import lstm_ref as R
 from oracle import models_ref as M
 
@@ -59,10 +64,33 @@ def ln_stats(z, eps=EPS):
     return mean, 1.0 / torch.sqrt(var + eps)
 
 
-def norm_role(Z, gamma, beta, reduce):
-    """LayerNorm of every frame of Z [B, T, H], then the pair mean where reduce == 2."""
+def drop_mask64(shape, p, seed, frame_shift=0):
+    """mask * scale of a layer's batch-first [B, T_out, H] output as float64: element (b, tau, j) has index
+    (b T_out + tau) H + j (tests/dropout_ref.py restates the hash; the scale is the kernels' float32 1 / (1 - p)).
+    ``frame_shift``: a deliberately WRONG mask for negative controls - the index of frame tau + frame_shift."""
+    B, T, H = shape
+    keep = D.mask((B, T, H), p, seed, first=frame_shift * H)
+    return torch.from_numpy(keep.astype(np.float64) * float(D.scale(p)))
+
+
+def layer_drop(drop, l):
+    """``drop`` = (p, seeds) or (p, seeds, frame_shifts), one seed (and shift) per layer -> layer l's (p, seed, shift)."""
+    if drop is None:
+        return None
+    return (drop[0], drop[1][l], drop[2][l] if len(drop) > 2 else 0)
+
+
+def norm_role(Z, gamma, beta, reduce, drop=None):
+    """LayerNorm of every frame of Z [B, T, H], then the pair mean where reduce == 2; with ``drop`` = (p, seed) or
+    (p, seed, frame_shift) of THIS layer, times mask * scale over the REDUCED output.  The kernel rounds the LayerNorm
+    (+ pair mean) to bf16 BEFORE it masks and scales (the reference's Dropout sees a bf16 tensor) and rounds the product
+    again at its store; float64 rounds nowhere, so a kept element of the kernel is within two bf16 roundings of this
+    value and a dropped one is exactly 0."""
     out = M.layer_norm(Z, gamma, beta, EPS)
-    return M.time_reduction(out, 2) if reduce == 2 else out
+    out = M.time_reduction(out, 2) if reduce == 2 else out
+    if drop is not None:
+        out = out * drop_mask64(out.shape, *drop)
+    return out
 
 
 def _recurrence(G_in, w_hh, h, c):
@@ -87,9 +115,11 @@ def _leaf(t):
     return t.detach().to(F64).cpu().clone().requires_grad_(True)
 
 
-def stack_forward64(x, in_gamma, in_beta, layers, reductions, h0=None, c0=None):
+def stack_forward64(x, in_gamma, in_beta, layers, reductions, h0=None, c0=None, drop=None):
     """x [B, T0, I0]; layers: per layer (w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta); reductions: 1 or 2 per layer; h0 / c0
-    [L, B, H] or None (zeros).  Returns Stack64: out [B, T', H], hN / cN [L, B, H], X0, the input norm's statistics
+    [L, B, H] or None (zeros); ``drop`` = (p, seeds) - one seed per layer, as EncoderStackFn takes them - puts
+    mask * scale behind every layer's norm role (``norm_role``), and a third item, per-layer frame shifts, makes the mask
+    deliberately wrong.  Returns Stack64: out [B, T', H], hN / cN [L, B, H], X0, the input norm's statistics
     [B, T0], per layer a Layer64 (X the normalised input, G_in the pre-activations' input part - the leaf of dG -, the
     gates, Y, h_{t-1}, the cell states, Z = Y (+ X) with its statistics [B, T], the layer's output) and ``leaves``:
     x, in_gamma, in_beta, h0, c0 and the per-layer parameter lists as float64 leaves of the graph."""
@@ -111,7 +141,7 @@ def stack_forward64(x, in_gamma, in_beta, layers, reductions, h0=None, c0=None):
         gates, Y, Hprev, C, hN, cN = _recurrence(G_in, w_hh, h, c)
         Z = Y if l == 0 else X + Y
         mean, rstd = ln_stats(Z.detach())
-        out = norm_role(Z, ln_g, ln_b, reductions[l])
+        out = norm_role(Z, ln_g, ln_b, reductions[l], layer_drop(drop, l))
         recs.append(Layer64(X, G_in, gates, Y, Hprev, C, Z, mean, rstd, out, hN, cN))
         hs.append(hN)
         cs.append(cN)
@@ -119,8 +149,9 @@ def stack_forward64(x, in_gamma, in_beta, layers, reductions, h0=None, c0=None):
     return Stack64(X, torch.stack(hs), torch.stack(cs), X0, in_mean, in_rstd, recs, lv)
 
 
-def stack_grads64(res, dout):
-    """Autograd of (out * dout).sum() through a ``stack_forward64`` result (once per result).  Returns a dict: ``dx``,
+def stack_grads64(res, dout, drop=None):
+    """Autograd of (out * dout).sum() through a ``stack_forward64`` result (once per result; ``drop`` is the one the
+    result was built with - its masks are part of the graph, so nothing is left to apply here).  Returns a dict: ``dx``,
     ``in_gamma``, ``in_beta``, ``layers`` (per layer [dW_ih, dW_hh, db_ih, db_hh, dln_gamma, dln_beta]) and ``dG`` (per
     layer [B, T, 4H], the gradient of every step's pre-activation, plain gate order)."""
     (res.out * dout.detach().to(F64).cpu()).sum().backward()
@@ -130,8 +161,9 @@ def stack_grads64(res, dout):
                 dG=[rec.G_in.grad for rec in res.layers])
 
 
-def layer_forward64(X, layer, reduce, residual, h0=None, c0=None):
-    """One layer on a given input X [B, T, I]: (w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta), h0 / c0 [B, H] or None.
+def layer_forward64(X, layer, reduce, residual, h0=None, c0=None, drop=None):
+    """One layer on a given input X [B, T, I]: (w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta), h0 / c0 [B, H] or None;
+    ``drop`` = this layer's (p, seed), as ``norm_role`` takes it (only ``out`` depends on it).
     No gradient.  Returns a Layer64 (G_in: the input product plus both biases)."""
     w_ih, w_hh, b_ih, b_hh, ln_g, ln_b = [p.detach().to(F64).cpu() for p in layer]
     X = X.detach().to(F64).cpu()
@@ -139,7 +171,8 @@ def layer_forward64(X, layer, reduce, residual, h0=None, c0=None):
     r = R.lstm_steps64(G_in, w_hh, h0, c0)
     Z = X + r.Y if residual else r.Y
     mean, rstd = ln_stats(Z)
-    return Layer64(X, G_in, r.gates, r.Y, r.Hprev, r.Cst, Z, mean, rstd, norm_role(Z, ln_g, ln_b, reduce), r.hN, r.cN)
+    return Layer64(X, G_in, r.gates, r.Y, r.Hprev, r.Cst, Z, mean, rstd, norm_role(Z, ln_g, ln_b, reduce, drop), r.hN,
+                   r.cN)
 
 
 def weight_grads_from_buffers(dG, X, Hprev):
