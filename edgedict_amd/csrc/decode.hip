@@ -1476,10 +1476,11 @@ extern "C" size_t edgedict_search_struct_bytes(int which) {
 }
 
 namespace {
-// internal-LM estimation is the frame-synchronous search's alone: the expansion searches refuse it, their size queries
-// return 0
-int no_ilm(const edgedict_search_opts_t& o, const char* what) {
+// internal-LM estimation and the n-gram LM are the frame-synchronous search's alone: the expansion searches refuse
+// them, their size queries return 0
+int no_sync_opts(const edgedict_search_opts_t& o, const char* what) {
     ED_CHECK_ARG(!o.ilm_weight, "%s: ilm_weight is not supported (internal-LM estimation is in sync_beam_search)", what);
+    ED_CHECK_ARG(!o.ngram, "%s: ngram is not supported (the n-gram LM is fused into sync_beam_search)", what);
     return ED_OK;
 }
 }  // namespace
@@ -1488,7 +1489,7 @@ extern "C" size_t edgedict_beam_workspace_bytes(const edgedict_search_net_t* pn,
                                                 int prefix, const edgedict_search_opts_t* opts) {
     if (!pn || !search_ptrs_ok(pn, opts)) return 0;
     const edgedict_search_opts_t o = search_opts_of(opts);
-    if (o.ilm_weight || B <= 0 || W <= 0 || max_expansions <= 0) return 0;
+    if (o.ilm_weight || o.ngram || B <= 0 || W <= 0 || max_expansions <= 0) return 0;
     const SearchNet n = search_net_of(*pn, nullptr, 0, 0, B, W, max_expansions, 0);
     const size_t base = beam_layout(n, (size_t)(T < 0 ? 0 : T) * n.EM + 1, prefix, false).total;
     return ws_total(base, n, o.lm, o.bias, true);
@@ -1506,7 +1507,7 @@ int beam_search_run(const edgedict_search_net_t* pn, const void* E1, long long e
     const edgedict_search_opts_t o = search_opts_of(opts);
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
-    if (int rc = no_ilm(o, nb ? "beam_search_nbest" : "beam_search")) return rc;
+    if (int rc = no_sync_opts(o, nb ? "beam_search_nbest" : "beam_search")) return rc;
     ED_CHECK_ARG(!nb || !prefix,
                  "beam_search_nbest: prefix = 1 is not supported (the prefix merge changes a hypothesis' score at frame "
                  "starts, so the per-token increments would no longer add up to it)");
@@ -1876,7 +1877,7 @@ extern "C" size_t edgedict_beam_stream_state_bytes(const edgedict_search_opts_t*
                                                    int node_capacity) {
     if (!search_ptrs_ok(nullptr, opts)) return 0;
     const edgedict_search_opts_t o = search_opts_of(opts);
-    if (o.ilm_weight || S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
+    if (o.ilm_weight || o.ngram || S <= 0 || W <= 0 || L <= 0 || H <= 0 || node_capacity <= 0) return 0;
     return beam_stream_state_layout(S, L, H, W, node_capacity, o.lm, o.bias).total;
 }
 
@@ -1884,7 +1885,7 @@ extern "C" size_t edgedict_beam_stream_workspace_bytes(const edgedict_search_net
                                                        int node_capacity, const edgedict_search_opts_t* opts) {
     if (!pn || !search_ptrs_ok(pn, opts)) return 0;
     const edgedict_search_opts_t o = search_opts_of(opts);
-    if (o.ilm_weight || S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
+    if (o.ilm_weight || o.ngram || S <= 0 || W <= 0 || max_expansions <= 0 || node_capacity <= 0) return 0;
     const SearchNet n = search_net_of(*pn, nullptr, 0, 0, S, W, max_expansions, 0);
     const size_t base = beam_layout(n, (size_t)node_capacity, 0, true).total;
     return ws_total(base, n, o.lm, o.bias, false);
@@ -1899,7 +1900,7 @@ extern "C" int edgedict_beam_stream_reset(const edgedict_search_opts_t* opts, in
     const edgedict_search_opts_t o = search_opts_of(opts);
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
-    if (int rc = no_ilm(o, "beam_stream_reset")) return rc;
+    if (int rc = no_sync_opts(o, "beam_stream_reset")) return rc;
     ED_CHECK_ARG(S > 0 && L > 0 && H > 0 && W > 0 && node_capacity > 0, "beam_stream_reset: bad shape");
     ED_CHECK_ARG(state, "beam_stream_reset: null state");
     ED_CHECK_ARG(!lm || (lm->L > 0 && lm->H > 0), "beam_stream_reset: bad LM shape");
@@ -1952,7 +1953,7 @@ extern "C" int edgedict_beam_stream_advance(const edgedict_search_net_t* pn, con
     const edgedict_search_opts_t o = search_opts_of(opts);
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
-    if (int rc = no_ilm(o, "beam_stream_advance")) return rc;
+    if (int rc = no_sync_opts(o, "beam_stream_advance")) return rc;
     const StreamDetailArgs detail{detail_state, detail_workspace, commit_frame_host, commit_logp_host};
     const bool any_detail = detail_state || detail_workspace || commit_frame_host || commit_logp_host;
     const StreamDetailArgs* dt = any_detail ? &detail : nullptr;

@@ -35,9 +35,18 @@
 // kernels and the persistent state are untouched.  On the fused step the frame keeps its launch count (the joint-hidden
 // kernel writes both hidden vectors from one product, the logits kernel runs on 2 B W rows); composed, two launches more.
 //
+// The back-off n-gram (opts->ngram, the third LM kind SB_LM_NGRAM; ngram_tables.hpp): a row carries ONE int32 state,
+// the state AFTER its sequence (the automaton's convention, not the LSTM's), `start` for the empty one.  No step and no
+// [B W, V] buffer: sync_row_topw_ngram's workgroup builds the row's image - step(s_i, .) in fp64 and next(s_i, .) - in
+// dynamic LDS from the back-off chain of s_i, as ngram_rows of ngram.hip fills its HBM row, scores from it,
+//   c = c + (weight * step(s_i, k) + bonus)        (ngram_term: product rounded, then the bonus; never through fp32),
+// and writes a kept candidate's next state beside its score and token; the select kernel reads that field, so it walks
+// no table.  A frame's launch list is the plain search's.  One LM at a time: opts->lm with opts->ngram is refused.
+//
 // Second half of the file: the streaming form (edgedict_sync_stream_*), the same frame loop on a persistent state.
 #include "bias_tables.hpp"
 #include "decode_net.hpp"
+#include "ngram_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -84,7 +93,18 @@ struct SyncFuse {
     const int32_t* bias_exc_tok;
     const int32_t* bias_exc_next;
     int bias_S, bias_V;
+    int32_t* ng_st;             // [B*W]  the n-gram state AFTER the row's sequence (ng_start: the empty one)
+    int32_t* ng_next;           // [B*W][W] beside c_k: the state after the candidate's token (per call: workspace)
+    int ng_start;
 };
+
+// the LM kind of a kernel instantiation (false / true of the forms without an n-gram are the first two)
+constexpr int SB_LM_NONE = 0, SB_LM_LSTM = 1, SB_LM_NGRAM = 2;
+// The n-gram's image of a row in dynamic LDS: lp fp64 [V], next int32 [V], 12 bytes a symbol.  With the top-W kernel's
+// static LDS (112 bytes) it has to fit the 64 KiB a launch gets without a function attribute; 1 KiB is left spare.
+constexpr int SB_NGRAM_MAX_V = 5376;
+constexpr int SB_NGRAM_MAX_ORDER = 6;
+static_assert((size_t)SB_NGRAM_MAX_V * 12 + 1024 <= 65536, "the n-gram image must fit 64 KiB of LDS");
 
 __device__ __forceinline__ float sb_block_sum_max(float x, bool is_max, float* s_f) {
     x = is_max ? wave_max(x) : wave_sum(x);
@@ -133,11 +153,20 @@ constexpr int SB_VPT = 8;
 // candidate in the CACHED form and once per candidate and pass in the other.
 // ILM (sync_row_topw_ilm): a third max / sum pass over the row's internal-LM logits that skips `blank`, and behind the LM
 // term  c = c - ilm_w * (double)lp_ilm[k]  (__dsub_rn / __dmul_rn: no contraction), so ilm_w = 0 leaves every bit.
-template <bool CACHED, bool LM, bool BIAS, bool ILM = false>
+// LM == SB_LM_NGRAM (sync_row_topw_ngram): before the scoring passes the workgroup builds the row's n-gram image in dynamic
+// LDS, ng_lp[v] = step(s, v) in fp64 and ng_nx[v] = next(s, v), the way ngram_rows fills its HBM row: the back-off chain
+// s_0 = s, s_1 = fail(s_0), ... of at most `order` states with its prefix sums acc_j, every column from the unigram level
+// (acc_d + uni_lp), then level by level towards the longest context (acc_j + arc_lp over the columns of s_j's arcs), a
+// barrier between levels, so that a column ends with the longest context that has it - step()'s answer, in step()'s order
+// of additions.  lp and next of a column are written by the same thread in the same level.  Every clamp of
+// ngram_tables.hpp is kept: whatever the tables hold, the fill reads inside them, writes inside [0, V) and ends.
+// score(v) gains  c = c + ngram_term(weight, ng_lp[v], bonus)  for v != blank, and thread j writes pick j's next state.
+template <bool CACHED, int LM, bool BIAS, bool ILM = false>
 __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const SyncFuse& f,
                                                    const float* __restrict__ logits,
                                                    const float* __restrict__ lm_logits, int t, int W, int V, int blank,
-                                                   const float* __restrict__ ilm_logits = nullptr, double ilm_w = 0.0) {
+                                                   const float* __restrict__ ilm_logits = nullptr, double ilm_w = 0.0,
+                                                   const NgramTables* lt = nullptr) {
     const int r = blockIdx.x, tid = threadIdx.x;
     if (t >= p.lens[r / W]) return;
     const double base = p.logp[r];
@@ -155,7 +184,7 @@ __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const Sync
     const float logs = logf(s);
     const float* zl = nullptr;
     float ml = 0.f, logsl = 0.f;
-    if constexpr (LM) {
+    if constexpr (LM == SB_LM_LSTM) {
         zl = lm_logits + (size_t)r * V;
         ml = -INFINITY;
         for (int v = tid; v < V; v += 256) ml = fmaxf(ml, zl[v]);
@@ -185,10 +214,57 @@ __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const Sync
         st = bias_state(f, f.bias_st[r]);
         pend_s = f.bias_pend[st];
     }
+    extern __shared__ double ng_lds[];
+    double* ng_lp = ng_lds;                     // [V]
+    int* ng_nx = (int*)(ng_lds + V);            // [V]
+    if constexpr (LM == SB_LM_NGRAM) {
+        const NgramTables& g = *lt;
+        const int s0 = ngram_state(g, f.ng_st[r]);
+        int chain[SB_NGRAM_MAX_ORDER];
+        double acc[SB_NGRAM_MAX_ORDER + 1];
+        int d = 0, s = s0;
+        acc[0] = 0.0;
+#pragma unroll
+        for (int it = 0; it < SB_NGRAM_MAX_ORDER; ++it) {
+            if (it < g.lm_order && s != 0) {
+                chain[it] = s;
+                acc[it + 1] = acc[it] + g.lm_backoff[s];
+                s = ngram_state(g, g.lm_fail[s]);
+                d = it + 1;
+            } else {
+                chain[it] = 0;
+                acc[it + 1] = acc[it];
+            }
+        }
+        const double base_acc = acc[SB_NGRAM_MAX_ORDER];        // = acc[d]: the levels behind the chain add nothing
+        for (int k = tid; k < V; k += 256) {
+            const bool isb = k == blank;
+            ng_lp[k] = isb ? 0.0 : base_acc + g.lm_uni_lp[k];
+            ng_nx[k] = isb ? s0 : ngram_state(g, g.lm_uni_next[k]);
+        }
+#pragma unroll
+        for (int j = SB_NGRAM_MAX_ORDER - 1; j >= 0; --j) {
+            if (j >= d) continue;                               // (uniform in the workgroup)
+            __syncthreads();
+            int lo, hi;
+            ngram_row(g, chain[j], lo, hi);
+            const double a = acc[j];
+            for (int i = lo + tid; i < hi; i += 256) {
+                const int k = g.lm_arc_tok[i];
+                if (k < 0 || k >= V || k == blank) continue;    // eos, or a corrupt entry
+                ng_lp[k] = a + g.lm_arc_lp[i];
+                ng_nx[k] = ngram_state(g, g.lm_arc_next[i]);
+            }
+        }
+        __syncthreads();
+    }
     auto score = [&](int v) -> double {
         double c = base + (double)((z[v] - m) - logs);
-        if constexpr (LM) {
+        if constexpr (LM == SB_LM_LSTM) {
             if (v != blank) c = c + __dadd_rn(__dmul_rn(f.lm_w, (double)((zl[v] - ml) - logsl)), f.lm_b);
+        }
+        if constexpr (LM == SB_LM_NGRAM) {
+            if (v != blank) c = __dadd_rn(c, ngram_term(lt->lm_weight, ng_lp[v], lt->lm_bonus));
         }
         if constexpr (ILM) {
             if (v != blank) c = __dsub_rn(c, __dmul_rn(ilm_w, (double)((zi[v] - mi) - logsi)));
@@ -248,19 +324,20 @@ __device__ __forceinline__ void sync_row_topw_body(const SyncPtrs& p, const Sync
         p.c_score[(size_t)r * W + tid] = my_best;
         p.c_k[(size_t)r * W + tid] = my_arg;
         p.c_lp[(size_t)r * W + tid] = my_arg < V ? (z[my_arg] - m) - logs : 0.f;
+        if constexpr (LM == SB_LM_NGRAM) f.ng_next[(size_t)r * W + tid] = my_arg < V ? ng_nx[my_arg] : f.ng_start;
     }
 }
 
 template <bool CACHED>
 __global__ __launch_bounds__(256) void sync_row_topw(SyncPtrs p, const float* __restrict__ logits, int t, int W, int V) {
-    sync_row_topw_body<CACHED, false, false>(p, SyncFuse{}, logits, nullptr, t, W, V, -1);
+    sync_row_topw_body<CACHED, SB_LM_NONE, false>(p, SyncFuse{}, logits, nullptr, t, W, V, -1);
 }
 
 template <bool CACHED, bool LM, bool BIAS>
 __global__ __launch_bounds__(256) void sync_row_topw_fused(SyncPtrs p, SyncFuse f, const float* __restrict__ logits,
                                                            const float* __restrict__ lm_logits, int t, int W, int V,
                                                            int blank) {
-    sync_row_topw_body<CACHED, LM, BIAS>(p, f, logits, lm_logits, t, W, V, blank);
+    sync_row_topw_body<CACHED, LM ? SB_LM_LSTM : SB_LM_NONE, BIAS>(p, f, logits, lm_logits, t, W, V, blank);
 }
 
 template <bool CACHED, bool LM, bool BIAS>
@@ -268,7 +345,17 @@ __global__ __launch_bounds__(256) void sync_row_topw_ilm(SyncPtrs p, SyncFuse f,
                                                          const float* __restrict__ lm_logits,
                                                          const float* __restrict__ ilm_logits, double ilm_w, int t, int W,
                                                          int V, int blank) {
-    sync_row_topw_body<CACHED, LM, BIAS, true>(p, f, logits, lm_logits, t, W, V, blank, ilm_logits, ilm_w);
+    sync_row_topw_body<CACHED, LM ? SB_LM_LSTM : SB_LM_NONE, BIAS, true>(p, f, logits, lm_logits, t, W, V, blank, ilm_logits,
+                                                                         ilm_w);
+}
+
+// the n-gram form, with or without ILME (ilm_logits null / ilm_w unread without); dynamic LDS: 12 V bytes
+template <bool CACHED, bool BIAS, bool ILM>
+__global__ __launch_bounds__(256) void sync_row_topw_ngram(SyncPtrs p, SyncFuse f, NgramTables lt,
+                                                           const float* __restrict__ logits,
+                                                           const float* __restrict__ ilm_logits, double ilm_w, int t, int W,
+                                                           int V, int blank) {
+    sync_row_topw_body<CACHED, SB_LM_NGRAM, BIAS, ILM>(p, f, logits, nullptr, t, W, V, blank, ilm_logits, ilm_w, &lt);
 }
 
 // One workgroup per utterance.  Wave 0, lane j = the j-th kept candidate: a W-way merge of the rows' sorted lists picks
@@ -306,7 +393,10 @@ __device__ __forceinline__ void sb_gather_rows(const int* s_src, const float* __
     }
 }
 
-template <bool STREAM, bool LM, bool BIAS>
+// LM == SB_LM_NGRAM: the row's n-gram state is a small field of wave 0 as the automaton's is - the kept candidate's next
+// state comes from the top-W kernel's ng_next (no table is walked here), a blank child keeps its parent's, the fold
+// carries it as it carries c_st / f_st, rows behind n_new get ng_start.  There are no LM state buffers to gather.
+template <bool STREAM, int LM, bool BIAS>
 __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFuse& f, const float* __restrict__ h_new,
                                                  const float* __restrict__ c_new, const float* __restrict__ lm_h_new,
                                                  const float* __restrict__ lm_c_new, int t, int cur, int W, int B, int L,
@@ -323,7 +413,7 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
                 ((float4*)p.hs[cur ^ 1])[at] = ((const float4*)p.hs[cur])[at];
                 ((float4*)p.cs[cur ^ 1])[at] = ((const float4*)p.cs[cur])[at];
             }
-            if constexpr (LM)
+            if constexpr (LM == SB_LM_LSTM)
                 sb_gather_rows(nullptr, f.lm_hs[cur], f.lm_cs[cur], nullptr, nullptr, f.lm_hs[cur ^ 1], f.lm_cs[cur ^ 1],
                                r0, W, (size_t)B * W, f.lm_L, f.lm_H);
         }
@@ -373,6 +463,8 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
         const int is_blank = k == blank;
         int c_st = 0;
         if constexpr (BIAS) c_st = (is_blank || k < 0 || k >= f.bias_V) ? par_st : bias_goto(f, par_st, k);
+        int c_ng = 0;
+        if constexpr (LM == SB_LM_NGRAM) c_ng = !kept ? f.ng_start : is_blank ? f.ng_st[r0 + sel_i] : f.ng_next[ci];
         const unsigned long long c_hash = is_blank ? par_hash : (par_hash ^ (unsigned long long)(k + 1)) * SB_PRIME;
         const int c_len = is_blank ? par_len : par_len + 1;
         // the other kept candidate with the same sequence, if there is one
@@ -398,6 +490,8 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
         const float f_lp = __shfl(lp, src, 64);
         int f_st = 0;
         if constexpr (BIAS) f_st = __shfl(c_st, src, 64);
+        int f_ng = 0;
+        if constexpr (LM == SB_LM_NGRAM) f_ng = __shfl(c_ng, src, 64);
         const unsigned long long below = (1ull << lane) - 1ull;
         const unsigned long long m_alive = __ballot(alive);
         const unsigned long long m_new = __ballot(alive && !f_blank);
@@ -422,12 +516,14 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
                 p.pred[row] = f_k;
                 s_src[pos] = f_i | 0x100;
             }
-            if constexpr (LM) f.lm_pred[row] = c_len == 0 ? f.lm_bos : (f_blank ? f_tok : f_k);
+            if constexpr (LM == SB_LM_LSTM) f.lm_pred[row] = c_len == 0 ? f.lm_bos : (f_blank ? f_tok : f_k);
+            if constexpr (LM == SB_LM_NGRAM) f.ng_st[row] = f_ng;
             if constexpr (BIAS) f.bias_st[row] = f_st;
         }
         if (lane >= n_new && lane < W) {
             const int row = r0 + lane;
-            if constexpr (LM) f.lm_pred[row] = f.lm_bos;
+            if constexpr (LM == SB_LM_LSTM) f.lm_pred[row] = f.lm_bos;
+            if constexpr (LM == SB_LM_NGRAM) f.ng_st[row] = f.ng_start;
             if constexpr (BIAS) f.bias_st[row] = 0;
             p.logp[row] = -(double)INFINITY;
             p.hash[row] = SB_HASH0;
@@ -460,7 +556,7 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
         ((float4*)hs_n)[dst] = hv;
         ((float4*)cs_n)[dst] = cv;
     }
-    if constexpr (LM)
+    if constexpr (LM == SB_LM_LSTM)
         sb_gather_rows(s_src, f.lm_hs[cur], f.lm_cs[cur], lm_h_new, lm_c_new, f.lm_hs[cur ^ 1], f.lm_cs[cur ^ 1], r0, W,
                        BW, f.lm_L, f.lm_H);
 }
@@ -468,7 +564,7 @@ __device__ __forceinline__ void sync_select_body(const SyncPtrs& p, const SyncFu
 __global__ __launch_bounds__(256) void sync_select(SyncPtrs p, const float* __restrict__ h_new,
                                                    const float* __restrict__ c_new, int t, int cur, int W, int B, int L,
                                                    int H, int NODES, int blank, int bos) {
-    sync_select_body<false, false, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
+    sync_select_body<false, SB_LM_NONE, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
                                           bos, nullptr);
 }
 
@@ -476,11 +572,11 @@ __global__ __launch_bounds__(256) void sync_stream_select(SyncPtrs p, const floa
                                                           const float* __restrict__ c_new, int t, int cur, int W, int B,
                                                           int L, int H, int NODES, int blank, int bos,
                                                           const int32_t* __restrict__ frame0) {
-    sync_select_body<true, false, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
+    sync_select_body<true, SB_LM_NONE, false>(p, SyncFuse{}, h_new, c_new, nullptr, nullptr, t, cur, W, B, L, H, NODES, blank,
                                          bos, frame0);
 }
 
-template <bool STREAM, bool LM, bool BIAS>
+template <bool STREAM, int LM, bool BIAS>
 __global__ __launch_bounds__(256) void sync_select_fused(SyncPtrs p, SyncFuse f, const float* __restrict__ h_new,
                                                          const float* __restrict__ c_new,
                                                          const float* __restrict__ lm_h_new,
@@ -490,12 +586,13 @@ __global__ __launch_bounds__(256) void sync_select_fused(SyncPtrs p, SyncFuse f,
     sync_select_body<STREAM, LM, BIAS>(p, f, h_new, c_new, lm_h_new, lm_c_new, t, cur, W, B, L, H, NODES, blank, bos, frame0);
 }
 
-// the fused forms' part of sync_init: the LM steps on lm_bos, the automaton stands on its root
+// the fused forms' part of sync_init: the LM steps on lm_bos, the automaton stands on its root, the n-gram on `start`
 __global__ void sync_init_fused(SyncFuse f, int BW) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= BW) return;
     if (f.lm_pred) f.lm_pred[r] = f.lm_bos;
     if (f.bias_st) f.bias_st[r] = 0;
+    if (f.ng_st) f.ng_st[r] = f.ng_start;
 }
 
 // Read-out: an utterance's beam ranked by logp descending (ties keep beam order), every path walked root to leaf into
@@ -600,10 +697,10 @@ SearchNet sync_net_of(const edgedict_search_net_t& n, int rows, int W, int NODES
 // 256), so every plain offset holds in every form.  The rows' part - what SyncFuse points at - lives in the offline
 // workspace or in the streams' persistent state; the LM step's buffers are always workspace.
 struct SyncFuseRows {
-    size_t lm_hs0, lm_hs1, lm_cs0, lm_cs1, lm_pred, bias_st, total;
+    size_t lm_hs0, lm_hs1, lm_cs0, lm_cs1, lm_pred, bias_st, ng_st, total;
 };
 SyncFuseRows sync_fuse_rows_layout(size_t base, size_t rows, const edgedict_beam_lm_t* lm,
-                                   const edgedict_beam_bias_t* bias) {
+                                   const edgedict_beam_bias_t* bias, const edgedict_ngram_lm_t* ng) {
     SyncFuseRows a{};
     size_t o = base;
     auto take = [&](size_t bytes) { size_t r = o; o += align256(bytes); return r; };
@@ -616,8 +713,22 @@ SyncFuseRows sync_fuse_rows_layout(size_t base, size_t rows, const edgedict_beam
         a.lm_pred = take(rows * 4);
     }
     if (bias) a.bias_st = take(rows * 4);
+    if (ng) a.ng_st = take(rows * 4);           // (last: every offset of the forms without an n-gram holds)
     a.total = o;
     return a;
+}
+// the n-gram's per-call scratch - the candidates' next states [rows][W] - behind every other part of a workspace
+struct SyncNgramWs {
+    size_t ng_next, total;
+};
+SyncNgramWs sync_ngram_ws_layout(size_t base, size_t rows, size_t W, const edgedict_ngram_lm_t* ng) {
+    SyncNgramWs w{};
+    w.total = base;
+    if (ng) {
+        w.ng_next = base;
+        w.total = base + align256(rows * W * 4);
+    }
+    return w;
 }
 struct SyncFuseStep {
     size_t x, G, Hprev, Y0, Y1, Cst, h_new, c_new, logits, total;
@@ -658,21 +769,50 @@ int sync_layers_check(const edgedict_search_net_t& n, const char* what) {
 bool sync_fuse_dims_ok(const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias, int V) {
     return (!lm || (lm->V == V && lm->L > 0 && lm->E > 0 && lm->H > 0 && lm->H % 4 == 0)) && (!bias || bias->S > 0);
 }
+// An n-gram this search can use (null: none), checked before anything is launched; V / blank < 0: not known to the
+// caller (the streaming reset and state query), the advance checks them.  The size queries call it too: they return 0
+// where it fails, and the message says why.
+int sync_ngram_check(const edgedict_ngram_lm_t* ng, const edgedict_beam_lm_t* lm, int V, int blank, const char* what) {
+    if (!ng) return ED_OK;
+    ED_CHECK_ARG(!lm, "%s: opts->lm and opts->ngram are both set (one LM at a time)", what);
+    if (int rc = ed_ngram_check(ng, what)) return rc;
+    ED_CHECK_ARG(V < 0 || ng->V == V, "%s: the n-gram's vocabulary (V = %d) differs from the transducer's (V = %d)", what,
+                 ng->V, V);
+    ED_CHECK_ARG(blank < 0 || ng->blank == blank, "%s: the n-gram's blank (%d) differs from the transducer's (%d)", what,
+                 ng->blank, blank);
+    ED_CHECK_ARG(std::isfinite(ng->weight) && ng->weight >= 0.0, "%s: the n-gram's weight = %g (must be finite and >= 0)",
+                 what, ng->weight);
+    ED_CHECK_ARG(std::isfinite(ng->length_bonus), "%s: the n-gram's length_bonus = %g is not finite", what,
+                 ng->length_bonus);
+    ED_CHECK_ARG(ng->V <= SB_NGRAM_MAX_V,
+                 "%s: the n-gram's V = %d exceeds %d (the row's image, 12 bytes a symbol, has to fit 64 KiB of LDS)", what,
+                 ng->V, SB_NGRAM_MAX_V);
+    return ED_OK;
+}
 
 // One search call's fusion: the kernels' block, the LM as a network and its step's buffers
 struct SyncFusion {
-    bool lm, bias;
+    bool lm, bias, ngram;       // lm: the LSTM
+    NgramTables lt;
     SyncFuse f;
     LstmNet lm_net;
     StepBufs lmu;
 };
-// rows_base + ra: where the rows' part lives;  ws + wa: the LM step's buffers
+// rows_base + ra: where the rows' part lives;  ws + wa: the LM step's buffers;  ws + na: the n-gram's scratch
 SyncFusion sync_fuse_bind(char* rows_base, const SyncFuseRows& ra, char* ws, const SyncFuseStep* wa,
-                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias) {
+                          const edgedict_beam_lm_t* lm, const edgedict_beam_bias_t* bias,
+                          const edgedict_ngram_lm_t* ng = nullptr, const SyncNgramWs* na = nullptr) {
     SyncFusion u{};
     u.lm = lm != nullptr;
     u.bias = bias != nullptr;
+    u.ngram = ng != nullptr;
     SyncFuse& f = u.f;
+    if (ng) {
+        u.lt = ed_ngram_tables(ng);
+        f.ng_st = at<int32_t>(rows_base, ra.ng_st);
+        f.ng_next = na ? at<int32_t>(ws, na->ng_next) : nullptr;
+        f.ng_start = ng->start;
+    }
     if (lm) {
         f.lm_hs[0] = at<float>(rows_base, ra.lm_hs0); f.lm_hs[1] = at<float>(rows_base, ra.lm_hs1);
         f.lm_cs[0] = at<float>(rows_base, ra.lm_cs0); f.lm_cs[1] = at<float>(rows_base, ra.lm_cs1);
@@ -754,7 +894,8 @@ SyncIlm sync_ilm_bind(char* p, const SyncIlmWs& a, double w, bool fused, size_t 
 }
 
 // The frame's last two launches: the per-row top-W and the select / merge / gather.  fu and il null: the plain kernels.
-// ILME alone has no per-row state: its top-W kernel, then the plain select.
+// ILME alone has no per-row state: its top-W kernel, then the plain select.  An n-gram (fu->ngram; never with fu->lm):
+// sync_row_topw_ngram with 12 V bytes of dynamic LDS, then the select's SB_LM_NGRAM form.
 template <bool STREAM>
 void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u, int t, int cur, int W, int B, int L,
                       int H, int NODES, int V, int blank, int bos, const int32_t* frame0, hipStream_t s,
@@ -769,6 +910,28 @@ void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u
             hipLaunchKernelGGL(sync_select, dim3(B), dim3(256), 0, s, q, u.h_new, u.c_new, t, cur, W, B, L, H, NODES,
                                blank, bos);
     };
+    if (fu && fu->ngram) {      // the n-gram forms: LM kind SB_LM_NGRAM x BIAS x ILM x CACHED, the image in dynamic LDS
+        const size_t lds = (size_t)V * 12;
+        auto go = [&](auto bias_tag, auto ilm_tag) {
+            constexpr bool BIAS = decltype(bias_tag)::value, ILM = decltype(ilm_tag)::value;
+            const float* iz = il ? il->logits : nullptr;
+            const double iw = il ? il->w : 0.0;
+            if (cached)
+                hipLaunchKernelGGL((sync_row_topw_ngram<true, BIAS, ILM>), dim3(BW), dim3(256), lds, s, q, fu->f, fu->lt,
+                                   u.logits, iz, iw, t, W, V, blank);
+            else
+                hipLaunchKernelGGL((sync_row_topw_ngram<false, BIAS, ILM>), dim3(BW), dim3(256), lds, s, q, fu->f, fu->lt,
+                                   u.logits, iz, iw, t, W, V, blank);
+            hipLaunchKernelGGL((sync_select_fused<STREAM, SB_LM_NGRAM, BIAS>), dim3(B), dim3(256), 0, s, q, fu->f, u.h_new,
+                               u.c_new, (const float*)nullptr, (const float*)nullptr, t, cur, W, B, L, H, NODES, blank, bos,
+                               frame0);
+        };
+        if (fu->bias && il) go(std::true_type{}, std::true_type{});
+        else if (fu->bias) go(std::true_type{}, std::false_type{});
+        else if (il) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+        return;
+    }
     if (il) {
         const SyncFuse none{};
         const SyncFuse& f = fu ? fu->f : none;
@@ -821,19 +984,22 @@ void sync_launch_pick(const SyncPtrs& q, const SyncFusion* fu, const StepBufs& u
 
 }  // namespace
 
-// the plain size; an LM / a bias list append their parts behind it, ILME its buffers behind those
+// the plain size; an LM / a bias list / an n-gram append their parts behind it, ILME its buffers behind those, the
+// n-gram's candidate field behind everything
 extern "C" size_t edgedict_sync_beam_workspace_bytes(const edgedict_search_net_t* pn, int B, int T, int W,
                                                      const edgedict_search_opts_t* opts) {
     if (!pn || !search_ptrs_ok(pn, opts)) return 0;
     const edgedict_search_opts_t o = search_opts_of(opts);
     if (!sync_dims_ok(*pn, B, T, W) || !sync_fuse_dims_ok(o.lm, o.bias, pn->V) || !sync_ilm_ok(o.ilm_weight))
         return 0;
+    if (sync_ngram_check(o.ngram, o.lm, pn->V, pn->blank, "sync_beam_workspace_bytes")) return 0;
     const SearchNet net = sync_net_of(*pn, B * W, W, T * W);
     const size_t BW = (size_t)B * W, esz = net.esz;
     const size_t plain = sync_layout(net, B, W, T).total;
     const size_t fuse =
-        sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, esz, net.V, o.lm).total, BW, o.lm, o.bias).total;
-    return sync_ilm_layout(fuse, BW, esz, net.J, net.V, o.ilm_weight != nullptr).total;
+        sync_fuse_rows_layout(sync_fuse_step_layout(plain, BW, esz, net.V, o.lm).total, BW, o.lm, o.bias, o.ngram).total;
+    const size_t ilm = sync_ilm_layout(fuse, BW, esz, net.J, net.V, o.ilm_weight != nullptr).total;
+    return sync_ngram_ws_layout(ilm, BW, W, o.ngram).total;
 }
 
 extern "C" size_t edgedict_sync_beam_result_bytes(int B, int W, int max_tokens) {
@@ -853,6 +1019,7 @@ extern "C" int edgedict_sync_beam_search(const edgedict_search_net_t* pn, const 
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
     const double* ilm_weight = o.ilm_weight;
+    const edgedict_ngram_lm_t* ng = o.ngram;
     ED_CHECK_ARG(pn, "sync_beam_search: null pointer");
     const int BW = B * W, NODES = T * W;
     SearchNet net = sync_net_of(*pn, BW, W, NODES);
@@ -870,6 +1037,7 @@ extern "C" int edgedict_sync_beam_search(const edgedict_search_net_t* pn, const 
     if (int rc = check_lens(lens_host, B, T, "sync_beam_search", &maxlen)) return rc;
     if (int rc = sync_fuse_check(lm, bias, V, "sync_beam_search")) return rc;
     if (int rc = sync_ilm_check(ilm_weight, "sync_beam_search")) return rc;
+    if (int rc = sync_ngram_check(ng, lm, V, blank, "sync_beam_search")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     char* p = (char*)workspace;
     const SyncWs w = sync_layout(net, B, W, T);
@@ -902,10 +1070,14 @@ extern "C" int edgedict_sync_beam_search(const edgedict_search_net_t* pn, const 
     hipLaunchKernelGGL(sync_init, dim3((BW + 255) / 256), dim3(256), 0, s, q, B, W, bos);
     SyncFusion fusion{};
     const SyncFusion* fu = nullptr;
-    if (lm || bias) {
+    const size_t fuse_end =
+        sync_fuse_rows_layout(sync_fuse_step_layout(w.total, BW, net.esz, V, lm).total, BW, lm, bias, ng).total;
+    const size_t ilm_end = sync_ilm_layout(fuse_end, BW, net.esz, J, V, ilm_weight != nullptr).total;
+    if (lm || bias || ng) {
         const SyncFuseStep wa = sync_fuse_step_layout(w.total, BW, net.esz, V, lm);
-        const SyncFuseRows ra = sync_fuse_rows_layout(wa.total, BW, lm, bias);
-        fusion = sync_fuse_bind(p, ra, p, &wa, lm, bias);
+        const SyncFuseRows ra = sync_fuse_rows_layout(wa.total, BW, lm, bias, ng);
+        const SyncNgramWs na = sync_ngram_ws_layout(ilm_end, BW, W, ng);
+        fusion = sync_fuse_bind(p, ra, p, &wa, lm, bias, ng, &na);
         fu = &fusion;
         if (lm) {       // the empty sequence's LM state is zero, in both buffers as the prediction network's
             const size_t lst = (size_t)BW * lm->L * lm->H * 4;
@@ -920,8 +1092,6 @@ extern "C" int edgedict_sync_beam_search(const edgedict_search_net_t* pn, const 
     SyncIlm ilm{};
     const SyncIlm* il = nullptr;
     if (ilm_weight) {
-        const size_t fuse_end =
-            sync_fuse_rows_layout(sync_fuse_step_layout(w.total, BW, net.esz, V, lm).total, BW, lm, bias).total;
         const SyncIlmWs ia = sync_ilm_layout(fuse_end, BW, net.esz, J, V, true);
         ilm = sync_ilm_bind(p, ia, *ilm_weight, fused, BW, V, u);
         il = &ilm;
@@ -1096,6 +1266,7 @@ __global__ __launch_bounds__(256) void sync_stream_reset_fused_kernel(SyncFuse f
     if (tid < W) {
         if (f.lm_pred) f.lm_pred[r0 + tid] = f.lm_bos;
         if (f.bias_st) f.bias_st[r0 + tid] = 0;
+        if (f.ng_st) f.ng_st[r0 + tid] = f.ng_start;
     }
     if (!f.lm_pred) return;
     const int H4 = f.lm_H / 4, LH4 = f.lm_L * H4;
@@ -1217,7 +1388,9 @@ extern "C" size_t edgedict_sync_stream_state_bytes(const edgedict_search_opts_t*
     if (!search_ptrs_ok(nullptr, opts)) return 0;
     const edgedict_search_opts_t o = search_opts_of(opts);
     if (!sync_stream_dims_ok(S, L, H, W, node_capacity) || !sync_fuse_dims_ok(o.lm, o.bias, o.lm ? o.lm->V : 0)) return 0;
-    return sync_fuse_rows_layout(sync_stream_state_layout(S, W, L, H, node_capacity).total, (size_t)S * W, o.lm, o.bias)
+    if (sync_ngram_check(o.ngram, o.lm, -1, -1, "sync_stream_state_bytes")) return 0;
+    return sync_fuse_rows_layout(sync_stream_state_layout(S, W, L, H, node_capacity).total, (size_t)S * W, o.lm, o.bias,
+                                 o.ngram)
         .total;
 }
 
@@ -1229,12 +1402,14 @@ extern "C" size_t edgedict_sync_stream_workspace_bytes(const edgedict_search_net
     if (!sync_stream_dims_ok(S, pn->L, pn->H, W, node_capacity) || !sync_dims_ok(*pn, S, 1, W) ||
         !sync_fuse_dims_ok(o.lm, o.bias, pn->V) || !sync_ilm_ok(o.ilm_weight))
         return 0;
+    if (sync_ngram_check(o.ngram, o.lm, pn->V, pn->blank, "sync_stream_workspace_bytes")) return 0;
     const SearchNet net = sync_net_of(*pn, S * W, W, node_capacity);
     const size_t SW = (size_t)S * W, esz = net.esz;
     const size_t plain = sync_stream_ws_layout(net, S, W, node_capacity).total;
-    return sync_ilm_layout(sync_fuse_step_layout(plain, SW, esz, net.V, o.lm).total, SW, esz, net.J, net.V,
-                           o.ilm_weight != nullptr)
-        .total;
+    const size_t ilm = sync_ilm_layout(sync_fuse_step_layout(plain, SW, esz, net.V, o.lm).total, SW, esz, net.J, net.V,
+                                       o.ilm_weight != nullptr)
+                           .total;
+    return sync_ngram_ws_layout(ilm, SW, W, o.ngram).total;
 }
 
 extern "C" size_t edgedict_sync_stream_result_bytes(int S, int W, int max_tokens) {
@@ -1260,10 +1435,12 @@ extern "C" int edgedict_sync_stream_reset(const edgedict_search_opts_t* opts, in
     const edgedict_search_opts_t o = search_opts_of(opts);
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
+    const edgedict_ngram_lm_t* ng = o.ngram;
     SYNC_STREAM_CHECK_SHAPE("sync_stream_reset", S, L, H, W, node_capacity);
     ED_CHECK_ARG(bos >= 0, "sync_stream_reset: bos = %d outside the vocabulary", bos);
     ED_CHECK_ARG(state, "sync_stream_reset: null pointer (state)");
     if (int rc = sync_fuse_check(lm, bias, lm ? lm->V : (bias ? bias->V : 0), "sync_stream_reset")) return rc;
+    if (int rc = sync_ngram_check(ng, lm, -1, -1, "sync_stream_reset")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     char* st = (char*)state;
     const SyncStreamState a = sync_stream_state_layout(S, W, L, H, node_capacity);
@@ -1271,12 +1448,14 @@ extern "C" int edgedict_sync_stream_reset(const edgedict_search_opts_t* opts, in
     int32_t* frames_done = at<int32_t>(st, a.frames_done);
     long long* n_committed = at<long long>(st, a.n_committed);
     SyncFusion fusion{};
-    if (lm || bias)
-        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, (size_t)S * W, lm, bias), nullptr, nullptr, lm, bias);
+    const bool any_fused = lm || bias || ng;
+    if (any_fused)
+        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, (size_t)S * W, lm, bias, ng), nullptr, nullptr, lm, bias,
+                                ng);
     if (!mask || !mask_on_host) {
         hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(S), dim3(256), 0, s, q, frames_done, n_committed, mask, 0, S, W,
                            L, H, bos);
-        if (lm || bias)
+        if (any_fused)
             hipLaunchKernelGGL(sync_stream_reset_fused_kernel, dim3(S), dim3(256), 0, s, fusion.f, mask, 0, S, W);
     } else {            // host mask: one launch per run of selected streams
         for (int b = 0; b < S;) {
@@ -1285,7 +1464,7 @@ extern "C" int edgedict_sync_stream_reset(const edgedict_search_opts_t* opts, in
             while (e < S && mask[e]) ++e;
             hipLaunchKernelGGL(sync_stream_reset_kernel, dim3(e - b), dim3(256), 0, s, q, frames_done, n_committed,
                                (const int32_t*)nullptr, b, S, W, L, H, bos);
-            if (lm || bias)
+            if (any_fused)
                 hipLaunchKernelGGL(sync_stream_reset_fused_kernel, dim3(e - b), dim3(256), 0, s, fusion.f,
                                    (const int32_t*)nullptr, b, S, W);
             b = e;
@@ -1307,6 +1486,7 @@ extern "C" int edgedict_sync_stream_advance(const edgedict_search_net_t* pn, con
     const edgedict_beam_lm_t* lm = o.lm;
     const edgedict_beam_bias_t* bias = o.bias;
     const double* ilm_weight = o.ilm_weight;
+    const edgedict_ngram_lm_t* ng = o.ngram;
     ED_CHECK_ARG(pn, "sync_stream_advance: null pointer");
     const int SW = S * W;
     SearchNet net = sync_net_of(*pn, SW, W, NC);
@@ -1336,6 +1516,7 @@ extern "C" int edgedict_sync_stream_advance(const edgedict_search_net_t* pn, con
                  max_commit, cols);
     if (int rc = sync_fuse_check(lm, bias, V, "sync_stream_advance")) return rc;
     if (int rc = sync_ilm_check(ilm_weight, "sync_stream_advance")) return rc;
+    if (int rc = sync_ngram_check(ng, lm, V, blank, "sync_stream_advance")) return rc;
     hipStream_t s = (hipStream_t)stream_;
     char* p = (char*)workspace;
     char* st = (char*)state;
@@ -1352,9 +1533,11 @@ extern "C" int edgedict_sync_stream_advance(const edgedict_search_net_t* pn, con
     int32_t* frames_done = at<int32_t>(st, a.frames_done);
     SyncFusion fusion{};
     const SyncFusion* fu = nullptr;
-    if (lm || bias) {
+    if (lm || bias || ng) {
         const SyncFuseStep wa = sync_fuse_step_layout(w.total, SW, net.esz, V, lm);
-        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, SW, lm, bias), p, &wa, lm, bias);
+        const SyncNgramWs na =
+            sync_ngram_ws_layout(sync_ilm_layout(wa.total, SW, net.esz, J, V, ilm_weight != nullptr).total, SW, W, ng);
+        fusion = sync_fuse_bind(st, sync_fuse_rows_layout(a.total, SW, lm, bias, ng), p, &wa, lm, bias, ng, &na);
         fu = &fusion;
     }
 

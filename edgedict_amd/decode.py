@@ -41,7 +41,8 @@ plain kernels).  See ``edgedict_amd.bias``.
 ``ctc_beam_search`` is the first pass from the encoder alone: a CTC prefix beam search on the CTC head's logits
 (``Transducer(ctc_weight > 0)``; csrc/ctc_decode.hip), all frames inside one launch, returning ranked ``NBestResult``
 lists; it takes ``bias=`` too, and ``lm=`` - there an ``edgedict_amd.ngram.NGramLM``, a back-off n-gram in device
-tables read inside the walk (``lm_weight``, ``length_bonus``), not an ``LMModel``.  ``lm_rescore`` re-ranks any
+tables read inside the walk (``lm_weight``, ``length_bonus``), not an ``LMModel``.  The frame-synchronous search
+(``sync_beam_search*``) takes either kind as ``lm=``; the best-first ``beam_search*`` take an ``LMModel`` only.  ``lm_rescore`` re-ranks any
 search's ``NBestResult`` lists with such an n-gram (``NBestResult.lm_logp``; csrc/ngram.hip).
 
 ``sync_beam_search`` (``_nbest``, ``_enc``, ``_rows``) is a SECOND RNN-T beam search, frame-synchronous (at most one
@@ -294,7 +295,8 @@ class SearchNetStruct(ctypes.Structure):
 
 class SearchOpts(ctypes.Structure):
     """ctypes mirror of ``edgedict_search_opts_t`` (include/edgedict_hip.h)."""
-    _fields_ = [("lm", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("ilm_weight", ctypes.c_void_p)]
+    _fields_ = [("lm", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("ilm_weight", ctypes.c_void_p),
+                ("ngram", ctypes.c_void_p)]
 
 
 class _SearchNet:
@@ -353,17 +355,32 @@ class _SearchNet:
                 _ptr_array(self.b_hh), self.H, _lib.ptr(self.wpc), _lib.ptr(self.bp))
 
 
-def _opts(flm=None, bref=None, ilm=None):
+def _opts(flm=None, bref=None, ilm=None, ng=None):
     """``const edgedict_search_opts_t*`` of a native call: the fusion LM ``flm`` (``FusionLM``), the bias list ``bref``
-    (``ContextGraph.ref``), the ILME weight ``ilm`` (a ``c_double``).  None - a null pointer, the plain search - when
-    all three are absent.  The pointer keeps what it names alive."""
-    if flm is None and bref is None and ilm is None:
+    (``ContextGraph.ref``), the ILME weight ``ilm`` (a ``c_double``), the n-gram ``ng`` (an ``NGramStruct``:
+    ``NGramLM.struct(device, weight, bonus)``).  None - a null pointer, the plain search - when all four are absent.
+    The pointer keeps what it names alive."""
+    if flm is None and bref is None and ilm is None and ng is None:
         return None
     o = SearchOpts(lm=None if flm is None else ctypes.addressof(flm.struct),
                    bias=None if bref is None else ctypes.addressof(bref._obj),
-                   ilm_weight=None if ilm is None else ctypes.addressof(ilm))
-    o.keep = (flm, bref, ilm)
+                   ilm_weight=None if ilm is None else ctypes.addressof(ilm),
+                   ngram=None if ng is None else ctypes.addressof(ng))
+    o.keep = (flm, bref, ilm, ng)
     return ctypes.pointer(o)
+
+
+def _sync_lm_opts(lm, cd, device, lm_weight, length_bonus, lm_bos):
+    """``(flm, ng)`` of ``_opts`` for the ``lm=`` of a frame-synchronous search: an ``LMModel`` becomes a ``FusionLM``,
+    an ``NGramLM`` its ``NGramStruct`` on ``device`` (``lm_bos`` is not read with an n-gram: the empty sequence stands
+    on the table's ``start``)."""
+    from .lm import FusionLM
+    from .ngram import NGramLM
+    if lm is None:
+        return None, None
+    if isinstance(lm, NGramLM):
+        return None, lm.struct(device, lm_weight, length_bonus)
+    return FusionLM(lm, cd, lm_weight, length_bonus, lm_bos), None
 
 
 def joint_rows(model, enc_out):
@@ -752,11 +769,21 @@ def _check_sync_width(W):
         raise ValueError("sync_beam_search: beam width W = %r outside [1, %d]" % (W, SYNC_BEAM_MAX_W))
 
 
-def _check_sync_fusion(model, lm, lm_weight, bias):
-    """The fusion argument rules of the ``sync_beam_search*`` entry points (raised before anything is launched)."""
+def _check_sync_fusion(model, lm, lm_weight, bias, length_bonus=0.0):
+    """The fusion argument rules of the ``sync_beam_search*`` entry points (raised before anything is launched).  ``lm``
+    is an ``LMModel`` (``check_fusion_args``) or an ``NGramLM`` (``ngram.check_ngram_args``: a finite ``lm_weight >= 0``,
+    a finite ``length_bonus``, the transducer's vocabulary and blank, at most ``SYNC_NGRAM_MAX_V`` symbols)."""
     from .bias import check_bias_args
-    from .lm import check_fusion_args
-    check_fusion_args(lm, lm_weight, _vocab(model), False)
+    from .lm import LMModel, check_fusion_args
+    from .ngram import SYNC_NGRAM_MAX_V, NGramLM, check_ngram_args
+    if isinstance(lm, NGramLM):
+        check_ngram_args(lm, lm_weight, length_bonus, _vocab(model), int(model.blank), "the transducer's",
+                         SYNC_NGRAM_MAX_V)
+    elif lm is not None and not isinstance(lm, LMModel):
+        raise ValueError("lm must be an edgedict_amd.lm.LMModel or an edgedict_amd.ngram.NGramLM (got %s)"
+                         % type(lm).__name__)
+    else:
+        check_fusion_args(lm, lm_weight, _vocab(model), False)
     check_bias_args(bias, _vocab(model), False)
 
 
@@ -882,6 +909,16 @@ def sync_beam_search_fusion(model, xs, xlen=None, W=10, *, lm=None, lm_weight=No
     ``skip_blank``: a threshold in (0, 1] - the search then runs only on the encoder frames whose CTC blank posterior
     is at most the threshold (``skip_blank_frames``; the model needs a CTC head).  None: nothing of this runs.
 
+    ``lm`` may also be an ``edgedict_amd.ngram.NGramLM``, a back-off n-gram in device tables (one LM at a time; the type
+    dispatches).  A row then carries one integer n-gram state - the state AFTER its tokens, the table's ``start`` (the
+    context ``(BOS)``) for the empty sequence; ``lm_bos`` is not read - and the LM term of a non-blank candidate is
+    ``lm_weight * step(s_i, k) + length_bonus`` in fp64, bit-equal to ``NGramLM.step`` on the host.  No LM step runs: the
+    per-row top-W kernel builds the row's n-gram image in LDS, so a frame keeps the plain search's launches.  Rules
+    (``ngram.check_ngram_args``, ``ValueError`` before anything is launched): ``lm_weight`` required, finite and
+    ``>= 0``; ``length_bonus`` finite; the n-gram's vocabulary and blank equal to the transducer's; at most
+    ``ngram.SYNC_NGRAM_MAX_V`` = 5376 symbols (the image has to fit 64 KiB of LDS).  ``NBestResult.lm_logp`` is not
+    filled by the search (``lm_rescore`` does that).
+
     ``ilm_weight``: internal-LM estimation (ILME; a finite number ``>= 0``, with or without ``lm`` / ``bias``).  The
     transducer's prediction network and joint hold a language model of the training transcripts; its log-probabilities
     ``lp_ilm_i`` - the log-softmax over the NON-BLANK symbols of the joint evaluated on an all-zero encoder row - are
@@ -910,7 +947,7 @@ def sync_beam_search_nbest(model, xs, xlen=None, W=10, *, lm=None, lm_weight=Non
     then goes through ``ctc_rescore`` (the module-level function; on the unskipped encoder output) before it is
     returned: ``ctc_logp`` filled, ``logp`` the combined score, ranked by it.  None: nothing of this runs.
     ``ilm_weight``: internal-LM estimation, as in ``sync_beam_search_fusion``."""
-    _check_sync_fusion(model, lm, lm_weight, bias)
+    _check_sync_fusion(model, lm, lm_weight, bias, length_bonus)
     _check_ilm_weight(ilm_weight)
     if skip_blank is not None:
         _check_skip(model, skip_blank)
@@ -941,7 +978,7 @@ def sync_beam_search_nbest_enc(model, enc_out, lens=None, W=10, *, lm=None, lm_w
                                bias=None, ctc_rescore=None, ilm_weight=None):
     """``sync_beam_search_nbest`` over a given encoder output, as ``sync_beam_search_enc``.  ``ctc_rescore``: as there,
     the head scoring this ``enc_out``."""
-    _check_sync_fusion(model, lm, lm_weight, bias)
+    _check_sync_fusion(model, lm, lm_weight, bias, length_bonus)
     _check_ilm_weight(ilm_weight)
     _check_sync_width(W)
     if ctc_rescore is not None:
@@ -969,8 +1006,7 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     """``sync_beam_search_nbest_enc`` from the joint's encoder rows, as ``sync_beam_search_rows``.  ``max_tokens``
     bounds a hypothesis' length (default T: one token per frame at most); a longer one raises, it is never cut."""
     from .bias import active
-    from .lm import FusionLM
-    _check_sync_fusion(model, lm, lm_weight, bias)
+    _check_sync_fusion(model, lm, lm_weight, bias, length_bonus)
     ilm = _check_ilm_weight(ilm_weight)
     _check_sync_width(W)
     _lib.require_cuda(E1)
@@ -985,9 +1021,9 @@ def sync_beam_search_nbest_rows(model, E1, B, T, P, lens=None, W=10, max_tokens=
     lib = _lib.load()
     MT = T if max_tokens is None else int(max_tokens)
     dev = E1.device
-    flm = FusionLM(lm, cd, lm_weight, length_bonus, lm_bos) if lm is not None else None
+    flm, ng = _sync_lm_opts(lm, cd, dev, lm_weight, length_bonus, lm_bos)
     bref = active(bias).ref(dev) if active(bias) is not None else None
-    nref, opts = net.ref(P), _opts(flm, bref, ilm)          # (no feature: a null opts, the plain search)
+    nref, opts = net.ref(P), _opts(flm, bref, ilm, ng)      # (no feature: a null opts, the plain search)
     nbytes = lib.edgedict_sync_beam_workspace_bytes(nref, B, T, W, opts)
     if opts is not None and nbytes == 0:
         raise ValueError("sync_beam_search: shapes out of range (the LM's hidden width must be a multiple of 4)")
@@ -1371,7 +1407,7 @@ class StreamingSyncBeamSearch:
     def _setup(self, model, n_streams, W, node_capacity, lm=None, lm_weight=None, length_bonus=0.0, lm_bos=1, bias=None,
                ilm_weight=None):
         from .bias import active
-        _check_sync_fusion(model, lm, lm_weight, bias)
+        _check_sync_fusion(model, lm, lm_weight, bias, length_bonus)
         self._ilm = _check_ilm_weight(ilm_weight)       # None, or the weight as the c_double the advance points at
         _check_sync_width(W)
         if n_streams < 1:
@@ -1408,9 +1444,8 @@ class StreamingSyncBeamSearch:
 
     def _opts(self):
         """The ``opts`` of this search's native calls (None: the plain search)."""
-        from .lm import FusionLM
-        return _opts(None if self.lm is None else FusionLM(self.lm, self.cd, *self._lm_args),
-                     None if self.bias is None else self.bias.ref(self.device), self._ilm)
+        flm, ng = _sync_lm_opts(self.lm, self.cd, self.device, *self._lm_args)
+        return _opts(flm, None if self.bias is None else self.bias.ref(self.device), self._ilm, ng)
 
     def _alloc(self):
         """The persistent state and the workspace, sized for the current forms (LM, bias list)."""
@@ -1609,6 +1644,11 @@ class StreamingSyncFusionBeamSearch(StreamingSyncBeamSearch):
     (``len`` counts committed tokens too).  The bias list is shared by all streams; ``set_bias`` swaps it between
     utterances.  Without an LM and without a list (or with an empty one) the plain kernels run until ``set_bias`` gives
     the search a list.  With an LM a frame is ``6 + L + lm.nlayers + 1`` launches on the fused steps.
+
+    ``lm`` may be an ``edgedict_amd.ngram.NGramLM`` instead (``sync_beam_search_fusion`` states the score and the
+    rules): the rows' n-gram states (one int32 each) live in the persistent state behind the fused rows' part, ``reset``
+    puts them back on the table's ``start``, compaction does not touch them, and a frame is the plain search's
+    ``6 + L`` launches.  ``lm_bos`` is not read with an n-gram.
 
     ``ilm_weight``: internal-LM estimation as in ``sync_beam_search_fusion``, with or without ``lm`` / ``bias``;
     ``nbest()`` is then bit for bit ``sync_beam_search_nbest_rows(..., ilm_weight=)``.  It carries no per-row state: the

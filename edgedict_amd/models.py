@@ -1458,8 +1458,9 @@ class Transducer(nn.Module):
         """Frame-synchronous beam search (one symbol per frame at most, all B x W hypotheses in one step per frame,
         equal sequences merged by log-add; ``1 <= W <= 32``): a different algorithm from ``beam_search``, several times
         fewer launches.  ``lm`` / ``lm_weight`` / ``length_bonus`` / ``lm_bos`` / ``bias``: LM shallow fusion and
-        contextual biasing, as ``beam_search`` takes them; ``skip_blank``: blank-frame skipping, as there.
-        ``ilm_weight`` (a finite number ``>= 0``): internal-LM estimation - the model's own prior over the non-blank
+        contextual biasing, as ``beam_search`` takes them; ``skip_blank``: blank-frame skipping, as there.  Here ``lm``
+        may also be an ``edgedict_amd.ngram.NGramLM`` (a back-off n-gram read inside the top-W kernel: no LM step per
+        frame, ``lm_bos`` not read).  ``ilm_weight`` (a finite number ``>= 0``): internal-LM estimation - the model's own prior over the non-blank
         symbols (``ilm_score``) is subtracted with this weight.  Returns ``(seqs, scores)`` in ``beam_search``'s types.
         See ``decode.sync_beam_search_fusion``."""
         from .decode import sync_beam_search_fusion

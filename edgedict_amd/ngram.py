@@ -3,7 +3,9 @@ LSTM ``lm.LMModel``), held in a few device tables and cheap enough to be read in
 
 ``NGramLM`` builds the model on the host (plain Python / numpy) from an ARPA file (``from_arpa``) or from token lists
 (``train``) and uploads it once per device, as ``bias.ContextGraph`` does its automaton.  The CTC prefix beam search
-reads it (``loss.ctc_prefix_beam(..., lm=, lm_weight=, length_bonus=)``, csrc/ctc_decode.hip); csrc/ngram.hip scores
+reads it (``loss.ctc_prefix_beam(..., lm=, lm_weight=, length_bonus=)``, csrc/ctc_decode.hip), and so does the
+frame-synchronous RNN-T search (``decode.sync_beam_search*(lm=)`` and its streaming forms, csrc/decode_sync.hip: a
+row's image of ``step(s, .)`` / ``next(s, .)`` in LDS, vocabularies up to ``SYNC_NGRAM_MAX_V``); csrc/ngram.hip scores
 sentences (``score_nbest`` / ``score_lists``, ``decode.lm_rescore``) and writes dense per-state rows (``logprobs``).
 
 Symbols and states
@@ -42,6 +44,9 @@ from .tokenizer import BOS, NUL
 
 LN10 = math.log(10.0)
 MAX_ORDER = 6
+# the largest vocabulary the frame-synchronous search takes an n-gram for: a row's image (12 bytes a symbol) has to fit
+# the 64 KiB of LDS a launch gets (SB_NGRAM_MAX_V of csrc/decode_sync.hip)
+SYNC_NGRAM_MAX_V = 5376
 
 
 class NGramStruct(ctypes.Structure):
@@ -445,8 +450,10 @@ class NGramLM:
         return [total[b, :len(seqs)].copy() for b, seqs in enumerate(lists)]
 
 
-def check_ngram_args(lm, lm_weight, length_bonus, V=None, blank=None):
-    """The argument rules of ``lm=`` on the CTC prefix search (raised before anything is launched)."""
+def check_ngram_args(lm, lm_weight, length_bonus, V=None, blank=None, owner="the head's", max_V=None):
+    """The argument rules of ``lm=`` on the CTC prefix search, and - with ``owner="the transducer's"`` and
+    ``max_V=SYNC_NGRAM_MAX_V`` - of an ``NGramLM`` on the frame-synchronous search (raised before anything is
+    launched)."""
     if lm is None:
         if lm_weight is not None:
             raise ValueError("lm_weight without lm")
@@ -462,6 +469,9 @@ def check_ngram_args(lm, lm_weight, length_bonus, V=None, blank=None):
     if not np.isfinite(lb):
         raise ValueError("length_bonus must be finite (got %r)" % length_bonus)
     if V is not None and lm.V != V:
-        raise ValueError("the n-gram's vocabulary (vocab_size = %d) differs from the head's (V = %d)" % (lm.V, V))
+        raise ValueError("the n-gram's vocabulary (vocab_size = %d) differs from %s (V = %d)" % (lm.V, owner, V))
     if blank is not None and lm.blank != blank:
         raise ValueError("the n-gram's blank (%d) differs from the search's (%d)" % (lm.blank, blank))
+    if max_V is not None and lm.V > max_V:
+        raise ValueError("the n-gram's vocabulary (vocab_size = %d) exceeds %d: the search keeps a row's n-gram image "
+                         "(12 bytes a symbol) in 64 KiB of LDS" % (lm.V, max_V))

@@ -452,7 +452,8 @@ class BatchedStreamSyncFusionBeamDecoder(BatchedStreamSyncBeamDecoder):
     and ``bias`` (a contextual-biasing list, ``edgedict_amd.bias.ContextGraph``), as in
     ``decode.StreamingSyncFusionBeamSearch``; ``self.search.set_bias`` swaps the list between utterances.  After any
     chunk ``nbest()`` is what the offline fused search over the stream's audio so far returns.  ``ilm_weight``:
-    internal-LM estimation, as in ``decode.sync_beam_search_fusion``."""
+    internal-LM estimation, as in ``decode.sync_beam_search_fusion``.  ``lm`` is an ``LMModel`` or an
+    ``edgedict_amd.ngram.NGramLM`` (no LM step per frame; ``lm_bos`` is then not read)."""
 
     def __init__(self, transducer, flags, n_streams, W=10, node_capacity=None, dither=None, *, lm=None, lm_weight=None,
                  length_bonus=0.0, lm_bos=1, bias=None, ilm_weight=None):

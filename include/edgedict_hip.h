@@ -836,7 +836,12 @@ int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, int T, int 
  *   edgedict_search_opts_t  lm: LM shallow fusion, bias: contextual biasing, ilm_weight (a HOST double): internal-LM
  *                           estimation - each specified in its own block below.  A null member switches its feature off,
  *                           a null opts pointer is all members null: the plain search, launch for launch and bit for bit.
- *                           The expansion searches (edgedict_beam_*) refuse ilm_weight before they touch the device
+ *                           ngram: a back-off n-gram LM (edgedict_ngram_lm_t below) fused into the frame-synchronous
+ *                           search, specified in that search's block; lm and ngram both non-null is an argument error
+ *                           (one LM at a time).  The expansion searches (edgedict_beam_*) refuse ilm_weight and ngram
+ *                           before they touch the device.  The struct GREW AT ITS END (ngram, 24 -> 32 bytes) without a
+ *                           new ABI version: every member is read, so a caller must pass the struct of this header -
+ *                           a binding checks edgedict_search_struct_bytes(1) == 32
  * A descriptor leads every argument list: net where the function needs the network (opts then stands in front of the
  * trailing buffers), opts where it does not.  A non-null net / opts below address 4096 - the integer a caller written
  * for ABI version 1 passes in that place - is an argument error (size queries: 0), never dereferenced.
@@ -845,6 +850,7 @@ int edgedict_stream_encoder_step(const void* xs, int x_dtype, int B, int T, int 
  */
 struct edgedict_beam_lm_t;
 struct edgedict_beam_bias_t;
+struct edgedict_ngram_lm_t;
 typedef struct edgedict_search_net_t {
     int dtype;
     int J;
@@ -870,6 +876,7 @@ typedef struct edgedict_search_opts_t {
     const struct edgedict_beam_lm_t* lm;
     const struct edgedict_beam_bias_t* bias;
     const double* ilm_weight;
+    const struct edgedict_ngram_lm_t* ngram;
 } edgedict_search_opts_t;
 size_t edgedict_search_struct_bytes(int which);
 
@@ -1522,6 +1529,39 @@ int edgedict_ilm_logits(int dtype, const void* dec, int R, int P2, int J, const 
                         float* logits, void* workspace, void* stream);
 int edgedict_ilm_logprobs(const float* logits, const int32_t* targets, const int32_t* ylen, int B, int U, int V,
                           int blank, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The back-off n-gram LM in the frame-synchronous search, offline and streaming: opts->ngram (an edgedict_ngram_lm_t,
+ * above; null: the calls without it, same kernels, same layouts, same bits) of the edgedict_sync_* entry points.
+ * opts->lm and opts->ngram both non-null is an argument error: one LM at a time.  bias and ilm_weight combine with it.
+ *
+ * A row carries ONE int32 n-gram state s: the state AFTER its token sequence (the phrase automaton's convention, not
+ * the LSTM's); the empty sequence stands on ngram->start, the context (BOS).  A non-blank candidate scores, in fp64
+ * without contraction and in this order,
+ *   c = logp_i + (double)lp_i[k];  c = c + (weight * step(s_i, k) + length_bonus);
+ *   c = c - ilm_weight * (double)lp_ilm_i[k];  c = c + (held[goto(a_i, k)] - pend[a_i])
+ * (a term is absent when its feature is), step(s, k) the fp64 value of the chain of additions stated with
+ * edgedict_ngram_lm_t - never rounded through fp32, so the n-gram term is the host's bit for bit.  Blank keeps
+ * logp_i + lp_i[blank]; token_logp stays lp_i[k].  A token child takes next(s_i, k), a blank child or a folded pair the
+ * parent's state, a row left without a hypothesis `start`.  weight = length_bonus = 0 is bit-equal to the plain search
+ * (every table value finite).
+ *
+ * No launch and no [B W, V] buffer more per frame: the per-row top-W kernel builds the row's image (step(s_i, .) fp64 [V]
+ * and next(s_i, .) int32 [V], 12 bytes a symbol) in dynamic LDS from the back-off chain of s_i - the unigram level first,
+ * then every longer context's arcs over it, a barrier between levels - and writes, beside a kept candidate's score and
+ * token, its next state (int32 [B W][W], workspace); the select kernel reads that and keeps a per-row ng_st [B W].
+ * V <= 5376: the image and the kernel's static LDS fit the 64 KiB a launch gets.
+ *
+ *   sync_beam_workspace_bytes            the size without it + ng_st [B W] behind the fused rows' part + the candidates'
+ *                                        next states [B W][W] behind everything else
+ *   sync_stream_state_bytes              ng_st [S W] APPENDED behind the fused rows' part: every other offset holds
+ *   sync_stream_workspace_bytes          the size without it + the candidates' next states
+ *   sync_stream_reset                    the selected streams' rows back on `start`
+ * Checked before anything is launched (-1 and a message that the entry point's name leads; size queries: 0, and the
+ * reason is left in edgedict_last_error): the rules of edgedict_ngram_logprobs for the struct, ngram->V == V and
+ * ngram->blank == blank (the reset and the state query know neither: the advance checks), weight finite and >= 0,
+ * length_bonus finite, V <= 5376, lm and ngram not both set.  lm->bos has no counterpart: nothing but `start` is read.
+ */
 
 #ifdef __cplusplus
 }
