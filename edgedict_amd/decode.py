@@ -1659,6 +1659,261 @@ class StreamingSyncFusionBeamSearch(StreamingSyncBeamSearch):
         self._setup(model, n_streams, W, node_capacity, lm, lm_weight, length_bonus, lm_bos, bias, ilm_weight)
 
 
+class StreamingCTCBeamSearch:
+    """The CTC prefix beam search of ``loss.ctc_prefix_beam`` for S streams whose head logits arrive chunk by chunk
+    (csrc/ctc_decode.hip, ``edgedict_ctc_stream_*``).  It works on raw head logits ``[S, Tc, V]`` and needs no model.
+
+    Every stream's beam - up to W ranked prefixes with ``pb`` / ``pnb``, bias total, LM total, token-tree node, automaton
+    state and n-gram state - lives in a persistent device state, so after any number of advances ``nbest()`` is bit for
+    bit what ``ctc_prefix_beam`` (same ``W``, ``cand``, ``blank``, ``bias``, ``lm`` keywords) returns for the stream's
+    frames since its reset: tokens, frames, ``token_logp`` and ``logp`` alike.  An advance is three launches whatever
+    the chunk's length - the offline row pass on the chunk, one walk launch with one wave per stream that loads the beam,
+    runs all of the chunk's frames and stores it, one compaction launch - and ONE device-to-host read, for the commits.
+
+    The compaction commits the tokens from the tree's root down to the lowest common ancestor of the live prefixes' nodes
+    (no later frame can change them; they move to a host-side log with their frames and log-probs), makes that ancestor
+    the root and renumbers the nodes a live prefix still reaches densely, so the device tree stays bounded by
+    ``node_capacity`` however long a stream runs.  A prefix that is in the beam is never cut away by its child: the
+    ancestor of a set that holds both is the parent or above.
+
+    ``node_capacity`` (NC): token-tree nodes per stream, default ``32 * W + 1024`` as ``StreamingSyncBeamSearch``.  An
+    advance adds at most ``n_frames[s] * W`` nodes, so one with ``live[s] + n_frames[s] * W > NC`` (``live_nodes()``: 1
+    after a reset) raises ``RuntimeError`` before anything is launched and leaves the state as it was.
+
+    ``W`` in 1 .. 32, ``cand`` in 1 .. 64 (default ``min(V - 1, 32)``), ``bias`` a ``ContextGraph``, ``lm`` an
+    ``edgedict_amd.ngram.NGramLM`` with ``lm_weight`` (an LSTM ``LMModel`` raises ``TypeError``) and ``length_bonus``:
+    ``ctc_prefix_beam``'s rules, raised before anything is launched.  No ``skip_blank``, no rescoring inside the stream,
+    no end-of-sentence term.  A stream with no frames since its reset holds the empty hypothesis with ``logp`` 0."""
+
+    _EMPTY = (np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64))
+
+    def __init__(self, n_streams, V, W=10, cand=None, blank=0, node_capacity=None, *, bias=None, lm=None, lm_weight=None,
+                 length_bonus=0.0):
+        from .bias import active, check_bias_args
+        from .loss import CTC_BEAM_MAX_CAND, CTC_BEAM_MAX_W
+        from .ngram import check_ngram_args
+        S, V, W, blank = int(n_streams), int(V), int(W), int(blank)
+        if S < 1:
+            raise ValueError("n_streams must be >= 1")
+        if V < 2:
+            raise ValueError("V = %d: need at least the blank and one symbol" % V)
+        if not 0 <= blank < V:
+            raise ValueError("blank %d outside [0, %d)" % (blank, V))
+        if not 1 <= W <= CTC_BEAM_MAX_W:
+            raise ValueError("W = %d outside [1, %d]" % (W, CTC_BEAM_MAX_W))
+        cand = min(V - 1, 32) if cand is None else int(cand)
+        if not 1 <= cand <= CTC_BEAM_MAX_CAND:
+            raise ValueError("cand = %d outside [1, %d]" % (cand, CTC_BEAM_MAX_CAND))
+        NC = int(node_capacity) if node_capacity else 32 * W + 1024
+        if NC < W:
+            raise ValueError("node_capacity = %d is below W = %d: not even one frame fits" % (NC, W))
+        check_bias_args(bias, V, False)
+        check_ngram_args(lm, lm_weight, length_bonus, V, blank)
+        self.S, self.V, self.W, self.cand, self.blank, self.NC = S, V, W, cand, blank, NC
+        self.bias = active(bias)
+        self.lm, self._lm_weight, self._length_bonus = lm, lm_weight, float(length_bonus)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        sbytes = lib.edgedict_ctc_stream_state_bytes(S, W, NC)
+        if sbytes == 0:
+            raise ValueError("StreamingCTCBeamSearch: shapes out of range (S = %d, W = %d, node_capacity = %d)"
+                             % (S, W, NC))
+        self._state = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+        self._ws, self._ws_tc = None, 0
+        self._result, self._result_mt = None, 0
+        self._live = np.ones(S, dtype=np.int32)              # token-tree nodes per stream after the last compaction
+        self._frames = np.zeros(S, dtype=np.int64)           # frames per stream since its reset
+        self._tail = np.zeros(S, dtype=np.int32)             # tokens of its longest uncommitted hypothesis tail
+        # the advance's read: [S][1 + NC] records {int32, int32, float32 bits, 0}; record 0 = (commits, live nodes,
+        # longest tail)
+        self._commit_buf = np.zeros((S, NC + 1, 4), dtype=np.int32)
+        self._committed = [self._EMPTY[0]] * S
+        self._committed_frames = [self._EMPTY[1]] * S
+        self._committed_logp = [self._EMPTY[2]] * S
+        self.reset()
+
+    def _opts(self):
+        """``(const edgedict_ctc_beam_opts_t*, the objects it points into)`` of this search's native calls."""
+        from .ngram import CtcBeamOpts
+        opts = CtcBeamOpts()
+        keep = [opts]
+        if self.bias is not None:
+            opts.bias = ctypes.addressof(self.bias.tables(self.device)["struct"])
+        if self.lm is not None:
+            lms = self.lm.struct(self.device, self._lm_weight, self._length_bonus)
+            keep.append(lms)
+            opts.ngram = ctypes.addressof(lms)
+        return ctypes.byref(opts), keep
+
+    def _mask(self, mask):
+        if mask is None:
+            return np.ones(self.S, dtype=bool)
+        m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+        return m.astype(bool).reshape(self.S)
+
+    def reset(self, mask=None):
+        """Every stream, or those where ``mask[s]`` is true, back to the empty hypothesis with an empty committed log;
+        its frames count from 0 again."""
+        sel = self._mask(mask)
+        md = None if mask is None else torch.from_numpy(sel.astype(np.int32)).to(self.device)
+        opts, keep = self._opts()
+        rc = _lib.load().edgedict_ctc_stream_reset(self.S, self.W, self.NC, opts, _lib.ptr(md), _lib.ptr(self._state),
+                                                   _lib.stream_ptr())
+        _lib.check(rc, "ctc_stream_reset")
+        self._frames[sel] = 0
+        self._live[sel] = 1
+        self._tail[sel] = 0
+        for s in np.nonzero(sel)[0]:
+            self._committed[s], self._committed_frames[s], self._committed_logp[s] = self._EMPTY
+
+    def set_bias(self, graph, mask=None):
+        """Swap the bias list (a ``ContextGraph``, or None / an empty one for "no bias"), with
+        ``StreamingSyncBeamSearch.set_bias``'s rules: the list is shared by all streams and the entries of a stream in
+        mid-utterance hold states of the old automaton, so EVERY stream must be fresh - no frames since its reset - or
+        ``ValueError`` is raised.  ``mask`` (None: all) only names the streams the caller swaps the list for.  Nothing is
+        launched: a fresh stream stands on state 0, the root of every automaton, and the state's layout does not depend
+        on the list."""
+        from .bias import active, check_bias_args
+        check_bias_args(graph, self.V, False)
+        sel = self._mask(mask)
+        busy = np.nonzero(self._frames > 0)[0]
+        for s in busy:
+            if sel[s]:
+                raise ValueError("set_bias: stream %d has advanced over %d frames since its reset (reset it first)"
+                                 % (s, self._frames[s]))
+        if len(busy):
+            raise ValueError("set_bias: the bias list is shared by all streams and stream %d, outside the mask, is in "
+                             "the middle of an utterance" % busy[0])
+        self.bias = active(graph)
+
+    def advance(self, logits, n_frames=None):
+        """Advance every stream over the first ``n_frames[s]`` frames (host ints, default all Tc; 0: the stream sits
+        this chunk out) of ``logits`` [S, Tc, V] (float32 or bfloat16, contiguous, on the device)."""
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("logits must be float32 or bfloat16, got %s" % logits.dtype)
+        if logits.dim() != 3 or logits.shape[0] != self.S or logits.shape[2] != self.V:
+            raise ValueError("advance: logits must be [S=%d, Tc, V=%d], got %s" % (self.S, self.V, tuple(logits.shape)))
+        if not logits.is_contiguous():
+            raise ValueError("logits must be contiguous")
+        Tc = int(logits.shape[1])
+        if Tc < 1:
+            raise ValueError("advance: logits must hold at least one frame (Tc = %d)" % Tc)
+        if n_frames is None:
+            nf = np.full(self.S, Tc, dtype=np.int32)
+        else:
+            nf = np.ascontiguousarray(n_frames.cpu().numpy() if torch.is_tensor(n_frames) else n_frames, dtype=np.int32)
+            if nf.shape != (self.S,) or (nf < 0).any() or (nf > Tc).any():
+                raise ValueError("advance: n_frames must be [S] ints in [0, %d]" % Tc)
+        _lib.require_cuda(logits)
+        need = self._live.astype(np.int64) + nf.astype(np.int64) * self.W
+        if (need > self.NC).any():
+            s = int(np.argmax(need > self.NC))
+            raise RuntimeError("StreamingCTCBeamSearch: stream %d may need %d token-tree nodes (%d live + %d frames x "
+                               "W = %d), node_capacity is %d" % (s, need[s], self._live[s], nf[s], self.W, self.NC))
+        lib = _lib.load()
+        if Tc > self._ws_tc:                 # the chunk workspace grows with the longest chunk seen
+            wbytes = lib.edgedict_ctc_stream_workspace_bytes(self.S, Tc, self.W, self.cand, self.NC)
+            if wbytes == 0:
+                raise ValueError("advance: S x Tc x cand = %d x %d x %d out of range" % (self.S, Tc, self.cand))
+            self._ws, self._ws_tc = torch.empty(wbytes, dtype=torch.uint8, device=self.device), Tc
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        opts, keep = self._opts()
+        rc = lib.edgedict_ctc_stream_advance(_lib.ptr(logits.detach()), _lib.dtype_code(logits.dtype), vp(nf), self.S, Tc,
+                                             self.V, self.blank, self.W, self.cand, self.NC, opts, vp(self._live),
+                                             vp(self._commit_buf), self.NC, _lib.ptr(self._state), _lib.ptr(self._ws),
+                                             _lib.stream_ptr())
+        _lib.check(rc, "ctc_stream_advance")
+        self._frames += nf
+        self._tail[:] = self._commit_buf[:, 0, 2]
+        ncommit = self._commit_buf[:, 0, 0]
+        for s in np.nonzero(ncommit)[0]:
+            rec = self._commit_buf[s, 1:1 + ncommit[s]]
+            lp = np.ascontiguousarray(rec[:, 2]).view(np.float32).astype(np.float64)
+            self._committed[s] = np.concatenate([self._committed[s], rec[:, 0].astype(np.int64)])
+            self._committed_frames[s] = np.concatenate([self._committed_frames[s], rec[:, 1]])
+            self._committed_logp[s] = np.concatenate([self._committed_logp[s], lp])
+
+    def live_nodes(self):
+        """int32 [S]: every stream's token-tree nodes after the last advance's compaction (what the capacity rule
+        counts; 1, the root, after a reset)."""
+        return self._live.copy()
+
+    def frames_done(self):
+        """int64 [S]: frames per stream since its reset."""
+        return self._frames.copy()
+
+    def _read(self, top=False):
+        """The read-out: the ranked uncommitted tails of every stream as host arrays ``(tokens, frames, token_logp, ntok,
+        n_hyp, logp)``, [S, W, ...]; ``top=True``: entry 0 alone, [S, 1, ...] - one read of S rows instead of S W."""
+        lib = _lib.load()
+        S, W = self.S, self.W
+        MT = 16 * ((max(1, int(self._tail.max())) + 15) // 16)        # the longest tail, in steps of 16
+        if self._result_mt != MT:
+            self._result_mt = MT
+            self._result = (torch.empty(S * W * (3 * MT + 1), dtype=torch.int32, device=self.device),
+                            torch.empty(S * W + S, dtype=torch.float64, device=self.device))
+        ints, dbl = self._result
+        n = S * W * MT
+        tokens, frames, tlp, ntok = ints[:n], ints[n:2 * n], ints[2 * n:3 * n], ints[3 * n:]
+        logp, nhyp = dbl[:S * W], dbl[S * W:].view(torch.int32)
+        rc = lib.edgedict_ctc_stream_nbest(S, W, self.NC, _lib.ptr(self._state), MT, _lib.ptr(tokens), _lib.ptr(frames),
+                                           _lib.ptr(tlp), _lib.ptr(ntok), _lib.ptr(nhyp), _lib.ptr(logp),
+                                           _lib.stream_ptr())
+        _lib.check(rc, "ctc_stream_nbest")
+        if top:
+            # entry 0 of every stream, packed on the device: tokens, frames, token_lp bits, ntok, n_hyp, logp as int32
+            rows = lambda a: a.view(S, W, MT)[:, 0]
+            hi = torch.cat([rows(tokens), rows(frames), rows(tlp), ntok.view(S, W)[:, :1], nhyp[:S].view(S, 1),
+                            logp.view(S, W)[:, :1].contiguous().view(torch.int32)], dim=1).cpu().numpy()
+            tlogp = np.ascontiguousarray(hi[:, 2 * MT:3 * MT]).view(np.float32).astype(np.float64)
+            return (hi[:, None, :MT], hi[:, None, MT:2 * MT], tlogp[:, None], hi[:, 3 * MT:3 * MT + 1], hi[:, 3 * MT + 1],
+                    np.ascontiguousarray(hi[:, 3 * MT + 2:]).view(np.float64))
+        hi, hd = ints.cpu().numpy(), dbl.cpu().numpy()
+        tlogp = np.ascontiguousarray(hi[2 * n:3 * n]).view(np.float32).reshape(S, W, MT).astype(np.float64)
+        nhyp = np.ascontiguousarray(hd[S * W:]).view(np.int32)[:S]
+        return (hi[:n].reshape(S, W, MT), hi[n:2 * n].reshape(S, W, MT), tlogp, hi[3 * n:].reshape(S, W), nhyp,
+                hd[:S * W].reshape(S, W))
+
+    def nbest(self):
+        """Per stream a ranked ``NBestResult`` (``logp`` descending, entry 0 the answer): the list ``ctc_prefix_beam``
+        returns for the stream's frames since its reset, every hypothesis the committed log followed by its uncommitted
+        tail, in tokens, frames and ``token_logp`` alike.  Does not modify the state."""
+        prefix = list(zip(self._committed, self._committed_frames, self._committed_logp))
+        return _nbest_results(*self._read(), prefix)
+
+    def best(self):
+        """Per stream entry 0 of ``nbest()``: ``(list of int64 arrays (tokens, no blanks), fp64 tensor [S] = -log p)``."""
+        tokens, _, _, ntok, _, logp = self._read(top=True)
+        tails, n = tokens[:, 0].astype(np.int64), ntok[:, 0].tolist()
+        seqs = [np.concatenate([c, tails[s, :n[s]]]) if len(c) else tails[s, :n[s]].copy()
+                for s, c in enumerate(self._committed)]
+        return seqs, torch.from_numpy(-logp[:, 0])
+
+    def committed(self):
+        """Per stream the committed tokens (int64 arrays): a prefix of every hypothesis of ``nbest()`` that no later
+        frame can change."""
+        return [c.copy() for c in self._committed]
+
+    def committed_detail(self):
+        """Per stream ``(tokens int64, frames int32, token_logp float64)`` of the committed log."""
+        return [(t.copy(), f.copy(), l.copy())
+                for t, f, l in zip(self._committed, self._committed_frames, self._committed_logp)]
+
+    def idle_frames(self):
+        """int64 [S]: frames since the last token of each stream's best hypothesis was created - frames so far minus one
+        minus that token's frame -, or the frames since the reset where the best hypothesis is empty: what an
+        endpointer waits on.  Host arithmetic on what ``best()`` reads."""
+        _, frames, _, ntok, _, _ = self._read(top=True)
+        out = self._frames.copy()
+        for s in range(self.S):
+            n = int(ntok[s, 0])
+            if n > 0:
+                out[s] = self._frames[s] - 1 - int(frames[s, 0, n - 1])
+            elif len(self._committed_frames[s]):
+                out[s] = self._frames[s] - 1 - int(self._committed_frames[s][-1])
+        return out
+
+
 def emission_times(frames, flags, time_reduction=2):
     """Seconds (float64 tensor, shape of ``frames``) at which the encoder frames of ``Transducer.align`` /
     ``loss.rnnt_align`` - or the decoder's own, ``NBestResult.frames`` of ``beam_search_nbest`` / ``nbest()`` (counted

@@ -8,7 +8,8 @@ does not have: S concurrent streams advance in lock-step on one GPU, state tenso
 log-mel on the chunk, stateful encoder, then the on-device search loop of csrc/decode.hip in
 stream mode (raw-logit arg-max, the ``<unk>`` rule, prediction net advanced on non-blank).
 ``BatchedStreamBeamDecoder`` runs the beam search instead, its beams carried from chunk to chunk
-(``decode.StreamingBeamSearch``).
+(``decode.StreamingBeamSearch``); ``BatchedStreamCTCBeamDecoder`` runs the CTC prefix beam search on the
+encoder's CTC head (``decode.StreamingCTCBeamSearch``), without the prediction network and the joint.
 """
 import os
 import time
@@ -460,6 +461,90 @@ class BatchedStreamSyncFusionBeamDecoder(BatchedStreamSyncBeamDecoder):
         self._setup(transducer, flags, n_streams, W, node_capacity, dither,
                     dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_bos=lm_bos, bias=bias,
                          ilm_weight=ilm_weight))
+
+
+class BatchedStreamCTCBeamDecoder(StreamTransducerDecoder):
+    """S streams decoded concurrently with the CTC prefix beam search on the encoder's CTC head
+    (``Transducer.ctc_beam_search``): neither the prediction network nor the joint runs.
+
+    ``BatchedStreamSyncBeamDecoder``'s front - chunk geometry (``chunk_geometry``), feature transform, carried encoder
+    (h, c) -; behind it the head's logits ``model._ctc_logits(enc_out)`` and ``decode.StreamingCTCBeamSearch``, which
+    keeps every stream's beam from chunk to chunk, so after any chunk ``nbest()`` is what the offline search over the
+    stream's audio so far returns.  ``W``, ``cand``, ``node_capacity``, ``bias``, ``lm`` (an ``NGramLM``), ``lm_weight``,
+    ``length_bonus`` as there; ``self.search.set_bias`` swaps the list between utterances.  Raises ``RuntimeError`` on a
+    model built without ``ctc_weight > 0``."""
+
+    def __init__(self, transducer, flags, n_streams, W=10, cand=None, node_capacity=None, dither=None, *, bias=None,
+                 lm=None, lm_weight=None, length_bonus=0.0):
+        from .decode import StreamingCTCBeamSearch, _vocab
+        if getattr(transducer, "ctc_head", None) is None:
+            raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+        self.model = transducer.eval()
+        self.flags = flags
+        self.S = n_streams
+        dev = transducer.decoder.embed.weight.device
+        self.device = dev
+        _lib.require_cuda(transducer.decoder.embed.weight)
+        self.search = StreamingCTCBeamSearch(n_streams, _vocab(transducer), W=W, cand=cand, blank=transducer.blank,
+                                             node_capacity=node_capacity, bias=bias, lm=lm, lm_weight=lm_weight,
+                                             length_bonus=length_bonus)
+        self.transform = StackedLogFbank(
+            n_frame=flags.downsample, pad_to_divisible=False, win_length=flags.win_length,
+            hop_length=flags.hop_length, n_fft=flags.n_fft, n_filt=flags.feature_size,
+            dither=1e-5 if dither is None else dither).to(dev)
+        self.reset_profile()
+        self.reset()
+
+    @torch.no_grad()
+    def reset(self, mask=None):
+        """Reset every stream, or only those where ``mask[s]`` is true."""
+        enc = self.model.encoder.lstm
+        L, H = len(enc.lstms), enc.hidden_size
+        if mask is None or not hasattr(self, "enc_h"):
+            self.enc_h = torch.zeros(L, self.S, H, device=self.device)
+            self.enc_c = torch.zeros(L, self.S, H, device=self.device)
+            self.search.reset()
+            return
+        m = torch.as_tensor(mask).to(self.device).bool()
+        self.enc_h[:, m] = 0
+        self.enc_c[:, m] = 0
+        self.search.reset(m)
+
+    @torch.no_grad()
+    def encode(self, frames):
+        """frames: float32 [S, win_size] on the device -> the chunk's encoder output [S, Tc, P]; advances (h, c)."""
+        encoder_stack.check_wsr_error()
+        xs, _ = self.transform(frames)
+        enc_out, (self.enc_h, self.enc_c) = self.model.encoder(xs, (self.enc_h, self.enc_c))
+        return enc_out
+
+    @torch.no_grad()
+    def decode(self, frames):
+        """frames: float32 [S, win_size] on the device -> ``(list of int64 arrays, fp64 tensor [S])``: every stream's
+        best hypothesis over its audio so far (tokens without blanks, -log p), as ``best()`` returns it."""
+        t0 = time.time()
+        enc_out = self.encode(frames)
+        self.encoder_elapsed.append(time.time() - t0)
+        t0 = time.time()
+        self.search.advance(self.model._ctc_logits(enc_out).contiguous())
+        out = self.search.best()
+        self.joint_elapsed.append(time.time() - t0)
+        return out
+
+    def best(self):
+        return self.search.best()
+
+    def committed(self):
+        return self.search.committed()
+
+    def nbest(self):
+        return self.search.nbest()
+
+    def committed_detail(self):
+        return self.search.committed_detail()
+
+    def idle_frames(self):
+        return self.search.idle_frames()
 
 
 class PytorchStreamDecoder(StreamTransducerDecoder):

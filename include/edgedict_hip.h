@@ -1348,6 +1348,61 @@ int edgedict_ctc_beam_search_fused(const void* logits, int dtype, const int32_t*
                                    void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Streaming CTC prefix beam search: the search above for S streams whose head logits arrive chunk by chunk.  The beams
+ * live in a persistent device STATE; after any number of advances a stream's state holds exactly the beam that
+ * edgedict_ctc_beam_search_fused has after the same frames (same opts), bit for bit, and ctc_stream_nbest returns it.
+ *
+ * State per stream: the beam in ranked order (up to W entries of pb, pnb, bias total, LM total in fp64, and per entry
+ * node, parent, last token, depth below the tree's root, automaton state, n-gram state), the entry count, the node count,
+ * the frames since the reset, and the token tree: node_capacity (NC) nodes of int4 (parent, token, frame, lp bits), the
+ * root in node 0.  The layout does not depend on opts.
+ *
+ *   ctc_stream_state_bytes(S, W, NC)                 device bytes of the state (contents undefined until a reset of
+ *                                                    all streams); 0 for S <= 0, W outside 1 .. 32, NC < W
+ *   ctc_stream_workspace_bytes(S, Tc, W, cand, NC)   device bytes of an advance over chunks of up to Tc frames; 0 for
+ *                                                    bad shapes (also Tc <= 0, cand outside 1 .. 64)
+ *   ctc_stream_reset    streams with mask[s] != 0 (mask: DEVICE int32 [S], null: all) -> the empty prefix alone: pb 0,
+ *                       pnb -inf, totals 0, automaton state 0, opts->ngram's start state (0 without one), a tree of the
+ *                       root, no frames.  One launch, no sync.
+ *   ctc_stream_advance  stream s takes the first n_frames_host[s] (HOST int32 [S], 0 .. Tc) frames of logits [S, Tc, V]
+ *                       (dtype code; rows behind are never read).  Three launches - the row pass of the offline search
+ *                       on the chunk, the walk (one wave per stream, all frames inside the launch, the beam loaded
+ *                       from and stored to the state, absolute frame numbers in new nodes), the compaction - then ONE
+ *                       device-to-host read and one stream synchronisation.  The compaction (one wave per stream, no
+ *                       atomics) finds the lowest common ancestor of the live entries' nodes, writes the tokens below
+ *                       the old root down to it as commit records, makes it the root (node 0) and renumbers the nodes
+ *                       a live entry still reaches densely, entries' node / parent renamed.
+ *                         live_host   HOST int32 [S], in and out: the stream's tree nodes (1 after a reset, else what
+ *                                     the previous advance wrote).  live[s] + n_frames[s] * W > NC is refused before
+ *                                     anything is launched: nothing is ever truncated.
+ *                         commit_host HOST [S][max_commit + 1] records of 16 bytes {int32, int32, float bits, 0}:
+ *                                     record 0 = (tokens committed by this advance, live nodes, tokens of the stream's
+ *                                     longest uncommitted hypothesis tail), records 1 .. = (token, frame since the
+ *                                     reset, lp) root-side first.  max_commit >= max over s of
+ *                                     min(NC, live[s] - 1 + n_frames[s]); NC always suffices.
+ *   ctc_stream_nbest    the uncommitted part, as edgedict_ctc_beam_search's outputs on DEVICE arrays: tokens / frames
+ *                       [S, W, max_tokens] int32 and token_lp fp32 (-1 / -1 / 0 behind ntok), ntok [S, W], n_hyp [S],
+ *                       logp [S, W] fp64 = (logadd(pb, pnb) + Bn) + Ln, -inf behind n_hyp.  max_tokens >= 1 and
+ *                       at least the longest tail the advances reported (a longer tail is cut to max_tokens).  One launch, no sync; the state is not
+ *                       modified.  A whole hypothesis is the stream's commit records so far followed by this part.
+ *
+ * W, cand, dtype, V, blank, opts (bias list, n-gram: vocabulary and blank, tables, weight) are checked as by
+ * edgedict_ctc_beam_search_fused, null and non-pointer arguments and NC < W too: ED_ERR_INVALID with a message naming
+ * ctc_stream_*, before anything is launched.  state and workspace 16-byte aligned.  Results are bit-identical from run
+ * to run.  The same opts must be given to the reset and to every advance of an utterance. */
+size_t edgedict_ctc_stream_state_bytes(int S, int W, int node_capacity);
+size_t edgedict_ctc_stream_workspace_bytes(int S, int Tc, int W, int cand, int node_capacity);
+int edgedict_ctc_stream_reset(int S, int W, int node_capacity, const edgedict_ctc_beam_opts_t* opts, const int32_t* mask,
+                              void* state, void* stream);
+int edgedict_ctc_stream_advance(const void* logits, int dtype, const int32_t* n_frames_host, int S, int Tc, int V,
+                                int blank, int W, int cand, int node_capacity, const edgedict_ctc_beam_opts_t* opts,
+                                int32_t* live_host, void* commit_host, int max_commit, void* state, void* workspace,
+                                void* stream);
+int edgedict_ctc_stream_nbest(int S, int W, int node_capacity, const void* state, int max_tokens, int32_t* tokens,
+                              int32_t* frames, float* token_lp, int32_t* ntok, int32_t* n_hyp, double* logp,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Blank-frame skipping ahead of the RNN-T beam searches (csrc/frame_skip.hip): the CTC head's blank posterior decides
  * which encoder frames a search sees.  No host sync inside either call, no atomics; results bit-identical from run to
  * run.
