@@ -13,6 +13,15 @@ if _os.environ.get("EDGEDICT_POISON", "0") == "1":
     from . import _poison as _poison  # noqa: E402,F401
 
 
+def weights_changed():
+    """Tell the engine that master weights were written in a way it cannot see: through ``p.data`` (``p.data.mul_()``,
+    ``p.data.copy_()``, ``dist.broadcast(p.data)``, EMA / checkpoint averaging) or through a raw pointer.  Every cached
+    image of a parameter (compute-dtype casts, transposes, packed LSTM images, the streaming decoder's bound plan) is
+    rebuilt at its next use.  Costs nothing until then; see INTEGRATION.md, "Changing weights"."""
+    from . import config
+    config.bump_param_epoch()
+
+
 def __getattr__(name):
     # the host-side classes a user builds before any search (imported on first use: they pull in nothing native)
     if name == "NGramLM":

@@ -95,3 +95,21 @@ def bump_param_epoch():
 
 def param_epoch():
     return _state["epoch"]
+
+
+def _after_torch_optimizer_step(_optimizer, _args, _kwargs):
+    bump_param_epoch()
+
+
+# torch's own fused optimisers (Adam / AdamW / SGD with fused=True) update the parameters in one multi-tensor kernel that
+# leaves their version counters alone (tests/test_weight_cache_host.py): like the engine's Adam kernel they are visible to
+# the caches only through the epoch.  One global hook behind every torch.optim step; a step on somebody else's parameters
+# costs this engine a rebuild of its images at their next use, never a stale one.  Optimisers that are no
+# torch.optim.Optimizer (apex, DeepSpeed, bitsandbytes) never reach it, and a torch without the global hook (< 2.0) has
+# none to offer: INTEGRATION.md sends both to edgedict_amd.weights_changed().
+try:
+    from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_hook  # noqa: E402
+except ImportError:
+    _register_step_hook = None
+if _register_step_hook is not None:
+    _register_step_hook(_after_torch_optimizer_step)

@@ -76,11 +76,12 @@ def supported(cd, H, I0, L, reductions):
 class _PackedLayer:
     """bf16 weight images of one LSTM layer, rebuilt when the fp32 masters change: the forward pass's images (wih_p,
     bias_p, whh_f) under ``key``, the ones only the backward pass reads (wih_t, whh_b, whh_s) under ``bwd_key``."""
-    __slots__ = ("key", "bwd_key", "ref", "wih_p", "wih_t", "bias_p", "whh_f", "whh_b", "whh_s")
+    __slots__ = ("key", "bwd_key", "ref", "pinned", "wih_p", "wih_t", "bias_p", "whh_f", "whh_b", "whh_s")
 
     def __init__(self, owner):
         self.key = self.bwd_key = None
         self.ref = weakref.ref(owner)
+        self.pinned = None      # the four masters' tensors the images were built from: their addresses stay taken while the entry lives
 
 
 _PACKED = {}
@@ -100,8 +101,9 @@ def packed_weights(w_ih, w_hh, b_ih, b_hh, backward_images=True):
     whh_s allocated but not built - their pointers can go into a descriptor, and ``fill_backward_images`` builds them
     before the backward pass reads them (``_Plan.backward``; ``prepack`` does it behind the forward images)."""
     ent = _PACKED.get(id(w_hh))
-    key = (w_ih.data_ptr(), w_hh.data_ptr(), w_ih._version, w_hh._version, b_ih._version,
-           b_hh._version, config.param_epoch(), BWD_SK)
+    # (the biases' addresses too: `b_ih.data = new` keeps the version counter, and bias_p is built from both)
+    key = (w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(), w_ih._version, w_hh._version,
+           b_ih._version, b_hh._version, config.param_epoch(), BWD_SK)
     if ent is None or ent.ref() is not w_hh or ent.key != key:     # (ids are recycled: the entry must be this tensor's)
         for k in [k for k, v in _PACKED.items() if v.ref() is None]:
             del _PACKED[k]                       # images of parameters that no longer exist
@@ -110,6 +112,9 @@ def packed_weights(w_ih, w_hh, b_ih, b_hh, backward_images=True):
         H = H4 // 4
         dev = w_ih.device
         srcs = _sources(w_ih, w_hh, b_ih, b_hh)
+        # `p.data = a; p.data = b` must not put b on the address this entry's key was taken from (set_data keeps the version
+        # counter): holding the sources keeps the allocator from handing those blocks out again
+        ent.pinned = tuple(t.detach() for t in (w_ih, w_hh, b_ih, b_hh))
         ent.wih_p = torch.empty(H4, I, dtype=BF16, device=dev)
         ent.wih_t = torch.empty(I, H4, dtype=BF16, device=dev)
         ent.bias_p = torch.empty(H4, dtype=F32, device=dev)

@@ -51,6 +51,8 @@ class _WeightCache:
         hit = self._store.get(key)
         # ids (and device addresses) are recycled once a tensor dies: the entry must belong to
         # THIS tensor object, not to a dead one that happened to share id, address and version
+        # (the entry also holds the tensor it was built from, hit[3]: while it lives the allocator cannot hand that
+        # address to another `.data` of the same parameter, so an equal address means the same storage)
         if hit is not None and hit[0] == ver and hit[2]() is p:
             return hit[1]
         # a miss: drop the copies of parameters that no longer exist (replicas of nn.DataParallel,
@@ -58,7 +60,7 @@ class _WeightCache:
         dead = [k for k, v in self._store.items() if v[2]() is None]
         for k in dead:
             del self._store[k]
-        src = p.detach()
+        src = pinned = p.detach()
         if not src.is_contiguous():
             src = src.contiguous()
         if transposed == "lstm_fwd":
@@ -78,7 +80,9 @@ class _WeightCache:
             for s in (torch.cuda.current_stream(t.device), side.peek(t.device)):
                 if s is not None:
                     t.record_stream(s)
-        self._store[key] = (ver, t, weakref.ref(p))
+        # `pinned` shares p's storage: `p.data = a; p.data = b` cannot put b where this image's source was (set_data keeps
+        # the version counter, so an address match would return the old image)
+        self._store[key] = (ver, t, weakref.ref(p), pinned)
         return t
 
     def clear(self):

@@ -76,6 +76,9 @@ class _ChunkPlan:
         # in-place update the version check - the plan holds the old tensors alive, so it must never outlive them silently
         self.slots = [(mod._parameters, name, p) for mod in m.modules() for name, p in mod._parameters.items() if p is not None]
         self.params = [p for _, _, p in self.slots]
+        # ... and the data_ptr check only means something while the old storage cannot be handed out again (`p.data = a;
+        # p.data = b` could otherwise put b on the address the signature was taken from)
+        self.pinned = [p.detach() for p in self.params]
         self.dec = dec
         self.sig = self._signature()
         k, M = tr.n_frame, fb.n_filt

@@ -155,6 +155,12 @@ print(json.dumps({"losses": losses, "sum": float(p.sum()), "sumsq": float((p * p
                   "probe": [float(x) for x in eng.flat.data[::1000003][:40]],
                   "fwd_mode": encoder_stack.last_mode(False), "bwd_mode": encoder_stack.last_mode(True),
                   "early": red.last_issued_early, "buckets": len(red.bounds), "by": list(red.last_early_by)}))
+sys.stdout.flush()
+if os.environ.get("EDGEDICT_DP_FORCE") == "1":
+    # leave in order: a process that exits with the communicator alive lets torch's watchdog thread race the
+    # interpreter's teardown, and an exception on that thread aborts the process after all the work was done
+    eng.close()
+    dist.destroy_process_group()
 """
 
 
