@@ -1173,8 +1173,8 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
                            denom, lpb, lpl, vec_ok, pk_off, nullptr, nullptr);
     ED_CHECK_LAUNCH("rnnt_lse_gather");
 
-    // one wave per (utterance, direction), C = ceil(U1 / 64) label columns per lane (rounded up to a power of two)
-    ED_CHECK_ARG(U1 <= 64 * 32, "rnnt_loss_forward: more than 2047 labels per utterance (U1 = %d)", U1);
+    // one wave per (utterance, direction), C = ceil(U1 / 64) label columns per lane (rounded up to a power of two).
+    // The one limit is check_common's U1 <= 1024, the same for the loss and the aligner: C = 16 is the widest walk
 #define ED_AB_LAUNCH(CC)                                                                                              \
     do {                                                                                                              \
         if (al_scores)                                                                                                \
@@ -1189,8 +1189,7 @@ static int loss_forward(const void* acts, int acts_dtype, const int32_t* labels,
     else if (cols <= 2) ED_AB_LAUNCH(2);
     else if (cols <= 4) ED_AB_LAUNCH(4);
     else if (cols <= 8) ED_AB_LAUNCH(8);
-    else if (cols <= 16) ED_AB_LAUNCH(16);
-    else ED_AB_LAUNCH(32);
+    else ED_AB_LAUNCH(16);
 #undef ED_AB_LAUNCH
     ED_CHECK_LAUNCH("rnnt_alpha_beta");
     if (al_scores) {

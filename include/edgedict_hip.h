@@ -66,8 +66,9 @@ int edgedict_abi_version(void);
  *   scale_b = grad_scale_host * (grad_scale_dev ? grad_scale_dev[b*grad_scale_stride] : 1)
  * (stride 0 = one scalar for the batch, stride 1 = per-utterance, reduction 'none') so that the 'mean' reduction's 1/B and autograd's incoming grad_output need no host sync.
  * Cells outside an utterance's (act_lens, label_lens+1) box get exact zeros.
- * Limits: U1 <= 1024; V*sizeof(dtype) must be a multiple of 16 for the vector path
- * (other V take a scalar path).
+ * Limits: U1 <= 1024, for every edgedict_rnnt_loss_* entry point and for the aligner's (edgedict_rnnt_align*) alike: a
+ * larger U1 is ED_ERR_INVALID before anything is launched, and no output is written (edgedict_rnnt_workspace_bytes
+ * itself has no limit).  V*sizeof(dtype) must be a multiple of 16 for the vector path (other V take a scalar path).
  */
 size_t edgedict_rnnt_workspace_bytes(int B, int T, int U1);
 int edgedict_rnnt_loss_forward(const void* acts, int acts_dtype, const int32_t* labels,

@@ -11,17 +11,24 @@ import pytest
 import torch
 
 import fastemit_ref as FR
+import rnnt_walk_cases as WC
 from oracle import packed_ref as PR
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = torch.float32, torch.bfloat16
 ROUTES = [("dense", F32), ("dense", BF16), ("packed", F32), ("packed", BF16), ("parts", BF16)]
+# The Viterbi walk rnnt_alpha_beta<C, true> at C = 4, 8, 16 label columns per lane (U1 = 129, 257, 513 and the limit,
+# 1024; U1 = 70 above is C = 2): the batches of tests/rnnt_walk_cases.py, whose lengths sit on the edges of each walk's
+# prefetch ring and of its last live lane
+WALK_SHAPES = [(WC.B_WALK, WC.T_WALK, U1, 8) for U1 in (129, 257, 513, 1024)]
 # (B, T, U1, V): row 0 is the full box (U_b = U_max), row 1 one frame, row 2 no labels, the others random
-SHAPES = [(5, 12, 6, 32), (4, 33, 70, 64), (6, 40, 9, 264), (3, 1, 4, 16)]
+SHAPES = [(5, 12, 6, 32), (4, 33, 70, 64), (6, 40, 9, 264), (3, 1, 4, 16)] + WALK_SHAPES
 
 
 def _lens(seed, B, T, U1):
+    if (B, T, U1, 8) in WALK_SHAPES:
+        return WC.length_rows(T, U1, rotate=3 if U1 in (257, 1024) else 0)
     rng = np.random.default_rng(seed)
     al = rng.integers(1, T + 1, size=B).astype(np.int32)
     ll = rng.integers(0, U1, size=B).astype(np.int32)
@@ -126,7 +133,16 @@ def test_random_ragged_batches(hip_lib, route, dtype, B, T, U1, V):
 def test_planted_alignment_is_recovered_exactly(hip_lib, route, dtype):
     """+10 on the transitions of a chosen alignment over noise of scale 1: leaving it costs a step of log-probability
     ~ -10 against ~ -0.003 per step on it, so it is the best path by a margin no rounding bridges."""
-    B, T, U1, V = 6, 40, 9, 264
+    _planted(route, dtype, 6, 40, 9, 264)
+
+
+@pytest.mark.parametrize("route,dtype", ROUTES, ids=[r + "-" + ("f32" if d == F32 else "bf16") for r, d in ROUTES])
+def test_planted_alignment_is_recovered_exactly_on_the_long_axis(hip_lib, route, dtype):
+    """The same at U1 = 513: 16 label columns per lane, a prefetch ring of one step, a back-trace of up to 528 steps."""
+    _planted(route, dtype, WC.B_WALK, WC.T_WALK, 513, 8)
+
+
+def _planted(route, dtype, B, T, U1, V):
     rng = np.random.default_rng(42)
     al, ll = _lens(9, B, T, U1)
     labels = rng.integers(1, V, size=(B, U1 - 1)).astype(np.int32)
