@@ -73,6 +73,12 @@ prior - the log-softmax over the non-blank symbols of the joint on an all-zero e
 non-blank candidate's score inside the frame loop (csrc/decode_sync.hip, csrc/decode_fused.hip), with or without
 ``lm=`` / ``bias=``.  ``ilm_logits`` is the raw kernel call, ``Transducer.ilm_logprobs`` / ``ilm_score`` score a text
 with the internal LM (csrc/ilm_score.hip).  Not for the best-first searches.  None launches nothing new.
+
+``hypothesis_confidence`` / ``ctc_hypothesis_confidence`` (``Transducer.confidence``) are a post-pass over the
+``NBestResult`` lists of any of these searches: token, word and utterance confidences from the acoustic model's whole
+output distribution on each token's frame (normalised Tsallis or Shannon entropy, ``confidence_measure``), by
+re-evaluating the joint at every token's (frame, prefix) - or reading the CTC head's logits there - and reducing each
+row of logits to five statistics (csrc/confidence.hip).  LM, ILME and bias terms take no part; no search changes.
 """
 import ctypes
 
@@ -1925,3 +1931,327 @@ def emission_times(frames, flags, time_reduction=2):
     step = flags.hop_length * max(1, flags.downsample) * int(time_reduction) / float(getattr(flags, "sample_rate", 16000))
     out = frames.to(torch.float64) * step
     return torch.where(frames < 0, torch.full_like(out, float("nan")), out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Confidence of N-best hypotheses: a post-pass over the lists any search returned (csrc/confidence.hip).
+CONF_METHODS = ("prob", "max_prob", "entropy", "tsallis")
+CONF_AGGREGATES = ("min", "mean", "prod")
+CONF_LOGITS_BYTES = 64 << 20        # the fp32 logits buffer of one chunk of hypothesis_confidence stays at or under this
+
+
+def confidence_measure(stats, V, method="tsallis", alpha=1.0 / 3.0):
+    """A confidence in ``[0, 1]`` per row of ``stats`` [..., 5] (``loss.row_confidence``'s columns), on the host in
+    float64.  The distribution is the row's softmax over all ``V`` symbols, the blank included.
+
+        ``"prob"``      ``exp(logp)``: the probability of the row's token
+        ``"max_prob"``  ``exp(logp_max)``: the largest probability of the row
+        ``"entropy"``   ``1 - H / ln V``: one minus the Shannon entropy normalised by its maximum
+        ``"tsallis"``   ``1 - (1 - sum_v p_v^alpha) / (1 - V^(1 - alpha))``: one minus the Tsallis entropy of order
+                        ``alpha`` normalised by its maximum (Laptev & Ginsburg 2022), ``0 < alpha < 1``; ``alpha``
+                        must be the one the statistics were computed with
+
+    The result is clipped to ``[0, 1]``: a uniform row gives 0 for the two entropy measures, a one-hot row 1.  NaN
+    statistics stay NaN.  No calibration is claimed for any of them."""
+    stats = np.asarray(stats, dtype=np.float64)
+    V, alpha = int(V), float(alpha)
+    if stats.shape[-1] != 5:
+        raise ValueError("confidence_measure: stats must be [..., 5]")
+    if V < 2:
+        raise ValueError("confidence_measure: V = %d, need at least two symbols" % V)
+    if method == "prob":
+        c = np.exp(stats[..., 0])
+    elif method == "max_prob":
+        c = np.exp(stats[..., 1])
+    elif method == "entropy":
+        c = 1.0 - stats[..., 3] / np.log(V)
+    elif method == "tsallis":
+        if not 0.0 < alpha < 1.0:
+            raise ValueError("confidence_measure: alpha must lie inside (0, 1), got %r" % (alpha,))
+        c = 1.0 - (1.0 - np.exp(stats[..., 4])) / (1.0 - V ** (1.0 - alpha))
+    else:
+        raise ValueError("confidence_measure: method must be one of %s, got %r" % (", ".join(CONF_METHODS), method))
+    return np.clip(c, 0.0, 1.0)
+
+
+class WordTable:
+    """Which tokens end a word: ``word_end`` bool [V] (a token with it set is the LAST token of its word: the
+    reference's CharBPE pieces ending in ``</w>``) and ``separators``, token ids that stand between words and belong to
+    none (the char tokenizer's space)."""
+
+    def __init__(self, word_end, separators=()):
+        self.word_end = np.asarray(word_end, dtype=bool).reshape(-1)
+        self.separators = sorted(int(k) for k in separators)
+        if any(k < 0 or k >= self.word_end.size for k in self.separators):
+            raise ValueError("WordTable: a separator id lies outside [0, %d)" % self.word_end.size)
+
+    def spans(self, tokens):
+        """``[(first, last), ...]``: the token index ranges (inclusive) of the words of one hypothesis.  A word ends at
+        a token with ``word_end`` set; a separator ends the word before it and is part of none; a trailing run without
+        an end marker is still a word."""
+        out, start = [], None
+        for u, k in enumerate(int(t) for t in tokens):
+            if k in self.separators:
+                if start is not None:
+                    out.append((start, u - 1))
+                start = None
+                continue
+            if start is None:
+                start = u
+            if 0 <= k < self.word_end.size and self.word_end[k]:
+                out.append((start, u))
+                start = None
+        if start is not None:
+            out.append((start, len(tokens) - 1))
+        return out
+
+
+def word_table(tokenizer, V):
+    """The ``WordTable`` of a tokenizer's first ``V`` pieces, from their texts (``stream._token_text``): a piece that
+    ends in ``</w>`` ends a word, a piece that is a single space is a separator."""
+    from .stream import _token_text
+    texts = [_token_text(tokenizer, i) for i in range(int(V))]
+    return WordTable([bool(t) and t.endswith("</w>") for t in texts], [i for i, t in enumerate(texts) if t == " "])
+
+
+def aggregate_confidence(values, how="min"):
+    """``min`` / ``mean`` / ``prod`` of token confidences (float64); NaN for none."""
+    values = np.asarray(values, dtype=np.float64)
+    if how not in CONF_AGGREGATES:
+        raise ValueError("aggregate must be one of %s, got %r" % (", ".join(CONF_AGGREGATES), how))
+    if values.size == 0:
+        return float("nan")
+    return float({"min": np.min, "mean": np.mean, "prod": np.prod}[how](values))
+
+
+def word_confidence(tokens, frames, values, table, aggregate="min"):
+    """The words of one hypothesis as ``(first_token, last_token, start_frame, end_frame, confidence)``: token indices
+    into the hypothesis, the frames of the word's first and last token (``emission_times`` turns them into seconds),
+    and the ``aggregate`` of the tokens' confidences ``values``."""
+    return [(a, b, int(frames[a]), int(frames[b]), aggregate_confidence(values[a:b + 1], aggregate))
+            for a, b in table.spans(tokens)]
+
+
+class Confidence:
+    """The confidences of one utterance's N-best list, hypothesis ``i`` in the list's own order:
+
+    ``token[i]``      float64 array, one value in ``[0, 1]`` per token (``confidence_measure`` with ``method``, ``alpha``)
+    ``raw[i]``        float64 [len, 5]: the statistics behind them, ``loss.CONF_COLUMNS`` (``raw[i][:, 0]`` is the
+                      acoustic model's own log-probability of the token: ``token_logp`` without LM and bias terms)
+    ``top[i]``        int32 array: the most probable symbol at each token's place (the blank included)
+    ``utterance``     float64 [n]: the ``aggregate`` over each hypothesis' tokens; NaN for an empty hypothesis
+    ``word[i]``       None, or with ``words=`` a list of ``(first_token, last_token, start_frame, end_frame, confidence)``
+    """
+
+    def __init__(self, token, raw, top, utterance, word, method, alpha, aggregate):
+        self.token, self.raw, self.top, self.word = list(token), list(raw), list(top), list(word)
+        self.utterance = np.asarray(utterance, dtype=np.float64)
+        self.method, self.alpha, self.aggregate = method, alpha, aggregate
+
+    def __len__(self):
+        return len(self.token)
+
+
+def _check_confidence(what, method, alpha, aggregate, words):
+    if method not in CONF_METHODS:
+        raise ValueError("%s: method must be one of %s, got %r" % (what, ", ".join(CONF_METHODS), method))
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError("%s: alpha must be a number inside (0, 1), got %r" % (what, alpha)) from None
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("%s: alpha must lie inside (0, 1), got %r" % (what, alpha))
+    if aggregate not in CONF_AGGREGATES:
+        raise ValueError("%s: aggregate must be one of %s, got %r" % (what, ", ".join(CONF_AGGREGATES), aggregate))
+    if words is not None and not isinstance(words, WordTable):
+        raise TypeError("%s: words must be a decode.WordTable (decode.word_table builds one)" % what)
+    return alpha
+
+
+def _confidence_rows(what, results, enc_out, lens, V, blank):
+    """The argument rules both passes share, then the compact rows: ``(results, lens, hyps, enc_row, tok)`` with
+    ``hyps`` the (utterance, index, tokens, frames) of every non-empty hypothesis in list order and ``enc_row`` /
+    ``tok`` int32 arrays with one entry per live token (``enc_row = b * T + frame``), hypothesis after hypothesis."""
+    _lib.require_cuda(enc_out)
+    if enc_out.dim() != 3:
+        raise ValueError("%s: enc_out must be [B, T, P]" % what)
+    B, T, _ = enc_out.shape
+    results = list(results)
+    if len(results) != B:
+        raise ValueError("%s: %d lists for a batch of %d utterances" % (what, len(results), B))
+    lens = np.full(B, T, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > T).any():
+        raise ValueError("%s: lens must be [B] ints in [0, %d]" % (what, T))
+    hyps, enc_row, tok = [], [], []
+    for b, r in enumerate(results):
+        for i in range(len(r)):
+            t = np.asarray(r.tokens[i], dtype=np.int64).reshape(-1)
+            f = np.asarray(r.frames[i], dtype=np.int64).reshape(-1)
+            if t.shape != f.shape:
+                raise ValueError("%s: utterance %d, hypothesis %d: %d tokens but %d frames" % (what, b, i, t.size, f.size))
+            if t.size == 0:
+                continue
+            if (f < 0).any() or (f >= lens[b]).any():
+                raise ValueError("%s: utterance %d, hypothesis %d: a frame outside [0, %d)" % (what, b, i, lens[b]))
+            if (t < 0).any() or (t >= V).any() or (t == blank).any():
+                raise ValueError("%s: utterance %d, hypothesis %d: a token that is blank or outside [0, %d)"
+                                 % (what, b, i, V))
+            hyps.append((b, i, t, f))
+            enc_row.append(b * T + f)
+            tok.append(t)
+    cat = lambda a: np.concatenate(a).astype(np.int32) if a else np.zeros(0, dtype=np.int32)      # noqa: E731
+    return results, lens, hyps, cat(enc_row), cat(tok)
+
+
+def _confidence_results(results, hyps, host, R, V, method, alpha, aggregate, words):
+    """One ``Confidence`` per utterance from the pass's single host read ``host`` (None: no live token): fp32 words,
+    ``[R, 5]`` statistics and behind them the R int32 arg-maxes."""
+    stats, top = np.zeros((0, 5)), np.zeros(0, dtype=np.int32)
+    if R:
+        stats = host[:R * 5].reshape(R, 5).astype(np.float64)
+        top = host[R * 5:].view(np.int32)
+    out, at, pos = [], {}, 0
+    for b, i, t, f in hyps:
+        at[(b, i)] = (pos, t.size)
+        pos += t.size
+    for b, r in enumerate(results):
+        token, raw, tops, word = [], [], [], []
+        for i in range(len(r)):
+            o, n = at.get((b, i), (0, 0))
+            raw.append(stats[o:o + n].copy() if n else np.zeros((0, 5)))
+            tops.append(top[o:o + n].copy() if n else np.zeros(0, dtype=np.int32))
+            token.append(confidence_measure(raw[-1], V, method, alpha))
+            word.append(None if words is None else
+                        word_confidence(r.tokens[i], r.frames[i], token[-1], words, aggregate))
+        out.append(Confidence(token, raw, tops, [aggregate_confidence(c, aggregate) for c in token], word, method, alpha,
+                              aggregate))
+    return out
+
+
+def confidence_hidden_rows(E1, D1, enc_row, dec_row, b1=None, out=None):
+    """The raw call of csrc/confidence.hip ``conf_hidden_rows``: ``hid[r] = tanh(E1[enc_row[r]] + D1[dec_row[r]] + b1)``
+    in the dtype of ``E1`` [n_enc_rows, J] and ``D1`` [n_dec_rows, J] (contiguous, on the device), ``enc_row`` /
+    ``dec_row`` int32 [R] device tensors, ``b1`` fp32 [J] or None (nothing added).  A row with an index out of range is
+    NaN and nothing is read for it.  Returns ``hid`` [R, J] (``out`` if given).  No host sync."""
+    _lib.require_cuda(E1, D1, enc_row, dec_row, b1, out)
+    if E1.dim() != 2 or D1.dim() != 2 or E1.dtype != D1.dtype or E1.shape[1] != D1.shape[1]:
+        raise ValueError("confidence_hidden_rows: E1 and D1 must be [rows, J] of one dtype")
+    if not (E1.is_contiguous() and D1.is_contiguous()):
+        raise ValueError("confidence_hidden_rows: E1 and D1 must be contiguous")
+    J, R = E1.shape[1], enc_row.shape[0]
+    for v in (enc_row, dec_row):
+        if v.dtype != torch.int32 or v.shape != (R,) or not v.is_contiguous():
+            raise ValueError("confidence_hidden_rows: enc_row and dec_row must be contiguous int32 [R]")
+    if b1 is not None and (b1.dtype != torch.float32 or b1.shape != (J,) or not b1.is_contiguous()):
+        raise ValueError("confidence_hidden_rows: b1 must be contiguous fp32 [J]")
+    if out is None:
+        out = torch.empty(R, J, dtype=E1.dtype, device=E1.device)
+    elif out.shape != (R, J) or out.dtype != E1.dtype or not out.is_contiguous():
+        raise ValueError("confidence_hidden_rows: out must be contiguous [R, J] in the operands' dtype")
+    if R and J:
+        _lib.call("conf_hidden_rows", dtype_code(E1.dtype), E1 if E1.shape[0] else None, E1.shape[0],
+                  D1 if D1.shape[0] else None, D1.shape[0], b1, enc_row, dec_row, R, J, out)
+    return out
+
+
+@torch.no_grad()
+def hypothesis_confidence(model, enc_out, lens, results, *, method="tsallis", alpha=1.0 / 3.0, aggregate="min", words=None,
+                          chunk_rows=None):
+    """Token, word and utterance confidences of N-best lists from the transducer's own output distribution:
+    ``results`` (one ``NBestResult`` per utterance of ``enc_out`` [B, T, P], compute dtype, device; ``lens`` host ints,
+    encoder frames per utterance, or None for all T) from ANY search over this encoder output - best-first,
+    frame-synchronous, ``skip_blank=`` (its frames are in the original numbering), a stream's ``nbest()`` on the kept
+    encoder output, a list read from disk.  No search runs again: the joint is re-evaluated at every token's
+    ``(frame, prefix)`` and each row of logits is reduced to ``loss.row_confidence``'s statistics.
+
+    The pass: compact rows for the live tokens only (no ``[B, N, U]`` padding of the rows), ONE int32 upload (the padded
+    hypotheses for the prediction network and per row ``enc_row = b T + frame``, ``dec_row``, ``token``); the prediction
+    network teacher-forced on every non-empty hypothesis, BOS in front (row ``u`` is its output after ``y_<u``);
+    ``joint_rows`` and ``D1 = dec W1d^T + b1`` through ``ops.gemm``; then per chunk of rows the gathered hidden kernel,
+    the logits product (``ops.gemm``, fp32) and the row kernel; ONE read to the host.  A chunk keeps the fp32 logits
+    buffer at or under 64 MiB (``chunk_rows`` overrides the rows per chunk).  Values are rounded where the search's
+    composed step rounds them, so ``raw[i][:, 0]`` reproduces a plain search's ``token_logp`` up to summation order.
+
+    This is the ACOUSTIC model's distribution: LM, internal-LM and bias terms of the search that made the list take no
+    part (``token_logp`` contains them, ``raw[i][:, 0]`` does not).  ``method`` / ``alpha``: ``confidence_measure``;
+    ``aggregate`` (``min`` / ``mean`` / ``prod``) folds token values into words and utterances; ``words``: a
+    ``WordTable`` - ``Confidence.word`` is then filled.  Returns one ``Confidence`` per utterance.
+
+    Raised before anything is launched: ``ValueError`` for a frame outside ``[0, lens[b])``, a token that is blank or
+    outside ``[0, V)``, a ``results`` length other than ``B``, a bad ``method`` / ``alpha`` / ``aggregate``;
+    ``RuntimeError`` for a CPU ``enc_out``.  If every hypothesis is empty nothing is launched.  No calibration is
+    claimed: there is no corpus here to measure one on."""
+    from .loss import _conf_row_stats
+    what = "hypothesis_confidence"
+    V = _vocab(model)
+    alpha = _check_confidence(what, method, alpha, aggregate, words)
+    if chunk_rows is not None and int(chunk_rows) < 1:
+        raise ValueError("%s: chunk_rows must be >= 1" % what)
+    results, lens, hyps, enc_row, tok = _confidence_rows(what, results, enc_out, lens, V, int(model.blank))
+    R = int(tok.size)
+    if R == 0:
+        return _confidence_results(results, hyps, None, 0, V, method, alpha, aggregate, words)
+    enc_out = enc_out.contiguous()
+    B, T, P = enc_out.shape
+    dev, cd = enc_out.device, enc_out.dtype
+    Nh, U = len(hyps), max(t.size for _, _, t, _ in hyps)
+    # one upload: the padded hypotheses [Nh, U], then enc_row, dec_row, token [R] each
+    host = np.zeros(Nh * U + 3 * R, dtype=np.int32)
+    padded, dec_row = host[:Nh * U].reshape(Nh, U), host[Nh * U + R:Nh * U + 2 * R]
+    pos = 0
+    for h, (_, _, t, _) in enumerate(hyps):
+        padded[h, :t.size] = t
+        dec_row[pos:pos + t.size] = h * (U + 1) + np.arange(t.size)
+        pos += t.size
+    host[Nh * U:Nh * U + R] = enc_row
+    host[Nh * U + 2 * R:] = tok
+    up = torch.from_numpy(host).to(dev)
+    d_enc, d_dec, d_tok = (up[Nh * U + k * R:Nh * U + (k + 1) * R] for k in range(3))
+    net = _SearchNet(model, cd)
+    h_dec, _ = model.decoder(up[:Nh * U].view(Nh, U))               # [Nh, U + 1, P2]
+    h_dec = h_dec.reshape(Nh * (U + 1), net.P2)
+    if h_dec.dtype != cd:
+        h_dec = ops.cast(h_dec, cd)
+    E1 = net.e1(enc_out)
+    D1 = ops.gemm(h_dec, net.w1c[:, P:], bias=net.b1)              # the search step's first product, bias included
+    chunk = int(chunk_rows) if chunk_rows is not None else max(1, CONF_LOGITS_BYTES // (4 * V))
+    chunk = min(chunk, R)
+    out = torch.empty(R * 6, dtype=torch.float32, device=dev)       # stats [R, 5], then top [R] (int32 bits)
+    stats, top = out[:R * 5].view(R, 5), out[R * 5:].view(torch.int32)
+    hid = torch.empty(chunk, net.J, dtype=cd, device=dev)
+    logits = torch.empty(chunk, V, dtype=torch.float32, device=dev)
+    for lo in range(0, R, chunk):
+        n = min(chunk, R - lo)
+        confidence_hidden_rows(E1, D1, d_enc[lo:lo + n], d_dec[lo:lo + n], None, hid[:n])
+        ops.gemm(hid[:n], net.w2c, out=logits[:n], bias=net.b2)
+        _conf_row_stats(logits, V, n, None, d_tok[lo:lo + n], n, V, net.blank, alpha, stats[lo:lo + n], top[lo:lo + n])
+    return _confidence_results(results, hyps, out.cpu().numpy(), R, V, method, alpha, aggregate, words)
+
+
+@torch.no_grad()
+def ctc_hypothesis_confidence(model, enc_out, lens, results, *, method="tsallis", alpha=1.0 / 3.0, aggregate="min",
+                              words=None):
+    """``hypothesis_confidence`` for lists of ``ctc_beam_search`` (or any list whose frames are the frames a CTC path
+    creates its tokens on), from the CTC head's distribution: the rows are the head's logits (``model._ctc_logits``, in
+    the compute dtype) on each token's frame, read by the row kernel through its gather index.  Neither the prediction
+    network nor the joint runs.  One int32 upload, one launch, one read to the host.  The n-gram LM and bias terms of
+    the search take no part.  Arguments, errors and the return value as there; ``RuntimeError`` on a model built
+    without ``ctc_weight > 0``."""
+    from .loss import _conf_row_stats
+    what = "ctc_hypothesis_confidence"
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("this model has no CTC head: construct it with Transducer(..., ctc_weight > 0)")
+    V = _vocab(model)
+    alpha = _check_confidence(what, method, alpha, aggregate, words)
+    results, lens, hyps, enc_row, tok = _confidence_rows(what, results, enc_out, lens, V, int(model.blank))
+    R = int(tok.size)
+    if R == 0:
+        return _confidence_results(results, hyps, None, 0, V, method, alpha, aggregate, words)
+    enc_out = enc_out.contiguous()
+    B, T, _ = enc_out.shape
+    up = torch.from_numpy(np.concatenate([enc_row, tok])).to(enc_out.device)
+    logits = model._ctc_logits(enc_out).contiguous().view(B * T, V)
+    out = torch.empty(R * 6, dtype=torch.float32, device=enc_out.device)
+    _conf_row_stats(logits, V, B * T, up[:R], up[R:], R, V, int(model.blank), alpha, out[:R * 5].view(R, 5),
+                    out[R * 5:].view(torch.int32))
+    return _confidence_results(results, hyps, out.cpu().numpy(), R, V, method, alpha, aggregate, words)

@@ -1133,3 +1133,59 @@ def mwer_rows(lists, ys, ylen, with_reference):
             v["label_lens"][r], v["row_utt"][r], v["row_slot"][r], v["row_dense"][r] = refs[b].size, b, -1, -1
             r += 1
     return rows
+
+
+CONF_COLUMNS = ("logp", "logp_max", "logp_blank", "entropy", "log_sum_p_alpha")
+
+
+def row_confidence(logits, tokens, rows=None, alpha=1.0 / 3.0, ld=None, blank=0):
+    """The five statistics of rows of logits that the confidence measures are built from (csrc/confidence.hip
+    ``conf_row_stats``; ``decode.confidence_measure`` turns them into a number in ``[0, 1]``).  ``logits`` float32 /
+    bfloat16 ``[N, V]`` raw, unit column stride, on the device; ``ld`` the distance between rows in elements (None:
+    ``logits.stride(0)``, so a ``[:, :V]`` view of a wider buffer reads as it should; nothing behind column ``V`` is
+    read).  ``tokens`` int32 ``[R]``; ``rows`` int32 ``[R]`` or None: output row ``r`` reads ``logits[rows[r]]``
+    (repeats and any order allowed), None: row ``r`` with ``R <= N``.  ``0 < alpha < 1``.  Returns ``(stats, top)``
+    on the device, no host sync: ``stats`` float32 ``[R, 5]`` in the order of ``CONF_COLUMNS`` -
+
+        ``logp``       log-softmax at ``tokens[r]``, as ``(z[k] - max z) - log sum exp(z - max z)``: the searches' form
+        ``logp_max``   the largest log-probability of the row
+        ``logp_blank`` the blank's
+        ``entropy``    the Shannon entropy of the row's softmax in nats, over all ``V`` symbols
+        ``log_sum_p_alpha``   ``log sum_v p_v^alpha``, the sum inside the Tsallis and Renyi entropies of order ``alpha``
+
+    - and ``top`` int32 ``[R]``, the arg max (lowest index on ties).  A ``-inf`` logit has probability 0 and adds nothing
+    to any sum.  A token outside ``[0, V)`` gives NaN in ``logp`` only; a row holding a NaN or no logit above ``-inf``,
+    and a ``rows[r]`` outside ``[0, N)`` (nothing is read for it), give five NaN and ``top = -1``.  One wave per row, no
+    atomics: the same bits on every run.  Needs ``V >= 2``."""
+    _lib.require_cuda(logits, tokens, rows)
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("row_confidence: logits must be float32 / bfloat16 [N, V]")
+    N, V = logits.shape
+    if V < 2 or (V > 1 and logits.stride(1) != 1):
+        raise ValueError("row_confidence: logits need V >= 2 columns of unit stride")
+    ld = int(logits.stride(0) if N > 1 else max(logits.stride(0), V)) if ld is None else int(ld)
+    if ld < V:
+        raise ValueError("row_confidence: ld = %d is below V = %d" % (ld, V))
+    if tokens.dtype != torch.int32 or tokens.dim() != 1 or not tokens.is_contiguous():
+        raise ValueError("row_confidence: tokens must be contiguous int32 [R]")
+    R = tokens.shape[0]
+    if rows is not None and (rows.dtype != torch.int32 or rows.shape != (R,) or not rows.is_contiguous()):
+        raise ValueError("row_confidence: rows must be contiguous int32 [R]")
+    if rows is None and R > N:
+        raise ValueError("row_confidence: %d tokens for %d rows of logits" % (R, N))
+    alpha, blank = float(alpha), int(blank)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("row_confidence: alpha must lie inside (0, 1), got %r" % (alpha,))
+    if not 0 <= blank < V:
+        raise ValueError("row_confidence: blank %d outside [0, %d)" % (blank, V))
+    stats = torch.empty(R, 5, dtype=torch.float32, device=logits.device)
+    top = torch.empty(R, dtype=torch.int32, device=logits.device)
+    if R:
+        _conf_row_stats(logits, ld, N, rows, tokens, R, V, blank, alpha, stats, top)
+    return stats, top
+
+
+def _conf_row_stats(logits, ld, N, rows, tokens, R, V, blank, alpha, stats, top):
+    """The launch of ``row_confidence`` into given outputs (``decode.hypothesis_confidence`` fills slices of one)."""
+    _lib.call("conf_row_stats", logits.detach(), _lib.dtype_code(logits.dtype), ctypes.c_longlong(ld), N, rows, tokens,
+              R, V, blank, float(alpha), stats, top)

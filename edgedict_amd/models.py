@@ -1499,6 +1499,31 @@ class Transducer(nn.Module):
         perplexity of a text is ``exp(-ilm_score.sum() / ylen.sum())``: the number to choose ``ilm_weight`` by."""
         return self.ilm_logprobs(ys, ylen).sum(dim=1)
 
+    @torch.no_grad()
+    def confidence(self, xs, xlen, results, head="rnnt", **kw):
+        """Token, word and utterance confidences of N-best lists (one ``decode.NBestResult`` per utterance, from any
+        search on this input, or read from disk): the encoder as the N-best searches run it, then
+        ``decode.hypothesis_confidence`` (``head="rnnt"``: the joint re-evaluated at every token's frame and prefix) or
+        ``decode.ctc_hypothesis_confidence`` (``head="ctc"``: the CTC head's logits on every token's frame, for
+        ``ctc_beam_search`` lists; RuntimeError on a model built without ``ctc_weight > 0``).  Keywords ``method``
+        (``"tsallis"``, ``"entropy"``, ``"max_prob"``, ``"prob"``), ``alpha``, ``aggregate``, ``words`` as there.
+        Returns one ``decode.Confidence`` per utterance.  It is the acoustic model's distribution: LM and bias terms of
+        the search that made the lists take no part.  Run it in ``eval()`` mode, or dropout takes part."""
+        from . import _lib, decode
+        if head not in ("rnnt", "ctc"):
+            raise ValueError("confidence: head must be 'rnnt' or 'ctc', got %r" % (head,))
+        if head == "ctc":
+            enc_out, lens = self._ctc_encode(xs, xlen)
+            return decode.ctc_hypothesis_confidence(self, enc_out, lens, results, **kw)
+        _lib.require_cuda(xs)
+        enc_out, _ = self.encoder(xs)
+        enc_out = enc_out.contiguous()
+        lens = None
+        if xlen is not None:
+            xl = xlen.detach().cpu() if torch.is_tensor(xlen) else torch.as_tensor(xlen)
+            lens = self.scale_length(enc_out, xl).numpy().astype("int32")
+        return decode.hypothesis_confidence(self, enc_out, lens, results, **kw)
+
     EVALUATE_SEARCHES = ("greedy", "ctc_greedy", "beam", "sync_beam")
     last_error_rate = None       # the metrics.ErrorRateResult of the last evaluate_step
 

@@ -1619,6 +1619,40 @@ int edgedict_ilm_logprobs(const float* logits, const int32_t* targets, const int
  * length_bonus finite, V <= 5376, lm and ngram not both set.  lm->bos has no counterpart: nothing but `start` is read.
  */
 
+/* ------------------------------------------------------------------------------------
+ * Confidence of N-best hypotheses (csrc/confidence.hip): the two kernels of a post-pass over the lists any search
+ * returned.  The caller re-evaluates the joint at every token's (encoder frame, prefix) - conf_hidden_rows between two
+ * edgedict_gemm calls - or takes the CTC head's logits, and conf_row_stats reduces each row of logits to five
+ * statistics of the acoustic model's output distribution over all V symbols, the blank included.  LM and bias terms
+ * take no part.  Nothing is allocated, nothing synchronises, no atomics: the same bits on every run.
+ *
+ *   conf_hidden_rows  hid [R, J] (dtype) = tanh(E1[enc_row[r], :] + D1[dec_row[r], :] + b1): E1 [n_enc_rows, J] and
+ *                     D1 [n_dec_rows, J] contiguous in dtype, b1 fp32 [J] or null (nothing is added: D1 then already
+ *                     holds the bias, as the search step's first product does), enc_row / dec_row int32 [R] on the
+ *                     device.  The sum is formed in fp32 from the stored operands and hid is rounded once: the rounding
+ *                     points of the search's composed step.  16-byte loads and stores when J is a multiple of the 16-byte
+ *                     width and the three pointers are 16-byte aligned, element by element otherwise.  A row whose
+ *                     index lies outside [0, n_enc_rows) / [0, n_dec_rows) is written as NaN and nothing is read for it.
+ *   conf_row_stats    logits [n_logit_rows, ld] in dtype (fp32 or bf16; ld >= V elements between rows; what lies behind
+ *                     column V is never read), rows int32 [R] or null (row r reads logits row rows[r]; null: row r, and
+ *                     R <= n_logit_rows), tokens int32 [R], 0 < alpha < 1.  One wave per row, 4 per workgroup; a row of
+ *                     V <= 2048 is read once into registers, a longer one once per pass.  In fp32, with m = max z,
+ *                     s = sum e^(z - m), a = sum e^(z - m) (z - m), q = sum e^(alpha (z - m)) (a -inf logit adds exactly
+ *                     0 to all three), stats fp32 [R, 5] =
+ *                       { logp = (z[tokens[r]] - m) - log s,  logp_max = -log s,  logp_blank = (z[blank] - m) - log s,
+ *                         H = log s - a / s  (Shannon entropy, nats),  log sum_v p_v^alpha = log q - alpha log s }
+ *                     and top int32 [R] = arg max z, the lowest index on ties.  A token outside [0, V) gives NaN in logp
+ *                     only.  A row that holds a NaN or nothing above -inf, and a rows[r] outside [0, n_logit_rows) (for
+ *                     which nothing is read), give five NaN and top = -1; other rows are not affected.
+ * Checked before the launch (-1 and a message): dtype, R > 0, J > 0, V >= 2, ld >= V, blank inside [0, V), alpha inside
+ * (0, 1), null pointers.
+ */
+int edgedict_conf_hidden_rows(int dtype, const void* E1, int n_enc_rows, const void* D1, int n_dec_rows, const float* b1,
+                              const int32_t* enc_row, const int32_t* dec_row, int R, int J, void* hid, void* stream);
+int edgedict_conf_row_stats(const void* logits, int dtype, long long ld, int n_logit_rows, const int32_t* rows,
+                            const int32_t* tokens, int R, int V, int blank, float alpha, float* stats, int32_t* top,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
